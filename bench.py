@@ -9,17 +9,28 @@ With --gpus N each rank runs the same per-GPU batch (config 4: 8 x 16 = 128 imag
 per-step communication; the final images are all-gathered once over RCCL.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--precision fp32|fp16] [--arch A0|A1] [--size 256] [--batch 16]
+                    [--full] [--dump-outputs DIR]
 
 The headline (`value`, `dtype`) is measured in the REFERENCE's precision: fp32 storage and arithmetic (the reference runs this path
-in fp32 everywhere, SURVEY.md section 8 legend), rel-L2 <= 1e-5 vs the fp32 CPU oracle.  The fp16-storage / fp16-MFMA mode
-(tolerance 5e-3) is timed in the same run and reported as the labelled secondary object `fp16`.
+in fp32 everywhere, SURVEY.md section 8 legend), rel-L2 <= 1e-5 vs the fp32 CPU oracle.  With --full the fp16-storage / fp16-MFMA
+mode (tolerance 5e-3) is timed in the same run and reported as the labelled secondary object `fp16`.
+
+A plain run (no --full) does only what the headline needs: build the model, W warm-up steps, K timed steps, the result line
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds per timed step, ...).  Everything else listed
+below -- per-kernel roofline timing, the parity probe against the CPU oracle, the other precision modes, the other BASELINE
+configurations and the CPU baseline -- runs only with --full (--dump-ops alone switches the per-op timing on, for its table).
+
+--dump-outputs DIR writes what the timed path computed in its last step, as float32 arrays: DIR/sample.npy = the batch of images
+after the last timed denoising step (all ranks' images, gathered, with --gpus N > 1); with --train DIR/loss.npy and DIR/params.npy
+(the parameters after the last optimizer step, flattened).  At most 64 MiB in all: a larger array is written as a fixed, seeded
+sample of its elements.  Inputs and weights are seeded, so two runs with the same arguments compute on identical inputs.
 
 `--gpus N` with N > 1 and no torchrun environment: this process starts the N ranks itself (torch.distributed.run, one rank per
 GPU, RCCL) BEFORE touching the GPU and relays their output; under the driver's own `python -m torch.distributed.run ... bench.py
 --gpus N` launch the ranks read RANK / LOCAL_RANK / WORLD_SIZE from the environment.  A world size that differs from --gpus is
 an error, never a silent single-rank run.
 
-Prints ONE JSON line (rank 0).  Extra objects: `roofline` (MFMA implicit-GEMM conv kernel, per-launch
+Prints ONE JSON line (rank 0).  Extra objects of --full: `roofline` (MFMA implicit-GEMM conv kernel, per-launch
 HIP-event timing on the launch stream inside the timed region; `roofline.hbm_bound` = the HBM-bound kernels of the step -- first conv,
 head conv, GroupNorm apply, Philox noise, DDPM update -- each with its algorithmic bytes, duration and GB/s against the 8 TB/s peak),
 `cpu_baseline` (the CPU oracle timed on the host cores on a bounded sample of the same workload, plus BASELINE config 1 -- MNIST,
@@ -56,6 +67,21 @@ TOLERANCE = {"fp32": "rel-L2 <= 1e-5 per UNet forward vs the fp32 CPU oracle (fp
                        "inputs of any magnitude -- tests/test_gpu_fp32x3_domain.py)",
              "fp16": "rel-L2 <= 5e-3 per UNet forward vs the fp32 CPU oracle (fp16 storage, fp16 MFMA, fp32 accumulate)"}
 HBM_PEAK = 8.0e12
+DUMP_CAP_BYTES = 64 * 2**20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every tensor as out_dir/<name>.npy in float32.  A tensor larger than its share of DUMP_CAP_BYTES is written as
+    a 1-D sample of its elements at indices drawn from a fixed seed (the same indices in every run of the same shape)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_CAP_BYTES // (4 * len(arrays))
+    for name, a in arrays.items():
+        a = a.detach().float()
+        if a.numel() > share:
+            idx = torch.randint(0, a.numel(), (share,), generator=torch.Generator().manual_seed(0)).sort().values
+            a = a.flatten()[idx.to(a.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), a.cpu().numpy())
 
 
 def build_model(arch, size, precision, dev, timesteps=1000, in_ch=3):
@@ -330,7 +356,7 @@ def spawn_ranks(n):
 
 def time_sampling(args, m, dev, rank, world, use_dist, dist, timing=True):
     """warm-up, then EXACTLY args.steps denoising steps between two barrier + synchronize; returns (seconds [max over ranks],
-    final x_t, roofline dict or None)"""
+    final x_t, roofline dict or None, all ranks' final images gathered or None)"""
     N, S = args.batch, args.size
     shape = (N, 3, S, S)
     seed, sample0 = 3, rank * N
@@ -465,7 +491,7 @@ def time_sampling(args, m, dev, rank, world, use_dist, dist, timing=True):
             rows = [dict(s, ms=t / runs) for s, t in zip(stats, ms)]
             with open(args.dump_ops if prec == args.precision else args.dump_ops + "." + prec, "w") as f:
                 json.dump(rows, f, indent=1)
-    return dt, x_t, roof
+    return dt, x_t, roof, gathered
 
 
 def main():
@@ -476,7 +502,8 @@ def main():
     ap.add_argument("--precision", default="fp32x3", choices=list(PEAK),
                     help="headline precision mode.  Default fp32x3: fp32 storage and fp32-grade arithmetic (every conv product as three "
                          "fp16 MFMAs on hi+lo split operands; held to the same 1e-5 gate as the exact-fp32 mode, measured error below "
-                         "it).  The exact-fp32-MFMA mode and the fp16 mode are timed in the same run as labelled secondary objects")
+                         "it).  With --full the exact-fp32-MFMA mode and the fp16 mode are timed in the same run as labelled secondary "
+                         "objects")
     ap.add_argument("--arch", default="A0", choices=list(ARCHS))
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--batch", type=int, default=16)
@@ -488,6 +515,10 @@ def main():
     ap.add_argument("--train", action="store_true", help="time the TRAINING step (forward + MSE + backward + fused AdamW [+ gradient "
                     "all-reduce for N > 1]) instead of the sampling step; SURVEY section 8f rank 1 / BASELINE config 5")
     ap.add_argument("--in-ch", type=int, default=3)
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline: per-kernel roofline "
+                    "timing, the parity probe, the other precision modes, the other BASELINE configurations, the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed step "
+                    "computed as DIR/<name>.npy (float32, at most 64 MiB in all)")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
@@ -521,17 +552,20 @@ def main():
     if args.graph and m is not None:
         m.model.enable_graph(True)
         args.no_op_timing = True  # the event-bracketing executor cannot be captured
-    dt, x_t, roof = time_sampling(args, m, dev, rank, world, use_dist, dist)
+    dt, x_t, roof, gathered = time_sampling(args, m, dev, rank, world, use_dist, dist, timing=args.full or bool(args.dump_ops))
     finite = bool(torch.isfinite(x_t).all())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"sample": x_t if gathered is None else gathered})
+    del gathered
     parity = None
-    if not stub and world == 1 and not args.no_cpu_baseline and not args.graph:
+    if args.full and not stub and world == 1 and not args.no_cpu_baseline and not args.graph:
         try:
             parity = parity_probe(m, args.arch, S)
         except Exception as e:  # the measurement stands on its own; say why the probe is missing
             parity = {"error": repr(e)}
 
     secondary = {}
-    if not stub and not args.no_secondary:
+    if args.full and not stub and not args.no_secondary:
         # the other precision modes, same workload, same run: labelled extras, never the headline
         del m, x_t
         for prec in ("fp32", "fp16"):
@@ -539,7 +573,7 @@ def main():
                 continue
             torch.cuda.empty_cache()
             m2 = build_model(args.arch, S, prec, dev)
-            dt2, x2, roof2 = time_sampling(args, m2, dev, rank, world, use_dist, dist)
+            dt2, x2, roof2, _ = time_sampling(args, m2, dev, rank, world, use_dist, dist)
             entry = {"value": world * args.steps / dt2, "unit": "steps/s", "ms_per_step": dt2 / args.steps * 1e3, "dtype": DTYPE_NAME[prec],
                      "precision_mode": prec, "tolerance": TOLERANCE[prec], "outputs_finite": bool(torch.isfinite(x2).all()), "roofline": roof2}
             if parity and "probe_output" in parity:  # same seed -> same weights: how far is this mode from the headline mode's output?
@@ -577,14 +611,14 @@ def main():
         if roof:
             res["roofline"] = roof
         res.update(secondary)
-        if world == 1 and not stub and not args.no_secondary and (args.arch, S, N) == ("A0", 256, 16):
+        if args.full and world == 1 and not stub and not args.no_secondary and (args.arch, S, N) == ("A0", 256, 16):
             for name, fn in (("configs", lambda: short_config_runs(dev)), ("train_fp16", lambda: short_train_run(dev))):
                 try:
                     r_ = fn()
                     res.update(r_ if name == "configs" else {name: r_})
                 except Exception as e:  # the headline stands on its own; say why an extra is missing
                     res[name] = {"error": repr(e)}
-        if not args.no_cpu_baseline and world == 1 and not stub:
+        if args.full and not args.no_cpu_baseline and world == 1 and not stub:
             res["cpu_baseline"] = cpu_baseline(args.arch, S, N)
         print(json.dumps(res), flush=True)
     if use_dist:
@@ -632,6 +666,11 @@ def train_main(args, world, rank, dev, use_dist):
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        with torch.no_grad():
+            params = torch.cat([p.detach().float().flatten() for p in unet.parameters()])
+        dump_outputs(args.dump_outputs, {"loss": loss, "params": params})
+        del params
     if rank == 0:
         res = {"metric": f"training steps/sec (UNet fwd + MSE + bwd + AdamW) at {S}x{S} bs={N}", "value": world * args.steps / dt,
                "unit": "steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,

@@ -14,11 +14,11 @@ mkdir -p $OUT
 cd $ROOT
 if [ "$PART" != "B" ]; then
 echo "[1] bench lines"; date
-python3 bench.py > $OUT/${TAG}_bench_default.json
+python3 bench.py --full > $OUT/${TAG}_bench_default.json
 python3 bench.py --no-cpu-baseline --no-secondary --steps 20 --warmup 5 --dump-ops $OUT/${TAG}_bench_fp32x3_per_op_hip_events.json > $OUT/${TAG}_bench_fp32x3_line.json
-python3 bench.py --arch A1 --batch 8 --no-cpu-baseline --steps 10 --warmup 3 > $OUT/${TAG}_bench_A1_256_bs8.json
+python3 bench.py --full --arch A1 --batch 8 --no-cpu-baseline --steps 10 --warmup 3 > $OUT/${TAG}_bench_A1_256_bs8.json
 python3 bench.py --arch A1 --batch 8 --no-cpu-baseline --no-secondary --steps 10 --warmup 3 --dump-ops $OUT/${TAG}_bench_A1_256_bs8_fp32x3_per_op_hip_events.json > /dev/null
-python3 bench.py --size 64 --no-cpu-baseline --steps 200 --warmup 10 --no-op-timing > $OUT/${TAG}_bench_A0_64_bs16.json
+python3 bench.py --full --size 64 --no-cpu-baseline --steps 200 --warmup 10 --no-op-timing > $OUT/${TAG}_bench_A0_64_bs16.json
 python3 bench.py --size 64 --no-cpu-baseline --no-secondary --steps 100 --warmup 10 --dump-ops $OUT/${TAG}_bench_A0_64_bs16_fp32x3_per_op_hip_events.json > /dev/null
 python3 bench.py --train --precision fp16 --steps 10 --warmup 3 --no-cpu-baseline > $OUT/${TAG}_bench_train_fp16.json
 python3 bench.py --train --precision fp16 --arch A1 --size 512 --batch 2 --in-ch 13 --steps 10 --warmup 3 --no-cpu-baseline > $OUT/${TAG}_bench_train_config5_bs2_fp16.json
@@ -28,9 +28,9 @@ echo "[2] end-to-end calls"; date
 echo "[3] rocprofv3 kernel stats (three precision modes, A1, training)"; date
 cd /tmp && export TMPDIR=/tmp
 for MODE in fp32x3 fp16 fp32; do
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_ks_$MODE -- python3 $ROOT/bench.py --precision $MODE --steps 10 --warmup 3 --no-cpu-baseline --no-secondary > $OUT/${TAG}_ks_$MODE.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_ks_$MODE -- python3 $ROOT/bench.py --full --precision $MODE --steps 10 --warmup 3 --no-cpu-baseline --no-secondary > $OUT/${TAG}_ks_$MODE.log 2>&1
 done
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_ks_A1 -- python3 $ROOT/bench.py --arch A1 --batch 8 --steps 10 --warmup 3 --no-cpu-baseline --no-secondary > $OUT/${TAG}_ks_A1.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_ks_A1 -- python3 $ROOT/bench.py --full --arch A1 --batch 8 --steps 10 --warmup 3 --no-cpu-baseline --no-secondary > $OUT/${TAG}_ks_A1.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_ks_train -- python3 $ROOT/bench.py --train --precision fp16 --steps 10 --warmup 3 --no-cpu-baseline > $OUT/${TAG}_ks_train.log 2>&1
 fi
 if [ "$PART" != "A" ]; then

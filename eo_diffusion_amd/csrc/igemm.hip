@@ -2146,6 +2146,291 @@ template <typename T, bool SPLIT, bool BWD = false> static int launch_up4(IgemmP
 }
 
 // =============================================================================================
+// conv_s2_halo_kernel: 3x3 / stride 2 / pad 1 conv (Downsample.conv, unet_openai.py:255-274) on halo patches split by input PARITY.
+//
+// An 8 x 16 output tile at (ty0, tx0) reads the 17 x 33 input region starting at (2 ty0 - 1, 2 tx0 - 1).  Split by the parity (ry, rx)
+// of the position inside that region, it is four PLANES, each a dense map at pixel stride 2: plane (ry, rx) position (i, j) = input pixel
+// (2 (ty0 + i) - 1 + ry, 2 (tx0 + j) - 1 + rx).  Tap (dy, dx) = (2a + ry, 2b + rx) of output (ho', wo') reads plane position (ho' + a,
+// wo' + b): plane (0, 0) carries taps {0, 2} x {0, 2}, (0, 1) {0, 2} x {1}, (1, 0) {1} x {0, 2}, (1, 1) the centre -- 4 + 2 + 2 + 1 = 9
+// tap visits per channel chunk, every staged element fetched and split ONCE per chunk (the generic kernel gathers and splits the
+// A tile again for every tap).  Every plane is staged as a 9 x 17 patch (the 16-wide / 8-tall planes simply carry a row or column
+// that no tap reads), so the fragment addressing is the parity-class upsample conv's with a fixed pitch.
+// K loop: (channel chunk, plane) pairs in the order above, each with its own patch, in a ring of two patch buffers: the patch of the
+// next pair is issued at the first step of the current one and split in place (fp32 storage) behind the MFMAs of its last step.
+// Weights: the ordinary packed [tap][Cout][Cin] tensor (eod_pack_conv_weight / _split), one 128-row stage per K-step, two stages.
+// =============================================================================================
+template <typename T, bool SPLIT>
+__global__ __launch_bounds__(256, 2) void conv_s2_halo_kernel(const IgemmP p) {
+    static_assert(!SPLIT || sizeof(T) == 4, "the split-fp16 product is a mode of fp32 storage");
+    static_assert(SPLIT || sizeof(T) == 2, "fp16 storage or split fp32");
+    constexpr int NW = 4, WAVES_M = 2, WAVES_N = 2, BN = 128, BM = 128, MS = 16;
+    constexpr int PH = 9, PW = 17, PR = PH * PW, PG = (PR + 7) / 8, LAH = (PG + NW - 1) / NW;  // 153 rows, 20 groups, 5 pieces per wave
+    constexpr int ES = sizeof(T), EPC = 16 / ES, BKB = 128, BK = BKB / ES;
+    constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N, TM = WM / MS, TN = WN / MS;
+    constexpr int LB = (BN / 8) / NW;
+    constexpr int ABUF = PG * 1024, BSTAGE = BN * BKB;
+    static_assert(PG == NW * LAH && LAH * 4 <= 32, "every wave stages LAH whole pieces; 4 plane-validity bits per piece");
+    static_assert(LB <= 6, "wait_vm immediates");
+
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* const sA = smem;             // [2][ABUF]
+    char* const sB = smem + 2 * ABUF;  // [2][BSTAGE]
+
+    constexpr bool DIRECT = SPLIT;  // swapped MFMA operands + stores straight from the accumulators (see halo_epilogue_direct)
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave / WAVES_N, wn = wave % WAVES_N;
+    int tile_m, tile_n;
+    map_tile(p, tile_m, tile_n);
+    const int n0 = tile_n * BN;
+    const TileGeom g = make_geom<true, BM>(p, tile_m);  // patch mode on the OUTPUT map: ty0, tx0, n_first
+    float pre_bcol[DIRECT ? 1 : TN];  // epilogue operands fetched at entry (see conv3x3_halo_kernel)
+    f32x4 pre_bq[DIRECT ? TN : 1];
+    int pre_we[DIRECT ? TN : 1];
+    if constexpr (DIRECT) {
+        prefetch_bcol4<TN>(p, p.Cout, n0 + wn * WN, lane, g.n_first, pre_bq);
+        prefetch_wexp4<TN>(p, p.Cout, n0 + wn * WN, 0, lane, pre_we);
+    } else {
+        prefetch_bcol<TN, MS>(p, p.Cout, n0 + wn * WN, lane, g.n_first, pre_bcol);
+    }
+    float wsc1 = 1.0f;
+    if constexpr (SPLIT) wsc1 = p.w_scale[1];
+    AbScale asc = {EOD_SPLIT_ASCALE, 1.0f};  // split-fp16 product: operand scale of this tile's image (see conv3x3_halo_kernel)
+    if constexpr (SPLIT) {
+        if (p.a_bound) asc = ab_scale_of(ab_wave_bound(p.a_bound, g.n_first));
+    }
+
+    // per-lane patch rows: piece i of this wave = patch rows (wave + NW i) * 8 .. + 7, lane = (row srow, 16-byte slot sslot)
+    const int srow = lane >> 3, sslot = lane & 7;
+    int ppix[LAH];                   // input pixel of plane (0, 0) at this patch row (negative at the top / left border)
+    unsigned pvalid = 0, pck = 0;    // 4 validity bits per piece (plane ry * 2 + rx); source chunk per piece (swizzle)
+    const int bchunk0 = sslot ^ ((4 * wave + (srow >> 1)) & 7);
+#pragma unroll
+    for (int i = 0; i < LAH; ++i) {
+        const int prow = (wave + NW * i) * 8 + srow;
+        const int py = prow / PW, px = prow - py * PW;
+        const int hi = 2 * (g.ty0 + py) - 1, wi = 2 * (g.tx0 + px) - 1;
+        ppix[i] = hi * p.W + wi;
+#pragma unroll
+        for (int pl = 0; pl < 4; ++pl) {
+            const bool ok = prow < PR && (unsigned)(hi + (pl >> 1)) < (unsigned)p.H && (unsigned)(wi + (pl & 1)) < (unsigned)p.W;
+            if (ok) pvalid |= 1u << (4 * i + pl);
+        }
+        pck |= (unsigned)(sslot ^ ((px >> 1) & 7)) << (3 * i);
+    }
+    auto pchunk_of = [&](int i) { return (int)((pck >> (3 * i)) & 7u); };
+    unsigned b_v[LB];
+#pragma unroll
+    for (int i = 0; i < LB; ++i) {
+        const int row = (wave + NW * i) * 8 + srow;
+        b_v[i] = (n0 + row < p.Cout) ? (unsigned)(row * p.Cin * ES) + bchunk0 * 16 : EOD_OOB;
+    }
+    const __amdgpu_buffer_rsrc_t rsA = make_rsrc(p.a0 + (long long)g.n_first * p.H * p.W * p.C0 * ES);
+    const __amdgpu_buffer_rsrc_t rsB = make_rsrc(p.b + (long long)n0 * p.Cin * ES);
+    const int tapstride = p.Cout * p.Cin * ES;
+
+    auto issue_patch_piece = [&](int i, int kin, int pl, char* abuf) {
+        const int pc = pchunk_of(i);
+        unsigned v = ((pvalid >> (4 * i + pl)) & 1u) ? (unsigned)(ppix[i] + (pl >> 1) * p.W + (pl & 1)) * (unsigned)(p.C0 * ES) + pc * 16 : EOD_OOB;
+        if (kin + BK > p.C0) v = (kin + pc * EPC < p.C0) ? v : EOD_OOB;
+        blds16(rsA, v, (unsigned)(kin * ES), abuf + (wave + NW * i) * 1024);
+    };
+    auto split_piece = [&](int i, char* abuf) {  // SPLIT: fp32 chunk -> its half of the pair's [8 x hi | 8 x lo] image (zeros stay zeros)
+        char* ptr = abuf + (wave + NW * i) * 1024 + lane * 16;
+        const f32x4 f = *reinterpret_cast<const f32x4*>(ptr);
+        *reinterpret_cast<i32x4*>(ptr) = split_pair_exchange_scaled(f, asc.s, (pchunk_of(i) & 1) != 0);
+    };
+    auto issue_weights = [&](int tap, int kin, char* bst) {
+        const unsigned soff = (unsigned)(tap * tapstride) + (unsigned)(kin * ES);
+#pragma unroll
+        for (int i = 0; i < LB; ++i) {
+            unsigned v = b_v[i];
+            if (kin + BK > p.C0) v = (kin + (SPLIT ? (bchunk0 >> 1) * 8 : bchunk0 * EPC) < p.C0) ? v : EOD_OOB;
+            blds16(rsB, v, soff, bst + (wave + NW * i) * 1024);
+        }
+    };
+    auto wait_vm = [](int n) {  // s_waitcnt vmcnt(n) for a wave-uniform run-time n (the instruction takes an immediate)
+        switch (n) {
+            case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+            case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
+            case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
+            case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
+            case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
+            case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
+            default: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
+        }
+    };
+    // plane pl: taps per row / per column; tap s of the plane -> (a, b) and its 3x3 slot
+    auto plane_nb = [](int pl) { return (pl & 1) ? 1 : 2; };
+    auto plane_taps = [](int pl) { return ((pl >> 1) ? 1 : 2) * ((pl & 1) ? 1 : 2); };
+    auto tap_slot = [&](int pl, int s) {
+        const int nb = plane_nb(pl), a = s / nb, b = s - a * nb;
+        return (2 * a + (pl >> 1)) * 3 + 2 * b + (pl & 1);
+    };
+
+    typename AccLayout<MS>::vec acc[TM][TN];
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < AccLayout<MS>::R; ++r) acc[i][j][r] = 0.0f;
+
+    // fragment addresses (see conv_up4_halo_kernel): acur[v][b] for the column offsets b of a tap, rows via compile-time offsets
+    const int lr = lane & 15, lh = lane >> 4;
+    const int c0 = SPLIT ? 2 * ((0x2130 >> (4 * lh)) & 3) : lh, c1 = SPLIT ? c0 + 1 : 4 + lh;
+    int acur[2][2];
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        const int pxc = lr + b;
+        const int key = (pxc >> 1) & 7;
+        const int rowb = (wm * (WM / 16) * PW + pxc) * BKB;
+        acur[0][b] = rowb + ((c0 ^ key) << 4);
+        acur[1][b] = rowb + ((c1 ^ key) << 4);
+    }
+    const int bsw = (lr >> 1) & 7;
+    const int b_rd = (wn * WN + lr) * BKB;
+    const int boff0 = b_rd + ((c0 ^ bsw) << 4), boff1 = b_rd + ((c1 ^ bsw) << 4);
+
+    auto mfma_tap = [&](const char* abuf, int a, int b, const char* bst) {
+        if constexpr (SPLIT) {
+            i32x4 ah[TM], al[TM], bh[TN], bl[TN];
+#pragma unroll
+            for (int i = 0; i < TM; ++i) al[i] = *reinterpret_cast<const i32x4*>(abuf + acur[1][b] + (i + a) * PW * BKB);
+#pragma unroll
+            for (int j = 0; j < TN; ++j) bh[j] = *reinterpret_cast<const i32x4*>(bst + boff0 + j * MS * BKB);
+#pragma unroll
+            for (int i = 0; i < TM; ++i) ah[i] = *reinterpret_cast<const i32x4*>(abuf + acur[0][b] + (i + a) * PW * BKB);
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, bh[j]), __builtin_bit_cast(half8, al[i]), acc[i][j], 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < TN; ++j) bl[j] = *reinterpret_cast<const i32x4*>(bst + boff1 + j * MS * BKB);
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, bl[j]), __builtin_bit_cast(half8, ah[i]), acc[i][j], 0, 0, 0);
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, bh[j]), __builtin_bit_cast(half8, ah[i]), acc[i][j], 0, 0, 0);
+        } else {
+#pragma unroll
+            for (int v = 0; v < 2; ++v) {  // fp16 storage: two 32-k sub-steps per 64-channel chunk
+                i32x4 fa16[TM], fb16[TN];
+#pragma unroll
+                for (int i = 0; i < TM; ++i) fa16[i] = *reinterpret_cast<const i32x4*>(abuf + acur[v][b] + (i + a) * PW * BKB);
+#pragma unroll
+                for (int j = 0; j < TN; ++j) fb16[j] = *reinterpret_cast<const i32x4*>(bst + (v ? boff1 : boff0) + j * MS * BKB);
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j)
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, fa16[i]), __builtin_bit_cast(half8, fb16[j]), acc[i][j], 0, 0, 0);
+            }
+        }
+    };
+
+    const int KC = p.kc0;
+    {  // prologue: whole patch of (chunk 0, plane 0) + weights of step 0
+#pragma unroll
+        for (int i = 0; i < LAH; ++i) issue_patch_piece(i, 0, 0, sA);
+        issue_weights(tap_slot(0, 0), 0, sB);
+        if constexpr (SPLIT) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+            for (int i = 0; i < LAH; ++i) split_piece(i, sA);
+        }
+    }
+    int np_prev = 0;  // patch pieces this wave issued in the previous K-step (they sit behind that step's weight DMA in the vmcnt order)
+    int step = 0;
+    for (int cc = 0; cc < KC; ++cc) {
+        const int kin = cc * BK;
+        const bool more = cc + 1 < KC;
+#pragma unroll
+        for (int pl = 0; pl < 4; ++pl) {
+            const int NT = plane_taps(pl), nb = plane_nb(pl);
+            const bool has_next = pl < 3 || more;                 // a next (chunk, plane) pair exists
+            const int nkin = pl < 3 ? kin : kin + BK, npl = (pl + 1) & 3;
+            const char* abuf = sA + (pl & 1) * ABUF;              // pair q = 4 cc + pl lives in buffer q & 1 = pl & 1
+            char* abuf_next = sA + ((pl + 1) & 1) * ABUF;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                if (s >= NT) break;
+                // this step's weights have landed; at a pair's first step also every piece of its patch (issued one pair earlier)
+                if (s == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                else wait_vm(np_prev);
+                if constexpr (SPLIT) __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): my in-place splits are written
+                __builtin_amdgcn_s_barrier();
+                if (s + 1 < NT) issue_weights(tap_slot(pl, s + 1), kin, sB + ((step + 1) & 1) * BSTAGE);
+                else if (has_next) issue_weights(tap_slot(npl, 0), nkin, sB + ((step + 1) & 1) * BSTAGE);
+                int np = 0;
+                if (s == 0 && has_next) {  // the whole patch of the next pair: the buffer of the previous pair is free behind the barrier
+#pragma unroll
+                    for (int i = 0; i < LAH; ++i) issue_patch_piece(i, nkin, npl, abuf_next);
+                    np = LAH;
+                }
+                const int a = s / nb, b = s - a * nb;
+                mfma_tap(abuf, a, b, sB + (step & 1) * BSTAGE);
+                if constexpr (SPLIT) {
+                    if (s == NT - 1 && has_next) {
+                        // the next pair's pieces: a one-step pair issued them after its only weight DMA, a longer pair before the DMA of its
+                        // last step (the next step's weights, LB loads)
+                        if (NT == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                        else wait_vm(LB);
+#pragma unroll
+                        for (int i = 0; i < LAH; ++i) split_piece(i, abuf_next);
+                    }
+                }
+                np_prev = np;
+                ++step;
+            }
+        }
+    }
+    __builtin_amdgcn_s_waitcnt(0xc07f);
+    __builtin_amdgcn_s_barrier();  // every wave is done with the operand buffers: reuse them for the epilogue
+    IgemmP pe = p;
+    if constexpr (SPLIT) pe.alpha = p.alpha * wsc1 * asc.inv;
+    if constexpr (DIRECT) halo_epilogue_direct<BM, BN, WAVES_M, WAVES_N>(pe, g, acc, wave, lane, n0, pre_bq, pe.alpha, pre_we);
+    else igemm_epilogue<T, true, BM, BN, WAVES_M, WAVES_N, sizeof(T) == 4, MS>(pe, g, acc, smem, wave, lane, n0, nullptr, 0, pre_bcol);
+}
+
+template <typename T, bool SPLIT> static int launch_s2(IgemmP& p, hipStream_t st) {
+    constexpr int BK = 128 / (int)sizeof(T);
+    const size_t ring = 2 * (size_t)(20 * 1024) + 2 * (size_t)128 * 128;
+    const size_t epi = 4 * (size_t)64 * (64 + 4) * sizeof(float);
+    const size_t lds = ring > epi ? ring : epi;
+    auto kern = conv_s2_halo_kernel<T, SPLIT>;
+    static bool attr_done = false;
+    if (!attr_done) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        attr_done = true;
+    }
+    p.kc0 = (p.C0 + BK - 1) / BK;
+    p.kc1 = 0;
+    p.KT = p.kc0 * 9;
+    p.tiles_n = (p.Cout + 127) / 128;
+    p.tw_log2 = 4;  // 8 x 16 tiles of the OUTPUT map
+    p.th = 8;
+    p.tiles_pw = p.Wo / 16;
+    p.tiles_pi = p.tiles_pw * (p.Ho / 8);
+    p.tiles_m = p.tiles_pi * p.N;
+    p.tiles_per_image = p.tiles_pi;  // (statistics slots: tile of the image x 2 wave rows, as the generic kernel's 128-row tiles count them)
+    const long long nblk = (long long)p.tiles_m * p.tiles_n;
+    if (nblk <= 0 || nblk > 0x7fffffffLL) {
+        eod_set_error("conv_s2_halo: bad grid %lld", nblk);
+        return EOD_EINVAL;
+    }
+    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(256), lds, st, p);
+    EOD_CHECK_LAUNCH("conv_s2_halo");
+    return EOD_OK;
+}
+
+// =============================================================================================
 // conv_head_kernel: the UNet's output head, GroupNorm -> SiLU -> 3x3 conv to <= 16 channels, NCHW fp32 output (unet_openai.py:738-743).
 // 2 x 128 x 9 x Cout MACs per pixel against 512 bytes of input: HBM-bound, and in the halo kernel's frame (one barrier per tap for a
 // 12-MFMA step) bound by synchronisation instead (0.41 ms for 537 MB of input).  Here a tile's tap loop has NO barrier: the weights
@@ -2690,13 +2975,15 @@ __global__ __launch_bounds__(256) void splitk_reduce_stats_kernel(const float* _
 //   halo_splitk       EOD_HALO_SPLITK=0        3x3 convs on maps with fewer than two workgroups per CU unsplit in K (64-column tiles instead)
 //   first             EOD_FIRST=0              the fp32x3 first conv (tap-major weights) on the generic kernel instead of conv_first_x3_kernel
 //   head_tpw          EOD_HEAD_TPW=n           pixel tiles per workgroup of conv_head_kernel's chunk stream (0: chosen per launch = the default)
+//   s2_halo           EOD_S2_HALO=0            3x3 / stride-2 convs on the generic kernel instead of conv_s2_halo_kernel
 // (Round 2's EOD_IGEMM_CFG / EOD_MFMA_SHAPE / EOD_HALO_SPLIT_N / EOD_CONV_PARITY arms were measured slower and are gone: the fp16
 // products run on v_mfma_f32_16x16x32_f16, 384-column convs as 256 + 128, zero-insertion convs as four parity-class launches.)
-enum { OPT_SKIP_FUSE, OPT_HEAD, OPT_HALO_BN256, OPT_GN_FUSE_MAX_COUT, OPT_HALO_TPW, OPT_HALO_SPLITK, OPT_FIRST, OPT_HEAD_TPW, OPT_COUNT };
-static const char* const g_opt_name[OPT_COUNT] = {"skip_fuse", "head", "halo_bn256", "gn_fuse_max_cout", "halo_tpw", "halo_splitk", "first", "head_tpw"};
+enum { OPT_SKIP_FUSE, OPT_HEAD, OPT_HALO_BN256, OPT_GN_FUSE_MAX_COUT, OPT_HALO_TPW, OPT_HALO_SPLITK, OPT_FIRST, OPT_HEAD_TPW, OPT_S2_HALO, OPT_COUNT };
+static const char* const g_opt_name[OPT_COUNT] = {"skip_fuse", "head", "halo_bn256", "gn_fuse_max_cout", "halo_tpw", "halo_splitk", "first", "head_tpw",
+                                                  "s2_halo"};
 static const char* const g_opt_env[OPT_COUNT] = {"EOD_SKIP_FUSE", "EOD_HEAD", "EOD_HALO_BN256", "EOD_GN_FUSE_MAX_COUT", "EOD_HALO_TPW", "EOD_HALO_SPLITK",
-                                                 "EOD_FIRST", "EOD_HEAD_TPW"};
-static int g_opt[OPT_COUNT] = {1, 1, 1, -1, 1, 1, 1, 0};
+                                                 "EOD_FIRST", "EOD_HEAD_TPW", "EOD_S2_HALO"};
+static int g_opt[OPT_COUNT] = {1, 1, 1, -1, 1, 1, 1, 0, 1};
 static bool g_opt_init = false;
 static int opt(int k) {
     if (!g_opt_init) {
@@ -2939,6 +3226,17 @@ static int conv_up4_bwd(const eod_conv_desc* d, void* stream) {
     p.Hd = d->Ho; p.Wd = d->Wo; p.HWd = d->Ho * d->Wo;
     p.M = (long long)d->N * d->Ho * d->Wo; p.Ncols = d->Cout; p.taps = 9; p.alpha = d->alpha; p.nb1 = 1; p.tapmajor_log2 = -1;
     return launch_up4<half_t, false, true>(p, (hipStream_t)stream);
+}
+// 3x3 / stride 2 / pad 1 on conv_s2_halo_kernel (EOD_S2_HALO=0: the generic kernel, A/B): output maps that tile into 8 x 16 patches,
+// one source, 128-column tiles.  Only where the generic kernel runs unsplit in K, so both arms have the same workspace (none) and the
+// same statistics slots (8 x 16 tiles = the generic kernel's 128-row tiles, two wave rows each): the switch never changes a plan's
+// buffers.  (Odd input maps are covered: the plane positions outside the map are masked like the zero padding.)
+static int conv_splitk(const eod_conv_desc* d, int Ho, int Wo, bool halo);
+static bool conv_s2_halo_ok(const eod_conv_desc* d, int Ho, int Wo) {
+    const bool store_ok = d->dtype == EOD_F16 || (d->dtype == EOD_F32 && d->w_split);
+    return opt(OPT_S2_HALO) != 0 && d->ksize == 3 && d->stride == 2 && d->pad == 1 && !d->pad_tl && !d->upsample && d->C1 == 0 && !d->x2 &&
+           d->Cout > 64 && d->Cout % 8 == 0 && d->C0 % 8 == 0 && Ho % 8 == 0 && Wo % 16 == 0 && !d->out_nchw_f32 && !d->w_tapmajor &&
+           !d->gn_scale_shift && !d->skip_x && !d->x_presplit && !d->y_presplit_bound && store_ok && conv_splitk(d, Ho, Wo, false) <= 1;
 }
 // the UNet's output head on conv_head_kernel (EOD_HEAD=0: the 32-column halo instance, A/B)
 // the fp32x3 first conv (thin input, tap-major split weights) on conv_first_x3_kernel: 8 x 16 pixel tiles, 128-column workgroups
@@ -3196,6 +3494,7 @@ extern "C" int eod_conv2d_igemm(const eod_conv_desc* d, void* stream) {
         return d->dtype == EOD_F16 ? launch_up4<half_t, false>(p, st) : launch_up4<float, true>(p, st);
     }
     if (conv_first_ok(d, Ho, Wo)) return d->C0 == 4 ? launch_first<4>(p, st) : launch_first<8>(p, st);
+    if (conv_s2_halo_ok(d, Ho, Wo)) return d->dtype == EOD_F16 ? launch_s2<half_t, false>(p, st) : launch_s2<float, true>(p, st);
     if (conv_head_ok(d, halo_ok)) {  // output head: GroupNorm + SiLU fused, <= 16 channels, NCHW fp32 (conv_head_kernel)
         p.gn_ss = d->gn_scale_shift;
         p.gn_silu = d->gn_silu;

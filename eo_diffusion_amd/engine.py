@@ -650,11 +650,15 @@ class Program:
                     and self.L.eod_get_option(b"head") != 0  # mirrors conv_head_ok()
                 first = geo and bool(d.w_tapmajor) and bool(d.w_split) and d.Wo % 16 == 0 and d.Cout > 64 and d.C0 in (4, 8) and not d.out_nchw_f32 \
                     and self.L.eod_get_option(b"first") != 0  # mirrors conv_first_ok()
+                s2 = d.ksize == 3 and d.stride == 2 and d.pad == 1 and not d.pad_tl and not d.upsample and d.C1 == 0 and d.Cout > 64 \
+                    and d.Cout % 8 == 0 and d.Ho % 8 == 0 and d.Wo % 16 == 0 and not d.out_nchw_f32 and not d.w_tapmajor and not d.gn_scale_shift \
+                    and not d.skip_x and not d.x_presplit and not d.y_presplit_bound and self.precision != "fp32" and not d.workspace \
+                    and self.L.eod_get_option(b"s2_halo") != 0  # mirrors conv_s2_halo_ok() (no workspace: the generic kernel would run unsplit)
                 up4 = d.upsample == 3  # parity-class form of the nearest-2x conv: the algorithm's 9 taps are executed as 4 (pre-summed)
                 out.append(dict(kind="conv", flops=fl, bytes=by, exec_flops=fl * (4.0 / 9.0 if up4 else 1.0),
                                 kernel="conv_up4_halo_kernel" if up4 else "conv3x3_halo_kernel" if halo else
                                        "conv_head_kernel" if headk else "conv3x3_halo_kernel<BN=32>" if head else
-                                       "conv_first_x3_kernel" if first else "igemm_kernel",
+                                       "conv_first_x3_kernel" if first else "conv_s2_halo_kernel" if s2 else "igemm_kernel",
                                 label=f"conv{d.ksize}x{d.ksize}s{d.stride}{'u4' if up4 else 'u' if d.upsample else ''} {d.H}x{d.W} {cin}->{d.Cout}"
                                       + (f" +skip1x1 {sc}" if sc else "")))
             elif k == OP_GEMM:

@@ -8,9 +8,11 @@ import torch
 import torch.nn.functional as F
 
 from eo_diffusion_amd.engine import Program
+from tests import ref64
 from tests.gpu_util import DEV, TOL, run_program
 from tests.helpers import rel_l2
 from tests.synth import synth_input
+from tests.test_gpu_train_kernels import GATE, worst_row
 
 pytestmark = pytest.mark.gpu
 
@@ -810,59 +812,60 @@ def test_attention_forward_natural_layout_exact_fp32(T, heads, d, new_order, mag
 @pytest.mark.parametrize("N,H,W,Cx,Cout,ups", [(2, 16, 64, 40, 24, False), (1, 32, 32, 136, 128, False), (3, 16, 16, 8, 200, False),
                                                (1, 8, 128, 64, 64, False), (2, 16, 32, 24, 40, True), (1, 8, 8, 16, 16, True)])
 def test_conv3x3_backward_weights_kernel(N, H, W, Cx, Cout, ups):
-    """eod_conv3x3_wgrad (pixel-major staging + transposed LDS operand reads) + eod_wgrad_reduce vs torch's conv2d weight
-    gradient: 64- / 32- / 16-wide strips, channel counts that are not tile multiples, the nearest-2x input variant, several splits"""
+    """eod_conv3x3_wgrad (pixel-major staging + transposed LDS operand reads) + eod_wgrad_reduce vs the float64 per-tap reference
+    (tests/ref64.py): 64- / 32- / 16-wide strips, channel counts that are not tile multiples, the nearest-2x input variant, several
+    splits up to the trainer's 170 (more splits than strips: the tail splits are empty and must write zero tiles)"""
     from eo_diffusion_amd import _lib
     from eo_diffusion_amd.engine import current_stream_ptr
     L = _lib.lib()
     Ho, Wo = (2 * H, 2 * W) if ups else (H, W)
     x = synth_input(f"wx{N}{H}{W}{Cx}", (N, Cx, H, W), 11).half()
     dy = synth_input(f"wy{N}{H}{W}{Cout}", (N, Cout, Ho, Wo), 12, scale=0.5).half()
-    xin = F.interpolate(x.float(), scale_factor=2, mode="nearest") if ups else x.float()
-    ref = torch.nn.grad.conv2d_weight(xin, (Cout, Cx, 3, 3), dy.float(), padding=1)
     xd = x.permute(0, 2, 3, 1).contiguous().to(DEV)
     dyd = dy.permute(0, 2, 3, 1).contiguous().to(DEV)
+    ref = ref64.conv3x3_weight_grad(dyd, xd, upsample=ups)
     st = current_stream_ptr(torch.device(DEV))
-    for S in (1, 5):
-        partial = torch.full((S, 9, Cout, Cx), 7.0, dtype=torch.float32, device=DEV)
-        dw = torch.zeros((Cout, Cx, 3, 3), dtype=torch.float32, device=DEV)
+    for S in (1, 5, 170):
+        partial = torch.full((S, 9, Cout, Cx), float("nan"), dtype=torch.float32, device=DEV)
+        dw = torch.full((Cout, Cx, 3, 3), float("nan"), dtype=torch.float32, device=DEV)
         _lib.check(L.eod_conv3x3_wgrad(dyd.data_ptr(), xd.data_ptr(), _lib.EOD_F16, N, H, W, Cx, Ho, Wo, Cout, Cout, int(ups), partial.data_ptr(), Cx, S, st),
                    "conv3x3_wgrad")
         _lib.check(L.eod_wgrad_reduce(partial.data_ptr(), S, 3, Cout, Cx, Cx, 0, Cx, 1.0, dw.data_ptr(), st), "wgrad_reduce")
         torch.cuda.synchronize()
-        assert rel_l2(dw.cpu(), ref) < 2e-3, (S, rel_l2(dw.cpu(), ref))
+        assert rel_l2(dw, ref) < GATE["wgrad"] and worst_row(dw, ref) < GATE["wgrad_row"], (S, rel_l2(dw, ref), worst_row(dw, ref))
 
 
 @pytest.mark.parametrize("N,H,W,Cx,Cy,Cout", [(3, 5, 7, 40, 48, 40), (2, 16, 16, 136, 128, 128), (1, 32, 32, 8, 200, 200), (2, 8, 8, 264, 16, 16)])
 def test_conv1x1_backward_weights_kernel(N, H, W, Cx, Cy, Cout):
-    """eod_conv1x1_wgrad (gemm_tn_kernel over pixel ranges, operands read pixel-major as stored) + eod_wgrad_reduce vs torch's
-    conv2d weight gradient: ragged pixel counts (the last 64-row strip is partial), channel counts that are not tile multiples,
-    Cout < row pitch of dY, split counts that leave trailing splits empty"""
+    """eod_conv1x1_wgrad (gemm_tn_kernel over pixel ranges, operands read pixel-major as stored) + eod_wgrad_reduce vs the float64
+    reference: ragged pixel counts (the last 64-row strip is partial), channel counts that are not tile multiples, Cout < row pitch of
+    dY, split counts up to the trainer's 512 that leave trailing splits empty"""
     from eo_diffusion_amd import _lib
     from eo_diffusion_amd.engine import current_stream_ptr
     L = _lib.lib()
     x = synth_input(f"w1x{N}{H}{W}{Cx}", (N, Cx, H, W), 13).half()
     dy = synth_input(f"w1y{N}{H}{W}{Cy}", (N, Cy, H, W), 14, scale=0.5).half()
-    ref = torch.nn.grad.conv2d_weight(x.float(), (Cout, Cx, 1, 1), dy.float()[:, :Cout])
     xd = x.permute(0, 2, 3, 1).contiguous().to(DEV)
     dyd = dy.permute(0, 2, 3, 1).contiguous().to(DEV)
+    ref = ref64.conv1x1_weight_grad(dyd[..., :Cout], xd)
     st = current_stream_ptr(torch.device(DEV))
     npix = N * H * W
-    for S in (1, 3, 7):
-        partial = torch.full((S, 1, Cout, Cx), 7.0, dtype=torch.float32, device=DEV)
-        dw = torch.zeros((Cout, Cx, 1, 1), dtype=torch.float32, device=DEV)
+    for S in (1, 3, 7, 512):
+        partial = torch.full((S, 1, Cout, Cx), float("nan"), dtype=torch.float32, device=DEV)
+        dw = torch.full((Cout, Cx), float("nan"), dtype=torch.float32, device=DEV)
         _lib.check(L.eod_conv1x1_wgrad(dyd.data_ptr(), xd.data_ptr(), _lib.EOD_F16, npix, Cx, Cy, Cout, partial.data_ptr(), Cx, S, st), "conv1x1_wgrad")
         _lib.check(L.eod_wgrad_reduce(partial.data_ptr(), S, 1, Cout, Cx, Cx, 0, Cx, 1.0, dw.data_ptr(), st), "wgrad_reduce")
         torch.cuda.synchronize()
-        assert rel_l2(dw.cpu(), ref) < 2e-3, (S, rel_l2(dw.cpu(), ref))
+        assert rel_l2(dw, ref) < GATE["wgrad"] and worst_row(dw, ref) < GATE["wgrad_row"], (S, rel_l2(dw, ref), worst_row(dw, ref))
 
 
 @pytest.mark.parametrize("prec", ["fp32", "fp16"])
 @pytest.mark.parametrize("N,C0,C1,H,W,silu", [(2, 64, 0, 8, 8, True), (2, 104, 88, 7, 5, True), (1, 1280, 0, 6, 5, True), (2, 1536, 1024, 3, 3, False)])
 def test_group_norm_silu_backward_kernels(prec, N, C0, C1, H, W, silu):
     """the GroupNorm32(+SiLU) backward chain (statistics -> eod_gn_mean_rstd -> eod_gn_bwd_partial -> _finalize -> _params / _apply)
-    over one or two concat sources against torch autograd, called through the C ABI; the wide cases need several channel blocks
-    (more than 256 16-byte chunks per pixel) and a group that straddles the concat seam"""
+    over one or two concat sources against the float64 reference (tests/ref64.py), called through the C ABI; the wide cases need
+    several channel blocks (more than 256 16-byte chunks per pixel) and a group that straddles the concat seam; one slab and one
+    slab per pixel"""
     from eo_diffusion_amd import _lib
     from eo_diffusion_amd.engine import current_stream_ptr
     L = _lib.lib()
@@ -872,41 +875,37 @@ def test_group_norm_silu_backward_kernels(prec, N, C0, C1, H, W, silu):
     dy = synth_input(f"gby{N}{Ct}{H}", (N, Ct, H, W), 52).to(td).float()
     gam = 1.0 + 0.2 * synth_input("gbg", (Ct,), 53)
     bet = 0.1 * synth_input("gbb", (Ct,), 53)
-    xr = x.clone().requires_grad_(True)
-    gr, br = gam.clone().requires_grad_(True), bet.clone().requires_grad_(True)
-    y = F.group_norm(xr, G, gr, br, eps=1e-5)
-    if silu:
-        y = F.silu(y)
-    y.backward(dy)
+    flat = lambda t4: t4.permute(0, 2, 3, 1).reshape(N, HW, Ct)
+    rdx, rgam, rbet, _ = ref64.group_norm_backward(flat(x), flat(dy), gam, bet, G, 1e-5, silu_out=silu)
     st = current_stream_ptr(torch.device(DEV))
     nhwc = lambda t4: t4.permute(0, 2, 3, 1).contiguous().to(td).to(DEV)
     srcs = [(nhwc(x[:, :C0]), C0, 0)] + ([(nhwc(x[:, C0:]), C1, C0)] if C1 else [])
     dyd = nhwc(dy)
-    P = max(1, min(256, HW // 64))
-    f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=DEV)
-    parts = [f32(N, P, c, 2) for _, c, _ in srcs]
-    for (xs, c, _), pt in zip(srcs, parts):
-        _lib.check(L.eod_gn_partial(xs.data_ptr(), dt, N, HW, c, pt.data_ptr(), P, c, 0, st), "gn_partial")
-    p1 = (parts[1].data_ptr(), P, C1) if C1 else (0, 0, 0)
-    ss, mr = f32(N, Ct, 2), f32(N, G, 2)
-    gd, bd = gam.to(DEV), bet.to(DEV)
-    _lib.check(L.eod_gn_finalize(parts[0].data_ptr(), P, C0, p1[0], p1[1], p1[2], N, HW, G, 1e-5, gd.data_ptr(), bd.data_ptr(), 0, 0, ss.data_ptr(), 0, 0, st), "gn_finalize")
-    _lib.check(L.eod_gn_mean_rstd(parts[0].data_ptr(), P, C0, p1[0], p1[1], p1[2], N, HW, G, 1e-5, mr.data_ptr(), st), "gn_mean_rstd")
-    part, coef, gb = f32(N, P, Ct, 2), f32(N, Ct, 3), f32(N, Ct, 2)
-    for xs, c, off in srcs:
-        _lib.check(L.eod_gn_bwd_partial(xs.data_ptr(), dyd.data_ptr(), ss.data_ptr(), dt, N, HW, c, part.data_ptr(), P, Ct, off, int(silu), st), "gn_bwd_partial")
-    _lib.check(L.eod_gn_bwd_finalize(part.data_ptr(), P, Ct, N, HW, G, mr.data_ptr(), gd.data_ptr(), bd.data_ptr(), 0, 0, 0, 0, coef.data_ptr(), gb.data_ptr(), st), "gn_bwd_finalize")
-    dgam, dbet = f32(Ct), f32(Ct)
-    _lib.check(L.eod_gn_bwd_params(gb.data_ptr(), N, Ct, 1.0, dgam.data_ptr(), dbet.data_ptr(), st), "gn_bwd_params")
-    dxs = []
-    for xs, c, off in srcs:
-        dx = torch.empty_like(xs)
-        _lib.check(L.eod_gn_bwd_apply(xs.data_ptr(), dyd.data_ptr(), ss.data_ptr(), coef.data_ptr(), 0, dt, N, HW, c, Ct, off, int(silu), dx.data_ptr(), 0, st), "gn_bwd_apply")
-        dxs.append(dx.float().cpu().permute(0, 3, 1, 2))
-    torch.cuda.synchronize()
-    tol = 2e-5 if prec == "fp32" else 3e-3
-    assert rel_l2(torch.cat(dxs, 1), xr.grad) < tol
-    assert rel_l2(dgam.cpu(), gr.grad) < tol and rel_l2(dbet.cpu(), br.grad) < tol
+    f32 = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float32, device=DEV)
+    for P in (1, min(256, HW)):
+        parts = [f32(N, P, c, 2) for _, c, _ in srcs]
+        for (xs, c, _), pt in zip(srcs, parts):
+            _lib.check(L.eod_gn_partial(xs.data_ptr(), dt, N, HW, c, pt.data_ptr(), P, c, 0, st), "gn_partial")
+        p1 = (parts[1].data_ptr(), P, C1) if C1 else (0, 0, 0)
+        ss, mr = f32(N, Ct, 2), f32(N, G, 2)
+        gd, bd = gam.to(DEV), bet.to(DEV)
+        _lib.check(L.eod_gn_finalize(parts[0].data_ptr(), P, C0, p1[0], p1[1], p1[2], N, HW, G, 1e-5, gd.data_ptr(), bd.data_ptr(), 0, 0, ss.data_ptr(), 0, 0, st), "gn_finalize")
+        _lib.check(L.eod_gn_mean_rstd(parts[0].data_ptr(), P, C0, p1[0], p1[1], p1[2], N, HW, G, 1e-5, mr.data_ptr(), st), "gn_mean_rstd")
+        part, coef, gb = f32(N, P, Ct, 2), f32(N, Ct, 3), f32(N, Ct, 2)
+        for xs, c, off in srcs:
+            _lib.check(L.eod_gn_bwd_partial(xs.data_ptr(), dyd.data_ptr(), ss.data_ptr(), dt, N, HW, c, part.data_ptr(), P, Ct, off, int(silu), st), "gn_bwd_partial")
+        _lib.check(L.eod_gn_bwd_finalize(part.data_ptr(), P, Ct, N, HW, G, mr.data_ptr(), gd.data_ptr(), bd.data_ptr(), 0, 0, 0, 0, coef.data_ptr(), gb.data_ptr(), st), "gn_bwd_finalize")
+        dgam, dbet = f32(Ct), f32(Ct)
+        _lib.check(L.eod_gn_bwd_params(gb.data_ptr(), N, Ct, 1.0, dgam.data_ptr(), dbet.data_ptr(), st), "gn_bwd_params")
+        dxs = []
+        for xs, c, off in srcs:
+            dx = torch.full_like(xs, float("nan"))
+            _lib.check(L.eod_gn_bwd_apply(xs.data_ptr(), dyd.data_ptr(), ss.data_ptr(), coef.data_ptr(), 0, dt, N, HW, c, Ct, off, int(silu), dx.data_ptr(), 0, st), "gn_bwd_apply")
+            dxs.append(dx.float().cpu().reshape(N, HW, c))
+        torch.cuda.synchronize()
+        tol = GATE["gn_dx_f32"] if prec == "fp32" else GATE["gn_dx_f16"]
+        assert rel_l2(torch.cat(dxs, -1), rdx) < tol, (P, rel_l2(torch.cat(dxs, -1), rdx))
+        assert rel_l2(dgam.cpu(), rgam) < GATE["gn_params"] and rel_l2(dbet.cpu(), rbet) < GATE["gn_params"], (P, rel_l2(dgam.cpu(), rgam), rel_l2(dbet.cpu(), rbet))
 
 
 @pytest.mark.parametrize("case", [(2, 128, 8, 16, 128, False), (1, 96, 16, 32, 192, True), (3, 72, 24, 16, 256, False), (1, 640, 16, 16, 160, True)])
@@ -947,47 +946,48 @@ def test_conv_nearest_upsample_parity_class_backward_data_vs_autograd(case):
 @pytest.mark.parametrize("N,H,W,Cx,Cout", [(2, 8, 64, 40, 24), (1, 16, 32, 136, 128), (3, 8, 16, 8, 200), (1, 4, 128, 64, 64)])
 def test_conv3x3_backward_weights_parity_class_form(N, H, W, Cx, Cout):
     """eod_conv3x3_wgrad(ups = 2) + eod_wgrad_reduce(ksize 4) + eod_wgrad_up4_map: the weight gradient of a 3x3 conv over the nearest-2x
-    upsampling of X from the 16 class / tap correlations of the stride-2 views of dY (4/9 of the MACs of the nine-tap form) vs torch"""
+    upsampling of X from the 16 class / tap correlations of the stride-2 views of dY (4/9 of the MACs of the nine-tap form) vs the
+    float64 reference"""
     from eo_diffusion_amd import _lib
     from eo_diffusion_amd.engine import current_stream_ptr
     L = _lib.lib()
     x = synth_input(f"wcx{N}{H}{W}{Cx}", (N, Cx, H, W), 15).half()
     dy = synth_input(f"wcy{N}{H}{W}{Cout}", (N, Cout, 2 * H, 2 * W), 16, scale=0.5).half()
-    ref = torch.nn.grad.conv2d_weight(F.interpolate(x.float(), scale_factor=2, mode="nearest"), (Cout, Cx, 3, 3), dy.float(), padding=1)
     xd = x.permute(0, 2, 3, 1).contiguous().to(DEV)
     dyd = dy.permute(0, 2, 3, 1).contiguous().to(DEV)
+    ref = ref64.conv3x3_weight_grad(dyd, xd, upsample=True)
     st = current_stream_ptr(torch.device(DEV))
-    for S in (1, 3):
-        partial = torch.full((S, 16, Cout, Cx), 7.0, dtype=torch.float32, device=DEV)
-        t16 = torch.zeros((Cout, Cx, 16), dtype=torch.float32, device=DEV)
-        dw = torch.zeros((Cout, Cx, 3, 3), dtype=torch.float32, device=DEV)
+    for S in (1, 3, 64):  # (64: the trainer's split count of the 8 class / row-tap planes of one 128 x 128 tile)
+        partial = torch.full((S, 16, Cout, Cx), float("nan"), dtype=torch.float32, device=DEV)
+        t16 = torch.full((Cout, Cx, 16), float("nan"), dtype=torch.float32, device=DEV)
+        dw = torch.full((Cout, Cx, 3, 3), float("nan"), dtype=torch.float32, device=DEV)
         _lib.check(L.eod_conv3x3_wgrad(dyd.data_ptr(), xd.data_ptr(), _lib.EOD_F16, N, H, W, Cx, 2 * H, 2 * W, Cout, Cout, 2, partial.data_ptr(), Cx, S, st),
                    "conv3x3_wgrad")
         _lib.check(L.eod_wgrad_reduce(partial.data_ptr(), S, 4, Cout, Cx, Cx, 0, Cx, 1.0, t16.data_ptr(), st), "wgrad_reduce")
         _lib.check(L.eod_wgrad_up4_map(t16.data_ptr(), Cout, Cx, dw.data_ptr(), st), "wgrad_up4_map")
         torch.cuda.synchronize()
-        assert rel_l2(dw.cpu(), ref) < 2e-3, (S, rel_l2(dw.cpu(), ref))
+        assert rel_l2(dw, ref) < GATE["wgrad"] and worst_row(dw, ref) < GATE["wgrad_row"], (S, rel_l2(dw, ref), worst_row(dw, ref))
 
 
 @pytest.mark.parametrize("N,Ho,Wo,Cx,Cout", [(2, 8, 64, 40, 24), (1, 16, 32, 136, 128), (3, 8, 16, 8, 200), (1, 4, 128, 64, 64)])
 def test_conv3x3_backward_weights_stride2(N, Ho, Wo, Cx, Cout):
     """eod_conv3x3_wgrad(ups = 3): weight gradient of a stride-2 / pad-1 3x3 conv (Downsample.op) straight from the NHWC tensors -- X
-    gathered at pixel stride 2 in two column phases -- vs torch's conv2d weight gradient"""
+    gathered at pixel stride 2 in two column phases -- vs the float64 reference"""
     from eo_diffusion_amd import _lib
     from eo_diffusion_amd.engine import current_stream_ptr
     L = _lib.lib()
     H, W = 2 * Ho, 2 * Wo
     x = synth_input(f"w2x{N}{H}{W}{Cx}", (N, Cx, H, W), 17).half()
     dy = synth_input(f"w2y{N}{Ho}{Wo}{Cout}", (N, Cout, Ho, Wo), 18, scale=0.5).half()
-    ref = torch.nn.grad.conv2d_weight(x.float(), (Cout, Cx, 3, 3), dy.float(), stride=2, padding=1)
     xd = x.permute(0, 2, 3, 1).contiguous().to(DEV)
     dyd = dy.permute(0, 2, 3, 1).contiguous().to(DEV)
+    ref = ref64.conv3x3_weight_grad(dyd, xd, stride=2)
     st = current_stream_ptr(torch.device(DEV))
-    for S in (1, 3):
-        partial = torch.full((S, 9, Cout, Cx), 7.0, dtype=torch.float32, device=DEV)
-        dw = torch.zeros((Cout, Cx, 3, 3), dtype=torch.float32, device=DEV)
+    for S in (1, 3, 85):  # (85: the trainer's split count of the 6 (row tap, column phase) planes of one 128 x 128 tile)
+        partial = torch.full((S, 9, Cout, Cx), float("nan"), dtype=torch.float32, device=DEV)
+        dw = torch.full((Cout, Cx, 3, 3), float("nan"), dtype=torch.float32, device=DEV)
         _lib.check(L.eod_conv3x3_wgrad(dyd.data_ptr(), xd.data_ptr(), _lib.EOD_F16, N, H, W, Cx, Ho, Wo, Cout, Cout, 3, partial.data_ptr(), Cx, S, st),
                    "conv3x3_wgrad")
         _lib.check(L.eod_wgrad_reduce(partial.data_ptr(), S, 3, Cout, Cx, Cx, 0, Cx, 1.0, dw.data_ptr(), st), "wgrad_reduce")
         torch.cuda.synchronize()
-        assert rel_l2(dw.cpu(), ref) < 2e-3, (S, rel_l2(dw.cpu(), ref))
+        assert rel_l2(dw, ref) < GATE["wgrad"] and worst_row(dw, ref) < GATE["wgrad_row"], (S, rel_l2(dw, ref), worst_row(dw, ref))

@@ -1,0 +1,193 @@
+"""CPU: the float64 references of tests/ref64.py against torch autograd in float64 (conv2d weight gradients, F.group_norm, nn.Linear,
+nn.Embedding, nn.MSELoss) at small shapes, so that the GPU gates of tests/test_gpu_train_kernels.py rest on references that have been
+tested themselves."""
+import math
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from tests import ref64
+
+D = torch.float64
+
+
+def _g(seed):
+    return torch.Generator().manual_seed(seed)
+
+
+def _randn(shape, seed, scale=1.0):
+    return scale * torch.randn(shape, generator=_g(seed), dtype=D)
+
+
+def _nhwc(t):
+    return t.permute(0, 2, 3, 1)
+
+
+def _close(a, b, tol=1e-12):
+    a, b = a.to(D), b.to(D)
+    assert a.shape == b.shape, (a.shape, b.shape)
+    err = float((a - b).norm() / b.norm().clamp_min(1e-300))
+    assert err < tol, err
+
+
+@pytest.mark.parametrize("N,Cin,H,W,Cout,mode", [(2, 5, 6, 7, 4, "plain"), (1, 3, 4, 5, 6, "up"), (2, 4, 8, 6, 3, "s2"), (3, 2, 1, 1, 2, "plain"),
+                                                 (1, 2, 2, 2, 3, "up"), (1, 3, 2, 4, 2, "s2")])
+def test_conv3x3_weight_grad_matches_autograd(N, Cin, H, W, Cout, mode):
+    x = _randn((N, Cin, H, W), 1)
+    xin = F.interpolate(x, scale_factor=2, mode="nearest") if mode == "up" else x
+    stride = 2 if mode == "s2" else 1
+    Ho, Wo = (xin.shape[2] - 1) // stride + 1, (xin.shape[3] - 1) // stride + 1
+    dy = _randn((N, Cout, Ho, Wo), 2)
+    ref = torch.nn.grad.conv2d_weight(xin, (Cout, Cin, 3, 3), dy, stride=stride, padding=1)
+    got = ref64.conv3x3_weight_grad(_nhwc(dy), _nhwc(x), upsample=(mode == "up"), stride=stride)
+    _close(got, ref)
+
+
+def test_conv1x1_weight_grad_matches_autograd():
+    x, dy = _randn((2, 6, 5, 3), 3), _randn((2, 4, 5, 3), 4)
+    ref = torch.nn.grad.conv2d_weight(x, (4, 6, 1, 1), dy)[:, :, 0, 0]
+    _close(ref64.conv1x1_weight_grad(_nhwc(dy), _nhwc(x)), ref)
+
+
+@pytest.mark.parametrize("N,C,H,W,groups", [(2, 8, 3, 5, 4), (1, 12, 4, 4, 3), (3, 6, 1, 2, 2)])
+@pytest.mark.parametrize("silu", [False, True])
+@pytest.mark.parametrize("film", [False, True])
+def test_group_norm_backward_matches_autograd(N, C, H, W, groups, silu, film):
+    eps = 1e-5
+    x = (_randn((N, C, H, W), 5, 1.5) + 0.3).requires_grad_(True)
+    gam = (1.0 + 0.2 * _randn((C,), 6)).requires_grad_(True)
+    bet = (0.1 * _randn((C,), 7)).requires_grad_(True)
+    s = (0.3 * _randn((N, C), 8)).requires_grad_(True)
+    t = (0.2 * _randn((N, C), 9)).requires_grad_(True)
+    dy = _randn((N, C, H, W), 10)
+    y = F.group_norm(x, groups, gam, bet, eps=eps)
+    if film:
+        y = y * (1 + s[:, :, None, None]) + t[:, :, None, None]
+    if silu:
+        y = F.silu(y)
+    y.backward(dy)
+    flat = lambda v: v.detach().permute(0, 2, 3, 1).reshape(N, H * W, C)
+    fl = (s.detach(), t.detach()) if film else None
+    fwd = ref64.group_norm_forward(flat(x), gam.detach(), bet.detach(), groups, eps, silu_out=silu, film=fl)
+    _close(fwd, flat(y))
+    dx, dgam, dbet, dfilm = ref64.group_norm_backward(flat(x), flat(dy), gam.detach(), bet.detach(), groups, eps, silu_out=silu, film=fl)
+    _close(dx, flat(x.grad), 1e-11)
+    _close(dgam, gam.grad)
+    _close(dbet, bet.grad)
+    if film:
+        _close(dfilm, torch.cat([s.grad, t.grad], 1))
+    else:
+        assert dfilm is None
+    ss = ref64.group_norm_scale_shift(flat(x), gam.detach(), bet.detach(), groups, eps, film=fl)
+    pre = flat(x) * ss[:, None, :, 0] + ss[:, None, :, 1]
+    _close(ref64.silu(pre) if silu else pre, flat(y))
+
+
+def test_channel_sums():
+    g = _randn((3, 7, 5), 11)
+    dbias, demb = ref64.channel_sums(g, 0.25)
+    _close(dbias, 0.25 * g.sum((0, 1)))
+    _close(demb, g.sum(1))
+
+
+@pytest.mark.parametrize("act_in", [0, 1, 2])
+@pytest.mark.parametrize("with_pre", [False, True])
+def test_linear_backward_matches_autograd(act_in, with_pre):
+    N, K, J, scale = 3, 7, 5, 0.125
+    freqs = torch.exp(-math.log(10000.0) * torch.arange(K // 2, dtype=torch.float32) / (K // 2))
+    t = torch.tensor([0, 17, 999])
+    inp = ref64.sinusoid(t, freqs, K) if act_in == 2 else _randn((N, K), 12)
+    pre = _randn((N, K), 13) if with_pre else None
+    lin = torch.nn.Linear(K, J).double()
+    xin = inp.clone().requires_grad_(True)
+    out = lin(F.silu(xin) if act_in == 1 else xin)
+    dout = _randn((N, J), 14)
+    out.backward(dout)
+    dW, db, din = ref64.linear_backward(dout, inp, lin.weight.detach(), act_in=act_in, scale=scale, pre=pre)
+    _close(dW, scale * lin.weight.grad)
+    _close(db, scale * lin.bias.grad)
+    want = (dout @ lin.weight.detach()) * (ref64.dsilu(pre) if with_pre else 1.0)
+    _close(din, want)
+    if not with_pre and act_in == 0:
+        _close(din, xin.grad)
+    if with_pre:  # din * SiLU'(pre) is the gradient w.r.t. pre of a layer whose input was SiLU(pre)
+        p = pre.clone().requires_grad_(True)
+        (lin(F.silu(p)) * dout).sum().backward()
+        _close(din, p.grad)
+
+
+def test_sinusoid_odd_width_and_temb_pre1():
+    t = torch.tensor([3, 500])
+    freqs = torch.tensor([1.0, 0.1, 0.01], dtype=torch.float32)
+    s = ref64.sinusoid(t, freqs, 7)
+    assert s.shape == (2, 7) and bool((s[:, 6] == 0).all())
+    arg = (t.float()[:, None] * freqs[None, :]).double()
+    _close(s[:, :3], torch.cos(arg))
+    _close(s[:, 3:6], torch.sin(arg))
+    w1, b1 = _randn((4, 7), 15), _randn((4,), 16)
+    _close(ref64.temb_pre1(t, freqs, w1, b1), torch.nn.functional.linear(s, w1, b1))
+
+
+def test_embedding_backward_matches_autograd():
+    emb = torch.nn.Embedding(6, 4).double()
+    y = torch.tensor([2, 0, 2, 5, 2])
+    dout = _randn((5, 4), 17)
+    emb(y).backward(dout)
+    got = ref64.embedding_backward(dout, y, 6, 0.5)
+    _close(got, 0.5 * emb.weight.grad)
+    assert bool((got[[1, 3, 4]] == 0).all())
+
+
+@pytest.mark.parametrize("stride,pad,dy,dx,ups,row_pad,extra", [(1, 1, 0, 2, 0, 1, 8), (2, 1, 2, 0, 0, 0, 0), (1, 1, 1, 1, 1, 0, 16), (1, 0, 0, 0, 0, 0, 4)])
+def test_transpose_gather_by_loops(stride, pad, dy, dx, ups, row_pad, extra):
+    N, H, W, C = 2, 3, 4, 3
+    src = torch.arange(1, N * H * W * C + 1, dtype=torch.float32).reshape(N, H, W, C)
+    He, We = (2 * H, 2 * W) if ups else (H, W)
+    Ho, Wo = (He + 2 * pad - 3) // stride + 1 if pad else He, (We + 2 * pad - 3) // stride + 1 if pad else We
+    K = N * (Ho + 2 * row_pad) * Wo
+    got = ref64.transpose_gather(src, K + extra, Ho, Wo, stride, pad, dy, dx, ups, row_pad)
+    want = torch.zeros((C, K + extra))
+    for n in range(N):
+        for ho in range(Ho):
+            for wo in range(Wo):
+                hi, wi = ho * stride - pad + dy, wo * stride - pad + dx
+                if 0 <= hi < He and 0 <= wi < We:
+                    k = (n * (Ho + 2 * row_pad) + ho + row_pad) * Wo + wo
+                    want[:, k] = src[n, hi // 2 if ups else hi, wi // 2 if ups else wi]
+    assert torch.equal(got, want)
+
+
+def test_rowsum_segments():
+    x = _randn((3, 20), 18)
+    got = ref64.rowsum_segments(x, 3, 6, 2.0)
+    _close(got, 2.0 * torch.stack([x[:, 6 * s:6 * s + 6].sum(1) for s in range(3)]))
+
+
+def test_gemm_tn_and_gemm_nt_on_strided_buffers():
+    M, N, K, nb0, nb1 = 3, 4, 5, 2, 3
+    a, b = _randn((400,), 19), _randn((400,), 20)
+    lda, ldb, sa, sb = 8, 9, (120, 11), (130, 7)
+    got = ref64.gemm_tn(a, b, M=M, N=N, K=K, lda=lda, ldb=ldb, alpha=0.5, nb0=nb0, nb1=nb1, sa=sa, sb=sb, a_off=3, b_off=1)
+    for b0 in range(nb0):
+        for b1 in range(nb1):
+            A = torch.stack([a[3 + b0 * sa[0] + b1 * sa[1] + k * lda:][:M] for k in range(K)])   # [K][M]
+            B = torch.stack([b[1 + b0 * sb[0] + b1 * sb[1] + k * ldb:][:N] for k in range(K)])
+            _close(got[b0, b1], 0.5 * A.t() @ B)
+    sa_neg = (120, -10)   # negative inner stride (the dY shifts of the exact-fp32 backward-weights GEMMs)
+    got = ref64.gemm_nt(a, b, M=M, N=N, K=K, lda=lda, ldb=ldb, alpha=2.0, nb0=nb0, nb1=nb1, sa=sa_neg, sb=sb, a_off=40, b_off=0)
+    for b0 in range(nb0):
+        for b1 in range(nb1):
+            A = torch.stack([a[40 + b0 * sa_neg[0] + b1 * sa_neg[1] + m * lda:][:K] for m in range(M)])   # [M][K]
+            B = torch.stack([b[b0 * sb[0] + b1 * sb[1] + n * ldb:][:K] for n in range(N)])
+            _close(got[b0, b1], 2.0 * A @ B.t())
+
+
+def test_mse_loss_matches_autograd():
+    p = _randn((5, 7), 21).requires_grad_(True)
+    t = _randn((5, 7), 22)
+    loss = torch.nn.MSELoss()(p, t)
+    loss.backward()
+    l64, d64 = ref64.mse_loss(p.detach(), t)
+    _close(l64, loss.detach())
+    _close(d64, p.grad)

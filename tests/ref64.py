@@ -1,8 +1,9 @@
-"""float64 references of the training-path kernels (csrc/train.hip), in plain torch.
+"""float64 references of the training-path kernels (csrc/train.hip) and of the conv entry point (eod_conv2d_igemm, csrc/igemm.hip),
+in plain torch.
 
 Nothing here imports the library, so the CPU suite can test every reference against torch autograd
 (tests/test_ref64.py) and the GPU suite can gate the kernels on references that have themselves been tested
-(tests/test_gpu_train_kernels.py).  Every function takes tensors on any device, computes in float64 on that
+(tests/test_gpu_train_kernels.py, tests/test_gpu_conv_programs.py).  Every function takes tensors on any device, computes in float64 on that
 device and returns float64.  Activation tensors are NHWC, as the kernels store them ([N][H][W][C], or [N][HW][C]).
 
 The conv references are per-tap float64 matmuls over shifted, strided or upsampled views of the zero-padded
@@ -214,3 +215,167 @@ def mse_loss(pred, target):
     """nn.MSELoss(reduction='mean'): (loss, dLoss/dpred)"""
     d = pred.to(F64) - target.to(F64)
     return d.square().mean(), 2.0 * d / d.numel()
+
+
+# ================================================================================================ eod_conv2d_igemm (include/eodiff.h)
+def zero_insert2x(x):
+    """upsample = 2: z[2i][2j] = x[i][j] on a (2H x 2W) map, zeros elsewhere"""
+    N, H, W, C = x.shape
+    z = torch.zeros((N, 2 * H, 2 * W, C), dtype=x.dtype, device=x.device)
+    z[:, ::2, ::2] = x
+    return z
+
+
+def conv_input(x, x2=None, *, upsample=0, pad_tl=0, gn_scale_shift=None, gn_silu=False):
+    """the A operand of the conv as the kernel sees it, NHWC float64: virtual concat x | x2, input GroupNorm from the {scale, shift}
+    table [N][C0+C1][2] (a = x * scale + shift, optional SiLU), then the virtual upsampling (1 / 3: nearest 2x, 2: zero insertion) and
+    the extra zero row / column on top / left (pad_tl)"""
+    a = x.to(F64) if x2 is None else torch.cat([x.to(F64), x2.to(F64)], -1)
+    if gn_scale_shift is not None:
+        ss = gn_scale_shift.to(F64)
+        a = a * ss[:, None, None, :, 0] + ss[:, None, None, :, 1]
+        if gn_silu:
+            a = silu(a)
+    if upsample in (1, 3):
+        a = upsample2x(a)
+    elif upsample == 2:
+        a = zero_insert2x(a)
+    else:
+        assert upsample == 0, upsample
+    if pad_tl:
+        a = torch.nn.functional.pad(a, (0, 0, 1, 0, 1, 0))
+    return a
+
+
+def _taps(a, w, ksize, stride, pad):
+    """sum over taps of (shifted, strided view of the zero-padded NHWC map a) @ w[:, :, ky, kx]^T"""
+    N, H, W, C = a.shape
+    Ho, Wo = (H + 2 * pad - ksize) // stride + 1, (W + 2 * pad - ksize) // stride + 1
+    ap = torch.nn.functional.pad(a, (0, 0, pad, pad, pad, pad)) if pad else a
+    w = w.reshape(w.shape[0], C, ksize, ksize)
+    y = torch.zeros((N, Ho, Wo, w.shape[0]), dtype=F64, device=a.device)
+    for ky in range(ksize):
+        for kx in range(ksize):
+            v = ap[:, ky:ky + stride * (Ho - 1) + 1:stride, kx:kx + stride * (Wo - 1) + 1:stride, :]
+            y += v @ w[:, :, ky, kx].t()
+    return y
+
+
+def block_sum2x2(g):
+    N, H, W, C = g.shape
+    return g.reshape(N, H // 2, 2, W // 2, 2, C).sum((2, 4))
+
+
+def up4_class_kernels(w_oihw):
+    """the [4 Cout][Cin][3][3] class-kernel tensor of the parity-class form (include/eodiff.h, eod_conv_up4_ok): output pixel
+    (2i + p, 2j + q) of the 3x3 conv over the nearest-2x image reads stored rows {i - 1 + p, i + p} only, with the taps that meet the
+    same stored pixel summed (p = 0: [w0 | w1 + w2], p = 1: [w0 + w1 | w2]; columns alike).  Row block 2p + q holds class (p, q)'s
+    kernel in the tap slots dy' in {p, p + 1}, dx' in {q, q + 1}, zeros elsewhere."""
+    w = w_oihw.to(F64)
+    Cout = w.shape[0]
+    sums = {0: [[0], [1, 2]], 1: [[0, 1], [2]]}
+    wc = torch.zeros((4 * Cout,) + tuple(w.shape[1:]), dtype=F64, device=w.device)
+    for p in (0, 1):
+        for q in (0, 1):
+            for a, rows in enumerate(sums[p]):
+                for b, cols in enumerate(sums[q]):
+                    wc[(2 * p + q) * Cout:(2 * p + q + 1) * Cout, :, p + a, q + b] = w[:, :, rows][:, :, :, cols].sum((2, 3))
+    return wc
+
+
+def space_to_depth2(x):
+    """[N][2H][2W][C] -> [N][H][W][4C], channel (2p + q) C + c of pixel (i, j) = x[2i + p][2j + q][c]"""
+    N, H2, W2, C = x.shape
+    return x.reshape(N, H2 // 2, 2, W2 // 2, 2, C).permute(0, 1, 3, 2, 4, 5).reshape(N, H2 // 2, W2 // 2, 4 * C)
+
+
+def conv_forward(x, x2, w_oihw, *, ksize, stride=1, pad=1, upsample=0, pad_tl=0, gn_scale_shift=None, gn_silu=False, alpha=1.0, bias=None,
+                 cbias=None, cbias_stride=0, res=None, skip_x=None, skip_x2=None, skip_w=None, absolute=False, class_w=None):
+    """y [N][Ho][Wo][Cout] float64 of eod_conv2d_igemm:
+        y = alpha * (sum_{tap, c} A(n, ho*stride - pad + dy, wo*stride - pad + dx, c) * w[co][c][dy][dx] + sum_c skip_w[co][c] * X(n, ho, wo, c))
+            + bias[co] + cbias[n * cbias_stride + co] + res[n][ho][wo][co]
+    with A = conv_input(...) and X = skip_x | skip_x2 at the output resolution (the fused 1x1 skip conv shares the accumulator).
+    upsample = 4 is the backward-data of the nearest-2x conv: x = dY [N][2 Ho][2 Wo][C0], w_oihw = the FORWARD conv's weight
+    [C0][Cout][3][3], y = dX = the 2 x 2 block sum of the transposed conv of dY on the fine grid.
+    class_w (upsample 3 and 4 only): the class-kernel tensor [4 rows][cols][3][3] (up4_class_kernels of the forward weight) AS THE KERNEL
+    GETS IT, e.g. rounded to fp16 after the tap sums: the same function computed class by class from it instead of from w_oihw -- four
+    plain 3x3 convs of the stored map (upsample 3), one 3x3 conv of the 2 x 2 space-to-depth view of dY (upsample 4).
+    absolute = True: every term replaced by its absolute value (conv_abs_bound)."""
+    ab = (lambda t: t.abs()) if absolute else (lambda t: t)
+    w = None if w_oihw is None else ab(w_oihw.to(F64))
+    if class_w is not None:
+        assert upsample in (3, 4) and ksize == 3 and stride == 1 and pad == 1 and not pad_tl and x2 is None and gn_scale_shift is None
+        wc = ab(class_w.to(F64))
+        if upsample == 3:
+            N, H, W, _ = x.shape
+            Cout = wc.shape[0] // 4
+            y = torch.empty((N, 2 * H, 2 * W, Cout), dtype=F64, device=x.device)
+            for p in (0, 1):
+                for q in (0, 1):
+                    y[:, p::2, q::2] = _taps(ab(x.to(F64)), wc[(2 * p + q) * Cout:(2 * p + q + 1) * Cout], 3, 1, 1)
+        else:
+            y = _taps(space_to_depth2(ab(x.to(F64))), wc.flip(2, 3).transpose(0, 1), 3, 1, 1)
+    elif upsample == 4:
+        assert ksize == 3 and stride == 1 and pad == 1 and not pad_tl and x2 is None and gn_scale_shift is None
+        # dfine[i][j][ci] = sum_{ky, kx, co} dY[i + 1 - ky][j + 1 - kx][co] * w[co][ci][ky][kx]: a 3x3 conv with the flipped, transposed weight
+        y = block_sum2x2(_taps(ab(x.to(F64)), w.flip(2, 3).transpose(0, 1), 3, 1, 1))
+    else:
+        a = conv_input(x, x2, upsample=upsample, pad_tl=pad_tl, gn_scale_shift=gn_scale_shift, gn_silu=gn_silu)
+        y = _taps(ab(a), w, ksize, stride, pad)
+    if skip_x is not None:
+        xs = skip_x.to(F64) if skip_x2 is None else torch.cat([skip_x.to(F64), skip_x2.to(F64)], -1)
+        y = y + ab(xs) @ ab(skip_w.to(F64)).reshape(y.shape[-1], -1).t()
+    y = y * abs(alpha) if absolute else y * alpha
+    N, Cout = y.shape[0], y.shape[-1]
+    if bias is not None:
+        y = y + ab(bias.to(F64))
+    if cbias is not None:
+        idx = torch.arange(N, device=y.device)[:, None] * cbias_stride + torch.arange(Cout, device=y.device)[None, :]
+        y = y + ab(cbias.to(F64).flatten()[idx])[:, None, None, :]
+    if res is not None:
+        y = y + ab(res.to(F64))
+    return y
+
+
+def conv_abs_bound(x, x2, w_oihw, **kw):
+    """the sum of conv_forward with every term replaced by its absolute value: sum |a| |w| + |bias| + |cbias| + |res| (+ the skip term
+    likewise).  It scales the element-wise error metric and does not shrink where the true sum cancels."""
+    return conv_forward(x, x2, w_oihw, absolute=True, **kw)
+
+
+def stats_of(y):
+    """[N][C][2] float64: per (image, channel) sum and sum of squares of an NHWC tensor"""
+    y = y.to(F64).flatten(1, -2)
+    return torch.stack([y.sum(1), y.square().sum(1)], -1)
+
+
+AB_KMIN, AB_KMAX, AB_KMIN_ATTN = -113, 60, -48  # csrc/common.h
+
+
+def presplit_scale(bound, kmin=AB_KMIN):
+    """the power-of-two operand scale s_n a bound table [N][32] implies (csrc/common.h): B_n = the row maximum (NaN counts as inf),
+    s_n = 2^k with k = 14 - floor(log2 B_n), clamped to [kmin, 60], so that B_n * s_n lies in [2^14, 2^15).  float64 [N]"""
+    b = bound.float()
+    b = torch.where(b == b, b, torch.full_like(b, float("inf"))).max(1).values.contiguous()
+    eb = (b.view(torch.int32) >> 23) & 0xff
+    k = (141 - eb).clamp(kmin, AB_KMAX)
+    return torch.pow(torch.tensor(2.0, dtype=F64, device=bound.device), k.to(F64))
+
+
+def presplit_encode(x, s):
+    """the pre-split layout: x [N][...][C] (C % 8 == 0), s [N] -> a float32-typed tensor of the same shape whose
+    every 8 channels hold [8 x fp16 hi | 8 x fp16 lo] with hi = fp16(s_n x), lo = fp16(s_n x - hi)"""
+    assert x.shape[-1] % 8 == 0
+    v = x.to(F64) * s.to(F64).reshape((-1,) + (1,) * (x.dim() - 1))
+    hi = v.to(torch.float16)
+    lo = (v - hi.to(F64)).to(torch.float16)
+    shp = x.shape[:-1] + (x.shape[-1] // 8, 8)
+    packed = torch.cat([hi.reshape(shp), lo.reshape(shp)], -1).contiguous()
+    return packed.view(torch.float32).reshape(x.shape)
+
+
+def presplit_decode(p, s):
+    """inverse of presplit_encode: (hi + lo) / s_n in float64"""
+    h = p.contiguous().view(torch.float16).reshape(p.shape[:-1] + (p.shape[-1] // 8, 16)).to(F64)
+    v = (h[..., :8] + h[..., 8:]).reshape(p.shape)
+    return v / s.to(F64).reshape((-1,) + (1,) * (p.dim() - 1))

@@ -191,3 +191,153 @@ def test_mse_loss_matches_autograd():
     l64, d64 = ref64.mse_loss(p.detach(), t)
     _close(l64, loss.detach())
     _close(d64, p.grad)
+
+
+# ================================================================================================ the conv entry point's references
+def _nchw(t):
+    return t.permute(0, 3, 1, 2)
+
+
+def _conv_case(seed, N, H, W, C0, C1, Cout, ksize):
+    x = _randn((N, H, W, C0), seed)
+    x2 = _randn((N, H, W, C1), seed + 1) if C1 else None
+    w = _randn((Cout, C0 + C1, ksize, ksize), seed + 2, 0.3)
+    return x, x2, w
+
+
+def _torch_conv(a_nhwc, w, stride, pad):
+    return _nhwc(F.conv2d(_nchw(a_nhwc), w, stride=stride, padding=pad))
+
+
+@pytest.mark.parametrize("N,H,W,C0,C1,Cout,ksize,stride,pad", [
+    (2, 5, 7, 3, 0, 4, 3, 1, 1), (1, 6, 4, 2, 3, 5, 3, 1, 1), (2, 5, 7, 3, 0, 4, 3, 2, 1), (1, 7, 5, 2, 2, 3, 3, 2, 1), (2, 4, 6, 3, 2, 4, 1, 1, 0),
+    (1, 5, 5, 4, 0, 2, 1, 2, 0), (1, 4, 4, 2, 0, 3, 3, 1, 0), (3, 1, 1, 2, 0, 2, 3, 1, 1)])
+def test_conv_forward_matches_conv2d(N, H, W, C0, C1, Cout, ksize, stride, pad):
+    x, x2, w = _conv_case(20, N, H, W, C0, C1, Cout, ksize)
+    a = x if x2 is None else torch.cat([x, x2], -1)
+    ref = _torch_conv(a, w, stride, pad)
+    _close(ref64.conv_forward(x, x2, w, ksize=ksize, stride=stride, pad=pad), ref)
+    _close(ref64.conv_abs_bound(x, x2, w, ksize=ksize, stride=stride, pad=pad), _torch_conv(a.abs(), w.abs(), stride, pad))
+
+
+@pytest.mark.parametrize("ups", [1, 3])
+@pytest.mark.parametrize("H,W,pad_tl", [(3, 3, 1), (4, 5, 0), (3, 3, 0), (1, 2, 1)])
+def test_conv_forward_nearest_upsampling_and_pad_tl(ups, H, W, pad_tl):
+    x, x2, w = _conv_case(30, 2, H, W, 3, 2, 4, 3)
+    a = F.interpolate(_nchw(torch.cat([x, x2], -1)), scale_factor=2, mode="nearest")
+    if pad_tl:
+        a = F.pad(a, (1, 0, 1, 0))
+    ref = _nhwc(F.conv2d(a, w, padding=1))
+    got = ref64.conv_forward(x, x2, w, ksize=3, pad=1, upsample=ups, pad_tl=pad_tl)
+    assert got.shape[1:3] == (2 * H + pad_tl, 2 * W + pad_tl)  # (3 x 3 -> 7 x 7)
+    _close(got, ref)
+
+
+@pytest.mark.parametrize("H,W", [(3, 4), (5, 5), (8, 6), (7, 9)])
+def test_conv_forward_zero_insertion_is_the_stride2_backward_data(H, W):
+    """upsample = 2 with the flipped, transposed weight = the float64 autograd gradient of the stride-2 conv (even and odd maps: the
+    gradient of an odd map's last row / column lies beyond the zero-inserted grid, so the comparison crops to it)"""
+    Cin, Cout, N = 3, 4, 2
+    xin = _randn((N, Cin, H, W), 40).requires_grad_(True)
+    w = _randn((Cout, Cin, 3, 3), 41, 0.3)
+    y = F.conv2d(xin, w, stride=2, padding=1)
+    dy = _randn(tuple(y.shape), 42)
+    (dx,) = torch.autograd.grad(y, xin, dy)
+    got = ref64.conv_forward(_nhwc(dy), None, w.flip(2, 3).transpose(0, 1), ksize=3, pad=1, upsample=2)
+    Ho, Wo = y.shape[2:]
+    assert got.shape[1:3] == (2 * Ho, 2 * Wo)
+    _close(got[:, :H, :W], _nhwc(dx)[:, :min(H, 2 * Ho), :min(W, 2 * Wo)])
+    z = ref64.zero_insert2x(_nhwc(dy))
+    assert float(z[:, 1::2].abs().max()) == 0 and float(z[:, :, 1::2].abs().max()) == 0 and torch.equal(z[:, ::2, ::2], _nhwc(dy))
+
+
+@pytest.mark.parametrize("H,W", [(2, 3), (4, 4), (1, 1)])
+def test_conv_forward_upsample4_is_the_backward_data_of_the_nearest2x_conv(H, W):
+    Cin, Cout, N = 3, 5, 2
+    xin = _randn((N, Cin, H, W), 50).requires_grad_(True)
+    w = _randn((Cout, Cin, 3, 3), 51, 0.3)
+    y = F.conv2d(F.interpolate(xin, scale_factor=2, mode="nearest"), w, padding=1)
+    dy = _randn(tuple(y.shape), 52)
+    (dx,) = torch.autograd.grad(y, xin, dy)
+    got = ref64.conv_forward(_nhwc(dy), None, w, ksize=3, pad=1, upsample=4)
+    assert got.shape == (N, H, W, Cin)
+    _close(got, _nhwc(dx))
+    bound = ref64.conv_abs_bound(_nhwc(dy), None, w, ksize=3, pad=1, upsample=4)
+    assert bool((bound >= got.abs() * (1 - 1e-12)).all())
+
+
+@pytest.mark.parametrize("silu", [False, True])
+@pytest.mark.parametrize("cbias_stride", [0, 9])
+def test_conv_forward_epilogue_groupnorm_and_fused_skip(silu, cbias_stride):
+    N, H, W, C0, C1, Cout = 3, 4, 5, 3, 2, 4
+    x, x2, w = _conv_case(60, N, H, W, C0, C1, Cout, 3)
+    ss = torch.stack([_randn((N, C0 + C1), 63, 1.3), _randn((N, C0 + C1), 64, 0.5)], -1)  # scales of both signs
+    bias, cbias, res = _randn((Cout,), 65), _randn((N * 9 + Cout,), 66), _randn((N, H, W, Cout), 67)
+    sx, sx2, sw = _randn((N, H, W, 4), 68), _randn((N, H, W, 2), 69), _randn((Cout, 6, 1, 1), 70, 2.0)
+    alpha = -0.75
+    a = torch.cat([x, x2], -1) * ss[:, None, None, :, 0] + ss[:, None, None, :, 1]
+    if silu:
+        a = F.silu(a)
+    cb = torch.stack([cbias[n * cbias_stride:n * cbias_stride + Cout] for n in range(N)])
+    ref = alpha * (_torch_conv(a, w, 1, 1) + _torch_conv(torch.cat([sx, sx2], -1), sw, 1, 0)) + bias + cb[:, None, None, :] + res
+    kw = dict(ksize=3, pad=1, gn_scale_shift=ss, gn_silu=silu, alpha=alpha, bias=bias, cbias=cbias, cbias_stride=cbias_stride, res=res,
+              skip_x=sx, skip_x2=sx2, skip_w=sw)
+    _close(ref64.conv_forward(x, x2, w, **kw), ref)
+    refb = 0.75 * (_torch_conv(a.abs(), w.abs(), 1, 1) + _torch_conv(torch.cat([sx, sx2], -1).abs(), sw.abs(), 1, 0)) + bias.abs() \
+        + cb.abs()[:, None, None, :] + res.abs()
+    _close(ref64.conv_abs_bound(x, x2, w, **kw), refb)
+    _close(ref64.conv_forward(x, None, w[:, :C0], ksize=3, pad=1, skip_x=sx, skip_w=sw[:, :4]),
+           _torch_conv(x, w[:, :C0], 1, 1) + _torch_conv(sx, sw[:, :4], 1, 0))
+
+
+def test_stats_of():
+    y = _randn((3, 4, 5, 6), 80)
+    s = ref64.stats_of(y)
+    _close(s[..., 0], y.sum((1, 2)))
+    _close(s[..., 1], (y * y).sum((1, 2)))
+
+
+def test_presplit_scale_follows_the_bound_table():
+    tab = torch.zeros((6, 32))
+    tab[0, 3], tab[1, 31], tab[2, 0], tab[3, 5], tab[4, 7] = 1.0, 3.999, 2.0 ** 14, 1e-30, float("nan")
+    tab[0, 9] = 0.25  # a smaller entry elsewhere does not matter
+    s = ref64.presplit_scale(tab)
+    assert s.tolist() == [2.0 ** 14, 2.0 ** 13, 1.0, 2.0 ** 60, 2.0 ** -113, 2.0 ** 60]
+    assert ref64.presplit_scale(tab, kmin=ref64.AB_KMIN_ATTN)[4] == 2.0 ** -48
+    for b in (0.7, 1.0, 1.9, 123.4, 5e-7, 3e12):
+        sb = float(ref64.presplit_scale(torch.full((1, 32), b))[0]) * b
+        assert 2 ** 14 <= sb < 2 ** 15 * (1 + 1e-7), (b, sb)
+
+
+def test_presplit_layout_roundtrip():
+    """encode -> decode to 2^-21 relative of the image maximum's scale for every element, 2^-21 relative for elements within 2^10 of it;
+    the layout is [8 x fp16 hi | 8 x fp16 lo] per 8 channels"""
+    N, C = 3, 24
+    x = (_randn((N, 5, 4, C), 90) * torch.tensor([1.0, 2.0 ** 10, 2.0 ** -10], dtype=D).reshape(3, 1, 1, 1)).float()
+    tab = torch.zeros((N, 32))
+    tab[:, 4] = 1.5 * x.abs().amax((1, 2, 3))
+    s = ref64.presplit_scale(tab)
+    p = ref64.presplit_encode(x, s)
+    assert p.dtype == torch.float32 and p.shape == x.shape
+    h = p.view(torch.float16).reshape(N, 5, 4, C // 8, 16)
+    v = (x.double() * s.reshape(3, 1, 1, 1)).reshape(N, 5, 4, C // 8, 8)
+    assert torch.equal(h[..., :8], v.to(torch.float16))
+    assert float(h.abs().max()) < 2 ** 15
+    back = ref64.presplit_decode(p, s)
+    big = x.abs() > x.abs().amax((1, 2, 3), keepdim=True) * 2.0 ** -10
+    assert float(((back - x.double()).abs() / x.double().abs())[big].max()) < 2.0 ** -21
+    assert float(((back - x.double()).abs() / x.abs().amax((1, 2, 3), keepdim=True).double()).max()) < 2.0 ** -21
+
+
+@pytest.mark.parametrize("H,W", [(2, 3), (4, 4), (1, 1)])
+def test_conv_forward_from_class_kernels_is_the_same_function(H, W):
+    """upsample 3 and 4 computed class by class from up4_class_kernels(w) = the nine-tap forms from w itself"""
+    x, _, w = _conv_case(100, 2, H, W, 3, 0, 5, 3)
+    wc = ref64.up4_class_kernels(w)
+    assert wc.shape == (20, 3, 3, 3) and float(wc[:5, :, 2].abs().max()) == 0 and float(wc[15:, :, :, 0].abs().max()) == 0
+    _close(wc[:5, :, 1, 1], w[:, :, 1:, 1:].sum((2, 3)))
+    _close(ref64.conv_forward(x, None, None, ksize=3, pad=1, upsample=3, class_w=wc), ref64.conv_forward(x, None, w, ksize=3, pad=1, upsample=3))
+    dy = _randn((2, 2 * H, 2 * W, 5), 103)
+    _close(ref64.conv_forward(dy, None, None, ksize=3, pad=1, upsample=4, class_w=wc), ref64.conv_forward(dy, None, w, ksize=3, pad=1, upsample=4))
+    s2d = ref64.space_to_depth2(dy)
+    assert torch.equal(s2d[:, :, :, 5:10], dy[:, 0::2, 1::2])

@@ -8,6 +8,7 @@ Deliberate differences: buffers live on the model's device instead o
 (ddim.py:18-22); the masked branch supplies the q_sample noise the reference forgot (ddim.py:147,
 upstream intent ddpm.py:280,1335); the unused second randn_like per step (ddim.py:171) is still drawn
 in rng="torch" mode so that the global generator advances exactly as in the reference.
+`sample_scene` (no counterpart in the reference) runs the same steps on a scene larger than the UNet's image size, tiled.
 """
 import numpy as np
 import torch
@@ -117,6 +118,90 @@ class DDIMSampler(object):
                                               unconditional_guidance_scale=unconditional_guidance_scale,
                                               unconditional_conditioning=unconditional_conditioning,
                                               _noise=None if step_noises is None else step_noises[i])
+            if callback:
+                callback(i)
+            if img_callback:
+                img_callback(pred_x0, i)
+            if index % log_every_t == 0 or index == total_steps - 1:
+                intermediates["x_inter"].append(img)
+                intermediates["pred_x0"].append(pred_x0)
+        return img, intermediates
+
+    @torch.no_grad()
+    def sample_scene(self, S, scene_size, *, overlap=0, tile_batch=16, conditioning=None, mask=None, x0=None, eta=0.0, x_T=None,
+                     temperature=1.0, unconditional_guidance_scale=1.0, unconditional_conditioning=None, step_noises=None,
+                     mix_noises=None, callback=None, img_callback=None, log_every_t=100, verbose=False, progress=True):
+        """DDIM over ONE scene [1, C, H, W] larger than the UNet's image size (see EODiffusion.sampling_scene and
+        eo_diffusion_amd/tiling.py): per step the RePaint mix (mask / x0 scene-sized), the UNet on overlapping tiles in chunks of
+        tile_batch, the blend of the noise estimates, ONE scene-level eod_ddim_step.  Classifier-free guidance runs per chunk through
+        the doubled-batch call of p_sample_ddim and the COMBINED estimate is blended.  conditioning / unconditional_conditioning are
+        scene-sized [1, Cc, H, W] (channel-concatenated inside the UNet) and are cut into the same tiles once.  step_noises /
+        mix_noises ([S, 1, C, H, W]) inject the draws as in ddim_sampling(); otherwise they come from the device generator, scene-sized
+        (the eta-noise only when sigma_t != 0).  With overlap = 0 and injected draws the result equals sample() on the tiles, bit for
+        bit.  Returns (scene, intermediates) like sample()."""
+        from ..tiling import gather_padded, tile_slots, tiled_estimate
+        what = "DDIMSampler.sample_scene"
+        m = self.model
+        device = m.betas.device
+        plan, device = m._scene_args(what, scene_size, overlap, device)
+        C = m.in_channels
+        chunk, _ = tile_slots(plan, tile_batch)
+        if (mask is None) != (x0 is None):
+            raise _lib.EodError(f"{what}: mask and x0 go together (RePaint mix of the known region)")
+        if mask is not None:
+            x0 = m._scene_tensor(what, "x0", x0, C, plan, device)
+            mk = torch.as_tensor(mask)
+            if mk.dim() < 2 or tuple(mk.shape[-2:]) != (plan.H, plan.W):
+                raise _lib.EodError(f"{what}: `mask` must be scene-sized ({plan.H} x {plan.W}), got {tuple(mk.shape)}")
+            mask = m._broadcast_mask(mk.to(device), x0)
+        guided = unconditional_conditioning is not None and unconditional_guidance_scale != 1.0
+        c_tiles = uc_tiles = None
+        if conditioning is not None:
+            c_tiles = gather_padded(m._scene_tensor(what, "conditioning", conditioning, None, plan, device), plan, tile_batch)
+        if guided:
+            if c_tiles is None:
+                raise _lib.EodError(f"{what}: classifier-free guidance needs `conditioning` next to `unconditional_conditioning`")
+            uc_tiles = gather_padded(m._scene_tensor(what, "unconditional_conditioning", unconditional_conditioning, c_tiles.shape[1],
+                                                     plan, device), plan, tile_batch)
+        img = torch.randn((1, C, plan.H, plan.W), device=device) if x_T is None else m._scene_tensor(what, "x_T", x_T, C, plan, device)
+        self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
+        time_range = np.flip(self.ddim_timesteps)
+        total_steps = self.ddim_timesteps.shape[0]
+        intermediates = {"x_inter": [img], "pred_x0": [img]}
+        it = tqdm(time_range, desc="DDIM Sampler (scene)", total=total_steps) if progress else time_range
+
+        def eps(x, lo, ts):
+            c = None if c_tiles is None else c_tiles[lo:lo + chunk]
+            if not guided:
+                return m.model(x, ts, cond=c)
+            e_both = m.model(torch.cat([x] * 2), torch.cat([ts] * 2), cond=torch.cat([uc_tiles[lo:lo + chunk], c]))
+            e_u, e_c = e_both[:chunk], e_both[chunk:]
+            e_t = torch.empty_like(e_c)
+            _lib.check(_lib.lib().eod_cfg_combine(e_u.data_ptr(), e_c.data_ptr(), float(unconditional_guidance_scale), e_t.data_ptr(),
+                                                  e_t.numel(), current_stream_ptr(device)), "eod_cfg_combine")
+            return e_t
+
+        for i, step in enumerate(it):
+            index = total_steps - i - 1
+            if mask is not None:
+                ts1 = torch.full((1,), int(step), device=device, dtype=torch.long)
+                nz = (m._scene_tensor(what, "mix_noises[i]", mix_noises[i], C, plan, device) if mix_noises is not None
+                      else torch.randn_like(x0))
+                img = m._repaint_mix(img, x0, mask, ts1, nz)
+            ts = torch.full((chunk,), int(step), device=device, dtype=torch.long)
+            e_t = tiled_estimate(img, plan, tile_batch, lambda x, lo: eps(x, lo, ts))
+            sigma_t = float(self.ddim_sigmas[index])
+            if step_noises is not None:
+                noise = m._scene_tensor(what, "step_noises[i]", step_noises[i], C, plan, device)
+            else:
+                noise = torch.randn_like(img) if sigma_t != 0.0 else None
+            x_prev, pred_x0 = torch.empty_like(img), torch.empty_like(img)
+            _lib.check(_lib.lib().eod_ddim_step(img.data_ptr(), e_t.data_ptr(), _lib.ptr(noise), float(self.ddim_alphas[index]),
+                                                float(self.ddim_alphas_prev[index]), sigma_t,
+                                                float(self.ddim_sqrt_one_minus_alphas[index]), float(temperature),
+                                                x_prev.data_ptr(), pred_x0.data_ptr(), img.numel(), current_stream_ptr(device)),
+                       "eod_ddim_step")
+            img = x_prev
             if callback:
                 callback(i)
             if img_callback:

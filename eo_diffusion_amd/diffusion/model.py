@@ -10,7 +10,8 @@ Differences from the reference that are deliberate (and documented in DESIGN.md)
   * PNG dumps happen only when `save=True` (the reference's `A and B or C and D and save` precedence
     slip at model.py:62 writes some regardless);
   * optional keyword-only extras on `sampling`: injected x_T / per-step noises (parity tests) and a
-    counter-based Philox noise source keyed by the GLOBAL sample index (multi-GPU sharding).
+    counter-based Philox noise source keyed by the GLOBAL sample index (multi-GPU sharding);
+  * `sampling_scene`: the same chain on a scene larger than the UNet's image size, tiled (eo_diffusion_amd/tiling.py).
 """
 import math
 import os
@@ -209,6 +210,97 @@ class EODiffusion(nn.Module):
             pred = self.model(x_t, t, cond=cond, y=y)
             x_t = self._ddpm_update(x_t, pred, noise, t, clip=clipped_reverse_diffusion)
         return x_t
+
+    # ------------------------------------------------------------------ whole-scene sampling (no counterpart in the reference)
+    def _scene_args(self, what, scene_size, overlap, device):
+        """(plan, device) of a scene call; refuses before any launch"""
+        from ..tiling import TilePlan
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise _lib.EodError(f"{what}: device must be a HIP GPU ('cuda[:i]'); there is no CPU path")
+        try:
+            h, w = (int(v) for v in scene_size)
+        except (TypeError, ValueError):
+            raise _lib.EodError(f"{what}: scene_size is (H, W), got {scene_size!r}") from None
+        return TilePlan(h, w, self.image_size, overlap), dev
+
+    @staticmethod
+    def _scene_tensor(what, name, t, channels, plan, dev):
+        """a scene-sized argument [1, channels, H, W] (channels None: any) as contiguous fp32 on the device"""
+        t = torch.as_tensor(t)
+        if t.dim() != 4 or t.shape[0] != 1 or tuple(t.shape[2:]) != (plan.H, plan.W) or (channels is not None and t.shape[1] != channels):
+            want = f"[1, {'*' if channels is None else channels}, {plan.H}, {plan.W}]"
+            raise _lib.EodError(f"{what}: `{name}` must be scene-sized, {want}; got {tuple(t.shape)}")
+        return _f32c(t.to(dev))
+
+    def _scene_labels(self, y, chunk, dev):
+        if y is None:
+            return None
+        y = torch.as_tensor(y, device=dev).reshape(-1)
+        if y.numel() != 1:
+            raise _lib.EodError(f"scene sampling takes ONE class label for the scene (it is broadcast to every tile), got {y.numel()}")
+        return y.to(torch.int64).expand(chunk).contiguous()
+
+    @torch.no_grad()
+    def sampling_scene(self, scene_size, clipped_reverse_diffusion=True, device="cpu", cond=None, y=None, *, overlap=0, tile_batch=16,
+                       x_T=None, noises=None, rng="philox", seed=0, progress=True):
+        """Reverse chain over ONE scene [1, C, H, W], H, W >= image_size, with the UNet applied to overlapping image_size tiles
+        (eo_diffusion_amd/tiling.py).  Per step: RePaint mix on the scene (cond_type == "sum"; cond [1, C+1, H, W] split as in
+        sampling()) -> gather the tiles -> UNet on chunks of tile_batch tiles (same t, y broadcast, concatenated cond cut into the
+        same tiles once) -> blend the NOISE ESTIMATES with the plan's weights -> one scene-level eod_ddpm_step with one scene-level
+        noise draw.  Neighbouring tiles therefore share one noise field and one state; with overlap = 0 the result is, bit for bit,
+        what sampling() returns for the tiles.  The result does not depend on tile_batch.
+        rng="philox" (default; the scene is sample 0 of `seed`) | "torch" (the reference's draw order on scene-sized tensors);
+        x_T [1,C,H,W] / noises ([T,1,C,H,W] or a callable k -> tensor) inject the draws as in sampling()."""
+        from ..tiling import gather_padded, tile_slots
+        what = "EODiffusion.sampling_scene"
+        plan, dev = self._scene_args(what, scene_size, overlap, device)
+        if rng not in ("philox", "torch"):
+            raise _lib.EodError(f"{what}: rng is 'philox' or 'torch', got {rng!r}")
+        self._tables_on(dev)
+        shape = (1, self.in_channels, plan.H, plan.W)
+        chunk, _ = tile_slots(plan, tile_batch)
+        gt = mask = cond_tiles = None
+        if cond is not None and self.cond_type == "sum":
+            cond = self._scene_tensor(what, "cond", cond, None, plan, dev)
+            if cond.shape[1] < 4:
+                raise _lib.EodError(f"{what}: cond_type='sum' needs cond = cat(gt[3], mask[1]), got {cond.shape[1]} channels")
+            gt, mask = cond[:, :3].contiguous(), cond[:, 3][:, None].contiguous()
+        elif cond is not None:
+            cond_tiles = gather_padded(self._scene_tensor(what, "cond", cond, None, plan, dev), plan, tile_batch)
+        if x_T is not None:
+            x_t = self._scene_tensor(what, "x_T", x_T, self.in_channels, plan, dev)
+        elif rng == "philox":
+            x_t = self._philox(shape, dev, seed, 0, self.timesteps, 0)
+        else:
+            x_t = torch.randn(shape).to(dev)
+        y_chunk = self._scene_labels(y, chunk, dev)
+        steps = range(self.timesteps - 1, -1, -1)
+        it = tqdm(steps, desc="Sampling scene") if progress else steps
+        for k, i in enumerate(it):
+            if noises is not None:
+                noise = self._scene_tensor(what, "noises[k]", noises(k) if callable(noises) else noises[k], self.in_channels, plan, dev)
+            elif rng == "philox":
+                noise = self._philox(shape, dev, seed, 0, i, 1)
+            else:
+                noise = torch.randn_like(x_t)
+            x_t = self._scene_step(x_t, i, noise, plan, tile_batch, clipped_reverse_diffusion, gt, mask, cond_tiles, y_chunk)
+        return x_t
+
+    @torch.no_grad()
+    def _scene_step(self, x_t, i, noise, plan, tile_batch, clip, gt=None, mask=None, cond_tiles=None, y_chunk=None):
+        """one step of sampling_scene at timestep i: [RePaint mix on the scene] -> tiles -> UNet in chunks -> blended estimate -> scene
+        update.  cond_tiles: tiling.gather_padded(cond, plan, tile_batch); y_chunk: the label repeated tile_slots(...)[0] times."""
+        from ..tiling import tile_slots, tiled_estimate
+        dev = x_t.device
+        chunk, _ = tile_slots(plan, tile_batch)
+        t = torch.full((1,), i, dtype=torch.int64, device=dev)
+        t_chunk = torch.full((chunk,), i, dtype=torch.int64, device=dev)
+        if gt is not None:
+            x_t = self._repaint_mix(x_t, gt, mask, t, noise)
+        pred = tiled_estimate(x_t, plan, tile_batch, lambda x, lo: self.model(
+            x, t_chunk, cond=None if cond_tiles is None else cond_tiles[lo:lo + chunk], y=y_chunk))
+        return self._ddpm_update(x_t, pred, noise, t, clip=clip)
 
     def forward_only(self, img, device="cpu"):
         """Noising-only visualisation helper (model.py:77-84), without the reference's breakpoint()."""

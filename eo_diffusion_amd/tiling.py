@@ -1,0 +1,195 @@
+"""Whole-scene sampling: the tile plan and the two kernels between a scene-sized tensor and UNet-sized tiles.
+
+    plan  = TilePlan(H, W, tile, overlap)        host-side (numpy), importable without a GPU
+    tiles = gather_tiles(scene, plan)            [1,C,H,W] (or [C,H,W]) -> [n_tiles, C, tile, tile]    eod_scene_gather
+    scene = blend_tiles(tiles, plan)             [n_tiles, C, tile, tile] -> [1, C, H, W]              eod_scene_blend
+    e     = tiled_estimate(scene, plan, tile_batch, fn)   gather -> fn on chunks of tile_batch tiles -> blend
+
+Plan, per axis of length L: origins min(i * (tile - overlap), L - tile) until the axis is covered -- the last tile is shifted
+inwards, never padded.  Weights, per axis, [n][tile]: 1 in a tile's interior, a linear ramp (k + 1) / (o + 1) across the o pixels
+a tile shares with its neighbour (rising on the left side, falling on the right; o is the ACTUAL shared width, which is larger than
+`overlap` next to a shifted last tile; where both ramps of a tile meet they are multiplied), then normalised in float64 so that the
+weights of the tiles covering a coordinate sum to one, then rounded to fp32.  A coordinate covered by ONE tile gets exactly 1.0f,
+which is what makes overlap = 0 (and every tile interior) pass the UNet's estimate through bit for bit.  The 2-D weight of tile
+(iy, ix) at its local (ly, lx) is the fp32 product wy[iy][ly] * wx[ix][lx]; tiles are numbered row-major, i = iy * ntx + ix.
+
+The blend is  e[c, y, x] = sum over the tiles covering (y, x), in ascending i, of w_i * e_i : products rounded once, added left to
+right, no atomics -- a pure function of its inputs (csrc/scene.hip).  This maps to the reference's patch cutting in its data
+loaders (data_utils' patch_overlap), not to a line of its samplers: the reference never puts the patches back together."""
+import numpy as np
+
+from . import _lib
+
+
+def axis_plan(L, tile, overlap):
+    """origins (int32 [n]) and weights (float32 [n][tile]) of one axis; see the module docstring."""
+    L, tile, overlap = int(L), int(tile), int(overlap)
+    if tile < 1:
+        raise _lib.EodError(f"tile size must be positive, got {tile}")
+    if L < tile:
+        raise _lib.EodError(f"scene axis of {L} pixels is smaller than the {tile}-pixel tile (tiles are never padded)")
+    if not 0 <= overlap <= tile // 2:
+        raise _lib.EodError(f"overlap must be in [0, tile // 2] = [0, {tile // 2}], got {overlap}")
+    stride = tile - overlap
+    origins = []
+    while True:
+        o = min(len(origins) * stride, L - tile)
+        origins.append(o)
+        if o + tile >= L:
+            break
+    n = len(origins)
+    raw = np.ones((n, tile), dtype=np.float64)
+    for i in range(n - 1):
+        o = origins[i] + tile - origins[i + 1]  # pixels tile i shares with tile i + 1 (>= overlap; 0: they only touch)
+        if o > 0:
+            ramp = (np.arange(o, dtype=np.float64) + 1.0) / (o + 1.0)
+            raw[i + 1, :o] *= ramp
+            raw[i, tile - o:] *= ramp[::-1]
+    total = np.zeros(L, dtype=np.float64)
+    for i, o in enumerate(origins):
+        total[o:o + tile] += raw[i]
+    w = np.empty((n, tile), dtype=np.float32)
+    for i, o in enumerate(origins):
+        w[i] = (raw[i] / total[o:o + tile]).astype(np.float32)
+    return np.asarray(origins, dtype=np.int32), w
+
+
+class TilePlan:
+    """Tiling of an H x W scene into tile x tile windows that overlap by at least `overlap` pixels.
+
+    origins_y / origins_x: int32 [nty] / [ntx];  wy / wx: float32 [nty][tile] / [ntx][tile];  n_tiles = nty * ntx, row-major.
+    Raises EodError when the scene is smaller than a tile or overlap is outside [0, tile // 2]."""
+
+    def __init__(self, H, W, tile, overlap=0):
+        self.H, self.W, self.tile, self.overlap = int(H), int(W), int(tile), int(overlap)
+        self.origins_y, self.wy = axis_plan(H, tile, overlap)
+        self.origins_x, self.wx = axis_plan(W, tile, overlap)
+        self.nty, self.ntx = len(self.origins_y), len(self.origins_x)
+        self.n_tiles = self.nty * self.ntx
+        self._dev = {}
+
+    def __repr__(self):
+        return f"TilePlan(H={self.H}, W={self.W}, tile={self.tile}, overlap={self.overlap}: {self.nty} x {self.ntx} tiles)"
+
+    def origin(self, i):
+        """(y0, x0) of tile i"""
+        iy, ix = divmod(int(i), self.ntx)
+        return int(self.origins_y[iy]), int(self.origins_x[ix])
+
+    def origins(self):
+        return [self.origin(i) for i in range(self.n_tiles)]
+
+    def weight(self, i):
+        """the fp32 2-D weight [tile][tile] of tile i (host copy; the kernel forms the same product per element)"""
+        iy, ix = divmod(int(i), self.ntx)
+        return self.wy[iy][:, None] * self.wx[ix][None, :]
+
+    def cover_count(self):
+        """int [H][W]: how many tiles cover each pixel"""
+        cy = np.zeros(self.H, dtype=np.int64)
+        cx = np.zeros(self.W, dtype=np.int64)
+        for o in self.origins_y:
+            cy[o:o + self.tile] += 1
+        for o in self.origins_x:
+            cx[o:o + self.tile] += 1
+        return cy[:, None] * cx[None, :]
+
+    def device_tables(self, device):
+        """(origins_y, origins_x, wy, wx) as device tensors, uploaded once per device"""
+        import torch
+        dev = torch.device(device)
+        hit = self._dev.get(dev)
+        if hit is None:
+            hit = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (self.origins_y, self.origins_x, self.wy, self.wx))
+            self._dev[dev] = hit
+        return hit
+
+
+def _scene4(scene, what):
+    import torch
+    from .engine import require_gpu
+    require_gpu(scene, what)
+    x = scene if scene.dim() == 4 else scene[None]
+    if x.dim() != 4 or x.shape[0] != 1:
+        raise _lib.EodError(f"{what}: a scene is [1, C, H, W] or [C, H, W], got {tuple(scene.shape)}")
+    return x if (x.dtype == torch.float32 and x.is_contiguous()) else x.float().contiguous()
+
+
+def gather_tiles(scene, plan, out=None):
+    """scene [1, C, H, W] (or [C, H, W]) fp32 on the GPU -> tiles [n_tiles, C, tile, tile], tile i = the window at plan.origin(i).
+    `out`: a contiguous fp32 buffer of at least n_tiles tiles (its first n_tiles are written, and returned)."""
+    import torch
+    from .engine import current_stream_ptr
+    x = _scene4(scene, "gather_tiles")
+    _, c, h, w = x.shape
+    if (h, w) != (plan.H, plan.W):
+        raise _lib.EodError(f"gather_tiles: scene is {h} x {w}, the plan is for {plan.H} x {plan.W}")
+    s = plan.tile
+    if out is None:
+        out = torch.empty((plan.n_tiles, c, s, s), dtype=torch.float32, device=x.device)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 4 and out.shape[0] >= plan.n_tiles
+              and tuple(out.shape[1:]) == (c, s, s)):
+        raise _lib.EodError(f"gather_tiles: `out` must be a contiguous fp32 GPU tensor [>= {plan.n_tiles}, {c}, {s}, {s}], got {tuple(out.shape)}")
+    oy, ox, _, _ = plan.device_tables(x.device)
+    _lib.check(_lib.lib().eod_scene_gather(x.data_ptr(), out.data_ptr(), c, h, w, s, oy.data_ptr(), ox.data_ptr(), plan.nty, plan.ntx,
+                                           current_stream_ptr(x.device)), "eod_scene_gather")
+    return out[:plan.n_tiles]
+
+
+def blend_tiles(tiles, plan, out=None):
+    """tiles [>= n_tiles, C, tile, tile] fp32 on the GPU (the first n_tiles are read) -> scene [1, C, H, W]: the weighted sum of the
+    module docstring.  Every scene element is written."""
+    import torch
+    from .engine import current_stream_ptr, require_gpu
+    require_gpu(tiles, "blend_tiles")
+    s = plan.tile
+    if tiles.dim() != 4 or tiles.shape[0] < plan.n_tiles or tuple(tiles.shape[2:]) != (s, s):
+        raise _lib.EodError(f"blend_tiles: tiles must be [>= {plan.n_tiles}, C, {s}, {s}], got {tuple(tiles.shape)}")
+    e = tiles if (tiles.dtype == torch.float32 and tiles.is_contiguous()) else tiles.float().contiguous()
+    c = e.shape[1]
+    if out is None:
+        out = torch.empty((1, c, plan.H, plan.W), dtype=torch.float32, device=e.device)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == c * plan.H * plan.W):
+        raise _lib.EodError(f"blend_tiles: `out` must be a contiguous fp32 GPU tensor of {c} x {plan.H} x {plan.W} elements")
+    oy, ox, wy, wx = plan.device_tables(e.device)
+    _lib.check(_lib.lib().eod_scene_blend(e.data_ptr(), out.data_ptr(), wy.data_ptr(), wx.data_ptr(), oy.data_ptr(), ox.data_ptr(), c,
+                                          plan.H, plan.W, s, plan.nty, plan.ntx, current_stream_ptr(e.device)), "eod_scene_blend")
+    return out
+
+
+def tile_slots(plan, tile_batch):
+    """(chunk, slots): tiles go through the network `chunk` = min(tile_batch, n_tiles) at a time; the last chunk is padded with copies
+    of the last tile up to `slots` = a multiple of chunk, so ONE launch program (one batch size) serves the whole call."""
+    tile_batch = int(tile_batch)
+    if tile_batch < 1:
+        raise _lib.EodError(f"tile_batch must be at least 1, got {tile_batch}")
+    chunk = min(tile_batch, plan.n_tiles)
+    return chunk, -(-plan.n_tiles // chunk) * chunk
+
+
+def gather_padded(scene, plan, tile_batch):
+    """gather_tiles into a buffer of tile_slots(...) tiles; the padding slots repeat the last tile"""
+    import torch
+    x = _scene4(scene, "gather_padded")
+    chunk, slots = tile_slots(plan, tile_batch)
+    buf = torch.empty((slots, x.shape[1], plan.tile, plan.tile), dtype=torch.float32, device=x.device)
+    gather_tiles(x, plan, out=buf)
+    if slots > plan.n_tiles:
+        buf[plan.n_tiles:] = buf[plan.n_tiles - 1]
+    return buf
+
+
+def tiled_estimate(scene, plan, tile_batch, fn):
+    """One scene-sized network estimate: gather the plan's tiles, call fn(x_chunk, lo) -> e_chunk on consecutive chunks (x_chunk
+    [chunk, C, tile, tile], tile indices lo .. lo + chunk - 1; indices past n_tiles - 1 are padding, their output is dropped),
+    blend.  Allowed because a sample's bits do not depend on the batch it rides in: the result is the same for every tile_batch."""
+    import torch
+    chunk, slots = tile_slots(plan, tile_batch)
+    x_tiles = gather_padded(scene, plan, tile_batch)
+    e_tiles = None
+    for lo in range(0, slots, chunk):
+        e = fn(x_tiles[lo:lo + chunk], lo)
+        if e_tiles is None:
+            e_tiles = torch.empty((slots,) + tuple(e.shape[1:]), dtype=torch.float32, device=e.device)
+        e_tiles[lo:lo + chunk].copy_(e)  # (a graph-replayed network returns the same buffer every call)
+    return blend_tiles(e_tiles, plan)

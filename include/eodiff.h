@@ -324,6 +324,21 @@ int eod_ldm_p_sample(const float* x, const float* eps, const float* noise, const
 int eod_randn_philox(float* out, int N, int64_t chw, uint64_t seed, int64_t sample0, int32_t step,
                      int32_t stream_id, void* stream);
 
+/* Whole-scene sampling (csrc/scene.hip; plan = eo_diffusion_amd/tiling.py TilePlan).  Tiles are s x s, numbered row-major
+ * i = iy * ntx + ix; tile (iy, ix) has its top-left corner at (origins_y[iy], origins_x[ix]).  origins_* are DEVICE int32 arrays,
+ * non-decreasing, every origin + s inside the scene; wy [nty][s] / wx [ntx][s] are DEVICE fp32 per-axis weight tables whose
+ * covering entries sum to one at every coordinate.  fp32, NCHW like every sampler tensor.
+ *   eod_scene_gather  tiles[i][c][ly][lx] = scene[c][origins_y[iy] + ly][origins_x[ix] + lx]          (bit-exact copy)
+ *   eod_scene_blend   scene[c][y][x] = sum over the tiles covering (y, x), in ascending (iy, ix), of
+ *                     (wy[iy][y - oy] * wx[ix][x - ox]) * tiles[i][c][y - oy][x - ox]: each product rounded once to fp32, the sum
+ *                     taken left to right in fp32, no atomics -- a pure function of the inputs, whatever the launch geometry.
+ * A tile whose origin lies outside the scene is NaN-filled by the gather, a pixel no tile covers is NaN in the blend (neither reads
+ * outside its buffers).  16-byte accesses where W, s, the origins and the pointers allow, scalar otherwise (odd W, odd origins). */
+int eod_scene_gather(const float* scene, float* tiles, int C, int H, int W, int s, const int32_t* origins_y,
+                     const int32_t* origins_x, int nty, int ntx, void* stream);
+int eod_scene_blend(const float* tiles, float* scene, const float* wy, const float* wx, const int32_t* origins_y,
+                    const int32_t* origins_x, int C, int H, int W, int s, int nty, int ntx, void* stream);
+
 /* harness-side elementwise ops of inference.py, fp32, bit-exact vs the torch expressions:
  *   eod_repaint_cond   :100-109  cond [N][C+1][hw] = cat(image [N][C][hw], invert ? 1 - mask : mask), mask [N][1][hw]
  *   eod_postprocess    :128      mode 0: y = clip(x, 0, 1) (data in [0,1]);  mode 1: y = (x + 1) / 2 (data in [-1,1])

@@ -145,6 +145,7 @@ SYMBOLS = {
     "eod_postprocess": (i32, [vp, vp, i64, i32, vp]),
     "eod_masked_preview": (i32, [vp, vp, vp, i32, i32, i64, f32, vp]),
     "eod_randn_philox": (i32, [vp, i32, i64, C.c_uint64, i64, i32, i32, vp]),
+    "eod_renoise": (i32, [vp, vp, f32, f32, vp, i32, i64, C.c_uint64, i64, i32, i32, vp]),
     "eod_scene_gather": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, vp]),
     "eod_scene_blend": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "eod_program_run": (i32, [C.POINTER(Op), i32, vp]),
@@ -163,7 +164,7 @@ class EodError(RuntimeError):
     pass
 
 
-ABI_VERSION = 104  # EOD_ABI_VERSION of the include/eodiff.h this file mirrors
+ABI_VERSION = 105  # EOD_ABI_VERSION of the include/eodiff.h this file mirrors
 
 
 def lib():

@@ -10,6 +10,7 @@
 //   repaint_mix   diffusion/model.py:58-60
 //   ddpm_step     diffusion/model.py:101-122 (clip=0), :126-150 (clip=1)
 //   ddim_step     diffusion/ddim.py:192-206
+//   renoise       (no reference line: the forward move of RePaint resampling)
 #include "common.h"
 
 // Caller-supplied timesteps index the schedule tables: an index outside [0, T) would read behind them (the reference's gather
@@ -243,27 +244,84 @@ __device__ __forceinline__ void philox_round(unsigned& c0, unsigned& c1, unsigne
 
 __device__ __forceinline__ float u01(unsigned u) { return ((float)(u >> 8) + 0.5f) * (1.0f / 16777216.0f); }
 
+// the four normals of quad `qd` (elements 4 qd .. 4 qd + 3) of sample `sample` for the key (seed, step, stream_id): the ONE statement of
+// the generator, shared by randn_philox_kernel and the in-register form of renoise_kernel so that both yield the same bits
+__device__ __forceinline__ void philox_normal4(long long qd, unsigned long long seed, long long sample, int step, int stream_id, float z[4]) {
+    unsigned c0 = (unsigned)qd, c1 = (unsigned)sample, c2 = (unsigned)step, c3 = (unsigned)stream_id ^ (unsigned)(qd >> 32);
+    unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        philox_round(c0, c1, c2, c3, k0, k1);
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    const float r0 = sqrtf(-2.0f * logf(u01(c0))), r1 = sqrtf(-2.0f * logf(u01(c2)));
+    const float a0 = 6.28318530717958647692f * u01(c1), a1 = 6.28318530717958647692f * u01(c3);
+    z[0] = r0 * cosf(a0);
+    z[1] = r0 * sinf(a0);
+    z[2] = r1 * cosf(a1);
+    z[3] = r1 * sinf(a1);
+}
+
 __global__ void randn_philox_kernel(float* __restrict__ out, long long chw, unsigned long long seed, long long sample0, int step,
                                     int stream_id) {
     const int n = blockIdx.y;
     const long long quads = (chw + 3) / 4;
     float* o = out + (long long)n * chw;
     for (long long qd = (long long)blockIdx.x * blockDim.x + threadIdx.x; qd < quads; qd += (long long)gridDim.x * blockDim.x) {
-        unsigned c0 = (unsigned)qd, c1 = (unsigned)(sample0 + n), c2 = (unsigned)step, c3 = (unsigned)stream_id ^ (unsigned)(qd >> 32);
-        unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-#pragma unroll
-        for (int r = 0; r < 10; ++r) {
-            philox_round(c0, c1, c2, c3, k0, k1);
-            k0 += 0x9E3779B9u;
-            k1 += 0xBB67AE85u;
-        }
-        const float r0 = sqrtf(-2.0f * logf(u01(c0))), r1 = sqrtf(-2.0f * logf(u01(c2)));
-        const float a0 = 6.28318530717958647692f * u01(c1), a1 = 6.28318530717958647692f * u01(c3);
-        const float z[4] = {r0 * cosf(a0), r0 * sinf(a0), r1 * cosf(a1), r1 * sinf(a1)};
+        float z[4];
+        philox_normal4(qd, seed, sample0 + n, step, stream_id, z);
         const long long e = qd * 4;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
             if (e + j < chw) o[e + j] = z[j];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// RePaint resampling: the forward move x_a -> x_b (b > a) between two levels of a chain, q(x_b | x_a) collapsed over the b - a single
+// steps: out = sqrt(r) * x + sqrt(1 - r) * z, r = acp_b / acp_a.  All samples of a call share the level (scalars by value, like
+// ddim_step).  GEN: z is generated in registers (philox_normal4, the bits eod_randn_philox would write for the same key) and never
+// passes through HBM; otherwise it is read from `noise`.  VEC: one 16-byte access per tensor and quad (chw % 4 == 0, aligned
+// pointers); the scalar form does the same arithmetic element by element.
+// ---------------------------------------------------------------------------------------------
+template <bool VEC, bool GEN>
+__global__ void renoise_kernel(const float* __restrict__ x, const float* __restrict__ noise, float acp_from, float acp_to,
+                               float* __restrict__ out, long long chw, unsigned long long seed, long long sample0, int step,
+                               int stream_id) {
+    const int n = blockIdx.y;
+    const float r = acp_to / acp_from;
+    const float ca = sqrtf(r);
+    const float cb = sqrtf(1.0f - r);
+    const long long quads = (chw + 3) / 4, base = (long long)n * chw;
+    for (long long qd = (long long)blockIdx.x * blockDim.x + threadIdx.x; qd < quads; qd += (long long)gridDim.x * blockDim.x) {
+        const long long e = base + qd * 4;
+        float z[4];
+        if (GEN) philox_normal4(qd, seed, sample0 + n, step, stream_id, z);
+        if (VEC) {
+            const f32x4 xv = *reinterpret_cast<const f32x4*>(x + e);
+            if (!GEN) {
+                const f32x4 zv = *reinterpret_cast<const f32x4*>(noise + e);
+                z[0] = zv[0]; z[1] = zv[1]; z[2] = zv[2]; z[3] = zv[3];
+            }
+            f32x4 o;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float p = ca * xv[j];
+                const float q = cb * z[j];
+                o[j] = p + q;
+            }
+            *reinterpret_cast<f32x4*>(out + e) = o;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (qd * 4 + j < chw) {
+                    const float p = ca * x[e + j];
+                    const float q = cb * (GEN ? z[j] : noise[e + j]);
+                    out[e + j] = p + q;
+                }
+            }
+        }
     }
 }
 
@@ -272,6 +330,25 @@ extern "C" int eod_randn_philox(float* out, int N, int64_t chw, uint64_t seed, i
     EOD_REQUIRE(out && N > 0 && chw > 0, "randn_philox: bad args");
     hipLaunchKernelGGL(randn_philox_kernel, dim3(blocks_for((chw + 3) / 4, 512), N), dim3(256), 0, (hipStream_t)stream, out, (long long)chw, (unsigned long long)seed, (long long)sample0, step, stream_id);
     EOD_CHECK_LAUNCH("randn_philox");
+    return EOD_OK;
+}
+
+extern "C" int eod_renoise(const float* x, const float* noise, float acp_from, float acp_to, float* out, int N, int64_t chw, uint64_t seed,
+                           int64_t sample0, int32_t step, int32_t stream_id, void* stream) {
+    EOD_REQUIRE(x && out && N > 0 && chw > 0, "renoise: bad args");
+    EOD_REQUIRE(acp_to > 0.0f && acp_to <= acp_from, "renoise: needs 0 < acp_to <= acp_from (a move UP the chain), got %g -> %g", (double)acp_from, (double)acp_to);
+    const bool vec = chw % 4 == 0 && eod_aligned16(x) && eod_aligned16(out) && (!noise || eod_aligned16(noise));
+    const dim3 grid(blocks_for((chw + 3) / 4, 512), N), block(256);
+#define EOD_RENOISE(V, G)                                                                                                             \
+    hipLaunchKernelGGL((renoise_kernel<V, G>), grid, block, 0, (hipStream_t)stream, x, noise, acp_from, acp_to, out, (long long)chw, \
+                       (unsigned long long)seed, (long long)sample0, step, stream_id)
+    if (noise) {
+        if (vec) EOD_RENOISE(true, false); else EOD_RENOISE(false, false);
+    } else {
+        if (vec) EOD_RENOISE(true, true); else EOD_RENOISE(false, true);
+    }
+#undef EOD_RENOISE
+    EOD_CHECK_LAUNCH("renoise");
     return EOD_OK;
 }
 

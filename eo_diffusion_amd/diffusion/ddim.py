@@ -9,13 +9,15 @@ Deliberate differences: buffers live on the model's device instead o
 upstream intent ddpm.py:280,1335); the unused second randn_like per step (ddim.py:171) is still drawn
 in rng="torch" mode so that the global generator advances exactly as in the reference.
 `sample_scene` (no counterpart in the reference) runs the same steps on a scene larger than the UNet's image size, tiled.
+`resample=(jump_length, jump_n_sample)` on sample / ddim_sampling / sample_scene: RePaint resampling over the INDICES of the DDIM
+steps (diffusion/util.py make_resample_schedule), the forward moves through eod_renoise with ddim_alphas at the two indices.
 """
 import numpy as np
 import torch
 
 from .. import _lib
 from ..engine import current_stream_ptr, require_gpu
-from .util import make_ddim_sampling_parameters, make_ddim_timesteps, noise_like
+from .util import make_ddim_sampling_parameters, make_ddim_timesteps, noise_like, resample_plan
 
 try:
     from tqdm import tqdm
@@ -67,7 +69,7 @@ class DDIMSampler(object):
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
                quantize_x0=False, eta=0.0, mask=None, x0=None, temperature=1.0, noise_dropout=0.0, score_corrector=None,
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.0,
-               unconditional_conditioning=None, **kwargs):
+               unconditional_conditioning=None, resample=None, jump_noises=None, **kwargs):
         if conditioning is not None:
             cbs = (conditioning[list(conditioning.keys())[0]] if isinstance(conditioning, dict) else conditioning).shape[0]
             if cbs != batch_size:
@@ -79,33 +81,40 @@ class DDIMSampler(object):
                                   noise_dropout=noise_dropout, temperature=temperature, score_corrector=score_corrector,
                                   corrector_kwargs=corrector_kwargs, x_T=x_T, log_every_t=log_every_t,
                                   unconditional_guidance_scale=unconditional_guidance_scale,
-                                  unconditional_conditioning=unconditional_conditioning, **kwargs)
+                                  unconditional_conditioning=unconditional_conditioning, resample=resample,
+                                  jump_noises=jump_noises, **kwargs)
 
     @torch.no_grad()
     def ddim_sampling(self, cond, shape, x_T=None, ddim_use_original_steps=False, callback=None, timesteps=None,
                       quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100, temperature=1.0,
                       noise_dropout=0.0, score_corrector=None, corrector_kwargs=None, unconditional_guidance_scale=1.0,
-                      unconditional_conditioning=None, *, step_noises=None, mix_noises=None, progress=True):
+                      unconditional_conditioning=None, *, step_noises=None, mix_noises=None, progress=True, resample=None,
+                      jump_noises=None):
+        """resample=(jump_length, jump_n_sample): RePaint resampling over the indices 0 .. total_steps - 1 of the steps this call walks.
+        After the listed evaluations the state (at ddim_alphas_prev[a + 1] = ddim_alphas[a]) is moved up to ddim_alphas[b] by
+        eod_renoise; step_noises / mix_noises are then indexed by the evaluation's position in the walk, jump_noises by the jump's
+        ordinal (otherwise randn_like when the jump happens); callbacks and intermediates see every executed step."""
         if ddim_use_original_steps:
             raise NotImplementedError("ddim_use_original_steps touches attributes the reference never defines (ddim.py:188-190)")
         device = self.model.betas.device
         b = shape[0]
-        img = torch.randn(shape, device=device) if x_T is None else x_T.to(device).float().contiguous()
         if timesteps is None:
             timesteps = self.ddim_timesteps
         else:
             subset_end = int(min(timesteps / self.ddim_timesteps.shape[0], 1) * self.ddim_timesteps.shape[0]) - 1
             timesteps = self.ddim_timesteps[:subset_end]
-        intermediates = {"x_inter": [img], "pred_x0": [img]}
-        time_range = np.flip(timesteps)
         total_steps = timesteps.shape[0]
-        it = tqdm(time_range, desc="DDIM Sampler", total=total_steps) if progress else time_range
+        visits, jump_after = resample_plan("DDIMSampler.ddim_sampling", resample, total_steps,
+                                           (("step_noises", step_noises), ("mix_noises", mix_noises)), jump_noises)
+        img = torch.randn(shape, device=device) if x_T is None else x_T.to(device).float().contiguous()
+        intermediates = {"x_inter": [img], "pred_x0": [img]}
+        it = tqdm(visits, desc="DDIM Sampler", total=len(visits)) if progress else visits
         if mask is not None:
             mask = self.model._broadcast_mask(mask, img)
         if x0 is not None:
             x0 = torch.as_tensor(x0).to(device).float().contiguous()  # (the mix noise below is then drawn on the device, too)
-        for i, step in enumerate(it):
-            index = total_steps - i - 1
+        for i, index in enumerate(it):
+            step = timesteps[index]
             ts = torch.full((b,), int(step), device=device, dtype=torch.long)
             if mask is not None:
                 assert x0 is not None
@@ -125,12 +134,17 @@ class DDIMSampler(object):
             if index % log_every_t == 0 or index == total_steps - 1:
                 intermediates["x_inter"].append(img)
                 intermediates["pred_x0"].append(pred_x0)
+            if i + 1 in jump_after:
+                j, a, b_up = jump_after[i + 1]
+                z = jump_noises[j].to(device) if jump_noises is not None else torch.randn_like(img)
+                img = self.model._renoise(img, self.ddim_alphas[a], self.ddim_alphas[b_up], z)
         return img, intermediates
 
     @torch.no_grad()
     def sample_scene(self, S, scene_size, *, overlap=0, tile_batch=16, conditioning=None, mask=None, x0=None, eta=0.0, x_T=None,
                      temperature=1.0, unconditional_guidance_scale=1.0, unconditional_conditioning=None, step_noises=None,
-                     mix_noises=None, callback=None, img_callback=None, log_every_t=100, verbose=False, progress=True):
+                     mix_noises=None, callback=None, img_callback=None, log_every_t=100, verbose=False, progress=True, resample=None,
+                     jump_noises=None):
         """DDIM over ONE scene [1, C, H, W] larger than the UNet's image size (see EODiffusion.sampling_scene and
         eo_diffusion_amd/tiling.py): per step the RePaint mix (mask / x0 scene-sized), the UNet on overlapping tiles in chunks of
         tile_batch, the blend of the noise estimates, ONE scene-level eod_ddim_step.  Classifier-free guidance runs per chunk through
@@ -138,13 +152,17 @@ class DDIMSampler(object):
         scene-sized [1, Cc, H, W] (channel-concatenated inside the UNet) and are cut into the same tiles once.  step_noises /
         mix_noises ([S, 1, C, H, W]) inject the draws as in ddim_sampling(); otherwise they come from the device generator, scene-sized
         (the eta-noise only when sigma_t != 0).  With overlap = 0 and injected draws the result equals sample() on the tiles, bit for
-        bit.  Returns (scene, intermediates) like sample()."""
+        bit.  resample=(jump_length, jump_n_sample) / jump_noises ([jumps, 1, C, H, W]): RePaint resampling as in ddim_sampling(), the
+        forward moves on the SCENE.  Returns (scene, intermediates) like sample()."""
         from ..tiling import gather_padded, tile_slots, tiled_estimate
         what = "DDIMSampler.sample_scene"
         m = self.model
         device = m.betas.device
         plan, device = m._scene_args(what, scene_size, overlap, device)
         C = m.in_channels
+        # (the walk is fixed, and the injected draws counted against it, before anything is launched; make_schedule below yields the same steps)
+        visits, jump_after = resample_plan(what, resample, make_ddim_timesteps("uniform", S, m.timesteps, verbose=False).shape[0],
+                                           (("step_noises", step_noises), ("mix_noises", mix_noises)), jump_noises)
         chunk, _ = tile_slots(plan, tile_batch)
         if (mask is None) != (x0 is None):
             raise _lib.EodError(f"{what}: mask and x0 go together (RePaint mix of the known region)")
@@ -165,10 +183,10 @@ class DDIMSampler(object):
                                                      plan, device), plan, tile_batch)
         img = torch.randn((1, C, plan.H, plan.W), device=device) if x_T is None else m._scene_tensor(what, "x_T", x_T, C, plan, device)
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
-        time_range = np.flip(self.ddim_timesteps)
         total_steps = self.ddim_timesteps.shape[0]
+        assert total_steps == len(set(visits))
         intermediates = {"x_inter": [img], "pred_x0": [img]}
-        it = tqdm(time_range, desc="DDIM Sampler (scene)", total=total_steps) if progress else time_range
+        it = tqdm(visits, desc="DDIM Sampler (scene)", total=len(visits)) if progress else visits
 
         def eps(x, lo, ts):
             c = None if c_tiles is None else c_tiles[lo:lo + chunk]
@@ -181,8 +199,8 @@ class DDIMSampler(object):
                                                   e_t.numel(), current_stream_ptr(device)), "eod_cfg_combine")
             return e_t
 
-        for i, step in enumerate(it):
-            index = total_steps - i - 1
+        for i, index in enumerate(it):
+            step = self.ddim_timesteps[index]
             if mask is not None:
                 ts1 = torch.full((1,), int(step), device=device, dtype=torch.long)
                 nz = (m._scene_tensor(what, "mix_noises[i]", mix_noises[i], C, plan, device) if mix_noises is not None
@@ -209,6 +227,11 @@ class DDIMSampler(object):
             if index % log_every_t == 0 or index == total_steps - 1:
                 intermediates["x_inter"].append(img)
                 intermediates["pred_x0"].append(pred_x0)
+            if i + 1 in jump_after:
+                j, a, b_up = jump_after[i + 1]
+                z = (m._scene_tensor(what, "jump_noises[j]", jump_noises[j], C, plan, device) if jump_noises is not None
+                     else torch.randn_like(img))
+                img = m._renoise(img, self.ddim_alphas[a], self.ddim_alphas[b_up], z)
         return img, intermediates
 
     @torch.no_grad()

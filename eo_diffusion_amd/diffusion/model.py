@@ -11,7 +11,9 @@ Differences from the reference that are deliberate (and documented in DESIGN.md)
     slip at model.py:62 writes some regardless);
   * optional keyword-only extras on `sampling`: injected x_T / per-step noises (parity tests) and a
     counter-based Philox noise source keyed by the GLOBAL sample index (multi-GPU sharding);
-  * `sampling_scene`: the same chain on a scene larger than the UNet's image size, tiled (eo_diffusion_amd/tiling.py).
+  * `sampling_scene`: the same chain on a scene larger than the UNet's image size, tiled (eo_diffusion_amd/tiling.py);
+  * `resample=(jump_length, jump_n_sample)` on both: RePaint resampling, the chain walks diffusion/util.py's make_resample_schedule
+    and moves up it with eod_renoise.
 """
 import math
 import os
@@ -22,6 +24,7 @@ import torch.nn as nn
 from .. import _lib
 from ..backbones.unet_openai import *  # noqa: F401,F403  (the reference re-exports these, model.py:5)
 from ..engine import current_stream_ptr, require_gpu
+from .util import resample_plan
 
 try:
     from tqdm import tqdm
@@ -167,19 +170,44 @@ class EODiffusion(nn.Module):
                                                current_stream_ptr(dev)), "eod_randn_philox")
         return out
 
+    def _renoise(self, x, acp_from, acp_to, noise=None, key=(0, 0, 0, 0)):
+        """forward move of RePaint resampling between two levels of a chain: sqrt(r) x + sqrt(1 - r) z, r = acp_to / acp_from, one fused
+        pass (eod_renoise).  z = `noise`, or with noise None generated in registers from the Philox key = (seed, sample0, step, stream_id)."""
+        x = _f32c(x)
+        z = None if noise is None else _f32c(noise)
+        assert z is None or z.shape == x.shape, (z.shape, x.shape)
+        out = torch.empty_like(x)
+        n = x.shape[0]
+        seed, sample0, step, stream_id = key
+        _lib.check(_lib.lib().eod_renoise(x.data_ptr(), _lib.ptr(z), float(acp_from), float(acp_to), out.data_ptr(), n, x.numel() // n,
+                                          seed, sample0, step, stream_id, current_stream_ptr(x.device)), "eod_renoise")
+        return out
+
+    @staticmethod
+    def _draw(seq, k):
+        """entry k of injected draws: a tensor / list, or a callable k -> tensor"""
+        return seq(k) if callable(seq) else seq[k]
+
     # ------------------------------------------------------------------ sampling loop (model.py:46-75)
     @torch.no_grad()
     def sampling(self, n_samples, clipped_reverse_diffusion=True, device="cpu", cond=None, y=None, idx=0, save=False,
-                 *, x_T=None, noises=None, rng="torch", seed=0, sample_offset=0, progress=True):
+                 *, x_T=None, noises=None, rng="torch", seed=0, sample_offset=0, progress=True, resample=None, jump_noises=None):
         """Reverse chain t = T-1 ... 0.  RNG order of the reference is kept: x_T is drawn on the CPU
         generator (model.py:48), one `randn_like` per step on the device generator (:55) used for BOTH the
         RePaint q_sample of gt (:59) and the reverse step (:69).
         Extras: x_T / noises ([T,n,C,H,W] or a callable k -> tensor) inject the draws; rng="philox" uses the
-        counter-based generator keyed by (seed, sample_offset + n, t) so results do not depend on sharding."""
+        counter-based generator keyed by (seed, sample_offset + n, t) so results do not depend on sharding.
+        resample=(jump_length, jump_n_sample): RePaint resampling.  The chain walks make_resample_schedule(T, ...) (levels =
+        timesteps): after the listed evaluations the state is moved from x_a up to x_b by eod_renoise and descends again; the mix at
+        the landing timestep replaces the known region as on every visit.  `noises` is then indexed by the evaluation's position in
+        the walk and `jump_noises` by the jump's ordinal; rng="philox": visit v = 0, 1, ... of timestep i draws with (step i, stream
+        1 + 2 v), the jump landing on b in front of visit v >= 1 of b with (step b, stream 2 v); rng="torch": randn_like in loop
+        order.  None: the single descent, today's bits."""
         dev = torch.device(device)
         if dev.type != "cuda":
             raise _lib.EodError("EODiffusion.sampling: device must be a HIP GPU ('cuda[:i]'); there is no CPU path")
         self._tables_on(dev)
+        visits, jump_after = resample_plan("EODiffusion.sampling", resample, self.timesteps, (("noises", noises),), jump_noises)
         shape = (n_samples, self.in_channels, self.image_size, self.image_size)
         if x_T is not None:
             x_t = _f32c(x_T.to(dev))
@@ -192,14 +220,16 @@ class EODiffusion(nn.Module):
             cond = cond.to(dev)
             gt, mask = cond[:n_samples, :3].contiguous(), cond[:n_samples, 3][:, None].contiguous()
             cond = None
-        steps = range(self.timesteps - 1, -1, -1)
-        it = tqdm(steps, desc="Sampling") if progress else steps
+        acp = self.alphas_cumprod.tolist() if jump_after else None  # ONE host copy of the buffer for the whole call
+        seen = {}  # timestep -> evaluations so far
+        it = tqdm(visits, desc="Sampling") if progress else visits
         for k, i in enumerate(it):
+            v = seen.get(i, 0)
+            seen[i] = v + 1
             if noises is not None:
-                noise = noises(k) if callable(noises) else noises[k]
-                noise = _f32c(noise.to(dev))
+                noise = _f32c(self._draw(noises, k).to(dev))
             elif rng == "philox":
-                noise = self._philox(shape, dev, seed, sample_offset, i, 1)
+                noise = self._philox(shape, dev, seed, sample_offset, i, 1 + 2 * v)
             else:
                 noise = torch.randn_like(x_t)
             t = torch.full((n_samples,), i, dtype=torch.int64, device=dev)
@@ -209,6 +239,14 @@ class EODiffusion(nn.Module):
                 _save_grid((x_t + 1.0) / 2.0, f"results/prova/s{idx}_{i}_pred.png", int(math.sqrt(n_samples)))
             pred = self.model(x_t, t, cond=cond, y=y)
             x_t = self._ddpm_update(x_t, pred, noise, t, clip=clipped_reverse_diffusion)
+            if k + 1 in jump_after:
+                j, a, b = jump_after[k + 1]
+                if jump_noises is not None:
+                    x_t = self._renoise(x_t, acp[a], acp[b], self._draw(jump_noises, j).to(dev))
+                elif rng == "philox":
+                    x_t = self._renoise(x_t, acp[a], acp[b], key=(seed, sample_offset, b, 2 * seen[b]))
+                else:
+                    x_t = self._renoise(x_t, acp[a], acp[b], torch.randn_like(x_t))
         return x_t
 
     # ------------------------------------------------------------------ whole-scene sampling (no counterpart in the reference)
@@ -243,7 +281,7 @@ class EODiffusion(nn.Module):
 
     @torch.no_grad()
     def sampling_scene(self, scene_size, clipped_reverse_diffusion=True, device="cpu", cond=None, y=None, *, overlap=0, tile_batch=16,
-                       x_T=None, noises=None, rng="philox", seed=0, progress=True):
+                       x_T=None, noises=None, rng="philox", seed=0, progress=True, resample=None, jump_noises=None):
         """Reverse chain over ONE scene [1, C, H, W], H, W >= image_size, with the UNet applied to overlapping image_size tiles
         (eo_diffusion_amd/tiling.py).  Per step: RePaint mix on the scene (cond_type == "sum"; cond [1, C+1, H, W] split as in
         sampling()) -> gather the tiles -> UNet on chunks of tile_batch tiles (same t, y broadcast, concatenated cond cut into the
@@ -251,13 +289,16 @@ class EODiffusion(nn.Module):
         noise draw.  Neighbouring tiles therefore share one noise field and one state; with overlap = 0 the result is, bit for bit,
         what sampling() returns for the tiles.  The result does not depend on tile_batch.
         rng="philox" (default; the scene is sample 0 of `seed`) | "torch" (the reference's draw order on scene-sized tensors);
-        x_T [1,C,H,W] / noises ([T,1,C,H,W] or a callable k -> tensor) inject the draws as in sampling()."""
+        x_T [1,C,H,W] / noises ([T,1,C,H,W] or a callable k -> tensor) inject the draws as in sampling().
+        resample=(jump_length, jump_n_sample) / jump_noises: RePaint resampling as in sampling(), with eod_renoise on the SCENE (one
+        state, one noise field, like the update) and the same Philox keys."""
         from ..tiling import gather_padded, tile_slots
         what = "EODiffusion.sampling_scene"
         plan, dev = self._scene_args(what, scene_size, overlap, device)
         if rng not in ("philox", "torch"):
             raise _lib.EodError(f"{what}: rng is 'philox' or 'torch', got {rng!r}")
         self._tables_on(dev)
+        visits, jump_after = resample_plan(what, resample, self.timesteps, (("noises", noises),), jump_noises)
         shape = (1, self.in_channels, plan.H, plan.W)
         chunk, _ = tile_slots(plan, tile_batch)
         gt = mask = cond_tiles = None
@@ -275,16 +316,28 @@ class EODiffusion(nn.Module):
         else:
             x_t = torch.randn(shape).to(dev)
         y_chunk = self._scene_labels(y, chunk, dev)
-        steps = range(self.timesteps - 1, -1, -1)
-        it = tqdm(steps, desc="Sampling scene") if progress else steps
+        acp = self.alphas_cumprod.tolist() if jump_after else None  # ONE host copy of the buffer for the whole call
+        seen = {}  # timestep -> evaluations so far
+        it = tqdm(visits, desc="Sampling scene") if progress else visits
         for k, i in enumerate(it):
+            v = seen.get(i, 0)
+            seen[i] = v + 1
             if noises is not None:
-                noise = self._scene_tensor(what, "noises[k]", noises(k) if callable(noises) else noises[k], self.in_channels, plan, dev)
+                noise = self._scene_tensor(what, "noises[k]", self._draw(noises, k), self.in_channels, plan, dev)
             elif rng == "philox":
-                noise = self._philox(shape, dev, seed, 0, i, 1)
+                noise = self._philox(shape, dev, seed, 0, i, 1 + 2 * v)
             else:
                 noise = torch.randn_like(x_t)
             x_t = self._scene_step(x_t, i, noise, plan, tile_batch, clipped_reverse_diffusion, gt, mask, cond_tiles, y_chunk)
+            if k + 1 in jump_after:
+                j, a, b = jump_after[k + 1]
+                if jump_noises is not None:
+                    z = self._scene_tensor(what, "jump_noises[j]", self._draw(jump_noises, j), self.in_channels, plan, dev)
+                    x_t = self._renoise(x_t, acp[a], acp[b], z)
+                elif rng == "philox":
+                    x_t = self._renoise(x_t, acp[a], acp[b], key=(seed, 0, b, 2 * seen[b]))
+                else:
+                    x_t = self._renoise(x_t, acp[a], acp[b], torch.randn_like(x_t))
         return x_t
 
     @torch.no_grad()

@@ -41,6 +41,55 @@ def make_ddim_timesteps(ddim_discr_method, num_ddim_timesteps, num_ddpm_timestep
     return steps_out
 
 
+def make_resample_schedule(num_levels, jump_length, jump_n_sample):
+    """RePaint resampling (Lugmayr et al. 2022, "time travel") as an exact integer schedule: (visits, jumps).
+    Levels are 0 .. num_levels - 1; the state is "at level i" before the UNet is evaluated at index i, and that evaluation takes it
+    to level i - 1 (-1 = the final image).  DDPM: a level is a timestep; DDIM: an index into ddim_timesteps.  Jump points are
+    range(0, num_levels - jump_length, jump_length): the first jump_n_sample - 1 times the state ARRIVES at a jump point j by a
+    reverse step it is re-noised to level j + jump_length and descends again; afterwards it passes.  Landing on a level by a jump
+    never triggers that level's own jump.
+    visits: the indices the UNet is evaluated at, in order.  jumps: (k, a, b) = after evaluation number k (counting from 1) the
+    state moves from level a up to level b = a + jump_length."""
+    from .._lib import EodError
+    for name, v in (("num_levels", num_levels), ("jump_length", jump_length), ("jump_n_sample", jump_n_sample)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise EodError(f"make_resample_schedule: {name} must be an integer >= 1, got {v!r}")
+    num_levels, jump_length, jump_n_sample = int(num_levels), int(jump_length), int(jump_n_sample)
+    left = {j: jump_n_sample - 1 for j in range(0, num_levels - jump_length, jump_length)}
+    visits, jumps = [], []
+    level = num_levels - 1
+    while level >= 0:
+        visits.append(level)
+        level -= 1
+        if left.get(level, 0) > 0:
+            left[level] -= 1
+            jumps.append((len(visits), level, level + jump_length))
+            level += jump_length
+    return visits, jumps
+
+
+def resample_plan(what, resample, num_levels, draws=(), jump_noises=None):
+    """The walk of one sampler call: (visits, jump_after).  resample None: today's single descent, no jumps; (jump_length,
+    jump_n_sample): make_resample_schedule.  jump_after[k] = (ordinal, a, b) for the jump that follows evaluation number k (from 1).
+    draws: (name, injected per-evaluation draws) pairs; with `resample` a tensor or list among them has one entry per evaluation, and
+    `jump_noises` one per jump (a callable is taken at its word) -- checked here, before any launch."""
+    from .._lib import EodError
+    if resample is None:
+        visits, jumps = range(num_levels - 1, -1, -1), []
+    else:
+        try:
+            jump_length, jump_n_sample = resample
+        except (TypeError, ValueError):
+            raise EodError(f"{what}: resample is (jump_length, jump_n_sample), got {resample!r}") from None
+        visits, jumps = make_resample_schedule(num_levels, jump_length, jump_n_sample)
+        for name, d in draws:
+            if d is not None and not callable(d) and len(d) != len(visits):
+                raise EodError(f"{what}: resample={tuple(resample)} evaluates the UNet {len(visits)} times, `{name}` has {len(d)} entries")
+    if jump_noises is not None and not callable(jump_noises) and len(jump_noises) != len(jumps):
+        raise EodError(f"{what}: the call makes {len(jumps)} resampling jumps, `jump_noises` has {len(jump_noises)} entries")
+    return visits, {k: (j, a, b) for j, (k, a, b) in enumerate(jumps)}
+
+
 def make_ddim_sampling_parameters(alphacums, ddim_timesteps, eta, verbose=True):
     """(sigmas, alphas, alphas_prev) with the reference's dtypes (util.py:80-91): alphas is an fp32
     tensor slice, alphas_prev a float64 ndarray, sigmas their mixed-type product."""

@@ -4,10 +4,13 @@ cloud mask that runs across tile borders, `EODiffusion.sampling_scene` with `con
 
 The UNet sees image_size x image_size tiles that overlap by `--overlap` pixels; the noise ESTIMATES of the tiles are blended and
 the scene is updated once per step with one scene-sized noise field, so neighbouring tiles agree where they meet and the result
-does not depend on `--tile-batch` (eo_diffusion_amd/tiling.py).  Weights are random unless `--ckpt` names a
+does not depend on `--tile-batch` (eo_diffusion_amd/tiling.py).  `--resample L U` turns on RePaint resampling: every
+L steps down the chain the scene is diffused L steps forward again and comes down once more, U times in all, so that the painted
+region and the known region agree where they meet (U x the UNet evaluations over most of the chain).  Weights are random unless `--ckpt` names a
 checkpoint of the reference's format ({"model": state_dict}): the example shows the call sequence, not a trained model.
 
     python examples/inpaint_scene.py --height 600 --width 777 --image-size 64 --overlap 16 --timesteps 50 --out scene.npy
+    python examples/inpaint_scene.py --timesteps 50 --resample 5 3
 """
 import argparse
 import os
@@ -21,6 +24,7 @@ import torch  # noqa: E402
 from eo_diffusion_amd import harness  # noqa: E402
 from eo_diffusion_amd.backbones.unet_openai import UNetModel  # noqa: E402
 from eo_diffusion_amd.diffusion.model import EODiffusion  # noqa: E402
+from eo_diffusion_amd.diffusion.util import resample_plan  # noqa: E402
 from eo_diffusion_amd.tiling import TilePlan  # noqa: E402
 
 
@@ -46,6 +50,8 @@ def main():
     ap.add_argument("--tile-batch", type=int, default=16)
     ap.add_argument("--timesteps", type=int, default=50)
     ap.add_argument("--precision", default="fp32x3", choices=["fp32", "fp32x3", "fp16"])
+    ap.add_argument("--resample", type=int, nargs=2, default=None, metavar=("L", "U"),
+                    help="RePaint resampling: jump length and number of descents per jump (default: one descent, no jumps)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--ckpt", default=None)
     ap.add_argument("--out", default="inpainted_scene.npy")
@@ -73,14 +79,15 @@ def main():
     cond = harness.assemble_repaint_cond(image * 2.0 - 1.0, mask)   # [1, 4, H, W]: the scene in [-1, 1] + (1 - mask) = keep
     t0 = time.perf_counter()
     scene = model.sampling_scene((args.height, args.width), True, device, cond=cond, overlap=args.overlap, tile_batch=args.tile_batch,
-                                 seed=args.seed, progress=False)
+                                 seed=args.seed, progress=False, resample=None if args.resample is None else tuple(args.resample))
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     out = harness.postprocess_samples(scene, data_nonneg=False)    # (x + 1) / 2
     np.save(args.out, out[0].cpu().numpy())
     keep = (mask == 0).expand_as(image)
     dev_kept = float((out - image)[keep].abs().max())
-    print(f"{plan.n_tiles} tiles x {args.timesteps} steps in {dt:.2f} s; wrote {args.out} {tuple(out.shape[1:])}; "
+    n_eval = len(resample_plan("inpaint_scene", args.resample, args.timesteps)[0])
+    print(f"{plan.n_tiles} tiles x {n_eval} evaluations in {dt:.2f} s; wrote {args.out} {tuple(out.shape[1:])}; "
           f"masked pixels {int(mask.sum())}; max |out - scene| over the kept region {dev_kept:.3f} (an untrained network only keeps "
           "what the last RePaint mix hands it)")
 

@@ -35,7 +35,7 @@ const char* eod_last_error(void);
  * buffer of eod_pack_conv_weight_split, the 4-int state of eod_adamw_step_guarded).  eod_version() returns the value the library was built
  * with; a binding compares it with the header it mirrors at load time (eo_diffusion_amd/_lib.py does) instead of finding out by an
  * out-of-bounds device write. */
-#define EOD_ABI_VERSION 104
+#define EOD_ABI_VERSION 105
 int eod_version(void);
 /* Kernel-selection options ("skip_fuse", "head", "halo_bn256", "halo_splitk", "first": 1 / 0; "gn_fuse_max_cout": n, -1 = default; "halo_tpw":
  * pixel tiles per workgroup of the streaming halo instances, 1 = off = default, 0 = chosen per launch): every option has one
@@ -323,6 +323,15 @@ int eod_ldm_p_sample(const float* x, const float* eps, const float* noise, const
  * -> results are invariant to how samples are sharded over ranks. */
 int eod_randn_philox(float* out, int N, int64_t chw, uint64_t seed, int64_t sample0, int32_t step,
                      int32_t stream_id, void* stream);
+/* RePaint resampling, the forward move between two levels a < b of a chain (q(x_b | x_a) collapsed over the b - a single steps):
+ *   out = ca * x + cb * z,  r = acp_to / acp_from,  ca = sqrtf(r),  cb = sqrtf(1.0f - r),  every operation rounded separately in fp32.
+ * acp_from / acp_to are the cumulative alpha products of the level left and the level reached (entries of alphas_cumprod for DDPM,
+ * of ddim_alphas for DDIM), shared by all N samples; 0 < acp_to <= acp_from, else EOD_EINVAL and nothing is launched.
+ * noise != NULL: z is read from noise [N][CHW].  noise == NULL: z is generated in registers, bit for bit what eod_randn_philox
+ * writes for (seed, sample0 + n, step, stream_id), and never passes through memory.  out must not alias x.
+ * 16-byte accesses where chw % 4 == 0 and the pointers are 16-byte aligned, element by element otherwise: same arithmetic. */
+int eod_renoise(const float* x, const float* noise, float acp_from, float acp_to, float* out, int N, int64_t chw,
+                uint64_t seed, int64_t sample0, int32_t step, int32_t stream_id, void* stream);
 
 /* Whole-scene sampling (csrc/scene.hip; plan = eo_diffusion_amd/tiling.py TilePlan).  Tiles are s x s, numbered row-major
  * i = iy * ntx + ix; tile (iy, ix) has its top-left corner at (origins_y[iy], origins_x[ix]).  origins_* are DEVICE int32 arrays,

@@ -148,6 +148,10 @@ SYMBOLS = {
     "eod_renoise": (i32, [vp, vp, f32, f32, vp, i32, i64, C.c_uint64, i64, i32, i32, vp]),
     "eod_scene_gather": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, vp]),
     "eod_scene_blend": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "eod_scene_tile_active": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, vp]),
+    "eod_scene_gather_list": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, vp, i32, vp]),
+    "eod_scene_blend_list": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "eod_scene_keep_known": (i32, [vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
     "eod_program_run": (i32, [C.POINTER(Op), i32, vp]),
     "eod_timer_create": (vp, [i32, i32]),
     "eod_timer_destroy": (None, [vp]),

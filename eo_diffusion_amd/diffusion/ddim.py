@@ -144,7 +144,7 @@ class DDIMSampler(object):
     def sample_scene(self, S, scene_size, *, overlap=0, tile_batch=16, conditioning=None, mask=None, x0=None, eta=0.0, x_T=None,
                      temperature=1.0, unconditional_guidance_scale=1.0, unconditional_conditioning=None, step_noises=None,
                      mix_noises=None, callback=None, img_callback=None, log_every_t=100, verbose=False, progress=True, resample=None,
-                     jump_noises=None):
+                     jump_noises=None, skip_known=False):
         """DDIM over ONE scene [1, C, H, W] larger than the UNet's image size (see EODiffusion.sampling_scene and
         eo_diffusion_amd/tiling.py): per step the RePaint mix (mask / x0 scene-sized), the UNet on overlapping tiles in chunks of
         tile_batch, the blend of the noise estimates, ONE scene-level eod_ddim_step.  Classifier-free guidance runs per chunk through
@@ -153,8 +153,13 @@ class DDIMSampler(object):
         mix_noises ([S, 1, C, H, W]) inject the draws as in ddim_sampling(); otherwise they come from the device generator, scene-sized
         (the eta-noise only when sigma_t != 0).  With overlap = 0 and injected draws the result equals sample() on the tiles, bit for
         bit.  resample=(jump_length, jump_n_sample) / jump_noises ([jumps, 1, C, H, W]): RePaint resampling as in ddim_sampling(), the
-        forward moves on the SCENE.  Returns (scene, intermediates) like sample()."""
-        from ..tiling import gather_padded, tile_slots, tiled_estimate
+        forward moves on the SCENE.  Returns (scene, intermediates) like sample().
+        skip_known=True (needs mask / x0): only the tiles whose window holds a hole pixel (a mask value != 1 in any channel) go through
+        the UNet, as in EODiffusion.sampling_scene; conditioning is cut for those tiles only.  The returned scene equals the
+        skip_known=False scene bit for bit at every estimated pixel and is `x0` at every other pixel.  intermediates and img_callback
+        see the RAW states, which are meaningful at estimated pixels only (elsewhere: a step with a zero estimate); only the
+        returned scene goes through keep_known.  No tile active: (x0, intermediates of x0 alone), the UNet is never called."""
+        from ..tiling import active_tiles, gather_padded, keep_known, tile_slots, tiled_estimate
         what = "DDIMSampler.sample_scene"
         m = self.model
         device = m.betas.device
@@ -163,15 +168,26 @@ class DDIMSampler(object):
         # (the walk is fixed, and the injected draws counted against it, before anything is launched; make_schedule below yields the same steps)
         visits, jump_after = resample_plan(what, resample, make_ddim_timesteps("uniform", S, m.timesteps, verbose=False).shape[0],
                                            (("step_noises", step_noises), ("mix_noises", mix_noises)), jump_noises)
-        chunk, _ = tile_slots(plan, tile_batch)
+        tile_slots(plan, tile_batch)  # (refuses a bad tile_batch)
         if (mask is None) != (x0 is None):
             raise _lib.EodError(f"{what}: mask and x0 go together (RePaint mix of the known region)")
+        if skip_known and mask is None:
+            raise _lib.EodError(f"{what}: skip_known=True needs a known region (mask and x0); there is nothing to skip without one")
+        full = plan  # (plan: the tiles that go through the UNet -- with skip_known the subset of the active ones)
         if mask is not None:
             x0 = m._scene_tensor(what, "x0", x0, C, plan, device)
             mk = torch.as_tensor(mask)
             if mk.dim() < 2 or tuple(mk.shape[-2:]) != (plan.H, plan.W):
                 raise _lib.EodError(f"{what}: `mask` must be scene-sized ({plan.H} x {plan.W}), got {tuple(mk.shape)}")
             mask = m._broadcast_mask(mk.to(device), x0)
+            if skip_known:
+                active = active_tiles(mask, full)
+                if active.size == 0:
+                    known = x0.clone()
+                    return known, {"x_inter": [known], "pred_x0": [known]}
+                if active.size < full.n_tiles:
+                    plan = full.subset(active)
+        chunk, _ = tile_slots(plan, tile_batch)
         guided = unconditional_conditioning is not None and unconditional_guidance_scale != 1.0
         c_tiles = uc_tiles = None
         if conditioning is not None:
@@ -232,7 +248,7 @@ class DDIMSampler(object):
                 z = (m._scene_tensor(what, "jump_noises[j]", jump_noises[j], C, plan, device) if jump_noises is not None
                      else torch.randn_like(img))
                 img = m._renoise(img, self.ddim_alphas[a], self.ddim_alphas[b_up], z)
-        return img, intermediates
+        return (img if plan is full else keep_known(img, x0, plan)), intermediates
 
     @torch.no_grad()
     def p_sample_ddim(self, x, c, t, index, repeat_noise=False, use_original_steps=False, quantize_denoised=False,

@@ -281,7 +281,7 @@ class EODiffusion(nn.Module):
 
     @torch.no_grad()
     def sampling_scene(self, scene_size, clipped_reverse_diffusion=True, device="cpu", cond=None, y=None, *, overlap=0, tile_batch=16,
-                       x_T=None, noises=None, rng="philox", seed=0, progress=True, resample=None, jump_noises=None):
+                       x_T=None, noises=None, rng="philox", seed=0, progress=True, resample=None, jump_noises=None, skip_known=False):
         """Reverse chain over ONE scene [1, C, H, W], H, W >= image_size, with the UNet applied to overlapping image_size tiles
         (eo_diffusion_amd/tiling.py).  Per step: RePaint mix on the scene (cond_type == "sum"; cond [1, C+1, H, W] split as in
         sampling()) -> gather the tiles -> UNet on chunks of tile_batch tiles (same t, y broadcast, concatenated cond cut into the
@@ -291,8 +291,16 @@ class EODiffusion(nn.Module):
         rng="philox" (default; the scene is sample 0 of `seed`) | "torch" (the reference's draw order on scene-sized tensors);
         x_T [1,C,H,W] / noises ([T,1,C,H,W] or a callable k -> tensor) inject the draws as in sampling().
         resample=(jump_length, jump_n_sample) / jump_noises: RePaint resampling as in sampling(), with eod_renoise on the SCENE (one
-        state, one noise field, like the update) and the same Philox keys."""
-        from ..tiling import gather_padded, tile_slots
+        state, one noise field, like the update) and the same Philox keys.
+        skip_known=True (needs the known region of cond_type == "sum"): only the tiles whose window holds a hole pixel (mask != 1) go
+        through the UNet -- classified once, before the loop (tiling.active_tiles: the call's one extra host synchronisation);
+        chunk = min(tile_batch, n_active).  The blended estimate is 0 where a covering tile was skipped; the mix replaces the state
+        there before every evaluation, so the result equals the skip_known=False scene bit for bit at every estimated pixel (all hole
+        pixels, and the known pixels whose covering tiles are all active) and is `gt` itself at every other pixel, where the full
+        call returns one reverse step applied to q_sample(gt, 0).  (Where q_sample(gt) is exactly -0.0 the two calls may differ in
+        the sign of a zero.)  Draws and Philox keys are those of the full call.  Every tile active: the full path is taken; none:
+        `gt` is returned and the UNet is never called."""
+        from ..tiling import active_tiles, gather_padded, keep_known, tile_slots
         what = "EODiffusion.sampling_scene"
         plan, dev = self._scene_args(what, scene_size, overlap, device)
         if rng not in ("philox", "torch"):
@@ -300,13 +308,26 @@ class EODiffusion(nn.Module):
         self._tables_on(dev)
         visits, jump_after = resample_plan(what, resample, self.timesteps, (("noises", noises),), jump_noises)
         shape = (1, self.in_channels, plan.H, plan.W)
-        chunk, _ = tile_slots(plan, tile_batch)
+        tile_slots(plan, tile_batch)  # (refuses a bad tile_batch)
+        if skip_known and (cond is None or self.cond_type != "sum"):
+            raise _lib.EodError(f"{what}: skip_known=True needs a known region (cond_type='sum' with cond = cat(gt, mask)); there is "
+                                "nothing to skip without one")
         gt = mask = cond_tiles = None
+        tiles = plan  # the tiles that go through the UNet: the plan, or with skip_known the subset of the active ones
         if cond is not None and self.cond_type == "sum":
             cond = self._scene_tensor(what, "cond", cond, None, plan, dev)
             if cond.shape[1] < 4:
                 raise _lib.EodError(f"{what}: cond_type='sum' needs cond = cat(gt[3], mask[1]), got {cond.shape[1]} channels")
             gt, mask = cond[:, :3].contiguous(), cond[:, 3][:, None].contiguous()
+            if skip_known:
+                if gt.shape[1] != self.in_channels:
+                    raise _lib.EodError(f"{what}: skip_known=True returns gt outside the estimated pixels; gt has {gt.shape[1]} channels, "
+                                        f"the state {self.in_channels}")
+                active = active_tiles(mask, plan)
+                if active.size == 0:
+                    return gt.clone()
+                if active.size < plan.n_tiles:
+                    tiles = plan.subset(active)
         elif cond is not None:
             cond_tiles = gather_padded(self._scene_tensor(what, "cond", cond, None, plan, dev), plan, tile_batch)
         if x_T is not None:
@@ -315,7 +336,7 @@ class EODiffusion(nn.Module):
             x_t = self._philox(shape, dev, seed, 0, self.timesteps, 0)
         else:
             x_t = torch.randn(shape).to(dev)
-        y_chunk = self._scene_labels(y, chunk, dev)
+        y_chunk = self._scene_labels(y, tile_slots(tiles, tile_batch)[0], dev)
         acp = self.alphas_cumprod.tolist() if jump_after else None  # ONE host copy of the buffer for the whole call
         seen = {}  # timestep -> evaluations so far
         it = tqdm(visits, desc="Sampling scene") if progress else visits
@@ -328,7 +349,7 @@ class EODiffusion(nn.Module):
                 noise = self._philox(shape, dev, seed, 0, i, 1 + 2 * v)
             else:
                 noise = torch.randn_like(x_t)
-            x_t = self._scene_step(x_t, i, noise, plan, tile_batch, clipped_reverse_diffusion, gt, mask, cond_tiles, y_chunk)
+            x_t = self._scene_step(x_t, i, noise, tiles, tile_batch, clipped_reverse_diffusion, gt, mask, cond_tiles, y_chunk)
             if k + 1 in jump_after:
                 j, a, b = jump_after[k + 1]
                 if jump_noises is not None:
@@ -338,12 +359,13 @@ class EODiffusion(nn.Module):
                     x_t = self._renoise(x_t, acp[a], acp[b], key=(seed, 0, b, 2 * seen[b]))
                 else:
                     x_t = self._renoise(x_t, acp[a], acp[b], torch.randn_like(x_t))
-        return x_t
+        return x_t if tiles is plan else keep_known(x_t, gt, tiles)
 
     @torch.no_grad()
     def _scene_step(self, x_t, i, noise, plan, tile_batch, clip, gt=None, mask=None, cond_tiles=None, y_chunk=None):
         """one step of sampling_scene at timestep i: [RePaint mix on the scene] -> tiles -> UNet in chunks -> blended estimate -> scene
-        update.  cond_tiles: tiling.gather_padded(cond, plan, tile_batch); y_chunk: the label repeated tile_slots(...)[0] times."""
+        update.  cond_tiles: tiling.gather_padded(cond, plan, tile_batch); y_chunk: the label repeated tile_slots(...)[0] times.
+        `plan`: a TilePlan, or a TileSubset (then only its tiles are evaluated and the estimate is 0 outside its estimated pixels)."""
         from ..tiling import tile_slots, tiled_estimate
         dev = x_t.device
         chunk, _ = tile_slots(plan, tile_batch)

@@ -4,6 +4,9 @@
     tiles = gather_tiles(scene, plan)            [1,C,H,W] (or [C,H,W]) -> [n_tiles, C, tile, tile]    eod_scene_gather
     scene = blend_tiles(tiles, plan)             [n_tiles, C, tile, tile] -> [1, C, H, W]              eod_scene_blend
     e     = tiled_estimate(scene, plan, tile_batch, fn)   gather -> fn on chunks of tile_batch tiles -> blend
+    idx   = active_tiles(mask, plan)             the tiles whose window holds a hole pixel of a RePaint mask      eod_scene_tile_active
+    sub   = plan.subset(idx)                     a TileSubset: goes wherever a plan goes above, on the listed tiles only
+    out   = keep_known(x, known, sub)            x at estimated pixels, known elsewhere                           eod_scene_keep_known
 
 Plan, per axis of length L: origins min(i * (tile - overlap), L - tile) until the axis is covered -- the last tile is shifted
 inwards, never padded.  Weights, per axis, [n][tile]: 1 in a tile's interior, a linear ramp (k + 1) / (o + 1) across the o pixels
@@ -15,7 +18,13 @@ which is what makes overlap = 0 (and every tile interior) pass the UNet's estima
 
 The blend is  e[c, y, x] = sum over the tiles covering (y, x), in ascending i, of w_i * e_i : products rounded once, added left to
 right, no atomics -- a pure function of its inputs (csrc/scene.hip).  This maps to the reference's patch cutting in its data
-loaders (data_utils' patch_overlap), not to a line of its samplers: the reference never puts the patches back together."""
+loaders (data_utils' patch_overlap), not to a line of its samplers: the reference never puts the patches back together.
+
+Tile subsets (skip_known of the scene samplers).  Known: mask == 1.  A HOLE pixel has a mask value other than exactly 1.0f in some mask
+channel (soft values and NaN included).  A tile is ACTIVE iff its window holds a hole pixel; a pixel is ESTIMATED iff every tile that
+covers it is active (every hole pixel is; a pixel that is not estimated is known).  With only the active tiles evaluated the blend has
+the unchanged weights, order and roundings at every estimated pixel and is 0.0f elsewhere -- where the RePaint mix replaces the state
+by q_sample(gt) before every network evaluation anyway, so the active tiles see the inputs of the full call."""
 import numpy as np
 
 from . import _lib
@@ -94,6 +103,25 @@ class TilePlan:
             cx[o:o + self.tile] += 1
         return cy[:, None] * cx[None, :]
 
+    def active_tiles(self, mask):
+        """ascending int32 indices of the tiles whose window holds a hole pixel of the host array `mask` ([H, W] or [..., H, W]: a
+        value != 1 in any leading index makes the pixel a hole, NaN included)"""
+        m = np.asarray(mask)
+        if m.ndim < 2 or tuple(m.shape[-2:]) != (self.H, self.W):
+            raise _lib.EodError(f"active_tiles: the mask must be [..., {self.H}, {self.W}], got {tuple(m.shape)}")
+        hole = (m != 1).reshape(-1, self.H, self.W).any(axis=0)
+        # an integral image answers every window in one pass
+        ii = np.zeros((self.H + 1, self.W + 1), dtype=np.int64)
+        ii[1:, 1:] = hole.cumsum(axis=0).cumsum(axis=1)
+        y0, x0 = self.origins_y.astype(np.int64)[:, None], self.origins_x.astype(np.int64)[None, :]
+        s = self.tile
+        count = ii[y0 + s, x0 + s] - ii[y0, x0 + s] - ii[y0 + s, x0] + ii[y0, x0]
+        return np.flatnonzero(count.reshape(-1) > 0).astype(np.int32)
+
+    def subset(self, indices):
+        """the TileSubset of the listed tiles (ascending, unique, in range -- refused otherwise)"""
+        return TileSubset(self, indices)
+
     def device_tables(self, device):
         """(origins_y, origins_x, wy, wx) as device tensors, uploaded once per device"""
         import torch
@@ -103,6 +131,89 @@ class TilePlan:
             hit = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (self.origins_y, self.origins_x, self.wy, self.wx))
             self._dev[dev] = hit
         return hit
+
+
+class TileSubset:
+    """Some tiles of a TilePlan, in ascending order: what gather_tiles / blend_tiles / tile_slots / gather_padded / tiled_estimate
+    work on when only these tiles go through the network.
+
+    plan; index int32 [n_tiles] (the listed tiles; n_tiles = how many are LISTED); slot_of int32 [plan.n_tiles] (position of a tile in
+    the list, -1 = absent); H, W, tile, overlap as the plan's.  Raises EodError for an empty, unsorted, repeated or out-of-range list."""
+
+    def __init__(self, plan, indices):
+        if not isinstance(plan, TilePlan):
+            raise _lib.EodError(f"TileSubset: a subset is taken of a TilePlan, got {type(plan).__name__}")
+        raw = np.asarray(list(indices) if not isinstance(indices, np.ndarray) else indices)
+        if raw.ndim != 1 or raw.size < 1:
+            raise _lib.EodError(f"TileSubset: the tile list must be a non-empty 1-D sequence of tile indices, got shape {tuple(raw.shape)}")
+        if not np.issubdtype(raw.dtype, np.integer):
+            raise _lib.EodError(f"TileSubset: tile indices are integers, got {raw.dtype}")
+        idx = raw.astype(np.int64)
+        if idx.min() < 0 or idx.max() >= plan.n_tiles:
+            raise _lib.EodError(f"TileSubset: tile indices must be in [0, {plan.n_tiles}), got {int(idx.min())} .. {int(idx.max())}")
+        if np.any(np.diff(idx) <= 0):
+            raise _lib.EodError("TileSubset: tile indices must be ascending and unique")
+        self.plan = plan
+        self.index = idx.astype(np.int32)
+        self.n_tiles = int(idx.size)
+        self.slot_of = np.full(plan.n_tiles, -1, dtype=np.int32)
+        self.slot_of[idx] = np.arange(idx.size, dtype=np.int32)
+        self.H, self.W, self.tile, self.overlap = plan.H, plan.W, plan.tile, plan.overlap
+        self._dev = {}
+
+    def __repr__(self):
+        return f"TileSubset({self.n_tiles} of {self.plan.n_tiles} tiles of {self.plan!r})"
+
+    def origin(self, k):
+        """(y0, x0) of the tile in slot k"""
+        return self.plan.origin(self.index[int(k)])
+
+    def estimated(self):
+        """bool [H][W]: the pixels whose covering tiles are all listed"""
+        p = self.plan
+        est = np.ones((p.H, p.W), dtype=bool)
+        for i in np.flatnonzero(self.slot_of < 0):
+            y0, x0 = p.origin(i)
+            est[y0:y0 + p.tile, x0:x0 + p.tile] = False
+        return est
+
+    def device_tables(self, device):
+        """(index, slot_of) as device int32 tensors, uploaded once per device"""
+        import torch
+        dev = torch.device(device)
+        hit = self._dev.get(dev)
+        if hit is None:
+            hit = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (self.index, self.slot_of))
+            self._dev[dev] = hit
+        return hit
+
+
+def active_tiles(mask, plan):
+    """TilePlan.active_tiles for a mask on the GPU ([H, W] or [..., H, W]): eod_scene_tile_active, then ONE device-to-host copy of
+    plan.n_tiles ints (the only synchronisation).  Ascending int32 tile indices (numpy)."""
+    import torch
+    from .engine import current_stream_ptr, require_gpu
+    require_gpu(mask, "active_tiles")
+    if not isinstance(plan, TilePlan):
+        raise _lib.EodError(f"active_tiles: `plan` is a TilePlan, got {type(plan).__name__}")
+    if mask.dim() < 2 or tuple(mask.shape[-2:]) != (plan.H, plan.W):
+        raise _lib.EodError(f"active_tiles: the mask must be [..., {plan.H}, {plan.W}], got {tuple(mask.shape)}")
+    m = mask.reshape(-1, plan.H, plan.W)
+    m = m if (m.dtype == torch.float32 and m.is_contiguous()) else m.float().contiguous()
+    active = torch.empty(plan.n_tiles, dtype=torch.int32, device=m.device)
+    oy, ox, _, _ = plan.device_tables(m.device)
+    _lib.check(_lib.lib().eod_scene_tile_active(m.data_ptr(), active.data_ptr(), m.shape[0], plan.H, plan.W, plan.tile, oy.data_ptr(),
+                                                ox.data_ptr(), plan.nty, plan.ntx, current_stream_ptr(m.device)), "eod_scene_tile_active")
+    return np.flatnonzero(active.cpu().numpy()).astype(np.int32)
+
+
+def _split(plan):
+    """(plan, subset or None) of an argument that is either"""
+    if isinstance(plan, TileSubset):
+        return plan.plan, plan
+    if isinstance(plan, TilePlan):
+        return plan, None
+    raise _lib.EodError(f"a TilePlan or a TileSubset is needed, got {type(plan).__name__}")
 
 
 def _scene4(scene, what):
@@ -117,20 +228,28 @@ def _scene4(scene, what):
 
 def gather_tiles(scene, plan, out=None):
     """scene [1, C, H, W] (or [C, H, W]) fp32 on the GPU -> tiles [n_tiles, C, tile, tile], tile i = the window at plan.origin(i).
-    `out`: a contiguous fp32 buffer of at least n_tiles tiles (its first n_tiles are written, and returned)."""
+    `out`: a contiguous fp32 buffer of at least n_tiles tiles (its first n_tiles are written, and returned).
+    `plan` may be a TileSubset: its n_tiles listed tiles, in the list's order (eod_scene_gather_list)."""
     import torch
     from .engine import current_stream_ptr
+    plan, sub = _split(plan)
     x = _scene4(scene, "gather_tiles")
     _, c, h, w = x.shape
     if (h, w) != (plan.H, plan.W):
         raise _lib.EodError(f"gather_tiles: scene is {h} x {w}, the plan is for {plan.H} x {plan.W}")
     s = plan.tile
+    n = plan.n_tiles if sub is None else sub.n_tiles
     if out is None:
-        out = torch.empty((plan.n_tiles, c, s, s), dtype=torch.float32, device=x.device)
-    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 4 and out.shape[0] >= plan.n_tiles
+        out = torch.empty((n, c, s, s), dtype=torch.float32, device=x.device)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 4 and out.shape[0] >= n
               and tuple(out.shape[1:]) == (c, s, s)):
-        raise _lib.EodError(f"gather_tiles: `out` must be a contiguous fp32 GPU tensor [>= {plan.n_tiles}, {c}, {s}, {s}], got {tuple(out.shape)}")
+        raise _lib.EodError(f"gather_tiles: `out` must be a contiguous fp32 GPU tensor [>= {n}, {c}, {s}, {s}], got {tuple(out.shape)}")
     oy, ox, _, _ = plan.device_tables(x.device)
+    if sub is not None:
+        index, _ = sub.device_tables(x.device)
+        _lib.check(_lib.lib().eod_scene_gather_list(x.data_ptr(), out.data_ptr(), c, h, w, s, oy.data_ptr(), ox.data_ptr(), plan.nty,
+                                                    plan.ntx, index.data_ptr(), n, current_stream_ptr(x.device)), "eod_scene_gather_list")
+        return out[:n]
     _lib.check(_lib.lib().eod_scene_gather(x.data_ptr(), out.data_ptr(), c, h, w, s, oy.data_ptr(), ox.data_ptr(), plan.nty, plan.ntx,
                                            current_stream_ptr(x.device)), "eod_scene_gather")
     return out[:plan.n_tiles]
@@ -138,13 +257,17 @@ def gather_tiles(scene, plan, out=None):
 
 def blend_tiles(tiles, plan, out=None):
     """tiles [>= n_tiles, C, tile, tile] fp32 on the GPU (the first n_tiles are read) -> scene [1, C, H, W]: the weighted sum of the
-    module docstring.  Every scene element is written."""
+    module docstring.  Every scene element is written.
+    `plan` may be a TileSubset: tiles holds its n_tiles listed tiles in the list's order; the result is the full blend at the
+    subset's estimated pixels and 0.0 at every other pixel (eod_scene_blend_list)."""
     import torch
     from .engine import current_stream_ptr, require_gpu
     require_gpu(tiles, "blend_tiles")
+    plan, sub = _split(plan)
     s = plan.tile
-    if tiles.dim() != 4 or tiles.shape[0] < plan.n_tiles or tuple(tiles.shape[2:]) != (s, s):
-        raise _lib.EodError(f"blend_tiles: tiles must be [>= {plan.n_tiles}, C, {s}, {s}], got {tuple(tiles.shape)}")
+    n = plan.n_tiles if sub is None else sub.n_tiles
+    if tiles.dim() != 4 or tiles.shape[0] < n or tuple(tiles.shape[2:]) != (s, s):
+        raise _lib.EodError(f"blend_tiles: tiles must be [>= {n}, C, {s}, {s}], got {tuple(tiles.shape)}")
     e = tiles if (tiles.dtype == torch.float32 and tiles.is_contiguous()) else tiles.float().contiguous()
     c = e.shape[1]
     if out is None:
@@ -152,14 +275,44 @@ def blend_tiles(tiles, plan, out=None):
     elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == c * plan.H * plan.W):
         raise _lib.EodError(f"blend_tiles: `out` must be a contiguous fp32 GPU tensor of {c} x {plan.H} x {plan.W} elements")
     oy, ox, wy, wx = plan.device_tables(e.device)
+    if sub is not None:
+        _, slot_of = sub.device_tables(e.device)
+        _lib.check(_lib.lib().eod_scene_blend_list(e.data_ptr(), out.data_ptr(), wy.data_ptr(), wx.data_ptr(), oy.data_ptr(), ox.data_ptr(),
+                                                   slot_of.data_ptr(), n, c, plan.H, plan.W, s, plan.nty, plan.ntx,
+                                                   current_stream_ptr(e.device)), "eod_scene_blend_list")
+        return out
     _lib.check(_lib.lib().eod_scene_blend(e.data_ptr(), out.data_ptr(), wy.data_ptr(), wx.data_ptr(), oy.data_ptr(), ox.data_ptr(), c,
                                           plan.H, plan.W, s, plan.nty, plan.ntx, current_stream_ptr(e.device)), "eod_scene_blend")
     return out
 
 
+def keep_known(x, known, subset, out=None):
+    """x, known [1, C, H, W] (or [C, H, W]) fp32 on the GPU -> [1, C, H, W]: x at the subset's estimated pixels, `known` at every
+    other pixel (the end of a skip_known call: what was never estimated is the known image itself)."""
+    import torch
+    from .engine import current_stream_ptr
+    if not isinstance(subset, TileSubset):
+        raise _lib.EodError(f"keep_known: a TileSubset is needed, got {type(subset).__name__}")
+    plan = subset.plan
+    a, b = _scene4(x, "keep_known"), _scene4(known, "keep_known")
+    if a.shape != b.shape or tuple(a.shape[2:]) != (plan.H, plan.W) or a.device != b.device:
+        raise _lib.EodError(f"keep_known: x {tuple(a.shape)} and known {tuple(b.shape)} must both be [1, C, {plan.H}, {plan.W}] on one GPU")
+    if out is None:
+        out = torch.empty_like(a)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == a.numel()):
+        raise _lib.EodError(f"keep_known: `out` must be a contiguous fp32 GPU tensor of {a.numel()} elements")
+    oy, ox, _, _ = plan.device_tables(a.device)
+    _, slot_of = subset.device_tables(a.device)
+    _lib.check(_lib.lib().eod_scene_keep_known(a.data_ptr(), b.data_ptr(), slot_of.data_ptr(), subset.n_tiles, oy.data_ptr(), ox.data_ptr(),
+                                               a.shape[1], plan.H, plan.W, plan.tile, plan.nty, plan.ntx, out.data_ptr(),
+                                               current_stream_ptr(a.device)), "eod_scene_keep_known")
+    return out
+
+
 def tile_slots(plan, tile_batch):
     """(chunk, slots): tiles go through the network `chunk` = min(tile_batch, n_tiles) at a time; the last chunk is padded with copies
-    of the last tile up to `slots` = a multiple of chunk, so ONE launch program (one batch size) serves the whole call."""
+    of the last tile up to `slots` = a multiple of chunk, so ONE launch program (one batch size) serves the whole call.
+    For a TileSubset n_tiles is the number of LISTED tiles."""
     tile_batch = int(tile_batch)
     if tile_batch < 1:
         raise _lib.EodError(f"tile_batch must be at least 1, got {tile_batch}")
@@ -168,7 +321,7 @@ def tile_slots(plan, tile_batch):
 
 
 def gather_padded(scene, plan, tile_batch):
-    """gather_tiles into a buffer of tile_slots(...) tiles; the padding slots repeat the last tile"""
+    """gather_tiles into a buffer of tile_slots(...) tiles; the padding slots repeat the last (listed) tile"""
     import torch
     x = _scene4(scene, "gather_padded")
     chunk, slots = tile_slots(plan, tile_batch)
@@ -182,7 +335,9 @@ def gather_padded(scene, plan, tile_batch):
 def tiled_estimate(scene, plan, tile_batch, fn):
     """One scene-sized network estimate: gather the plan's tiles, call fn(x_chunk, lo) -> e_chunk on consecutive chunks (x_chunk
     [chunk, C, tile, tile], tile indices lo .. lo + chunk - 1; indices past n_tiles - 1 are padding, their output is dropped),
-    blend.  Allowed because a sample's bits do not depend on the batch it rides in: the result is the same for every tile_batch."""
+    blend.  Allowed because a sample's bits do not depend on the batch it rides in: the result is the same for every tile_batch.
+    With a TileSubset for `plan` only the listed tiles are gathered and evaluated: `lo` is then a SLOT number (slot k holds tile
+    subset.index[k]; slots past n_tiles - 1 repeat the last listed tile), and the result is 0.0 at pixels that are not estimated."""
     import torch
     chunk, slots = tile_slots(plan, tile_batch)
     x_tiles = gather_padded(scene, plan, tile_batch)

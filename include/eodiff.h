@@ -348,6 +348,29 @@ int eod_scene_gather(const float* scene, float* tiles, int C, int H, int W, int 
 int eod_scene_blend(const float* tiles, float* scene, const float* wy, const float* wx, const int32_t* origins_y,
                     const int32_t* origins_x, int C, int H, int W, int s, int nty, int ntx, void* stream);
 
+/* A tile SUBSET of the same plan (tiling.py TileSubset): the tiles whose window holds a hole pixel of a RePaint mask, the only ones
+ * whose estimate the next mix does not throw away.  A value of the mask is a hole when it is != 1.0f (soft values and NaN included).
+ * `index` [n_list] DEVICE int32: the listed tiles, ascending; tiles [n_list][C][s][s] holds them in that order (slot k = tile
+ * index[k]); `slot_of` [nty * ntx] DEVICE int32: the slot of each tile, -1 = not listed.  1 <= n_list <= nty * ntx.  A pixel is
+ * ESTIMATED when it is covered and every tile covering it is listed.
+ *   eod_scene_tile_active   active[i] = 1 iff any of the Cm x s x s values of mask [Cm][H][W] in tile i's window is != 1.0f, else 0;
+ *                           every entry is written (one block-level reduction per tile, stored by one lane).
+ *   eod_scene_gather_list   tiles[k] = the window of tile index[k] (bit-exact copy).
+ *   eod_scene_blend_list    at an estimated pixel eod_scene_blend's sum on tiles[slot_of[i]]: same products, same left-to-right order
+ *                           in ascending i, same roundings; 0.0f at every other pixel.  Every scene element is written.
+ *   eod_scene_keep_known    out = x at estimated pixels, known elsewhere (x, known, out [C][H][W]).
+ * The tables are never trusted with an address: an index outside [0, nty * ntx) gives a NaN tile, a slot outside [0, n_list) counts as
+ * not listed (the device arrays cannot be checked on the host without a synchronisation; the counts are, before the launch). */
+int eod_scene_tile_active(const float* mask, int32_t* active, int Cm, int H, int W, int s, const int32_t* origins_y,
+                          const int32_t* origins_x, int nty, int ntx, void* stream);
+int eod_scene_gather_list(const float* scene, float* tiles, int C, int H, int W, int s, const int32_t* origins_y,
+                          const int32_t* origins_x, int nty, int ntx, const int32_t* index, int n_list, void* stream);
+int eod_scene_blend_list(const float* tiles, float* scene, const float* wy, const float* wx, const int32_t* origins_y,
+                         const int32_t* origins_x, const int32_t* slot_of, int n_list, int C, int H, int W, int s, int nty, int ntx,
+                         void* stream);
+int eod_scene_keep_known(const float* x, const float* known, const int32_t* slot_of, int n_list, const int32_t* origins_y,
+                         const int32_t* origins_x, int C, int H, int W, int s, int nty, int ntx, float* out, void* stream);
+
 /* harness-side elementwise ops of inference.py, fp32, bit-exact vs the torch expressions:
  *   eod_repaint_cond   :100-109  cond [N][C+1][hw] = cat(image [N][C][hw], invert ? 1 - mask : mask), mask [N][1][hw]
  *   eod_postprocess    :128      mode 0: y = clip(x, 0, 1) (data in [0,1]);  mode 1: y = (x + 1) / 2 (data in [-1,1])

@@ -16,14 +16,9 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..engine import current_stream_ptr, require_gpu
+from ..engine import current_stream_ptr, f32c, require_gpu
+from . import chain
 from .util import make_ddim_sampling_parameters, make_ddim_timesteps, noise_like, resample_plan
-
-try:
-    from tqdm import tqdm
-except Exception:  # pragma: no cover
-    def tqdm(it, **kw):
-        return it
 
 
 class DDIMSampler(object):
@@ -106,16 +101,15 @@ class DDIMSampler(object):
         total_steps = timesteps.shape[0]
         visits, jump_after = resample_plan("DDIMSampler.ddim_sampling", resample, total_steps,
                                            (("step_noises", step_noises), ("mix_noises", mix_noises)), jump_noises)
-        img = torch.randn(shape, device=device) if x_T is None else x_T.to(device).float().contiguous()
+        img = torch.randn(shape, device=device) if x_T is None else f32c(x_T.to(device))
         intermediates = {"x_inter": [img], "pred_x0": [img]}
-        it = tqdm(visits, desc="DDIM Sampler", total=len(visits)) if progress else visits
         if mask is not None:
             mask = self.model._broadcast_mask(mask, img)
         if x0 is not None:
-            x0 = torch.as_tensor(x0).to(device).float().contiguous()  # (the mix noise below is then drawn on the device, too)
-        for i, index in enumerate(it):
-            step = timesteps[index]
-            ts = torch.full((b,), int(step), device=device, dtype=torch.long)
+            x0 = f32c(torch.as_tensor(x0).to(device))  # (the mix noise below is then drawn on the device, too)
+
+        def step(img, i, index, visit):
+            ts = torch.full((b,), int(timesteps[index]), device=device, dtype=torch.long)
             if mask is not None:
                 assert x0 is not None
                 # RePaint mix (ddim.py:145-148); the q_sample noise is drawn here (upstream intent)
@@ -127,18 +121,53 @@ class DDIMSampler(object):
                                               unconditional_guidance_scale=unconditional_guidance_scale,
                                               unconditional_conditioning=unconditional_conditioning,
                                               _noise=None if step_noises is None else step_noises[i])
-            if callback:
-                callback(i)
-            if img_callback:
-                img_callback(pred_x0, i)
-            if index % log_every_t == 0 or index == total_steps - 1:
-                intermediates["x_inter"].append(img)
-                intermediates["pred_x0"].append(pred_x0)
-            if i + 1 in jump_after:
-                j, a, b_up = jump_after[i + 1]
-                z = jump_noises[j].to(device) if jump_noises is not None else torch.randn_like(img)
-                img = self.model._renoise(img, self.ddim_alphas[a], self.ddim_alphas[b_up], z)
+            return self._after_step(i, index, img, pred_x0, intermediates, callback, img_callback, log_every_t, total_steps)
+
+        img = self._walk(img, visits, jump_after, step, jump_noises, lambda name, z: z.to(device), "DDIM Sampler" if progress else None)
         return img, intermediates
+
+    # ------------------------------------------------------------------ what ddim_sampling and sample_scene share
+    def _walk(self, img, visits, jump_after, step, jump_noises, as_draw, desc):
+        """chain.walk over the INDICES of the DDIM steps; a jump a -> b is eod_renoise between ddim_alphas[a] and ddim_alphas[b] with
+        jump_noises[j] (brought into shape by as_draw(name, tensor)) or a randn_like drawn when the jump happens"""
+        def jump(img, j, a, b, visits_of_b):
+            z = as_draw("jump_noises[j]", jump_noises[j]) if jump_noises is not None else torch.randn_like(img)
+            return self.model._renoise(img, self.ddim_alphas[a], self.ddim_alphas[b], z)
+        return chain.walk(img, visits, jump_after, step, jump, desc)
+
+    @staticmethod
+    def _after_step(i, index, img, pred_x0, intermediates, callback, img_callback, log_every_t, total_steps):
+        """callbacks and intermediates of evaluation number i (at step index `index`); returns img"""
+        if callback:
+            callback(i)
+        if img_callback:
+            img_callback(pred_x0, i)
+        if index % log_every_t == 0 or index == total_steps - 1:
+            intermediates["x_inter"].append(img)
+            intermediates["pred_x0"].append(pred_x0)
+        return img
+
+    def _eps(self, x, t, c, unconditional_guidance_scale=1.0, unconditional_conditioning=None):
+        """the noise estimate of a batch (for a scene: of a chunk of tiles), plain or with classifier-free guidance"""
+        if unconditional_conditioning is None or unconditional_guidance_scale == 1.0:
+            return self.model.model(x, t, cond=c)
+        # classifier-free guidance (ddim.py:177-181): one UNet call on the doubled batch, then a fused combine
+        e_both = self.model.model(torch.cat([x] * 2), torch.cat([t] * 2), cond=torch.cat([unconditional_conditioning, c]))
+        e_u, e_c = e_both[: x.shape[0]], e_both[x.shape[0]:]
+        e_t = torch.empty_like(e_c)
+        _lib.check(_lib.lib().eod_cfg_combine(e_u.data_ptr(), e_c.data_ptr(), float(unconditional_guidance_scale),
+                                              e_t.data_ptr(), e_t.numel(), current_stream_ptr(x.device)), "eod_cfg_combine")
+        return e_t
+
+    def _ddim_update(self, x, e_t, noise, index, temperature):
+        """(x_prev, pred_x0) of step `index` in one pass; noise None: sigma_t is 0 and nothing is read"""
+        x = f32c(x)
+        x_prev, pred_x0 = torch.empty_like(x), torch.empty_like(x)
+        _lib.check(_lib.lib().eod_ddim_step(x.data_ptr(), e_t.data_ptr(), _lib.ptr(noise), float(self.ddim_alphas[index]),
+                                            float(self.ddim_alphas_prev[index]), float(self.ddim_sigmas[index]),
+                                            float(self.ddim_sqrt_one_minus_alphas[index]), float(temperature), x_prev.data_ptr(),
+                                            pred_x0.data_ptr(), x.numel(), current_stream_ptr(x.device)), "eod_ddim_step")
+        return x_prev, pred_x0
 
     @torch.no_grad()
     def sample_scene(self, S, scene_size, *, overlap=0, tile_batch=16, conditioning=None, mask=None, x0=None, eta=0.0, x_T=None,
@@ -148,7 +177,7 @@ class DDIMSampler(object):
         """DDIM over ONE scene [1, C, H, W] larger than the UNet's image size (see EODiffusion.sampling_scene and
         eo_diffusion_amd/tiling.py): per step the RePaint mix (mask / x0 scene-sized), the UNet on overlapping tiles in chunks of
         tile_batch, the blend of the noise estimates, ONE scene-level eod_ddim_step.  Classifier-free guidance runs per chunk through
-        the doubled-batch call of p_sample_ddim and the COMBINED estimate is blended.  conditioning / unconditional_conditioning are
+        the doubled-batch call p_sample_ddim makes (_eps) and the COMBINED estimate is blended.  conditioning / unconditional_conditioning are
         scene-sized [1, Cc, H, W] (channel-concatenated inside the UNet) and are cut into the same tiles once.  step_noises /
         mix_noises ([S, 1, C, H, W]) inject the draws as in ddim_sampling(); otherwise they come from the device generator, scene-sized
         (the eta-noise only when sigma_t != 0).  With overlap = 0 and injected draws the result equals sample() on the tiles, bit for
@@ -159,7 +188,7 @@ class DDIMSampler(object):
         skip_known=False scene bit for bit at every estimated pixel and is `x0` at every other pixel.  intermediates and img_callback
         see the RAW states, which are meaningful at estimated pixels only (elsewhere: a step with a zero estimate); only the
         returned scene goes through keep_known.  No tile active: (x0, intermediates of x0 alone), the UNet is never called."""
-        from ..tiling import active_tiles, gather_padded, keep_known, tile_slots, tiled_estimate
+        from ..tiling import gather_padded, keep_known, tile_slots, tiled_estimate, tiles_to_evaluate
         what = "DDIMSampler.sample_scene"
         m = self.model
         device = m.betas.device
@@ -171,8 +200,6 @@ class DDIMSampler(object):
         tile_slots(plan, tile_batch)  # (refuses a bad tile_batch)
         if (mask is None) != (x0 is None):
             raise _lib.EodError(f"{what}: mask and x0 go together (RePaint mix of the known region)")
-        if skip_known and mask is None:
-            raise _lib.EodError(f"{what}: skip_known=True needs a known region (mask and x0); there is nothing to skip without one")
         full = plan  # (plan: the tiles that go through the UNet -- with skip_known the subset of the active ones)
         if mask is not None:
             x0 = m._scene_tensor(what, "x0", x0, C, plan, device)
@@ -180,13 +207,10 @@ class DDIMSampler(object):
             if mk.dim() < 2 or tuple(mk.shape[-2:]) != (plan.H, plan.W):
                 raise _lib.EodError(f"{what}: `mask` must be scene-sized ({plan.H} x {plan.W}), got {tuple(mk.shape)}")
             mask = m._broadcast_mask(mk.to(device), x0)
-            if skip_known:
-                active = active_tiles(mask, full)
-                if active.size == 0:
-                    known = x0.clone()
-                    return known, {"x_inter": [known], "pred_x0": [known]}
-                if active.size < full.n_tiles:
-                    plan = full.subset(active)
+        plan = tiles_to_evaluate(what, full, mask, skip_known, "mask and x0")
+        if plan is None:
+            known = x0.clone()
+            return known, {"x_inter": [known], "pred_x0": [known]}
         chunk, _ = tile_slots(plan, tile_batch)
         guided = unconditional_conditioning is not None and unconditional_guidance_scale != 1.0
         c_tiles = uc_tiles = None
@@ -202,52 +226,25 @@ class DDIMSampler(object):
         total_steps = self.ddim_timesteps.shape[0]
         assert total_steps == len(set(visits))
         intermediates = {"x_inter": [img], "pred_x0": [img]}
-        it = tqdm(visits, desc="DDIM Sampler (scene)", total=len(visits)) if progress else visits
+        as_scene = lambda name, z: m._scene_tensor(what, name, z, C, plan, device)
 
-        def eps(x, lo, ts):
-            c = None if c_tiles is None else c_tiles[lo:lo + chunk]
-            if not guided:
-                return m.model(x, ts, cond=c)
-            e_both = m.model(torch.cat([x] * 2), torch.cat([ts] * 2), cond=torch.cat([uc_tiles[lo:lo + chunk], c]))
-            e_u, e_c = e_both[:chunk], e_both[chunk:]
-            e_t = torch.empty_like(e_c)
-            _lib.check(_lib.lib().eod_cfg_combine(e_u.data_ptr(), e_c.data_ptr(), float(unconditional_guidance_scale), e_t.data_ptr(),
-                                                  e_t.numel(), current_stream_ptr(device)), "eod_cfg_combine")
-            return e_t
-
-        for i, index in enumerate(it):
-            step = self.ddim_timesteps[index]
+        def step(img, i, index, visit):
+            t = int(self.ddim_timesteps[index])
             if mask is not None:
-                ts1 = torch.full((1,), int(step), device=device, dtype=torch.long)
-                nz = (m._scene_tensor(what, "mix_noises[i]", mix_noises[i], C, plan, device) if mix_noises is not None
-                      else torch.randn_like(x0))
-                img = m._repaint_mix(img, x0, mask, ts1, nz)
-            ts = torch.full((chunk,), int(step), device=device, dtype=torch.long)
-            e_t = tiled_estimate(img, plan, tile_batch, lambda x, lo: eps(x, lo, ts))
-            sigma_t = float(self.ddim_sigmas[index])
+                nz = as_scene("mix_noises[i]", mix_noises[i]) if mix_noises is not None else torch.randn_like(x0)
+                img = m._repaint_mix(img, x0, mask, torch.full((1,), t, device=device, dtype=torch.long), nz)
+            ts = torch.full((chunk,), t, device=device, dtype=torch.long)
+            e_t = tiled_estimate(img, plan, tile_batch, lambda x, lo: self._eps(
+                x, ts, None if c_tiles is None else c_tiles[lo:lo + chunk], unconditional_guidance_scale,
+                None if uc_tiles is None else uc_tiles[lo:lo + chunk]))
             if step_noises is not None:
-                noise = m._scene_tensor(what, "step_noises[i]", step_noises[i], C, plan, device)
+                noise = as_scene("step_noises[i]", step_noises[i])
             else:
-                noise = torch.randn_like(img) if sigma_t != 0.0 else None
-            x_prev, pred_x0 = torch.empty_like(img), torch.empty_like(img)
-            _lib.check(_lib.lib().eod_ddim_step(img.data_ptr(), e_t.data_ptr(), _lib.ptr(noise), float(self.ddim_alphas[index]),
-                                                float(self.ddim_alphas_prev[index]), sigma_t,
-                                                float(self.ddim_sqrt_one_minus_alphas[index]), float(temperature),
-                                                x_prev.data_ptr(), pred_x0.data_ptr(), img.numel(), current_stream_ptr(device)),
-                       "eod_ddim_step")
-            img = x_prev
-            if callback:
-                callback(i)
-            if img_callback:
-                img_callback(pred_x0, i)
-            if index % log_every_t == 0 or index == total_steps - 1:
-                intermediates["x_inter"].append(img)
-                intermediates["pred_x0"].append(pred_x0)
-            if i + 1 in jump_after:
-                j, a, b_up = jump_after[i + 1]
-                z = (m._scene_tensor(what, "jump_noises[j]", jump_noises[j], C, plan, device) if jump_noises is not None
-                     else torch.randn_like(img))
-                img = m._renoise(img, self.ddim_alphas[a], self.ddim_alphas[b_up], z)
+                noise = torch.randn_like(img) if float(self.ddim_sigmas[index]) != 0.0 else None
+            img, pred_x0 = self._ddim_update(img, e_t, noise, index, temperature)
+            return self._after_step(i, index, img, pred_x0, intermediates, callback, img_callback, log_every_t, total_steps)
+
+        img = self._walk(img, visits, jump_after, step, jump_noises, as_scene, "DDIM Sampler (scene)" if progress else None)
         return (img if plan is full else keep_known(img, x0, plan)), intermediates
 
     @torch.no_grad()
@@ -259,30 +256,8 @@ class DDIMSampler(object):
             raise NotImplementedError("use_original_steps (ddim.py:188-190) is not available in the reference either")
         if quantize_denoised or score_corrector is not None or noise_dropout > 0.0:
             raise NotImplementedError("quantize_denoised / score_corrector / noise_dropout are latent-diffusion leftovers")
-        device = x.device
         if _noise is None:
             _unused = torch.randn_like(x)  # ddim.py:171 draws a tensor that is never used; keep the RNG stream aligned
-        if unconditional_conditioning is None or unconditional_guidance_scale == 1.0:
-            e_t = self.model.model(x, t, cond=c)
-        else:
-            # classifier-free guidance (ddim.py:177-181): one UNet call on the doubled batch, then a fused combine
-            x_in = torch.cat([x] * 2)
-            t_in = torch.cat([t] * 2)
-            c_in = torch.cat([unconditional_conditioning, c])
-            e_both = self.model.model(x_in, t_in, cond=c_in)
-            e_u, e_c = e_both[: x.shape[0]], e_both[x.shape[0]:]
-            e_t = torch.empty_like(e_c)
-            _lib.check(_lib.lib().eod_cfg_combine(e_u.data_ptr(), e_c.data_ptr(), float(unconditional_guidance_scale),
-                                                  e_t.data_ptr(), e_t.numel(), current_stream_ptr(device)), "eod_cfg_combine")
-        a_t = float(self.ddim_alphas[index])
-        a_prev = float(self.ddim_alphas_prev[index])
-        sigma_t = float(self.ddim_sigmas[index])
-        s1m = float(self.ddim_sqrt_one_minus_alphas[index])
-        noise = _noise.to(device).float().contiguous() if _noise is not None else noise_like(x.shape, device, repeat_noise)
-        xx = x if (x.dtype == torch.float32 and x.is_contiguous()) else x.float().contiguous()
-        x_prev = torch.empty_like(xx)
-        pred_x0 = torch.empty_like(xx)
-        _lib.check(_lib.lib().eod_ddim_step(xx.data_ptr(), e_t.data_ptr(), noise.data_ptr(), a_t, a_prev, sigma_t, s1m,
-                                            float(temperature), x_prev.data_ptr(), pred_x0.data_ptr(), xx.numel(),
-                                            current_stream_ptr(device)), "eod_ddim_step")
-        return x_prev, pred_x0
+        e_t = self._eps(x, t, c, unconditional_guidance_scale, unconditional_conditioning)
+        noise = f32c(_noise.to(x.device)) if _noise is not None else noise_like(x.shape, x.device, repeat_noise)
+        return self._ddim_update(x, e_t, noise, index, temperature)

@@ -17,18 +17,9 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from ..engine import current_stream_ptr, require_gpu
+from ..engine import current_stream_ptr, f32c, require_gpu
+from .chain import tqdm
 from .util import extract_into_tensor, make_beta_schedule, noise_like
-
-try:
-    from tqdm import tqdm
-except Exception:  # pragma: no cover
-    def tqdm(it, **kw):
-        return it
-
-
-def _f32c(t):
-    return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
 
 
 class DDPM(nn.Module):
@@ -83,7 +74,7 @@ class DDPM(nn.Module):
     def q_sample(self, x_start, t, noise=None):
         require_gpu(x_start, "DDPM.q_sample")
         noise = torch.randn_like(x_start) if noise is None else noise
-        x0, nz = _f32c(x_start), _f32c(noise)
+        x0, nz = f32c(x_start), f32c(noise)
         t = t.to(device=x0.device, dtype=torch.int64).contiguous()
         out = torch.empty_like(x0)
         n = x0.shape[0]
@@ -101,7 +92,7 @@ class DDPM(nn.Module):
         t = t.to(device=x.device, dtype=torch.int64).contiguous()
         eps = self.model(x, t, cond=cond)
         noise = noise_like(x.shape, x.device, repeat_noise) if noise is None else noise.to(x.device)
-        xx, nz = _f32c(x), _f32c(noise)
+        xx, nz = f32c(x), f32c(noise)
         out = torch.empty_like(xx)
         n = xx.shape[0]
         _lib.check(_lib.lib().eod_ldm_p_sample(
@@ -118,14 +109,14 @@ class DDPM(nn.Module):
         (img = q_sample(x0, ts) * mask + (1 - mask) * img, :1334-1336)."""
         device = self.betas.device
         b = shape[0]
-        img = torch.randn(shape, device=device) if x_T is None else x_T.to(device).float().contiguous()
+        img = torch.randn(shape, device=device) if x_T is None else f32c(x_T.to(device))
         intermediates = [img]
         T = self.num_timesteps if timesteps is None else min(timesteps, self.num_timesteps)
         log_every_t = log_every_t or self.log_every_t
         if mask is not None:
             assert x0 is not None
             assert x0.shape[2:3] == mask.shape[2:3]
-            mask = mask.to(device).float().contiguous()
+            mask = f32c(mask.to(device))
         rng = reversed(range(0, T))
         it = tqdm(rng, desc="Sampling t", total=T) if verbose else rng
         for k, i in enumerate(it):
@@ -142,8 +133,8 @@ class DDPM(nn.Module):
     def _mask_mix(self, img, x0, mask, ts, noise):
         n, c, h, w = img.shape
         out = torch.empty_like(img)
-        _lib.check(_lib.lib().eod_repaint_mix(_f32c(img).data_ptr(), _f32c(x0).data_ptr(), mask.data_ptr(),
-                                              _f32c(noise).data_ptr(), ts.data_ptr(), self.sqrt_alphas_cumprod.data_ptr(),
+        _lib.check(_lib.lib().eod_repaint_mix(f32c(img).data_ptr(), f32c(x0).data_ptr(), mask.data_ptr(),
+                                              f32c(noise).data_ptr(), ts.data_ptr(), self.sqrt_alphas_cumprod.data_ptr(),
                                               self.sqrt_one_minus_alphas_cumprod.data_ptr(), out.data_ptr(), n, c, h * w,
                                               self.num_timesteps, current_stream_ptr(img.device)), "eod_repaint_mix")
         return out

@@ -23,18 +23,9 @@ import torch.nn as nn
 
 from .. import _lib
 from ..backbones.unet_openai import *  # noqa: F401,F403  (the reference re-exports these, model.py:5)
-from ..engine import current_stream_ptr, require_gpu
+from ..engine import current_stream_ptr, f32c, require_gpu
+from . import chain
 from .util import resample_plan
-
-try:
-    from tqdm import tqdm
-except Exception:  # pragma: no cover
-    def tqdm(it, **kw):
-        return it
-
-
-def _f32c(t):
-    return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
 
 
 class EODiffusion(nn.Module):
@@ -92,7 +83,7 @@ class EODiffusion(nn.Module):
         assert x_0.shape == noise.shape
         require_gpu(x_0, "EODiffusion._forward_diffusion")
         self._tables_on(x_0.device)
-        x0, nz, t = _f32c(x_0), _f32c(noise), self._t64(t, x_0.device)
+        x0, nz, t = f32c(x_0), f32c(noise), self._t64(t, x_0.device)
         out = torch.empty_like(x0)
         n = x0.shape[0]
         _lib.check(_lib.lib().eod_q_sample(x0.data_ptr(), nz.data_ptr(), t.data_ptr(),
@@ -104,7 +95,7 @@ class EODiffusion(nn.Module):
     def _repaint_mix(self, x_t, gt, mask, t, noise):
         """x_t <- mask*q_sample(gt,t,noise) + (1-mask)*x_t  (model.py:58-60), one fused pass."""
         n, c, h, w = x_t.shape
-        x, g, m, z = _f32c(x_t), _f32c(gt), _f32c(mask), _f32c(noise)
+        x, g, m, z = f32c(x_t), f32c(gt), f32c(mask), f32c(noise)
         assert g.shape == x.shape and m.shape in ((n, 1, h, w), (n, c, h, w)), (g.shape, m.shape)
         out = torch.empty_like(x)
         if m.shape[1] != 1:  # a mask per channel: every (sample, channel) plane is a one-channel sample of the same kernel
@@ -134,7 +125,7 @@ class EODiffusion(nn.Module):
         return m.expand(n, m.shape[1], h, w).contiguous()
 
     def _ddpm_update(self, x_t, pred, noise, t, clip):
-        x, e, z = _f32c(x_t), _f32c(pred), _f32c(noise)
+        x, e, z = f32c(x_t), f32c(pred), f32c(noise)
         out = torch.empty_like(x)
         n = x.shape[0]
         _lib.check(_lib.lib().eod_ddpm_step(x.data_ptr(), e.data_ptr(), z.data_ptr(), t.data_ptr(),
@@ -147,20 +138,18 @@ class EODiffusion(nn.Module):
 
     # ------------------------------------------------------------------ reverse steps (model.py:101-150)
     @torch.no_grad()
-    def _reverse_diffusion(self, x_t, t, noise, cond=None, y=None):
-        require_gpu(x_t, "EODiffusion._reverse_diffusion")
+    def _reverse(self, what, x_t, t, noise, cond, y, clip):
+        require_gpu(x_t, what)
         self._tables_on(x_t.device)
         t = self._t64(t, x_t.device)
         pred = self.model(x_t, t, cond=cond, y=y)
-        return self._ddpm_update(x_t, pred, noise, t, clip=False)
+        return self._ddpm_update(x_t, pred, noise, t, clip=clip)
 
-    @torch.no_grad()
+    def _reverse_diffusion(self, x_t, t, noise, cond=None, y=None):
+        return self._reverse("EODiffusion._reverse_diffusion", x_t, t, noise, cond, y, False)
+
     def _reverse_diffusion_with_clip(self, x_t, t, noise, cond=None, y=None):
-        require_gpu(x_t, "EODiffusion._reverse_diffusion_with_clip")
-        self._tables_on(x_t.device)
-        t = self._t64(t, x_t.device)
-        pred = self.model(x_t, t, cond=cond, y=y)
-        return self._ddpm_update(x_t, pred, noise, t, clip=True)
+        return self._reverse("EODiffusion._reverse_diffusion_with_clip", x_t, t, noise, cond, y, True)
 
     # ------------------------------------------------------------------ noise sources
     def _philox(self, shape, dev, seed, sample0, step, stream_id):
@@ -173,8 +162,8 @@ class EODiffusion(nn.Module):
     def _renoise(self, x, acp_from, acp_to, noise=None, key=(0, 0, 0, 0)):
         """forward move of RePaint resampling between two levels of a chain: sqrt(r) x + sqrt(1 - r) z, r = acp_to / acp_from, one fused
         pass (eod_renoise).  z = `noise`, or with noise None generated in registers from the Philox key = (seed, sample0, step, stream_id)."""
-        x = _f32c(x)
-        z = None if noise is None else _f32c(noise)
+        x = f32c(x)
+        z = None if noise is None else f32c(noise)
         assert z is None or z.shape == x.shape, (z.shape, x.shape)
         out = torch.empty_like(x)
         n = x.shape[0]
@@ -183,10 +172,47 @@ class EODiffusion(nn.Module):
                                           seed, sample0, step, stream_id, current_stream_ptr(x.device)), "eod_renoise")
         return out
 
-    @staticmethod
-    def _draw(seq, k):
-        """entry k of injected draws: a tensor / list, or a callable k -> tensor"""
-        return seq(k) if callable(seq) else seq[k]
+    # ------------------------------------------------------------------ the chain sampling() and sampling_scene() share
+    def _ddpm_step(self, x_t, i, noise, estimate, clip, gt=None, mask=None, on_mixed=None):
+        """one evaluation at timestep i: [RePaint mix with `noise`] -> estimate(x_t, t, i) -> eod_ddpm_step with the same `noise`"""
+        t = torch.full((x_t.shape[0],), i, dtype=torch.int64, device=x_t.device)
+        if gt is not None:
+            x_t = self._repaint_mix(x_t, gt, mask, t, noise)
+        if on_mixed is not None:
+            on_mixed(x_t, i)
+        return self._ddpm_update(x_t, estimate(x_t, t, i), noise, t, clip=clip)
+
+    def _x_T(self, shape, dev, rng, seed, sample0):
+        """the start of a chain that was not given one: Philox, or the reference's draw on the CPU generator (model.py:48)"""
+        if rng == "philox":
+            return self._philox(shape, dev, seed, sample0, self.timesteps, chain.X_T_STREAM)
+        return torch.randn(shape).to(dev)
+
+    def _ddpm_chain(self, x_T, visits, jump_after, estimate, clip, gt, mask, *, noises, jump_noises, as_draw, rng, seed, sample0, desc,
+                    on_mixed=None):
+        """x_T down resample_plan's walk.  Draws: injected (`noises` / `jump_noises`, brought into shape by as_draw(name, tensor)),
+        rng="philox" (chain.py's keys, samples sample0 ...) or the device generator in loop order: one randn_like per evaluation for
+        BOTH the mix and the update, one per jump."""
+        shape, dev = tuple(x_T.shape), x_T.device
+        acp = self.alphas_cumprod.tolist() if jump_after else None  # ONE host copy of the buffer for the whole call
+
+        def step(x_t, k, i, visit):
+            if noises is not None:
+                noise = as_draw("noises[k]", chain.pick(noises, k))
+            elif rng == "philox":
+                noise = self._philox(shape, dev, seed, sample0, i, chain.step_stream(visit))
+            else:
+                noise = torch.randn_like(x_t)
+            return self._ddpm_step(x_t, i, noise, estimate, clip, gt, mask, on_mixed)
+
+        def jump(x_t, j, a, b, visits_of_b):
+            if jump_noises is not None:
+                return self._renoise(x_t, acp[a], acp[b], as_draw("jump_noises[j]", chain.pick(jump_noises, j)))
+            if rng == "philox":
+                return self._renoise(x_t, acp[a], acp[b], key=(seed, sample0, b, chain.jump_stream(visits_of_b)))
+            return self._renoise(x_t, acp[a], acp[b], torch.randn_like(x_t))
+
+        return chain.walk(x_T, visits, jump_after, step, jump, desc)
 
     # ------------------------------------------------------------------ sampling loop (model.py:46-75)
     @torch.no_grad()
@@ -209,45 +235,20 @@ class EODiffusion(nn.Module):
         self._tables_on(dev)
         visits, jump_after = resample_plan("EODiffusion.sampling", resample, self.timesteps, (("noises", noises),), jump_noises)
         shape = (n_samples, self.in_channels, self.image_size, self.image_size)
-        if x_T is not None:
-            x_t = _f32c(x_T.to(dev))
-        elif rng == "philox":
-            x_t = self._philox(shape, dev, seed, sample_offset, self.timesteps, 0)
-        else:
-            x_t = torch.randn(shape).to(dev)
+        x_t = f32c(x_T.to(dev)) if x_T is not None else self._x_T(shape, dev, rng, seed, sample_offset)
         gt = mask = None
         if cond is not None and self.cond_type == "sum":
             cond = cond.to(dev)
             gt, mask = cond[:n_samples, :3].contiguous(), cond[:n_samples, 3][:, None].contiguous()
             cond = None
-        acp = self.alphas_cumprod.tolist() if jump_after else None  # ONE host copy of the buffer for the whole call
-        seen = {}  # timestep -> evaluations so far
-        it = tqdm(visits, desc="Sampling") if progress else visits
-        for k, i in enumerate(it):
-            v = seen.get(i, 0)
-            seen[i] = v + 1
-            if noises is not None:
-                noise = _f32c(self._draw(noises, k).to(dev))
-            elif rng == "philox":
-                noise = self._philox(shape, dev, seed, sample_offset, i, 1 + 2 * v)
-            else:
-                noise = torch.randn_like(x_t)
-            t = torch.full((n_samples,), i, dtype=torch.int64, device=dev)
-            if self.cond_type == "sum" and gt is not None:
-                x_t = self._repaint_mix(x_t, gt, mask, t, noise)
-            if save and (i % 25 == 0 and i <= 200 or i % 100 == 0 and i <= self.timesteps):
+
+        def save_grid(x_t, i):
+            if i % 25 == 0 and i <= 200 or i % 100 == 0 and i <= self.timesteps:
                 _save_grid((x_t + 1.0) / 2.0, f"results/prova/s{idx}_{i}_pred.png", int(math.sqrt(n_samples)))
-            pred = self.model(x_t, t, cond=cond, y=y)
-            x_t = self._ddpm_update(x_t, pred, noise, t, clip=clipped_reverse_diffusion)
-            if k + 1 in jump_after:
-                j, a, b = jump_after[k + 1]
-                if jump_noises is not None:
-                    x_t = self._renoise(x_t, acp[a], acp[b], self._draw(jump_noises, j).to(dev))
-                elif rng == "philox":
-                    x_t = self._renoise(x_t, acp[a], acp[b], key=(seed, sample_offset, b, 2 * seen[b]))
-                else:
-                    x_t = self._renoise(x_t, acp[a], acp[b], torch.randn_like(x_t))
-        return x_t
+
+        return self._ddpm_chain(x_t, visits, jump_after, lambda x, t, i: self.model(x, t, cond=cond, y=y), clipped_reverse_diffusion, gt, mask,
+                                noises=noises, jump_noises=jump_noises, as_draw=lambda name, z: f32c(z.to(dev)), rng=rng, seed=seed,
+                                sample0=sample_offset, desc="Sampling" if progress else None, on_mixed=save_grid if save else None)
 
     # ------------------------------------------------------------------ whole-scene sampling (no counterpart in the reference)
     def _scene_args(self, what, scene_size, overlap, device):
@@ -269,7 +270,7 @@ class EODiffusion(nn.Module):
         if t.dim() != 4 or t.shape[0] != 1 or tuple(t.shape[2:]) != (plan.H, plan.W) or (channels is not None and t.shape[1] != channels):
             want = f"[1, {'*' if channels is None else channels}, {plan.H}, {plan.W}]"
             raise _lib.EodError(f"{what}: `{name}` must be scene-sized, {want}; got {tuple(t.shape)}")
-        return _f32c(t.to(dev))
+        return f32c(t.to(dev))
 
     def _scene_labels(self, y, chunk, dev):
         if y is None:
@@ -300,7 +301,7 @@ class EODiffusion(nn.Module):
         call returns one reverse step applied to q_sample(gt, 0).  (Where q_sample(gt) is exactly -0.0 the two calls may differ in
         the sign of a zero.)  Draws and Philox keys are those of the full call.  Every tile active: the full path is taken; none:
         `gt` is returned and the UNet is never called."""
-        from ..tiling import active_tiles, gather_padded, keep_known, tile_slots
+        from ..tiling import gather_padded, keep_known, tile_slots, tiles_to_evaluate
         what = "EODiffusion.sampling_scene"
         plan, dev = self._scene_args(what, scene_size, overlap, device)
         if rng not in ("philox", "torch"):
@@ -309,73 +310,44 @@ class EODiffusion(nn.Module):
         visits, jump_after = resample_plan(what, resample, self.timesteps, (("noises", noises),), jump_noises)
         shape = (1, self.in_channels, plan.H, plan.W)
         tile_slots(plan, tile_batch)  # (refuses a bad tile_batch)
-        if skip_known and (cond is None or self.cond_type != "sum"):
-            raise _lib.EodError(f"{what}: skip_known=True needs a known region (cond_type='sum' with cond = cat(gt, mask)); there is "
-                                "nothing to skip without one")
         gt = mask = cond_tiles = None
-        tiles = plan  # the tiles that go through the UNet: the plan, or with skip_known the subset of the active ones
         if cond is not None and self.cond_type == "sum":
             cond = self._scene_tensor(what, "cond", cond, None, plan, dev)
             if cond.shape[1] < 4:
                 raise _lib.EodError(f"{what}: cond_type='sum' needs cond = cat(gt[3], mask[1]), got {cond.shape[1]} channels")
             gt, mask = cond[:, :3].contiguous(), cond[:, 3][:, None].contiguous()
-            if skip_known:
-                if gt.shape[1] != self.in_channels:
-                    raise _lib.EodError(f"{what}: skip_known=True returns gt outside the estimated pixels; gt has {gt.shape[1]} channels, "
-                                        f"the state {self.in_channels}")
-                active = active_tiles(mask, plan)
-                if active.size == 0:
-                    return gt.clone()
-                if active.size < plan.n_tiles:
-                    tiles = plan.subset(active)
-        elif cond is not None:
+            if skip_known and gt.shape[1] != self.in_channels:
+                raise _lib.EodError(f"{what}: skip_known=True returns gt outside the estimated pixels; gt has {gt.shape[1]} channels, "
+                                    f"the state {self.in_channels}")
+        tiles = tiles_to_evaluate(what, plan, mask, skip_known, "cond_type='sum' with cond = cat(gt, mask)")
+        if tiles is None:
+            return gt.clone()
+        if cond is not None and gt is None:
             cond_tiles = gather_padded(self._scene_tensor(what, "cond", cond, None, plan, dev), plan, tile_batch)
-        if x_T is not None:
-            x_t = self._scene_tensor(what, "x_T", x_T, self.in_channels, plan, dev)
-        elif rng == "philox":
-            x_t = self._philox(shape, dev, seed, 0, self.timesteps, 0)
-        else:
-            x_t = torch.randn(shape).to(dev)
-        y_chunk = self._scene_labels(y, tile_slots(tiles, tile_batch)[0], dev)
-        acp = self.alphas_cumprod.tolist() if jump_after else None  # ONE host copy of the buffer for the whole call
-        seen = {}  # timestep -> evaluations so far
-        it = tqdm(visits, desc="Sampling scene") if progress else visits
-        for k, i in enumerate(it):
-            v = seen.get(i, 0)
-            seen[i] = v + 1
-            if noises is not None:
-                noise = self._scene_tensor(what, "noises[k]", self._draw(noises, k), self.in_channels, plan, dev)
-            elif rng == "philox":
-                noise = self._philox(shape, dev, seed, 0, i, 1 + 2 * v)
-            else:
-                noise = torch.randn_like(x_t)
-            x_t = self._scene_step(x_t, i, noise, tiles, tile_batch, clipped_reverse_diffusion, gt, mask, cond_tiles, y_chunk)
-            if k + 1 in jump_after:
-                j, a, b = jump_after[k + 1]
-                if jump_noises is not None:
-                    z = self._scene_tensor(what, "jump_noises[j]", self._draw(jump_noises, j), self.in_channels, plan, dev)
-                    x_t = self._renoise(x_t, acp[a], acp[b], z)
-                elif rng == "philox":
-                    x_t = self._renoise(x_t, acp[a], acp[b], key=(seed, 0, b, 2 * seen[b]))
-                else:
-                    x_t = self._renoise(x_t, acp[a], acp[b], torch.randn_like(x_t))
+        as_scene = lambda name, z: self._scene_tensor(what, name, z, self.in_channels, plan, dev)
+        x_t = as_scene("x_T", x_T) if x_T is not None else self._x_T(shape, dev, rng, seed, 0)
+        estimate = self._scene_estimate(tiles, tile_batch, cond_tiles, self._scene_labels(y, tile_slots(tiles, tile_batch)[0], dev))
+        x_t = self._ddpm_chain(x_t, visits, jump_after, estimate, clipped_reverse_diffusion, gt, mask, noises=noises, jump_noises=jump_noises,
+                               as_draw=as_scene, rng=rng, seed=seed, sample0=0, desc="Sampling scene" if progress else None)
         return x_t if tiles is plan else keep_known(x_t, gt, tiles)
+
+    def _scene_estimate(self, plan, tile_batch, cond_tiles, y_chunk):
+        """estimate(x_t, t, i) of a scene: tiles -> UNet in chunks -> blended estimate (tiling.tiled_estimate)"""
+        from ..tiling import tile_slots, tiled_estimate
+        chunk, _ = tile_slots(plan, tile_batch)
+
+        def estimate(x_t, t, i):
+            t_chunk = torch.full((chunk,), i, dtype=torch.int64, device=x_t.device)
+            return tiled_estimate(x_t, plan, tile_batch, lambda x, lo: self.model(
+                x, t_chunk, cond=None if cond_tiles is None else cond_tiles[lo:lo + chunk], y=y_chunk))
+        return estimate
 
     @torch.no_grad()
     def _scene_step(self, x_t, i, noise, plan, tile_batch, clip, gt=None, mask=None, cond_tiles=None, y_chunk=None):
         """one step of sampling_scene at timestep i: [RePaint mix on the scene] -> tiles -> UNet in chunks -> blended estimate -> scene
         update.  cond_tiles: tiling.gather_padded(cond, plan, tile_batch); y_chunk: the label repeated tile_slots(...)[0] times.
         `plan`: a TilePlan, or a TileSubset (then only its tiles are evaluated and the estimate is 0 outside its estimated pixels)."""
-        from ..tiling import tile_slots, tiled_estimate
-        dev = x_t.device
-        chunk, _ = tile_slots(plan, tile_batch)
-        t = torch.full((1,), i, dtype=torch.int64, device=dev)
-        t_chunk = torch.full((chunk,), i, dtype=torch.int64, device=dev)
-        if gt is not None:
-            x_t = self._repaint_mix(x_t, gt, mask, t, noise)
-        pred = tiled_estimate(x_t, plan, tile_batch, lambda x, lo: self.model(
-            x, t_chunk, cond=None if cond_tiles is None else cond_tiles[lo:lo + chunk], y=y_chunk))
-        return self._ddpm_update(x_t, pred, noise, t, clip=clip)
+        return self._ddpm_step(x_t, i, noise, self._scene_estimate(plan, tile_batch, cond_tiles, y_chunk), clip, gt, mask)
 
     def forward_only(self, img, device="cpu"):
         """Noising-only visualisation helper (model.py:77-84), without the reference's breakpoint()."""

@@ -36,6 +36,11 @@ def require_gpu(t, what):
             "there is no CPU / eager fallback.")
 
 
+def f32c(t):
+    """`t` as contiguous fp32: itself when it already is (no copy, no launch)"""
+    return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
+
+
 class Act:
     """Channels-last activation handle: tensor of shape [N, H, W, C] in the storage dtype."""
     __slots__ = ("t", "N", "H", "W", "C", "stats", "bound", "presplit", "csum")

@@ -16,20 +16,16 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr
-from .engine import current_stream_ptr, require_gpu
-
-
-def _f32c(t):
-    return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
+from .engine import current_stream_ptr, f32c, require_gpu
 
 
 def assemble_repaint_cond(image, mask, invert=True):
     """cond [N, C+1, H, W] = cat(image, 1 - mask) (invert=True: the dataset's segmentation marks the region to REPAINT, the
     sampler wants 1 = keep, inference.py:102).  image [N,C,H,W], mask [N,1,H,W] or [N,H,W]."""
     require_gpu(image, "assemble_repaint_cond")
-    x = _f32c(image)
+    x = f32c(image)
     n, c, h, w = x.shape
-    m = _f32c(mask.to(x.device)).reshape(n, 1, h, w)
+    m = f32c(mask.to(x.device)).reshape(n, 1, h, w)
     out = torch.empty((n, c + 1, h, w), dtype=torch.float32, device=x.device)
     check(_lib.lib().eod_repaint_cond(ptr(x), ptr(m), ptr(out), n, c, h * w, int(bool(invert)), current_stream_ptr(x.device)), "eod_repaint_cond")
     return out
@@ -43,7 +39,7 @@ def postprocess_samples(samples, image=None, *, data_nonneg=None):
         if image is None:
             raise ValueError("postprocess_samples needs `image` or `data_nonneg`")
         data_nonneg = bool(image.min() >= 0)
-    x = _f32c(samples)
+    x = f32c(samples)
     out = torch.empty_like(x)
     check(_lib.lib().eod_postprocess(ptr(x), ptr(out), x.numel(), 0 if data_nonneg else 1, current_stream_ptr(x.device)), "eod_postprocess")
     return out
@@ -52,9 +48,9 @@ def postprocess_samples(samples, image=None, *, data_nonneg=None):
 def masked_preview(image, mask, lift=0.7):
     """inference.py:134: the conditioning picture that is saved next to the sample: image * (mask + 0.7).clip(0, 1)"""
     require_gpu(image, "masked_preview")
-    x = _f32c(image)
+    x = f32c(image)
     n, c, h, w = x.shape
-    m = _f32c(mask.to(x.device)).reshape(n, 1, h, w)
+    m = f32c(mask.to(x.device)).reshape(n, 1, h, w)
     out = torch.empty_like(x)
     check(_lib.lib().eod_masked_preview(ptr(x), ptr(m), ptr(out), n, c, h * w, float(lift), current_stream_ptr(x.device)), "eod_masked_preview")
     return out
@@ -65,7 +61,7 @@ def psnr(preds, target, data_range=1.0):
     elements): 10 log10(data_range^2 / mse).  The squared-error reduction runs on the GPU (eod_mse_loss)."""
     from .optim import mse_loss
     require_gpu(preds, "psnr")
-    loss, _ = mse_loss(_f32c(preds), _f32c(target.to(preds.device)), want_grad=False)
+    loss, _ = mse_loss(f32c(preds), f32c(target.to(preds.device)), want_grad=False)
     mse = float(loss)
     return float("inf") if mse == 0.0 else 10.0 * math.log10(data_range * data_range / mse)
 

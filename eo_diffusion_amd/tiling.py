@@ -7,6 +7,7 @@
     idx   = active_tiles(mask, plan)             the tiles whose window holds a hole pixel of a RePaint mask      eod_scene_tile_active
     sub   = plan.subset(idx)                     a TileSubset: goes wherever a plan goes above, on the listed tiles only
     out   = keep_known(x, known, sub)            x at estimated pixels, known elsewhere                           eod_scene_keep_known
+    tiles = tiles_to_evaluate(what, plan, mask, skip_known, needs)   what a scene sampler evaluates: plan | sub | None (nothing active)
 
 Plan, per axis of length L: origins min(i * (tile - overlap), L - tile) until the axis is covered -- the last tile is shifted
 inwards, never padded.  Weights, per axis, [n][tile]: 1 in a tile's interior, a linear ramp (k + 1) / (o + 1) across the o pixels
@@ -192,19 +193,32 @@ def active_tiles(mask, plan):
     """TilePlan.active_tiles for a mask on the GPU ([H, W] or [..., H, W]): eod_scene_tile_active, then ONE device-to-host copy of
     plan.n_tiles ints (the only synchronisation).  Ascending int32 tile indices (numpy)."""
     import torch
-    from .engine import current_stream_ptr, require_gpu
+    from .engine import current_stream_ptr, f32c, require_gpu
     require_gpu(mask, "active_tiles")
     if not isinstance(plan, TilePlan):
         raise _lib.EodError(f"active_tiles: `plan` is a TilePlan, got {type(plan).__name__}")
     if mask.dim() < 2 or tuple(mask.shape[-2:]) != (plan.H, plan.W):
         raise _lib.EodError(f"active_tiles: the mask must be [..., {plan.H}, {plan.W}], got {tuple(mask.shape)}")
-    m = mask.reshape(-1, plan.H, plan.W)
-    m = m if (m.dtype == torch.float32 and m.is_contiguous()) else m.float().contiguous()
+    m = f32c(mask.reshape(-1, plan.H, plan.W))
     active = torch.empty(plan.n_tiles, dtype=torch.int32, device=m.device)
     oy, ox, _, _ = plan.device_tables(m.device)
     _lib.check(_lib.lib().eod_scene_tile_active(m.data_ptr(), active.data_ptr(), m.shape[0], plan.H, plan.W, plan.tile, oy.data_ptr(),
                                                 ox.data_ptr(), plan.nty, plan.ntx, current_stream_ptr(m.device)), "eod_scene_tile_active")
     return np.flatnonzero(active.cpu().numpy()).astype(np.int32)
+
+
+def tiles_to_evaluate(what, plan, mask, skip_known, needs):
+    """The tiles a scene sampler `what` sends through the UNet: the plan itself, with skip_known the TileSubset of the active tiles
+    of the known region's `mask` (the plan when every tile is active; active_tiles: the call's one host synchronisation), or None
+    when no tile is active.  skip_known without a mask is refused; `needs` says what the sampler takes a known region from."""
+    if not skip_known:
+        return plan
+    if mask is None:
+        raise _lib.EodError(f"{what}: skip_known=True needs a known region ({needs}); there is nothing to skip without one")
+    active = active_tiles(mask, plan)
+    if active.size == 0:
+        return None
+    return plan if active.size == plan.n_tiles else plan.subset(active)
 
 
 def _split(plan):
@@ -217,13 +231,12 @@ def _split(plan):
 
 
 def _scene4(scene, what):
-    import torch
-    from .engine import require_gpu
+    from .engine import f32c, require_gpu
     require_gpu(scene, what)
     x = scene if scene.dim() == 4 else scene[None]
     if x.dim() != 4 or x.shape[0] != 1:
         raise _lib.EodError(f"{what}: a scene is [1, C, H, W] or [C, H, W], got {tuple(scene.shape)}")
-    return x if (x.dtype == torch.float32 and x.is_contiguous()) else x.float().contiguous()
+    return f32c(x)
 
 
 def gather_tiles(scene, plan, out=None):
@@ -261,14 +274,14 @@ def blend_tiles(tiles, plan, out=None):
     `plan` may be a TileSubset: tiles holds its n_tiles listed tiles in the list's order; the result is the full blend at the
     subset's estimated pixels and 0.0 at every other pixel (eod_scene_blend_list)."""
     import torch
-    from .engine import current_stream_ptr, require_gpu
+    from .engine import current_stream_ptr, f32c, require_gpu
     require_gpu(tiles, "blend_tiles")
     plan, sub = _split(plan)
     s = plan.tile
     n = plan.n_tiles if sub is None else sub.n_tiles
     if tiles.dim() != 4 or tiles.shape[0] < n or tuple(tiles.shape[2:]) != (s, s):
         raise _lib.EodError(f"blend_tiles: tiles must be [>= {n}, C, {s}, {s}], got {tuple(tiles.shape)}")
-    e = tiles if (tiles.dtype == torch.float32 and tiles.is_contiguous()) else tiles.float().contiguous()
+    e = f32c(tiles)
     c = e.shape[1]
     if out is None:
         out = torch.empty((1, c, plan.H, plan.W), dtype=torch.float32, device=e.device)

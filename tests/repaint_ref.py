@@ -6,13 +6,20 @@
                       level 0;
   renoise_coeffs      (ca, cb) of the forward move in numpy fp32, correctly rounded sqrt (oracle.sampler_ref._sqrt explains why numpy);
   renoise             ca * x + cb * z in separately rounded torch fp32 operations;
-  ddpm_resampled      the resampled DDPM / DDIM loops assembled from oracle.sampler_ref's step functions.
+  ddpm_resampled      the resampled DDPM / DDIM loops assembled from oracle.sampler_ref's step functions;
   ddim_resampled
+  EVALS, MOVES        the walk and every Philox key of T = 8, resample = (2, 2), written out by hand.
 """
 import numpy as np
 import torch
 
 from oracle import sampler_ref as SR
+
+
+# T = 8, resample = (2, 2), written out by hand: the 14 evaluations as (timestep, Philox stream id of its mix / step noise), and after
+# evaluation number k (from 1) the move (from level, to level, (step, stream id) of its noise)
+EVALS = [(7, 1), (6, 1), (5, 1), (6, 3), (5, 3), (4, 1), (3, 1), (4, 3), (3, 3), (2, 1), (1, 1), (2, 3), (1, 3), (0, 1)]
+MOVES = {3: (4, 6, (6, 2)), 7: (2, 4, (4, 2)), 11: (0, 2, (2, 2))}
 
 
 def resample_schedule(num_levels, jump_length, jump_n_sample):
@@ -29,6 +36,14 @@ def resample_schedule(num_levels, jump_length, jump_n_sample):
             if rep < U - 1:
                 jumps.append((len(visits), p, p + L))
     return visits + [0], jumps
+
+
+def walk_of(num_levels, resample):
+    """(levels visited in order, the evaluation numbers (from 1) a jump follows); resample None: the single descent"""
+    if resample is None:
+        return list(range(num_levels - 1, -1, -1)), set()
+    visits, jumps = resample_schedule(num_levels, *resample)
+    return visits, {k for k, _, _ in jumps}
 
 
 def renoise_coeffs(acp_from, acp_to):

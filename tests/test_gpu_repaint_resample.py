@@ -241,10 +241,7 @@ def test_resampled_ddim_call_vs_cpu_loop(eta, prec):
 
 
 # ------------------------------------------------------------------------------------------- 9. the Philox keys
-# T = 8, resample = (2, 2): the 14 evaluations as (timestep, stream id of its mix / step noise), and after evaluation number k the
-# move (from level, to level, (step, stream id) of its noise)
-EVALS = [(7, 1), (6, 1), (5, 1), (6, 3), (5, 3), (4, 1), (3, 1), (4, 3), (3, 3), (2, 1), (1, 1), (2, 3), (1, 3), (0, 1)]
-MOVES = {3: (4, 6, (6, 2)), 7: (2, 4, (4, 2)), 11: (0, 2, (2, 2))}
+EVALS, MOVES = RR.EVALS, RR.MOVES  # T = 8, resample = (2, 2): every draw's (step, stream id), written out by hand
 
 
 def _philox_loop(m, n, seed, offset, cond):
@@ -275,6 +272,27 @@ def test_philox_wiring_and_sharding():
     assert torch.equal(torch.cat([lo, hi]), full)
     assert not torch.equal(full, m.sampling(4, device=DEV, cond=cond, rng="philox", seed=9, progress=False))
     assert len({(s, i) for s, i in EVALS} | {key for _, _, key in MOVES.values()} | {(8, 0)}) == 14 + 3 + 1   # no two draws share a key
+
+
+def test_philox_wiring_of_a_scene():
+    """sampling_scene draws with the keys of sampling(): the scene is sample 0, its draws are scene-shaped"""
+    s, seed = 64, 9
+    m = _diffusion("fp32x3", False, 8, "sum")
+    plan = TilePlan(s + 24, 2 * s, s, 16)
+    shape = (1, 3, plan.H, plan.W)
+    _, _, cond = _scene_inputs(1, plan.H, plan.W, 62, True)
+    cond = cond.to(DEV)
+    gt, mask = cond[:, :3].contiguous(), cond[:, 3:].contiguous()
+    acp = m.alphas_cumprod.tolist()
+    x = philox(shape, seed, 0, 8, 0)
+    for k, (i, sid) in enumerate(EVALS):
+        x = m._scene_step(x, i, philox(shape, seed, 0, i, sid), plan, 16, True, gt, mask)
+        if k + 1 in MOVES:
+            a, b, (step, sid2) = MOVES[k + 1]
+            rc, x = renoise(x, None, acp[a], acp[b], key=(seed, 0, step, sid2))
+            assert rc == 0
+    got = m.sampling_scene((plan.H, plan.W), True, DEV, cond=cond, overlap=16, seed=seed, resample=(2, 2), progress=False)
+    assert bool(torch.isfinite(got).all()) and torch.equal(got, x)
 
 
 # ------------------------------------------------------------------------------------------- 10. scenes

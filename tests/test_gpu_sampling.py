@@ -6,6 +6,7 @@ import torch
 
 from tests.gpu_util import DEV, load_into
 from tests.helpers import bits_equal, gt, rel_l2, unet_cfgs
+from tests.repaint_ref import walk_of
 from tests.synth import synth_input, synth_state_dict
 
 pytestmark = pytest.mark.gpu
@@ -278,3 +279,69 @@ def test_hipgraph_capture_after_a_fractional_timestep_call():
         g1b = m.model(x1, t1).clone()                                         # replay
         m.model.enable_graph(False)
     assert bits_equal(g1, ref1) and bits_equal(g1b, ref1) and not bits_equal(reff, ref1)
+
+
+# ------------------------------------------------------------------------------------------- the order of torch's draws
+# With neither injected draws nor rng="philox" a sampler draws from torch's global generators, and the generators advance with it:
+# the order below is part of what a call computes.  Each test draws by hand in that order, injects the draws, and compares with the
+# sampler drawing for itself from the same seed.
+def _known(n, s, seed):
+    from tests.synth import rect_mask
+    return (synth_input("og", (n, 3, s, s), seed, uniform=True) * 2 - 1).to(DEV), rect_mask(n, s, s, seed).to(DEV)
+
+
+@pytest.mark.parametrize("resample", [None, (2, 2)])
+@pytest.mark.parametrize("masked", [False, True])
+def test_sampling_draws_from_torch_in_loop_order(masked, resample):
+    """x_T on the CPU generator; on the device generator one draw per evaluation (mix AND update) and one per jump, in walk order"""
+    T, n = 8, 2
+    shape = (n, 3, 16, 16)
+    m = _model("fp32", T=T, cond_type="sum" if masked else None)
+    cond = torch.cat(_known(n, 16, 81), 1) if masked else None
+    visits, jump_after = walk_of(T, resample)
+    torch.manual_seed(17)
+    x_T = torch.randn(shape)
+    noises, jump_noises = [], []
+    for k in range(len(visits)):
+        noises.append(torch.randn(shape, device=DEV))
+        if k + 1 in jump_after:
+            jump_noises.append(torch.randn(shape, device=DEV))
+    want = m.sampling(n, device=DEV, cond=cond, x_T=x_T, noises=noises, jump_noises=jump_noises if resample else None, resample=resample,
+                      progress=False)
+    torch.manual_seed(17)
+    got = m.sampling(n, device=DEV, cond=cond, resample=resample, progress=False)
+    assert bool(torch.isfinite(got).all()) and torch.equal(got, want)
+    assert len(jump_noises) == (3 if resample else 0)
+
+
+@pytest.mark.parametrize("resample", [None, (2, 2)])
+@pytest.mark.parametrize("masked", [False, True])
+def test_ddim_sampling_draws_from_torch_in_loop_order(masked, resample):
+    """all on the device generator: x_T; per evaluation the mix noise (only with a mask), the reference's unused draw, then the
+    eta-noise after the network; one per jump"""
+    from eo_diffusion_amd.diffusion.ddim import DDIMSampler
+    S, n = 4, 2
+    shape = (n, 3, 16, 16)
+    smp = DDIMSampler(_model("fp32", T=8))
+    kw = dict(eta=1.0, verbose=False, progress=False, log_every_t=1, resample=resample)
+    if masked:
+        kw["x0"], kw["mask"] = _known(n, 16, 82)
+    visits, jump_after = walk_of(S, resample)
+    torch.manual_seed(18)
+    x_T = torch.randn(shape, device=DEV)
+    mix, stp, jn = [], [], []
+    for k in range(len(visits)):
+        if masked:
+            mix.append(torch.randn(shape, device=DEV))
+        torch.randn(shape, device=DEV)                               # the unused draw
+        stp.append(torch.randn(shape, device=DEV))
+        if k + 1 in jump_after:
+            jn.append(torch.randn(shape, device=DEV))
+    want, want_i = smp.sample(S, n, shape[1:], x_T=x_T, step_noises=stp, mix_noises=mix if masked else None,
+                              jump_noises=jn if resample else None, **kw)
+    torch.manual_seed(18)
+    got, got_i = smp.sample(S, n, shape[1:], **kw)
+    assert bool(torch.isfinite(got).all()) and torch.equal(got, want)
+    assert len(got_i["pred_x0"]) == len(want_i["pred_x0"]) == 1 + len(visits)
+    assert all(torch.equal(a, b) for a, b in zip(got_i["pred_x0"], want_i["pred_x0"]))
+    assert len(jn) == (1 if resample else 0)

@@ -15,6 +15,7 @@ from eo_diffusion_amd import _lib
 from eo_diffusion_amd._lib import EodError
 from eo_diffusion_amd.tiling import TilePlan, blend_tiles, gather_tiles, tile_slots, tiled_estimate
 from tests.gpu_util import DEV
+from tests.repaint_ref import walk_of
 from tests.synth import rect_mask, synth_input, synth_state_dict
 
 pytestmark = pytest.mark.gpu
@@ -304,6 +305,72 @@ def test_baseline_sized_scene():
     assert a.shape == (1, 3, 512, 768) and bool(torch.isfinite(a).all())
     assert torch.equal(run(16), a)
     assert torch.equal(run(4), a) and torch.equal(run(5), a)        # 5: a padded last chunk (12 = 5 + 5 + 2 + 3 copies)
+
+
+# ------------------------------------------------------------------------------------------ 4b. the order of torch's draws
+@pytest.mark.parametrize("resample", [None, (2, 2)])
+@pytest.mark.parametrize("masked", [False, True])
+def test_sampling_scene_draws_from_torch_in_loop_order(masked, resample):
+    """rng="torch": x_T on the CPU generator; on the device generator one scene-sized draw per evaluation (mix AND update) and one
+    per jump, in walk order -- drawn by hand, injected, and compared with the sampler drawing for itself from the same seed"""
+    s, T = 64, 8
+    H, W = s + 24, 2 * s
+    shape = (1, 3, H, W)
+    m = _diffusion("fp32x3", False, T, "sum" if masked else None)
+    _, _, cond = _scene_inputs(1, H, W, 28, masked)
+    visits, jump_after = walk_of(T, resample)
+    torch.manual_seed(19)
+    x_T = torch.randn(shape)
+    noises, jump_noises = [], []
+    for k in range(len(visits)):
+        noises.append(torch.randn(shape, device=DEV))
+        if k + 1 in jump_after:
+            jump_noises.append(torch.randn(shape, device=DEV))
+    run = lambda **kw: m.sampling_scene((H, W), True, DEV, cond=cond, overlap=16, rng="torch", resample=resample, progress=False, **kw)
+    want = run(x_T=x_T, noises=noises, jump_noises=jump_noises if resample else None)
+    torch.manual_seed(19)
+    got = run()
+    assert bool(torch.isfinite(got).all()) and torch.equal(got, want)
+    assert len(jump_noises) == (3 if resample else 0)
+
+
+@pytest.mark.parametrize("eta", [0.0, 1.0])
+@pytest.mark.parametrize("resample", [None, (2, 2)])
+@pytest.mark.parametrize("masked", [False, True])
+def test_sample_scene_draws_from_torch_in_loop_order(masked, resample, eta):
+    """all on the device generator: x_T; per evaluation the mix noise (only with a mask) and, after the estimate, the eta-noise
+    ONLY where sigma_t != 0 (eta = 0: no step draw at all); one per jump.  No unused draw."""
+    from eo_diffusion_amd.diffusion.ddim import DDIMSampler
+    s, S = 64, 4
+    H, W = s + 24, 2 * s
+    shape = (1, 3, H, W)
+    smp = DDIMSampler(_diffusion("fp32x3", False, 8))
+    _, _, cond = _scene_inputs(1, H, W, 29, True)
+    kw = dict(overlap=16, eta=eta, progress=False, log_every_t=1, resample=resample)
+    if masked:
+        kw["x0"], kw["mask"] = cond[:, :3].contiguous().to(DEV), cond[:, 3:].contiguous().to(DEV)
+    smp.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=False)
+    drawn = [float(v) != 0.0 for v in smp.ddim_sigmas]
+    assert len(drawn) == S and all(drawn) == (eta != 0.0) and any(drawn) == (eta != 0.0)
+    visits, jump_after = walk_of(S, resample)
+    torch.manual_seed(20)
+    x_T = torch.randn(shape, device=DEV)
+    mix, stp, jn = [], [], []
+    for k, index in enumerate(visits):
+        if masked:
+            mix.append(torch.randn(shape, device=DEV))
+        if drawn[index]:
+            stp.append(torch.randn(shape, device=DEV))
+        if k + 1 in jump_after:
+            jn.append(torch.randn(shape, device=DEV))
+    want, want_i = smp.sample_scene(S, (H, W), x_T=x_T, step_noises=stp if eta else None, mix_noises=mix if masked else None,
+                                    jump_noises=jn if resample else None, **kw)
+    torch.manual_seed(20)
+    got, got_i = smp.sample_scene(S, (H, W), **kw)
+    assert bool(torch.isfinite(got).all()) and torch.equal(got, want)
+    assert len(got_i["pred_x0"]) == len(want_i["pred_x0"]) == 1 + len(visits)
+    assert all(torch.equal(a, b) for a, b in zip(got_i["pred_x0"], want_i["pred_x0"]))
+    assert len(stp) == (len(visits) if eta else 0) and len(jn) == (1 if resample else 0)
 
 
 # ------------------------------------------------------------------------ 5. one step against an emulation from public pieces

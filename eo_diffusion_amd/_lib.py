@@ -152,6 +152,11 @@ SYMBOLS = {
     "eod_scene_gather_list": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, vp, i32, vp]),
     "eod_scene_blend_list": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "eod_scene_keep_known": (i32, [vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "eod_scene_stack_gather": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp, i32, vp]),
+    "eod_scene_stack_blend": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "eod_scene_stack_tile_active": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp]),
+    "eod_scene_stack_keep_known": (i32, [vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "eod_scene_stats": (i32, [vp, vp, vp, i32, i64, vp]),
     "eod_program_run": (i32, [C.POINTER(Op), i32, vp]),
     "eod_timer_create": (vp, [i32, i32]),
     "eod_timer_destroy": (None, [vp]),
@@ -168,7 +173,7 @@ class EodError(RuntimeError):
     pass
 
 
-ABI_VERSION = 105  # EOD_ABI_VERSION of the include/eodiff.h this file mirrors
+ABI_VERSION = 106  # EOD_ABI_VERSION of the include/eodiff.h this file mirrors
 
 
 def lib():

@@ -173,7 +173,7 @@ class DDIMSampler(object):
     def sample_scene(self, S, scene_size, *, overlap=0, tile_batch=16, conditioning=None, mask=None, x0=None, eta=0.0, x_T=None,
                      temperature=1.0, unconditional_guidance_scale=1.0, unconditional_conditioning=None, step_noises=None,
                      mix_noises=None, callback=None, img_callback=None, log_every_t=100, verbose=False, progress=True, resample=None,
-                     jump_noises=None, skip_known=False):
+                     jump_noises=None, skip_known=False, n_scenes=1):
         """DDIM over ONE scene [1, C, H, W] larger than the UNet's image size (see EODiffusion.sampling_scene and
         eo_diffusion_amd/tiling.py): per step the RePaint mix (mask / x0 scene-sized), the UNet on overlapping tiles in chunks of
         tile_batch, the blend of the noise estimates, ONE scene-level eod_ddim_step.  Classifier-free guidance runs per chunk through
@@ -187,27 +187,42 @@ class DDIMSampler(object):
         the UNet, as in EODiffusion.sampling_scene; conditioning is cut for those tiles only.  The returned scene equals the
         skip_known=False scene bit for bit at every estimated pixel and is `x0` at every other pixel.  intermediates and img_callback
         see the RAW states, which are meaningful at estimated pixels only (elsewhere: a step with a zero estimate); only the
-        returned scene goes through keep_known.  No tile active: (x0, intermediates of x0 alone), the UNet is never called."""
-        from ..tiling import gather_padded, keep_known, tile_slots, tiled_estimate, tiles_to_evaluate
+        returned scene goes through keep_known.  No tile active: (x0, intermediates of x0 alone), the UNet is never called.
+        n_scenes=B > 1: a STACK of B scenes in one call, as in EODiffusion.sampling_scene: the state, the returned scene, intermediates and
+        what img_callback sees are [B, C, H, W]; x0, x_T, conditioning, unconditional_conditioning and the injected draws
+        ([S, B, C, H, W]) have leading dimension B, or 1 for one scene that stands for every member; mask broadcasts against
+        [B, C, H, W] as it does against [1, C, H, W] today.  The tiles of the whole stack go through the UNet in chunks of tile_batch
+        (a chunk may hold tiles of several scenes); skip_known classifies per scene.  With injected draws member b equals the
+        single-scene call on scene b's inputs and draws, bit for bit."""
+        from ..tiling import TileStack, gather_padded, keep_known, tile_slots, tiled_estimate, tiles_to_evaluate
         what = "DDIMSampler.sample_scene"
         m = self.model
         device = m.betas.device
         plan, device = m._scene_args(what, scene_size, overlap, device)
         C = m.in_channels
+        B = m._scene_count(what, n_scenes)
         # (the walk is fixed, and the injected draws counted against it, before anything is launched; make_schedule below yields the same steps)
         visits, jump_after = resample_plan(what, resample, make_ddim_timesteps("uniform", S, m.timesteps, verbose=False).shape[0],
                                            (("step_noises", step_noises), ("mix_noises", mix_noises)), jump_noises)
         tile_slots(plan, tile_batch)  # (refuses a bad tile_batch)
         if (mask is None) != (x0 is None):
             raise _lib.EodError(f"{what}: mask and x0 go together (RePaint mix of the known region)")
-        full = plan  # (plan: the tiles that go through the UNet -- with skip_known the subset of the active ones)
+        full = plan if B == 1 else TileStack(plan, B)  # (plan: the tiles that go through the UNet -- with skip_known the active ones only)
+        if B > 1:  # (every shape, before anything is launched)
+            for name, z, channels in (("x_T", x_T, C), ("x0", x0, C), ("conditioning", conditioning, None),
+                                      ("unconditional_conditioning", unconditional_conditioning, None)):
+                if z is not None:
+                    m._scene_shape(what, name, z, channels, plan, B)
         if mask is not None:
-            x0 = m._scene_tensor(what, "x0", x0, C, plan, device)
+            x0 = m._scene_tensor(what, "x0", x0, C, plan, device, B, expand=False)
             mk = torch.as_tensor(mask)
             if mk.dim() < 2 or tuple(mk.shape[-2:]) != (plan.H, plan.W):
                 raise _lib.EodError(f"{what}: `mask` must be scene-sized ({plan.H} x {plan.W}), got {tuple(mk.shape)}")
-            mask = m._broadcast_mask(mk.to(device), x0)
+            like = x0.expand(B, *x0.shape[1:])  # (a mask that is the same for every scene stays [1, ...]: it is classified once)
+            mask = m._broadcast_mask(mk.to(device), like if mk.dim() == 4 and mk.shape[0] != 1 else like[:1])
         plan = tiles_to_evaluate(what, full, mask, skip_known, "mask and x0")
+        if mask is not None and B > 1:
+            x0, mask = (z.expand(B, *z.shape[1:]).contiguous() for z in (x0, mask))
         if plan is None:
             known = x0.clone()
             return known, {"x_inter": [known], "pred_x0": [known]}
@@ -215,24 +230,24 @@ class DDIMSampler(object):
         guided = unconditional_conditioning is not None and unconditional_guidance_scale != 1.0
         c_tiles = uc_tiles = None
         if conditioning is not None:
-            c_tiles = gather_padded(m._scene_tensor(what, "conditioning", conditioning, None, plan, device), plan, tile_batch)
+            c_tiles = gather_padded(m._scene_tensor(what, "conditioning", conditioning, None, plan, device, B), plan, tile_batch)
         if guided:
             if c_tiles is None:
                 raise _lib.EodError(f"{what}: classifier-free guidance needs `conditioning` next to `unconditional_conditioning`")
             uc_tiles = gather_padded(m._scene_tensor(what, "unconditional_conditioning", unconditional_conditioning, c_tiles.shape[1],
-                                                     plan, device), plan, tile_batch)
-        img = torch.randn((1, C, plan.H, plan.W), device=device) if x_T is None else m._scene_tensor(what, "x_T", x_T, C, plan, device)
+                                                     plan, device, B), plan, tile_batch)
+        img = torch.randn((B, C, plan.H, plan.W), device=device) if x_T is None else m._scene_tensor(what, "x_T", x_T, C, plan, device, B)
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         total_steps = self.ddim_timesteps.shape[0]
         assert total_steps == len(set(visits))
         intermediates = {"x_inter": [img], "pred_x0": [img]}
-        as_scene = lambda name, z: m._scene_tensor(what, name, z, C, plan, device)
+        as_scene = lambda name, z: m._scene_tensor(what, name, z, C, plan, device, B)
 
         def step(img, i, index, visit):
             t = int(self.ddim_timesteps[index])
             if mask is not None:
                 nz = as_scene("mix_noises[i]", mix_noises[i]) if mix_noises is not None else torch.randn_like(x0)
-                img = m._repaint_mix(img, x0, mask, torch.full((1,), t, device=device, dtype=torch.long), nz)
+                img = m._repaint_mix(img, x0, mask, torch.full((B,), t, device=device, dtype=torch.long), nz)
             ts = torch.full((chunk,), t, device=device, dtype=torch.long)
             e_t = tiled_estimate(img, plan, tile_batch, lambda x, lo: self._eps(
                 x, ts, None if c_tiles is None else c_tiles[lo:lo + chunk], unconditional_guidance_scale,

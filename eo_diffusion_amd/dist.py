@@ -61,3 +61,39 @@ def sharded_sampling(model, n_samples, *, seed=0, clipped_reverse_diffusion=True
     local = model.sampling(hi - lo, clipped_reverse_diffusion=clipped_reverse_diffusion, device=dev, cond=c, y=yy,
                            rng="philox", seed=seed, sample_offset=lo, progress=progress)
     return gather_samples(local, n_samples, group=group, force_gather=force_gather)
+
+
+def _shard_of(z, n_total, lo, hi):
+    """rows [lo, hi) of a GLOBAL per-scene argument; one with leading dimension 1 (the same for every scene) is passed on as it is"""
+    if z is None:
+        return None
+    z = torch.as_tensor(z)
+    return z if z.shape[0] == 1 and n_total != 1 else z[lo:hi]
+
+
+@torch.no_grad()
+def sharded_sampling_scene(model, scene_size, n_scenes, *, seed=0, clipped_reverse_diffusion=True, cond=None, y=None, overlap=0,
+                           tile_batch=16, resample=None, skip_known=False, device=None, group=None, progress=False, force_gather=False):
+    """EODiffusion.sampling_scene(n_scenes=...) over all ranks of `group`: scenes shard like samples do.  Rank r runs the scenes
+    shard_bounds(n_scenes, world, r) as one stacked call with rng="philox" and sample_offset = lo -- scene b is sample b of `seed` on
+    every rank, so the result does not depend on the world size -- and the scenes are concatenated with ONE all-gather: every rank
+    returns [n_scenes, C, H, W].  cond / y are the GLOBAL tensors (leading dimension n_scenes, or 1 for one known scene / label shared
+    by all).  A rank whose shard is empty launches nothing and still takes part in the collective.  Every rank first checks the
+    GLOBAL arguments (EODiffusion.check_scene_args), so a bad argument is refused on all ranks alike, before any of them launches or
+    enters the collective -- a rank with an empty shard included."""
+    world = dist.get_world_size(group) if dist.is_initialized() else 1
+    rank = dist.get_rank(group) if dist.is_initialized() else 0
+    dev = device or f"cuda:{torch.cuda.current_device()}"
+    model.check_scene_args(scene_size, dev, n_scenes=n_scenes, cond=cond, y=y, overlap=overlap, tile_batch=tile_batch, resample=resample,
+                           skip_known=skip_known)
+    lo, hi = shard_bounds(n_scenes, world, rank)
+    h, w = (int(v) for v in scene_size)
+    if hi > lo:
+        yy = None if y is None else torch.as_tensor(y).reshape(-1)
+        local = model.sampling_scene((h, w), clipped_reverse_diffusion, dev, cond=_shard_of(cond, n_scenes, lo, hi),
+                                     y=None if yy is None else _shard_of(yy, n_scenes, lo, hi), overlap=overlap, tile_batch=tile_batch,
+                                     rng="philox", seed=seed, progress=progress, resample=resample, skip_known=skip_known,
+                                     n_scenes=hi - lo, sample_offset=lo)
+    else:
+        local = torch.empty((0, model.in_channels, h, w), dtype=torch.float32, device=dev)
+    return gather_samples(local, n_scenes, group=group, force_gather=force_gather)

@@ -8,6 +8,9 @@
     sub   = plan.subset(idx)                     a TileSubset: goes wherever a plan goes above, on the listed tiles only
     out   = keep_known(x, known, sub)            x at estimated pixels, known elsewhere                           eod_scene_keep_known
     tiles = tiles_to_evaluate(what, plan, mask, skip_known, needs)   what a scene sampler evaluates: plan | sub | None (nothing active)
+    stack = TileStack(plan, B)                   B scenes of one plan ([B, C, H, W]): goes wherever a plan goes above; tiles of every scene
+    part  = TileStack(plan, B, indices)          ... or the listed tiles only (global numbers b * n_tiles + i), like a TileSubset
+    mean, std = scene_stats(scenes)              [B, C, H, W] -> per-pixel mean and sample standard deviation, each [1, C, H, W]   eod_scene_stats
 
 Plan, per axis of length L: origins min(i * (tile - overlap), L - tile) until the axis is covered -- the last tile is shifted
 inwards, never padded.  Weights, per axis, [n][tile]: 1 in a tile's interior, a linear ramp (k + 1) / (o + 1) across the o pixels
@@ -25,7 +28,12 @@ Tile subsets (skip_known of the scene samplers).  Known: mask == 1.  A HOLE pixe
 channel (soft values and NaN included).  A tile is ACTIVE iff its window holds a hole pixel; a pixel is ESTIMATED iff every tile that
 covers it is active (every hole pixel is; a pixel that is not estimated is known).  With only the active tiles evaluated the blend has
 the unchanged weights, order and roundings at every estimated pixel and is 0.0f elsewhere -- where the RePaint mix replaces the state
-by q_sample(gt) before every network evaluation anyway, so the active tiles see the inputs of the full call."""
+by q_sample(gt) before every network evaluation anyway, so the active tiles see the inputs of the full call.
+
+Stacks (n_scenes of the scene samplers).  B scenes of ONE plan are tiled together: tile i of scene b has the global number
+g = b * n_tiles + i, the tiles of the whole stack go through the network in one sequence of chunks (a chunk may hold tiles of several
+scenes), and every rule above holds per scene: scene b is blended from its own tiles with the single scene's arithmetic, and a pixel
+of scene b is estimated iff every tile of scene b covering it is listed."""
 import numpy as np
 
 from . import _lib
@@ -189,12 +197,107 @@ class TileSubset:
         return hit
 
 
+class TileStack:
+    """n_scenes copies of one TilePlan, tiled together; with `indices` only the listed global tiles g = b * plan.n_tiles + i (ascending,
+    unique, in range -- refused otherwise, like a TileSubset).  Goes wherever a plan or a subset goes; scenes are then [B, C, H, W].
+
+    plan; n_scenes; listed (were indices given); index int32 [n_tiles] (the global numbers; n_tiles = how many tiles go through the
+    network); slot_of int32 [n_scenes * plan.n_tiles] (position in the list, -1 = absent; the identity without indices); H, W, tile,
+    overlap as the plan's."""
+
+    def __init__(self, plan, n_scenes, indices=None):
+        if not isinstance(plan, TilePlan):
+            raise _lib.EodError(f"TileStack: a stack is made of a TilePlan, got {type(plan).__name__}")
+        if isinstance(n_scenes, bool) or not isinstance(n_scenes, (int, np.integer)) or n_scenes < 1:
+            raise _lib.EodError(f"TileStack: n_scenes must be an integer >= 1, got {n_scenes!r}")
+        total = int(n_scenes) * plan.n_tiles
+        if total > 0x7fffffff:
+            raise _lib.EodError(f"TileStack: {n_scenes} scenes of {plan.n_tiles} tiles cannot be numbered in an int32")
+        self.plan, self.n_scenes, self.listed = plan, int(n_scenes), indices is not None
+        if indices is None:
+            self.index = np.arange(total, dtype=np.int32)
+            self.slot_of = self.index
+        else:
+            raw = np.asarray(list(indices) if not isinstance(indices, np.ndarray) else indices)
+            if raw.ndim != 1 or raw.size < 1:
+                raise _lib.EodError(f"TileStack: the tile list must be a non-empty 1-D sequence of global tile numbers, got shape {tuple(raw.shape)}")
+            if not np.issubdtype(raw.dtype, np.integer):
+                raise _lib.EodError(f"TileStack: tile numbers are integers, got {raw.dtype}")
+            idx = raw.astype(np.int64)
+            if idx.min() < 0 or idx.max() >= total:
+                raise _lib.EodError(f"TileStack: global tile numbers must be in [0, {total}), got {int(idx.min())} .. {int(idx.max())}")
+            if np.any(np.diff(idx) <= 0):
+                raise _lib.EodError("TileStack: global tile numbers must be ascending and unique")
+            self.index = idx.astype(np.int32)
+            self.slot_of = np.full(total, -1, dtype=np.int32)
+            self.slot_of[idx] = np.arange(idx.size, dtype=np.int32)
+        self.n_tiles = int(self.index.size)
+        self.H, self.W, self.tile, self.overlap = plan.H, plan.W, plan.tile, plan.overlap
+        self._dev = {}
+
+    def __repr__(self):
+        return f"TileStack({self.n_tiles} of {self.n_scenes} x {self.plan.n_tiles} tiles of {self.plan!r})"
+
+    def scene_of(self, k):
+        """(b, i): the scene and the tile of that scene's plan in slot k"""
+        return divmod(int(self.index[int(k)]), self.plan.n_tiles)
+
+    def origin(self, k):
+        """(y0, x0) of the tile in slot k"""
+        return self.plan.origin(self.scene_of(k)[1])
+
+    def per_scene(self):
+        """per scene, the ascending int32 tile numbers of its plan that are listed"""
+        nt = self.plan.n_tiles
+        return [(self.index[(self.index >= b * nt) & (self.index < (b + 1) * nt)] - b * nt).astype(np.int32) for b in range(self.n_scenes)]
+
+    def estimated(self):
+        """bool [n_scenes][H][W]: the pixels of each scene whose covering tiles (of that scene) are all listed"""
+        p = self.plan
+        est = np.ones((self.n_scenes, p.H, p.W), dtype=bool)
+        for g in np.flatnonzero(self.slot_of < 0):
+            b, i = divmod(int(g), p.n_tiles)
+            y0, x0 = p.origin(i)
+            est[b, y0:y0 + p.tile, x0:x0 + p.tile] = False
+        return est
+
+    def active_tiles(self, mask):
+        """ascending int32 GLOBAL numbers of the tiles whose window holds a hole pixel of the host array `mask` [n_scenes, ..., H, W]
+        (TilePlan.active_tiles, scene by scene)"""
+        m = np.asarray(mask)
+        if m.ndim < 3 or m.shape[0] != self.n_scenes or tuple(m.shape[-2:]) != (self.H, self.W):
+            raise _lib.EodError(f"active_tiles: the mask of a stack must be [{self.n_scenes}, ..., {self.H}, {self.W}], got {tuple(m.shape)}")
+        nt = self.plan.n_tiles
+        return np.concatenate([self.plan.active_tiles(m[b]).astype(np.int64) + b * nt for b in range(self.n_scenes)]).astype(np.int32)
+
+    def device_tables(self, device):
+        """(index, slot_of) as device int32 tensors, uploaded once per device"""
+        import torch
+        dev = torch.device(device)
+        hit = self._dev.get(dev)
+        if hit is None:
+            hit = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (self.index, self.slot_of))
+            self._dev[dev] = hit
+        return hit
+
+
 def active_tiles(mask, plan):
     """TilePlan.active_tiles for a mask on the GPU ([H, W] or [..., H, W]): eod_scene_tile_active, then ONE device-to-host copy of
     plan.n_tiles ints (the only synchronisation).  Ascending int32 tile indices (numpy)."""
     import torch
     from .engine import current_stream_ptr, f32c, require_gpu
     require_gpu(mask, "active_tiles")
+    if isinstance(plan, TileStack):  # a stacked mask [B, ..., H, W]: global numbers, one launch, one copy
+        stack, plan = plan, plan.plan
+        if mask.dim() < 3 or mask.shape[0] != stack.n_scenes or tuple(mask.shape[-2:]) != (plan.H, plan.W):
+            raise _lib.EodError(f"active_tiles: the mask of a stack must be [{stack.n_scenes}, ..., {plan.H}, {plan.W}], got {tuple(mask.shape)}")
+        m = f32c(mask.reshape(stack.n_scenes, -1, plan.H, plan.W))
+        active = torch.empty(stack.n_scenes * plan.n_tiles, dtype=torch.int32, device=m.device)
+        oy, ox, _, _ = plan.device_tables(m.device)
+        _lib.check(_lib.lib().eod_scene_stack_tile_active(m.data_ptr(), active.data_ptr(), stack.n_scenes, m.shape[1], plan.H, plan.W, plan.tile,
+                                                          oy.data_ptr(), ox.data_ptr(), plan.nty, plan.ntx, current_stream_ptr(m.device)),
+                   "eod_scene_stack_tile_active")
+        return np.flatnonzero(active.cpu().numpy()).astype(np.int32)
     if not isinstance(plan, TilePlan):
         raise _lib.EodError(f"active_tiles: `plan` is a TilePlan, got {type(plan).__name__}")
     if mask.dim() < 2 or tuple(mask.shape[-2:]) != (plan.H, plan.W):
@@ -210,11 +313,23 @@ def active_tiles(mask, plan):
 def tiles_to_evaluate(what, plan, mask, skip_known, needs):
     """The tiles a scene sampler `what` sends through the UNet: the plan itself, with skip_known the TileSubset of the active tiles
     of the known region's `mask` (the plan when every tile is active; active_tiles: the call's one host synchronisation), or None
-    when no tile is active.  skip_known without a mask is refused; `needs` says what the sampler takes a known region from."""
+    when no tile is active.  skip_known without a mask is refused; `needs` says what the sampler takes a known region from.
+    For a TileStack: the stack, a listed stack of the active (b, i) in ascending global order, or None; a mask with leading dimension
+    1 stands for every scene and is classified once."""
     if not skip_known:
         return plan
     if mask is None:
         raise _lib.EodError(f"{what}: skip_known=True needs a known region ({needs}); there is nothing to skip without one")
+    if isinstance(plan, TileStack):
+        B, nt = plan.n_scenes, plan.plan.n_tiles
+        if B > 1 and mask.shape[0] == 1:
+            one = active_tiles(mask, plan.plan).astype(np.int64)
+            active = (np.arange(B, dtype=np.int64)[:, None] * nt + one[None, :]).reshape(-1).astype(np.int32)
+        else:
+            active = active_tiles(mask, plan)
+        if active.size == 0:
+            return None
+        return plan if active.size == plan.n_tiles and not plan.listed else TileStack(plan.plan, B, active)
     active = active_tiles(mask, plan)
     if active.size == 0:
         return None
@@ -222,17 +337,28 @@ def tiles_to_evaluate(what, plan, mask, skip_known, needs):
 
 
 def _split(plan):
-    """(plan, subset or None) of an argument that is either"""
+    """(plan, subset or None) of an argument that is either; for a TileStack (plan, the stack when it is a listed one, else None)"""
     if isinstance(plan, TileSubset):
         return plan.plan, plan
     if isinstance(plan, TilePlan):
         return plan, None
-    raise _lib.EodError(f"a TilePlan or a TileSubset is needed, got {type(plan).__name__}")
+    if isinstance(plan, TileStack):
+        return plan.plan, (plan if plan.listed else None)
+    raise _lib.EodError(f"a TilePlan, a TileSubset or a TileStack is needed, got {type(plan).__name__}")
 
 
-def _scene4(scene, what):
+def _scenes_of(plan):
+    """None for a TilePlan / TileSubset (one scene, the single-scene entry points), B for a TileStack"""
+    return plan.n_scenes if isinstance(plan, TileStack) else None
+
+
+def _scene4(scene, what, n_scenes=None):
     from .engine import f32c, require_gpu
     require_gpu(scene, what)
+    if n_scenes is not None:
+        if scene.dim() != 4 or scene.shape[0] != n_scenes:
+            raise _lib.EodError(f"{what}: a stack of {n_scenes} scene(s) is [{n_scenes}, C, H, W], got {tuple(scene.shape)}")
+        return f32c(scene)
     x = scene if scene.dim() == 4 else scene[None]
     if x.dim() != 4 or x.shape[0] != 1:
         raise _lib.EodError(f"{what}: a scene is [1, C, H, W] or [C, H, W], got {tuple(scene.shape)}")
@@ -245,19 +371,25 @@ def gather_tiles(scene, plan, out=None):
     `plan` may be a TileSubset: its n_tiles listed tiles, in the list's order (eod_scene_gather_list)."""
     import torch
     from .engine import current_stream_ptr
+    B = _scenes_of(plan)
     plan, sub = _split(plan)
-    x = _scene4(scene, "gather_tiles")
+    x = _scene4(scene, "gather_tiles", B)
     _, c, h, w = x.shape
     if (h, w) != (plan.H, plan.W):
         raise _lib.EodError(f"gather_tiles: scene is {h} x {w}, the plan is for {plan.H} x {plan.W}")
     s = plan.tile
-    n = plan.n_tiles if sub is None else sub.n_tiles
+    n = (B or 1) * plan.n_tiles if sub is None else sub.n_tiles
     if out is None:
         out = torch.empty((n, c, s, s), dtype=torch.float32, device=x.device)
     elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 4 and out.shape[0] >= n
               and tuple(out.shape[1:]) == (c, s, s)):
         raise _lib.EodError(f"gather_tiles: `out` must be a contiguous fp32 GPU tensor [>= {n}, {c}, {s}, {s}], got {tuple(out.shape)}")
     oy, ox, _, _ = plan.device_tables(x.device)
+    if B is not None:  # a TileStack: `scene` is [B, C, H, W]
+        index = None if sub is None else sub.device_tables(x.device)[0]
+        _lib.check(_lib.lib().eod_scene_stack_gather(x.data_ptr(), out.data_ptr(), B, c, h, w, s, oy.data_ptr(), ox.data_ptr(), plan.nty, plan.ntx,
+                                                     _lib.ptr(index), n, current_stream_ptr(x.device)), "eod_scene_stack_gather")
+        return out[:n]
     if sub is not None:
         index, _ = sub.device_tables(x.device)
         _lib.check(_lib.lib().eod_scene_gather_list(x.data_ptr(), out.data_ptr(), c, h, w, s, oy.data_ptr(), ox.data_ptr(), plan.nty,
@@ -276,18 +408,25 @@ def blend_tiles(tiles, plan, out=None):
     import torch
     from .engine import current_stream_ptr, f32c, require_gpu
     require_gpu(tiles, "blend_tiles")
+    B = _scenes_of(plan)
     plan, sub = _split(plan)
     s = plan.tile
-    n = plan.n_tiles if sub is None else sub.n_tiles
+    n = (B or 1) * plan.n_tiles if sub is None else sub.n_tiles
     if tiles.dim() != 4 or tiles.shape[0] < n or tuple(tiles.shape[2:]) != (s, s):
         raise _lib.EodError(f"blend_tiles: tiles must be [>= {n}, C, {s}, {s}], got {tuple(tiles.shape)}")
     e = f32c(tiles)
     c = e.shape[1]
     if out is None:
-        out = torch.empty((1, c, plan.H, plan.W), dtype=torch.float32, device=e.device)
-    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == c * plan.H * plan.W):
-        raise _lib.EodError(f"blend_tiles: `out` must be a contiguous fp32 GPU tensor of {c} x {plan.H} x {plan.W} elements")
+        out = torch.empty((B or 1, c, plan.H, plan.W), dtype=torch.float32, device=e.device)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == (B or 1) * c * plan.H * plan.W):
+        raise _lib.EodError(f"blend_tiles: `out` must be a contiguous fp32 GPU tensor of {'' if B is None else f'{B} x '}{c} x {plan.H} x {plan.W} elements")
     oy, ox, wy, wx = plan.device_tables(e.device)
+    if B is not None:  # a TileStack: the result is [B, C, H, W]
+        slot_of = None if sub is None else sub.device_tables(e.device)[1]
+        _lib.check(_lib.lib().eod_scene_stack_blend(e.data_ptr(), out.data_ptr(), wy.data_ptr(), wx.data_ptr(), oy.data_ptr(), ox.data_ptr(),
+                                                    _lib.ptr(slot_of), n, B, c, plan.H, plan.W, s, plan.nty, plan.ntx,
+                                                    current_stream_ptr(e.device)), "eod_scene_stack_blend")
+        return out
     if sub is not None:
         _, slot_of = sub.device_tables(e.device)
         _lib.check(_lib.lib().eod_scene_blend_list(e.data_ptr(), out.data_ptr(), wy.data_ptr(), wx.data_ptr(), oy.data_ptr(), ox.data_ptr(),
@@ -304,18 +443,24 @@ def keep_known(x, known, subset, out=None):
     other pixel (the end of a skip_known call: what was never estimated is the known image itself)."""
     import torch
     from .engine import current_stream_ptr
-    if not isinstance(subset, TileSubset):
-        raise _lib.EodError(f"keep_known: a TileSubset is needed, got {type(subset).__name__}")
+    B = _scenes_of(subset)
+    if not (isinstance(subset, TileSubset) or (B is not None and subset.listed)):
+        raise _lib.EodError(f"keep_known: a TileSubset (or a TileStack with a tile list) is needed, got {type(subset).__name__}")
     plan = subset.plan
-    a, b = _scene4(x, "keep_known"), _scene4(known, "keep_known")
+    a, b = _scene4(x, "keep_known", B), _scene4(known, "keep_known", B)
     if a.shape != b.shape or tuple(a.shape[2:]) != (plan.H, plan.W) or a.device != b.device:
-        raise _lib.EodError(f"keep_known: x {tuple(a.shape)} and known {tuple(b.shape)} must both be [1, C, {plan.H}, {plan.W}] on one GPU")
+        raise _lib.EodError(f"keep_known: x {tuple(a.shape)} and known {tuple(b.shape)} must both be [{B or 1}, C, {plan.H}, {plan.W}] on one GPU")
     if out is None:
         out = torch.empty_like(a)
     elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == a.numel()):
         raise _lib.EodError(f"keep_known: `out` must be a contiguous fp32 GPU tensor of {a.numel()} elements")
     oy, ox, _, _ = plan.device_tables(a.device)
     _, slot_of = subset.device_tables(a.device)
+    if B is not None:
+        _lib.check(_lib.lib().eod_scene_stack_keep_known(a.data_ptr(), b.data_ptr(), slot_of.data_ptr(), subset.n_tiles, oy.data_ptr(),
+                                                         ox.data_ptr(), B, a.shape[1], plan.H, plan.W, plan.tile, plan.nty, plan.ntx,
+                                                         out.data_ptr(), current_stream_ptr(a.device)), "eod_scene_stack_keep_known")
+        return out
     _lib.check(_lib.lib().eod_scene_keep_known(a.data_ptr(), b.data_ptr(), slot_of.data_ptr(), subset.n_tiles, oy.data_ptr(), ox.data_ptr(),
                                                a.shape[1], plan.H, plan.W, plan.tile, plan.nty, plan.ntx, out.data_ptr(),
                                                current_stream_ptr(a.device)), "eod_scene_keep_known")
@@ -336,7 +481,7 @@ def tile_slots(plan, tile_batch):
 def gather_padded(scene, plan, tile_batch):
     """gather_tiles into a buffer of tile_slots(...) tiles; the padding slots repeat the last (listed) tile"""
     import torch
-    x = _scene4(scene, "gather_padded")
+    x = _scene4(scene, "gather_padded", _scenes_of(plan))
     chunk, slots = tile_slots(plan, tile_batch)
     buf = torch.empty((slots, x.shape[1], plan.tile, plan.tile), dtype=torch.float32, device=x.device)
     gather_tiles(x, plan, out=buf)
@@ -361,3 +506,24 @@ def tiled_estimate(scene, plan, tile_batch, fn):
             e_tiles = torch.empty((slots,) + tuple(e.shape[1:]), dtype=torch.float32, device=e.device)
         e_tiles[lo:lo + chunk].copy_(e)  # (a graph-replayed network returns the same buffer every call)
     return blend_tiles(e_tiles, plan)
+
+
+def scene_stats(stack, out=None):
+    """stack [B, C, H, W] fp32 on the GPU (B draws of one scene, or any B scenes of one size) -> (mean, std), each [1, C, H, W]: the
+    per-pixel mean and the sample standard deviation (divisor B - 1; B = 1: zeros) over the B members, one pass (eod_scene_stats:
+    s = x_0 + x_1 + ... left to right, mean = s / B, q = sum of (x_b - mean)^2 left to right, std = sqrt(q / (B - 1)), every
+    operation rounded separately in fp32).  `out`: a contiguous fp32 GPU buffer [2, C, H, W] that receives (mean, std)."""
+    import torch
+    from .engine import current_stream_ptr, f32c, require_gpu
+    require_gpu(stack, "scene_stats")
+    if stack.dim() != 4 or stack.shape[0] < 1 or stack.numel() == 0:
+        raise _lib.EodError(f"scene_stats: a stack is [B, C, H, W] with B >= 1, got {tuple(stack.shape)}")
+    x = f32c(stack)
+    b, c, h, w = x.shape
+    if out is None:
+        out = torch.empty((2, c, h, w), dtype=torch.float32, device=x.device)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (2, c, h, w)):
+        raise _lib.EodError(f"scene_stats: `out` must be a contiguous fp32 GPU tensor [2, {c}, {h}, {w}], got {tuple(out.shape)}")
+    _lib.check(_lib.lib().eod_scene_stats(x.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), b, c * h * w, current_stream_ptr(x.device)),
+               "eod_scene_stats")
+    return out[0:1], out[1:2]

@@ -12,6 +12,11 @@ checkpoint of the reference's format ({"model": state_dict}): the example shows 
     python examples/inpaint_scene.py --height 600 --width 777 --image-size 64 --overlap 16 --timesteps 50 --out scene.npy
     python examples/inpaint_scene.py --timesteps 50 --resample 5 3
     python examples/inpaint_scene.py --timesteps 50 --resample 5 3 --skip-known
+    python examples/inpaint_scene.py --timesteps 50 --skip-known --draws 8
+
+`--draws K` runs K draws of the one scene in ONE call (`n_scenes=K` with the known scene given once: draw b is Philox sample b of
+`--seed`, the tiles of all draws share the UNet's batches) and writes, next to the first draw, `*_mean.npy` and `*_std.npy`: the per-pixel
+mean of the draws and how far they disagree (`tiling.scene_stats`, the sample standard deviation; zero wherever the scene is known).
 
 `--skip-known` runs the UNet only on the tiles whose window holds a masked pixel (`skip_known=True`): the same bits wherever every
 covering tile is active, the known scene itself elsewhere, and a cost that follows the mask and not the scene.
@@ -29,7 +34,7 @@ from eo_diffusion_amd import harness  # noqa: E402
 from eo_diffusion_amd.backbones.unet_openai import UNetModel  # noqa: E402
 from eo_diffusion_amd.diffusion.model import EODiffusion  # noqa: E402
 from eo_diffusion_amd.diffusion.util import resample_plan  # noqa: E402
-from eo_diffusion_amd.tiling import TilePlan, active_tiles, tile_slots  # noqa: E402
+from eo_diffusion_amd.tiling import TilePlan, TileStack, active_tiles, scene_stats, tile_slots  # noqa: E402
 
 
 def synthetic_scene(h, w, seed):
@@ -57,6 +62,7 @@ def main():
     ap.add_argument("--resample", type=int, nargs=2, default=None, metavar=("L", "U"),
                     help="RePaint resampling: jump length and number of descents per jump (default: one descent, no jumps)")
     ap.add_argument("--skip-known", action="store_true", help="run the UNet only on the tiles whose window holds a masked pixel")
+    ap.add_argument("--draws", type=int, default=1, help="K draws of the scene in one call; also writes *_mean.npy and *_std.npy")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--ckpt", default=None)
     ap.add_argument("--out", default="inpainted_scene.npy")
@@ -86,17 +92,31 @@ def main():
     if args.skip_known:
         active = active_tiles(cond[:, 3:], plan)
         tiles = plan.subset(active) if 0 < active.size < plan.n_tiles else plan
+        if args.draws > 1 and active.size:                           # every draw has the same active tiles: K x the list
+            tiles = TileStack(plan, args.draws, (np.arange(args.draws)[:, None] * plan.n_tiles + active[None, :]).reshape(-1))
         chunk, slots = tile_slots(tiles, args.tile_batch)
-        print(f"skip_known: {active.size} of {plan.n_tiles} tiles active, {slots // chunk if active.size else 0} UNet launches of "
-              f"{chunk} tiles per step instead of {-(-plan.n_tiles // min(args.tile_batch, plan.n_tiles))}")
+        print(f"skip_known: {active.size} of {plan.n_tiles} tiles active{f' x {args.draws} draws' if args.draws > 1 else ''}, "
+              f"{slots // chunk if active.size else 0} UNet launches of {chunk} tiles per step instead of "
+              f"{-(-args.draws * plan.n_tiles // min(args.tile_batch, args.draws * plan.n_tiles))}")
+    elif args.draws > 1:
+        tiles = TileStack(plan, args.draws)
     t0 = time.perf_counter()
     scene = model.sampling_scene((args.height, args.width), True, device, cond=cond, overlap=args.overlap, tile_batch=args.tile_batch,
                                  seed=args.seed, progress=False, resample=None if args.resample is None else tuple(args.resample),
-                                 skip_known=args.skip_known)
+                                 skip_known=args.skip_known, n_scenes=args.draws)   # (cond [1, 4, H, W]: the same known scene for every draw)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     out = harness.postprocess_samples(scene, data_nonneg=False)    # (x + 1) / 2
     np.save(args.out, out[0].cpu().numpy())
+    if args.draws > 1:
+        mean, std = scene_stats(out)                                 # [1, 3, H, W] each, over the K draws
+        stem = args.out[:-4] if args.out.endswith(".npy") else args.out
+        np.save(stem + "_mean.npy", mean[0].cpu().numpy())
+        np.save(stem + "_std.npy", std[0].cpu().numpy())
+        hole = (mask != 0).expand_as(mean)
+        print(f"{args.draws} draws: wrote {stem}_mean.npy and {stem}_std.npy; per-pixel std over the draws: mean {float(std[hole].mean()):.4f} "
+              f"in the masked region, max {float(std[~hole].max()):.2e} over the kept region")
+    out = out[:1]
     keep = (mask == 0).expand_as(image)
     dev_kept = float((out - image)[keep].abs().max())
     n_eval = len(resample_plan("inpaint_scene", args.resample, args.timesteps)[0])

@@ -35,7 +35,7 @@ const char* eod_last_error(void);
  * buffer of eod_pack_conv_weight_split, the 4-int state of eod_adamw_step_guarded).  eod_version() returns the value the library was built
  * with; a binding compares it with the header it mirrors at load time (eo_diffusion_amd/_lib.py does) instead of finding out by an
  * out-of-bounds device write. */
-#define EOD_ABI_VERSION 105
+#define EOD_ABI_VERSION 106
 int eod_version(void);
 /* Kernel-selection options ("skip_fuse", "head", "halo_bn256", "halo_splitk", "first": 1 / 0; "gn_fuse_max_cout": n, -1 = default; "halo_tpw":
  * pixel tiles per workgroup of the streaming halo instances, 1 = off = default, 0 = chosen per launch): every option has one
@@ -370,6 +370,35 @@ int eod_scene_blend_list(const float* tiles, float* scene, const float* wy, cons
                          void* stream);
 int eod_scene_keep_known(const float* x, const float* known, const int32_t* slot_of, int n_list, const int32_t* origins_y,
                          const int32_t* origins_x, int C, int H, int W, int s, int nty, int ntx, float* out, void* stream);
+
+/* A STACK of B scenes of one plan (tiling.py TileStack): the same four kernels with a leading scene dimension; the entry points above
+ * are their B = 1 case.  scene / x / known / out are [B][C][H][W], mask is [B][Cm][H][W].  Tile i of scene b has the global number
+ * g = b * nty * ntx + i; the full forms hold tiles [B * nty * ntx][C][s][s] in that order.  `index` [n_list] lists global numbers,
+ * ascending; `slot_of` [B * nty * ntx] is the slot of each global tile or -1; 1 <= n_list <= B * nty * ntx.  A pixel of scene b is
+ * ESTIMATED when every tile OF SCENE b covering it is listed.  The blend's arithmetic per scene is eod_scene_blend's, to the bit: a
+ * scene's result does not depend on what else is in the stack.  The tables are trusted with no address, as above.
+ *   eod_scene_stack_gather       index == NULL: every tile of every scene (n_list ignored); else tiles[k] = the window of tile index[k]
+ *   eod_scene_stack_blend        slot_of == NULL: the full blend of every scene (n_list ignored); else the list blend, 0.0f where not estimated
+ *   eod_scene_stack_tile_active  active [B * nty * ntx], one verdict per global tile from its own scene's mask
+ *   eod_scene_stack_keep_known   out[b] = x[b] at scene b's estimated pixels, known[b] elsewhere */
+int eod_scene_stack_gather(const float* scene, float* tiles, int B, int C, int H, int W, int s, const int32_t* origins_y,
+                           const int32_t* origins_x, int nty, int ntx, const int32_t* index, int n_list, void* stream);
+int eod_scene_stack_blend(const float* tiles, float* scene, const float* wy, const float* wx, const int32_t* origins_y,
+                          const int32_t* origins_x, const int32_t* slot_of, int n_list, int B, int C, int H, int W, int s, int nty,
+                          int ntx, void* stream);
+int eod_scene_stack_tile_active(const float* mask, int32_t* active, int B, int Cm, int H, int W, int s, const int32_t* origins_y,
+                                const int32_t* origins_x, int nty, int ntx, void* stream);
+int eod_scene_stack_keep_known(const float* x, const float* known, const int32_t* slot_of, int n_list, const int32_t* origins_y,
+                               const int32_t* origins_x, int B, int C, int H, int W, int s, int nty, int ntx, float* out, void* stream);
+/* Per-element mean and sample standard deviation over the B members of a stack x [B][n] (K draws of one scene: n = C * H * W), one
+ * pass, every operation separately rounded in fp32:
+ *   s = x_0; s = s + x_b for ascending b;  mean = s / (float)B;  q = sum over ascending b of d * d with d = x_b - mean;
+ *   std = sqrtf(q / (float)(B - 1));  B = 1: std = 0.  Division and square root are the correctly rounded ones (IEEE fp32:
+ * the root is taken in fp64 and rounded, the device's own fp32 square root is 1 ulp).
+ * 16-byte accesses where n % 4 == 0 and the three pointers are 16-byte aligned, element by element otherwise: same arithmetic.
+ * (Member b starts at x + b * n: with n % 4 != 0 the members are misaligned against each other, so no split into a vector body
+ * and a scalar tail gives every member 16-byte loads; the whole array then takes the scalar form.) */
+int eod_scene_stats(const float* x, float* mean, float* std_out, int B, int64_t n, void* stream);
 
 /* harness-side elementwise ops of inference.py, fp32, bit-exact vs the torch expressions:
  *   eod_repaint_cond   :100-109  cond [N][C+1][hw] = cat(image [N][C][hw], invert ? 1 - mask : mask), mask [N][1][hw]

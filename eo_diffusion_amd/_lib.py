@@ -140,6 +140,7 @@ SYMBOLS = {
     "eod_ddpm_step": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, i32, i32, vp]),
     "eod_ddim_step": (i32, [vp, vp, vp, f32, f32, f32, f32, f32, vp, vp, i64, vp]),
     "eod_cfg_combine": (i32, [vp, vp, f32, vp, i64, vp]),
+    "eod_dpmpp_step": (i32, [vp, vp, vp, f32, f32, f32, f32, f32, f32, i32, vp, vp, i64, vp]),
     "eod_ldm_p_sample": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, i32, i32, vp]),
     "eod_repaint_cond": (i32, [vp, vp, vp, i32, i32, i64, i32, vp]),
     "eod_postprocess": (i32, [vp, vp, i64, i32, vp]),
@@ -173,7 +174,7 @@ class EodError(RuntimeError):
     pass
 
 
-ABI_VERSION = 106  # EOD_ABI_VERSION of the include/eodiff.h this file mirrors
+ABI_VERSION = 107  # EOD_ABI_VERSION of the include/eodiff.h this file mirrors
 
 
 def lib():

@@ -352,6 +352,102 @@ extern "C" int eod_renoise(const float* x, const float* noise, float acp_from, f
     return EOD_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// DPM-Solver++ (2M), one step of the data-prediction multistep solver (no reference line):
+//   se = s1m_as * e;  p0 = (x - se) / sqrtf(a_s)          -- ddim_step_kernel's very operations: the same pred_x0 bits
+//   [CLIP] p0 = fminf(fmaxf(p0, -1), 1)                   -- ddpm_step_kernel<true>'s clamp (a NaN becomes -1)
+//   D = SECOND ? (w_cur * p0) + (w_prev * d_prev) : p0
+//   x_next = (c_x * x) + (c_d * D);  pred_x0 = p0
+// every operation rounded once (-ffp-contract=off).  The level is shared by all samples: scalars by value, computed on the host in
+// float64 (diffusion/util.py dpm_coefficients).  VEC: one 16-byte access per tensor and quad; the scalar form does the same arithmetic.
+// ---------------------------------------------------------------------------------------------
+template <bool CLIP, bool SECOND>
+__device__ __forceinline__ void dpmpp_one(float xv, float e, float d, float sq_as, float s1m_as, float c_x, float c_d, float w_cur,
+                                          float w_prev, float& xn, float& p0) {
+    const float se = s1m_as * e;
+    p0 = (xv - se) / sq_as;
+    if (CLIP) p0 = fminf(fmaxf(p0, -1.0f), 1.0f);
+    float D = p0;
+    if (SECOND) {
+        const float u = w_cur * p0;
+        const float v = w_prev * d;
+        D = u + v;
+    }
+    const float p = c_x * xv;
+    const float q = c_d * D;
+    xn = p + q;
+}
+
+template <bool VEC, bool CLIP, bool SECOND>
+__global__ void dpmpp_step_kernel(const float* __restrict__ x, const float* __restrict__ e_t, const float* __restrict__ d_prev, float a_s,
+                                  float s1m_as, float c_x, float c_d, float w_cur, float w_prev, float* __restrict__ x_next,
+                                  float* __restrict__ pred_x0, long long numel) {
+    const float sq_as = sqrtf(a_s);
+    const long long quads = (numel + 3) / 4;
+    for (long long qd = (long long)blockIdx.x * blockDim.x + threadIdx.x; qd < quads; qd += (long long)gridDim.x * blockDim.x) {
+        const long long i0 = qd * 4;
+        if (VEC) {
+            const f32x4 xv = *reinterpret_cast<const f32x4*>(x + i0);
+            const f32x4 ev = *reinterpret_cast<const f32x4*>(e_t + i0);
+            f32x4 dv = {0.0f, 0.0f, 0.0f, 0.0f};
+            if (SECOND) dv = *reinterpret_cast<const f32x4*>(d_prev + i0);
+            f32x4 xn, p0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float a, b;
+                dpmpp_one<CLIP, SECOND>(xv[j], ev[j], dv[j], sq_as, s1m_as, c_x, c_d, w_cur, w_prev, a, b);
+                xn[j] = a;
+                p0[j] = b;
+            }
+            *reinterpret_cast<f32x4*>(x_next + i0) = xn;
+            *reinterpret_cast<f32x4*>(pred_x0 + i0) = p0;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (i0 + j < numel) {
+                    float a, b;
+                    dpmpp_one<CLIP, SECOND>(x[i0 + j], e_t[i0 + j], SECOND ? d_prev[i0 + j] : 0.0f, sq_as, s1m_as, c_x, c_d, w_cur, w_prev, a, b);
+                    x_next[i0 + j] = a;
+                    pred_x0[i0 + j] = b;
+                }
+            }
+        }
+    }
+}
+
+static inline bool eod_overlap(const float* a, const float* b, long long n) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b, bytes = (uintptr_t)n * sizeof(float);
+    return pa < pb + bytes && pb < pa + bytes;
+}
+
+extern "C" int eod_dpmpp_step(const float* x, const float* e_t, const float* d_prev, float a_s, float sqrt_1m_as, float c_x, float c_d,
+                              float w_cur, float w_prev, int clip, float* x_next, float* pred_x0, int64_t numel, void* stream) {
+    EOD_REQUIRE(x && e_t && x_next && pred_x0 && numel > 0, "dpmpp_step: bad args");
+    EOD_REQUIRE(a_s > 0.0f && a_s <= 1.0f, "dpmpp_step: needs 0 < a_s <= 1, got %g", (double)a_s);
+    EOD_REQUIRE(!eod_overlap(x_next, pred_x0, numel), "dpmpp_step: x_next and pred_x0 overlap");
+    EOD_REQUIRE(!d_prev || (!eod_overlap(x_next, d_prev, numel) && !eod_overlap(pred_x0, d_prev, numel)),
+                "dpmpp_step: x_next / pred_x0 must not alias d_prev (the history is read while they are written)");
+    const bool vec = numel % 4 == 0 && eod_aligned16(x) && eod_aligned16(e_t) && eod_aligned16(x_next) && eod_aligned16(pred_x0) &&
+                     (!d_prev || eod_aligned16(d_prev));
+    const dim3 grid(blocks_for((numel + 3) / 4, 2048)), block(256);
+#define EOD_DPMPP(V, C, S)                                                                                                              \
+    hipLaunchKernelGGL((dpmpp_step_kernel<V, C, S>), grid, block, 0, (hipStream_t)stream, x, e_t, d_prev, a_s, sqrt_1m_as, c_x, c_d, \
+                       w_cur, w_prev, x_next, pred_x0, (long long)numel)
+#define EOD_DPMPP_CS(V)                                           \
+    do {                                                          \
+        if (clip) {                                               \
+            if (d_prev) EOD_DPMPP(V, true, true); else EOD_DPMPP(V, true, false);   \
+        } else {                                                  \
+            if (d_prev) EOD_DPMPP(V, false, true); else EOD_DPMPP(V, false, false); \
+        }                                                         \
+    } while (0)
+    if (vec) EOD_DPMPP_CS(true); else EOD_DPMPP_CS(false);
+#undef EOD_DPMPP_CS
+#undef EOD_DPMPP
+    EOD_CHECK_LAUNCH("dpmpp_step");
+    return EOD_OK;
+}
+
 extern "C" int eod_cfg_combine(const float* e_uncond, const float* e_cond, float scale, float* out, int64_t numel, void* stream) {
     EOD_REQUIRE(e_uncond && e_cond && out && numel > 0, "cfg_combine: bad args");
     hipLaunchKernelGGL(cfg_combine_kernel, dim3(blocks_for(numel, 4096)), dim3(256), 0, (hipStream_t)stream, e_uncond, e_cond, scale, out, (long long)numel);

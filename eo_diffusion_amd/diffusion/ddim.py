@@ -194,16 +194,52 @@ class DDIMSampler(object):
         [B, C, H, W] as it does against [1, C, H, W] today.  The tiles of the whole stack go through the UNet in chunks of tile_batch
         (a chunk may hold tiles of several scenes); skip_known classifies per scene.  With injected draws member b equals the
         single-scene call on scene b's inputs and draws, bit for bit."""
-        from ..tiling import TileStack, gather_padded, keep_known, tile_slots, tiled_estimate, tiles_to_evaluate
+        from ..tiling import keep_known
         what = "DDIMSampler.sample_scene"
+        m = self.model
+        # (the walk is fixed, and the injected draws counted against it, before anything is launched; make_schedule below yields the same steps)
+        walk = lambda: resample_plan(what, resample, make_ddim_timesteps("uniform", S, m.timesteps, verbose=False).shape[0],
+                                     (("step_noises", step_noises), ("mix_noises", mix_noises)), jump_noises)
+        sc = self._scene_setup(what, scene_size, overlap, tile_batch, n_scenes, walk, mask, x0, skip_known, conditioning,
+                               unconditional_conditioning, unconditional_guidance_scale, x_T)
+        if sc.known is not None:
+            return sc.known, {"x_inter": [sc.known], "pred_x0": [sc.known]}
+        img, x0, mask, B, device = sc.img, sc.x0, sc.mask, sc.B, sc.device
+        self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
+        total_steps = self.ddim_timesteps.shape[0]
+        assert total_steps == len(set(sc.visits))
+        intermediates = {"x_inter": [img], "pred_x0": [img]}
+
+        def step(img, i, index, visit):
+            t = int(self.ddim_timesteps[index])
+            if mask is not None:
+                nz = sc.as_scene("mix_noises[i]", mix_noises[i]) if mix_noises is not None else torch.randn_like(x0)
+                img = m._repaint_mix(img, x0, mask, torch.full((B,), t, device=device, dtype=torch.long), nz)
+            e_t = self._scene_eps(sc, img, t, unconditional_guidance_scale)
+            if step_noises is not None:
+                noise = sc.as_scene("step_noises[i]", step_noises[i])
+            else:
+                noise = torch.randn_like(img) if float(self.ddim_sigmas[index]) != 0.0 else None
+            img, pred_x0 = self._ddim_update(img, e_t, noise, index, temperature)
+            return self._after_step(i, index, img, pred_x0, intermediates, callback, img_callback, log_every_t, total_steps)
+
+        img = self._walk(img, sc.visits, sc.jump_after, step, jump_noises, sc.as_scene, "DDIM Sampler (scene)" if progress else None)
+        return (img if sc.plan is sc.full else keep_known(img, x0, sc.plan)), intermediates
+
+    # ------------------------------------------------------------------ what the scene samplers (this one and DPMSolverSampler's) share
+    def _scene_setup(self, what, scene_size, overlap, tile_batch, n_scenes, walk, mask, x0, skip_known, conditioning,
+                     unconditional_conditioning, unconditional_guidance_scale, x_T):
+        """Everything of a scene call in front of its first step: the plan, every refusal (walk() -> (visits, jump_after) fixes the walk and
+        counts the injected draws, before anything is launched), mask / x0 scene-sized, the tiles to evaluate, the conditioning cut into
+        them, the start state.  Returns a namespace; `known` is not None when no tile is active (the call returns it, no UNet call)."""
+        from types import SimpleNamespace
+        from ..tiling import TileStack, gather_padded, tile_slots, tiles_to_evaluate
         m = self.model
         device = m.betas.device
         plan, device = m._scene_args(what, scene_size, overlap, device)
         C = m.in_channels
         B = m._scene_count(what, n_scenes)
-        # (the walk is fixed, and the injected draws counted against it, before anything is launched; make_schedule below yields the same steps)
-        visits, jump_after = resample_plan(what, resample, make_ddim_timesteps("uniform", S, m.timesteps, verbose=False).shape[0],
-                                           (("step_noises", step_noises), ("mix_noises", mix_noises)), jump_noises)
+        visits, jump_after = walk()
         tile_slots(plan, tile_batch)  # (refuses a bad tile_batch)
         if (mask is None) != (x0 is None):
             raise _lib.EodError(f"{what}: mask and x0 go together (RePaint mix of the known region)")
@@ -223,44 +259,31 @@ class DDIMSampler(object):
         plan = tiles_to_evaluate(what, full, mask, skip_known, "mask and x0")
         if mask is not None and B > 1:
             x0, mask = (z.expand(B, *z.shape[1:]).contiguous() for z in (x0, mask))
+        sc = SimpleNamespace(plan=plan, full=full, B=B, device=device, tile_batch=tile_batch, x0=x0, mask=mask, visits=visits,
+                             jump_after=jump_after, known=None, c_tiles=None, uc_tiles=None)
         if plan is None:
-            known = x0.clone()
-            return known, {"x_inter": [known], "pred_x0": [known]}
-        chunk, _ = tile_slots(plan, tile_batch)
+            sc.known = x0.clone()
+            return sc
+        sc.chunk, _ = tile_slots(plan, tile_batch)
         guided = unconditional_conditioning is not None and unconditional_guidance_scale != 1.0
-        c_tiles = uc_tiles = None
         if conditioning is not None:
-            c_tiles = gather_padded(m._scene_tensor(what, "conditioning", conditioning, None, plan, device, B), plan, tile_batch)
+            sc.c_tiles = gather_padded(m._scene_tensor(what, "conditioning", conditioning, None, plan, device, B), plan, tile_batch)
         if guided:
-            if c_tiles is None:
+            if sc.c_tiles is None:
                 raise _lib.EodError(f"{what}: classifier-free guidance needs `conditioning` next to `unconditional_conditioning`")
-            uc_tiles = gather_padded(m._scene_tensor(what, "unconditional_conditioning", unconditional_conditioning, c_tiles.shape[1],
-                                                     plan, device, B), plan, tile_batch)
-        img = torch.randn((B, C, plan.H, plan.W), device=device) if x_T is None else m._scene_tensor(what, "x_T", x_T, C, plan, device, B)
-        self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
-        total_steps = self.ddim_timesteps.shape[0]
-        assert total_steps == len(set(visits))
-        intermediates = {"x_inter": [img], "pred_x0": [img]}
-        as_scene = lambda name, z: m._scene_tensor(what, name, z, C, plan, device, B)
+            sc.uc_tiles = gather_padded(m._scene_tensor(what, "unconditional_conditioning", unconditional_conditioning, sc.c_tiles.shape[1],
+                                                        plan, device, B), plan, tile_batch)
+        sc.img = torch.randn((B, C, plan.H, plan.W), device=device) if x_T is None else m._scene_tensor(what, "x_T", x_T, C, plan, device, B)
+        sc.as_scene = lambda name, z: m._scene_tensor(what, name, z, C, plan, device, B)
+        return sc
 
-        def step(img, i, index, visit):
-            t = int(self.ddim_timesteps[index])
-            if mask is not None:
-                nz = as_scene("mix_noises[i]", mix_noises[i]) if mix_noises is not None else torch.randn_like(x0)
-                img = m._repaint_mix(img, x0, mask, torch.full((B,), t, device=device, dtype=torch.long), nz)
-            ts = torch.full((chunk,), t, device=device, dtype=torch.long)
-            e_t = tiled_estimate(img, plan, tile_batch, lambda x, lo: self._eps(
-                x, ts, None if c_tiles is None else c_tiles[lo:lo + chunk], unconditional_guidance_scale,
-                None if uc_tiles is None else uc_tiles[lo:lo + chunk]))
-            if step_noises is not None:
-                noise = as_scene("step_noises[i]", step_noises[i])
-            else:
-                noise = torch.randn_like(img) if float(self.ddim_sigmas[index]) != 0.0 else None
-            img, pred_x0 = self._ddim_update(img, e_t, noise, index, temperature)
-            return self._after_step(i, index, img, pred_x0, intermediates, callback, img_callback, log_every_t, total_steps)
-
-        img = self._walk(img, visits, jump_after, step, jump_noises, as_scene, "DDIM Sampler (scene)" if progress else None)
-        return (img if plan is full else keep_known(img, x0, plan)), intermediates
+    def _scene_eps(self, sc, img, t, unconditional_guidance_scale):
+        """the blended noise estimate of the scene state at timestep t: the UNet (plain or guided, _eps) on the tiles in chunks"""
+        from ..tiling import tiled_estimate
+        ts = torch.full((sc.chunk,), t, device=sc.device, dtype=torch.long)
+        return tiled_estimate(img, sc.plan, sc.tile_batch, lambda x, lo: self._eps(
+            x, ts, None if sc.c_tiles is None else sc.c_tiles[lo:lo + sc.chunk], unconditional_guidance_scale,
+            None if sc.uc_tiles is None else sc.uc_tiles[lo:lo + sc.chunk]))
 
     @torch.no_grad()
     def p_sample_ddim(self, x, c, t, index, repeat_noise=False, use_original_steps=False, quantize_denoised=False,

@@ -13,6 +13,11 @@ checkpoint of the reference's format ({"model": state_dict}): the example shows 
     python examples/inpaint_scene.py --timesteps 50 --resample 5 3
     python examples/inpaint_scene.py --timesteps 50 --resample 5 3 --skip-known
     python examples/inpaint_scene.py --timesteps 50 --skip-known --draws 8
+    python examples/inpaint_scene.py --timesteps 1000 --solver dpmpp --steps 25 --skip-known
+
+`--solver dpmpp` replaces the ancestral chain (one UNet evaluation per timestep) by `DPMSolverSampler.sample_scene`: DPM-Solver++ (2M)
+over `--steps` levels of a log-SNR grid, at most `--steps` evaluations whatever `--timesteps` is.  The same tiling, mask, resampling,
+`--skip-known` and `--draws`; the draws come from the torch generator seeded with `--seed`.
 
 `--draws K` runs K draws of the one scene in ONE call (`n_scenes=K` with the known scene given once: draw b is Philox sample b of
 `--seed`, the tiles of all draws share the UNet's batches) and writes, next to the first draw, `*_mean.npy` and `*_std.npy`: the per-pixel
@@ -63,6 +68,8 @@ def main():
                     help="RePaint resampling: jump length and number of descents per jump (default: one descent, no jumps)")
     ap.add_argument("--skip-known", action="store_true", help="run the UNet only on the tiles whose window holds a masked pixel")
     ap.add_argument("--draws", type=int, default=1, help="K draws of the scene in one call; also writes *_mean.npy and *_std.npy")
+    ap.add_argument("--solver", default="ddpm", choices=["ddpm", "dpmpp"], help="ddpm: one evaluation per timestep; dpmpp: DPM-Solver++ (2M)")
+    ap.add_argument("--steps", type=int, default=25, help="--solver dpmpp: the number of levels (at most that many UNet evaluations)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--ckpt", default=None)
     ap.add_argument("--out", default="inpainted_scene.npy")
@@ -100,10 +107,20 @@ def main():
               f"{-(-args.draws * plan.n_tiles // min(args.tile_batch, args.draws * plan.n_tiles))}")
     elif args.draws > 1:
         tiles = TileStack(plan, args.draws)
+    resample = None if args.resample is None else tuple(args.resample)
     t0 = time.perf_counter()
-    scene = model.sampling_scene((args.height, args.width), True, device, cond=cond, overlap=args.overlap, tile_batch=args.tile_batch,
-                                 seed=args.seed, progress=False, resample=None if args.resample is None else tuple(args.resample),
-                                 skip_known=args.skip_known, n_scenes=args.draws)   # (cond [1, 4, H, W]: the same known scene for every draw)
+    if args.solver == "dpmpp":
+        from eo_diffusion_amd.diffusion.dpm_solver import DPMSolverSampler
+        sampler = DPMSolverSampler(model)
+        scene, _ = sampler.sample_scene(args.steps, (args.height, args.width), overlap=args.overlap, tile_batch=args.tile_batch,
+                                        mask=cond[:, 3:], x0=cond[:, :3].contiguous(), clip_denoised=True, progress=False, resample=resample,
+                                        skip_known=args.skip_known, n_scenes=args.draws)   # (mask: 1 = keep, as the cond's last channel)
+        num_levels = sampler.num_evaluations
+    else:
+        scene = model.sampling_scene((args.height, args.width), True, device, cond=cond, overlap=args.overlap, tile_batch=args.tile_batch,
+                                     seed=args.seed, progress=False, resample=resample,
+                                     skip_known=args.skip_known, n_scenes=args.draws)   # (cond [1, 4, H, W]: the same known scene for every draw)
+        num_levels = args.timesteps
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     out = harness.postprocess_samples(scene, data_nonneg=False)    # (x + 1) / 2
@@ -119,7 +136,7 @@ def main():
     out = out[:1]
     keep = (mask == 0).expand_as(image)
     dev_kept = float((out - image)[keep].abs().max())
-    n_eval = len(resample_plan("inpaint_scene", args.resample, args.timesteps)[0])
+    n_eval = len(resample_plan("inpaint_scene", args.resample, num_levels)[0])
     print(f"{tiles.n_tiles} tiles x {n_eval} evaluations in {dt:.2f} s; wrote {args.out} {tuple(out.shape[1:])}; "
           f"masked pixels {int(mask.sum())}; max |out - scene| over the kept region {dev_kept:.3f} (an untrained network only keeps "
           "what the last RePaint mix hands it)")

@@ -35,7 +35,7 @@ const char* eod_last_error(void);
  * buffer of eod_pack_conv_weight_split, the 4-int state of eod_adamw_step_guarded).  eod_version() returns the value the library was built
  * with; a binding compares it with the header it mirrors at load time (eo_diffusion_amd/_lib.py does) instead of finding out by an
  * out-of-bounds device write. */
-#define EOD_ABI_VERSION 106
+#define EOD_ABI_VERSION 107
 int eod_version(void);
 /* Kernel-selection options ("skip_fuse", "head", "halo_bn256", "halo_splitk", "first": 1 / 0; "gn_fuse_max_cout": n, -1 = default; "halo_tpw":
  * pixel tiles per workgroup of the streaming halo instances, 1 = off = default, 0 = chosen per launch): every option has one
@@ -312,6 +312,21 @@ int eod_ddpm_step(const float* x_t, const float* pred, const float* noise, const
 int eod_ddim_step(const float* x, const float* e_t, const float* noise, float a_t, float a_prev,
                   float sigma_t, float sqrt_1m_at, float temperature, float* x_prev, float* pred_x0,
                   int64_t numel, void* stream);
+/* DPM-Solver++ (2M), one step of the data-prediction multistep solver from the level with cumulative alpha product a_s (no reference
+ * line).  Per element, every operation rounded once in fp32, in this order:
+ *   se = sqrt_1m_as * e_t
+ *   p0 = (x - se) / sqrtf(a_s)                     -- eod_ddim_step's operations: pred_x0 has its bits for the same (x, e_t, a, sqrt_1m_a)
+ *   clip != 0:  p0 = fminf(fmaxf(p0, -1), 1)       -- eod_ddpm_step's clamp (a NaN becomes -1)
+ *   D = d_prev ? (w_cur * p0) + (w_prev * d_prev) : p0
+ *   x_next = (c_x * x) + (c_d * D)
+ *   pred_x0 = p0                                   -- the next step's d_prev
+ * d_prev NULL: first order (w_cur / w_prev are not read).  The scalars are shared by all samples and come from the host
+ * (diffusion/util.py dpm_coefficients: float64, rounded once).  x, e_t, d_prev, x_next, pred_x0 are [numel] fp32.
+ * EOD_EINVAL with nothing launched: a null x / e_t / x_next / pred_x0, numel <= 0, a_s outside (0, 1] (NaN included), x_next or pred_x0
+ * overlapping d_prev or each other.  16-byte accesses where numel % 4 == 0 and all (five, or four) pointers are 16-byte aligned, element
+ * by element otherwise: same arithmetic. */
+int eod_dpmpp_step(const float* x, const float* e_t, const float* d_prev, float a_s, float sqrt_1m_as, float c_x, float c_d,
+                   float w_cur, float w_prev, int clip, float* x_next, float* pred_x0, int64_t numel, void* stream);
 /* classifier-free guidance of p_sample_ddim (ddim.py:177-181): out = e_uncond + scale * (e_cond - e_uncond) */
 int eod_cfg_combine(const float* e_uncond, const float* e_cond, float scale, float* out, int64_t numel, void* stream);
 /* table-driven DDPM step of the LDM-derived sampler: DDPM.p_sample ddpm.py:248-255 with predict_start_from_noise :221-225,

@@ -130,6 +130,7 @@ SYMBOLS = {
     "eod_pack_conv_weight_split": (i32, [vp, vp, vp, i32, i32, i32, i32, vp]),
     "eod_pack_conv_weight_split_pair": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "eod_conv_workspace_size": (i64, [C.POINTER(ConvDesc)]),
+    "eod_conv_kernel_name": (C.c_char_p, [C.POINTER(ConvDesc)]),
     "eod_gn_apply": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp]),
     "eod_attention_fwd": (i32, [C.POINTER(AttnDesc), vp]),
     "eod_softmax_rows": (i32, [vp, i64, vp, i64, i32, i64, i32, vp]),
@@ -174,7 +175,7 @@ class EodError(RuntimeError):
     pass
 
 
-ABI_VERSION = 107  # EOD_ABI_VERSION of the include/eodiff.h this file mirrors
+ABI_VERSION = 108  # EOD_ABI_VERSION of the include/eodiff.h this file mirrors
 
 
 def lib():

@@ -2860,16 +2860,7 @@ template <typename T, bool SPLIT> static int launch_head(IgemmP& p, hipStream_t 
     p.th = 8;
     p.tiles_pw = p.Wo / 16;
     p.tiles_pi = p.tiles_pw * (p.Ho / 8);
-    // runs of tpw consecutive tiles of one image per workgroup (the kernel's chunk stream): the longest run that still leaves every CU its
-    // two workgroups.  A tile's result does not depend on the run it is computed in, so the choice may depend on the batch.
-    int tpw = p.tpw;  // (the caller's request: the head_tpw option; 0 = choose)
-    if (tpw <= 0) {
-        tpw = 16;
-        while (tpw > 1 && (p.tiles_pi % tpw || (long long)p.tiles_pi * p.N / tpw < 512)) tpw >>= 1;
-    }
-    while (tpw > 1 && p.tiles_pi % tpw) --tpw;
-    p.tpw = tpw;
-    p.tiles_m = p.tiles_pi / tpw * p.N;  // (runs)
+    p.tiles_m = p.tiles_pi / p.tpw * p.N;  // (runs of p.tpw consecutive tiles of one image per workgroup: ConvPlan.tpw)
     if (p.tiles_m <= 0) {
         eod_set_error("conv_head: bad grid");
         return EOD_EINVAL;
@@ -3109,24 +3100,11 @@ static int launch_halo(IgemmP& p, hipStream_t st) {
     p.tiles_pi = p.tiles_pw * (p.Ho / TH);
     p.tiles_m = p.tiles_pi * p.N;
     p.tiles_per_image = p.tiles_pi;  // (statistics slots: tile of the image x WAVES_M)
-    // streaming instances (the kernel's STREAM): runs of tpw consecutive pixel tiles of one image per workgroup.  Which workgroup
-    // computes a tile never changes its result (same K order, same MFMAs, its own statistics slot), so the choice may depend on the batch.
-    p.tpw = 1;
-    if constexpr (SPLIT && MS == 16 && BN >= 128 && !SKIP && !UPS) {
-        const long long slots = 256LL * (NW == 4 ? 2 : 1);  // co-resident workgroups of the chip
-        int want = opt(OPT_HALO_TPW);
-        if (want <= 0) {  // at least two rounds of workgroups stay (measured on 256 x 256 and 128 x 128 maps: 4 ... 8 tiles per run tie)
-            want = 1;
-            while (want < 8 && (long long)p.tiles_m * p.tiles_n / (2 * want) >= 2 * slots) want *= 2;
-        }
-        while (want > 1 && p.tiles_pi % want) --want;
-        if (p.splitk > 1) want = 1;
-        if constexpr (!STREAM) {
-            if (want > 1) return launch_halo<T, BN, WAVES_M, WAVES_N, UPS, BSTAGES, GN, SPLIT, MS, SKIP, true>(p, st);
-        } else {
-            p.tpw = want;
-        }
+    // streaming instances (the kernel's STREAM): runs of p.tpw consecutive pixel tiles of one image per workgroup (ConvPlan.tpw)
+    if constexpr (SPLIT && MS == 16 && BN >= 128 && !SKIP && !UPS && !STREAM) {
+        if (p.tpw > 1) return launch_halo<T, BN, WAVES_M, WAVES_N, UPS, BSTAGES, GN, SPLIT, MS, SKIP, true>(p, st);
     }
+    if constexpr (!STREAM) p.tpw = 1;
     const long long nblk = (long long)(p.tiles_m / p.tpw) * p.tiles_n;
     if (nblk <= 0 || nblk > 0x7fffffffLL) {
         eod_set_error("conv_halo: bad grid %lld", nblk);
@@ -3138,28 +3116,18 @@ static int launch_halo(IgemmP& p, hipStream_t st) {
 }
 
 template <typename T, bool CONV> static int launch_T(IgemmP& p, int batch, hipStream_t st) {
-    if constexpr (sizeof(T) == 2) {  // fp16 products on v_mfma_f32_16x16x32_f16
-        if (p.Ncols <= 32) return launch_cfg<T, CONV, 128, 32, 4, 1, 2, false, 16>(p, batch, st);
-        if (p.Ncols <= 64) return launch_cfg<T, CONV, 128, 64, 4, 1, 2, false, 16>(p, batch, st);
-        return launch_cfg<T, CONV, 128, 128, 2, 2, 2, false, 16>(p, batch, st);
-    } else {                         // exact fp32: v_mfma_f32_32x32x2_f32
-        if (p.Ncols <= 32) return launch_cfg<T, CONV, 128, 32, 4, 1, 2>(p, batch, st);
-        if (p.Ncols <= 64) return launch_cfg<T, CONV, 128, 64, 4, 1, 2>(p, batch, st);
-        // (a 256x128 tile / 8 waves / 3-stage ring measured 0-5 % SLOWER than two co-resident 128x128 workgroups per CU)
-        return launch_cfg<T, CONV, 128, 128, 2, 2, 2>(p, batch, st);
-    }
+    constexpr int MS = sizeof(T) == 2 ? 16 : 32;  // fp16 products on v_mfma_f32_16x16x32_f16, exact fp32 on v_mfma_f32_32x32x2_f32
+    if (p.Ncols <= 32) return launch_cfg<T, CONV, 128, 32, 4, 1, 2, false, MS>(p, batch, st);
+    if (p.Ncols <= 64) return launch_cfg<T, CONV, 128, 64, 4, 1, 2, false, MS>(p, batch, st);
+    // (exact fp32: a 256x128 tile / 8 waves / 3-stage ring measured 0-5 % SLOWER than two co-resident 128x128 workgroups per CU)
+    return launch_cfg<T, CONV, 128, 128, 2, 2, 2, false, MS>(p, batch, st);
 }
 
-// fp32 conv as the split-fp16 product on the generic kernel (1x1, stride 2, ragged maps)
-static int launch_conv_split(IgemmP& p, int batch, hipStream_t st) {
-    if (p.Ncols <= 32) return launch_cfg<float, true, 128, 32, 4, 1, 2, true, 16>(p, batch, st);
-    if (p.Ncols <= 64) return launch_cfg<float, true, 128, 64, 4, 1, 2, true, 16>(p, batch, st);
-    // 256 columns per 8-wave workgroup: the pixel rows of a K-step are fetched and split once for two N-tiles (these launches are
-    // bound by that in-place split: four pieces per wave against 48 MFMAs) -- the qkv / proj 1x1 convs of the attention blocks
-    // whole tiles inside one image, no split-K, NHWC output: the instances with swapped MFMA operands and the direct epilogue
-    // (halo_epilogue_direct: no LDS transpose; fp32 or pre-split output)
-    const bool direct = p.splitk <= 1 && !p.out_nchw && p.HWd % 128 == 0 && p.M % 128 == 0 && !p.par && p.Ncols % 4 == 0;
-    if (p.Ncols % 256 == 0 && batch == 1 && ((p.M + 127) / 128) * (p.Ncols / 256) >= 256 && opt(OPT_HALO_BN256))
+// fp32 conv as the split-fp16 product on the generic kernel (1x1, stride 2, ragged maps); bn and direct come from the ConvPlan
+static int launch_conv_split(IgemmP& p, int bn, bool direct, int batch, hipStream_t st) {
+    if (bn == 32) return launch_cfg<float, true, 128, 32, 4, 1, 2, true, 16>(p, batch, st);
+    if (bn == 64) return launch_cfg<float, true, 128, 64, 4, 1, 2, true, 16>(p, batch, st);
+    if (bn == 256)
         return direct ? launch_cfg<float, true, 128, 256, 2, 4, 2, true, 16, true>(p, batch, st)
                       : launch_cfg<float, true, 128, 256, 2, 4, 2, true, 16>(p, batch, st);
     return direct ? launch_cfg<float, true, 128, 128, 2, 2, 2, true, 16, true>(p, batch, st)
@@ -3172,7 +3140,11 @@ extern "C" int eod_conv_tapmajor_ldk(int C0, int dtype) {
     return (9 * C0 + bk - 1) / bk * bk;
 }
 
-// which kernel configuration a conv descriptor gets (shared by the launcher and eod_conv_stats_slots)
+// ---- geometry predicates: pure functions of the descriptor (no options, no split-K factor: conv_plan() adds those) ----
+static int conv_out_hw(const eod_conv_desc* d, int eff) { return d->stride > 0 ? (eff + d->pad_tl + 2 * d->pad - d->ksize) / d->stride + 1 : 0; }
+// storage types whose products run on the fp16 MFMA (fp16, or fp32 with the split weights): every kernel but the generic one needs one
+static bool conv_mma16(const eod_conv_desc* d) { return d->dtype == EOD_F16 || (d->dtype == EOD_F32 && d->w_split); }
+// 3x3 / stride 1 / pad 1 on maps that tile into 8 x 16 patches: the halo-patch kernel
 static bool conv_uses_halo(const eod_conv_desc* d, int Ho, int Wo) {
     // wide convs (128-column tiles) and the narrow NCHW-fp32 head conv (32-column tiles, 4x1 waves)
     const bool shape_ok = ((d->Cout > 64 && !d->out_nchw_f32) || (d->Cout <= 32 && d->out_nchw_f32 && !d->upsample)) && d->upsample != 2;
@@ -3181,15 +3153,13 @@ static bool conv_uses_halo(const eod_conv_desc* d, int Ho, int Wo) {
     const bool w_ok = Wo % 16 == 0 || (Wo == 8 && d->Cout > 64 && !d->out_nchw_f32 && !d->upsample);
     return d->ksize == 3 && d->stride == 1 && d->pad == 1 && !d->pad_tl && w_ok && Ho % 8 == 0 && shape_ok && !d->w_tapmajor;
 }
-static int conv_waves_m(const eod_conv_desc* d, bool halo) { return (halo || d->Cout > 64) ? 2 : 4; }
-static int conv_bm(const eod_conv_desc* d, bool halo) { return 128; }
-
 // 1 if this conv can run as the split-fp16 product (fp32 storage, weights packed by eod_pack_conv_weight_split): whole chunk
 // pairs (8 channels) per source; every kernel variant has it except the thin-input (tap-major) first conv
-static bool conv_split_ok(const eod_conv_desc* d, int Ho, int Wo) {
-    // (thin-input first conv: the K axis is [tap][C0] flattened and padded to whole K-steps, so its 8-k pairs always exist)
+// (thin-input first conv: the K axis is [tap][C0] flattened and padded to whole K-steps, so its 8-k pairs always exist)
+static bool conv_split_ok(const eod_conv_desc* d) {
     return d->dtype == EOD_F32 && (d->w_tapmajor || (d->C0 % 8 == 0 && d->C1 % 8 == 0)) && d->upsample != 2;
 }
+extern "C" int eod_conv_split_ok(const eod_conv_desc* d) { return d && conv_split_ok(d) ? 1 : 0; }
 // zero-insertion upsampling through the four parity-class launches (see eod_conv2d_igemm); other geometries keep the single full-grid
 // launch that multiplies the inserted zeros
 static bool conv_parity_ok(const eod_conv_desc* d, int Ho, int Wo) {
@@ -3198,10 +3168,9 @@ static bool conv_parity_ok(const eod_conv_desc* d, int Ho, int Wo) {
 }
 // upsample = 3: nearest-2x upsampling + 3x3 conv as four 2x2-tap parity classes with pre-summed weights (conv_up4_halo_kernel)
 static bool conv_up4_ok(const eod_conv_desc* d) {
-    const bool store_ok = d->dtype == EOD_F16 || (d->dtype == EOD_F32 && d->w_split);
     return d->upsample == 3 && d->ksize == 3 && d->stride == 1 && d->pad == 1 && !d->pad_tl && d->C1 == 0 && !d->x2 && d->Cout > 64 &&
            d->Cout % 8 == 0 && d->C0 % 8 == 0 && (d->W % 16 == 0 || d->W == 8) && d->H % 8 == 0 && !d->out_nchw_f32 && !d->w_tapmajor &&
-           !d->gn_scale_shift && store_ok;  // (8-wide stored maps: the right half of the 8 x 16 tile masked, like conv3x3_halo_kernel's)
+           !d->gn_scale_shift && conv_mma16(d);  // (8-wide stored maps: the right half of the 8 x 16 tile masked, like conv3x3_halo_kernel's)
 }
 extern "C" int eod_conv_up4_ok(const eod_conv_desc* d) { return d && conv_up4_ok(d) ? 1 : 0; }
 // upsample = 4: backward-data of the parity-class upsample conv (conv_up4_halo_kernel<BWD>): x = dY [N][H][W][C0] on the (2H' x 2W') grid,
@@ -3212,105 +3181,31 @@ static bool conv_up4_bwd_ok(const eod_conv_desc* d) {
            d->Wo % 16 == 0 && d->Ho % 8 == 0 && !d->out_nchw_f32 && !d->w_tapmajor && !d->gn_scale_shift && !d->stats && !d->w_split;
 }
 extern "C" int eod_conv_up4_bwd_ok(const eod_conv_desc* d) { return d && conv_up4_bwd_ok(d) ? 1 : 0; }
-static int conv_up4_bwd(const eod_conv_desc* d, void* stream) {
-    EOD_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->C0 > 0 && d->Cout > 0 && d->x && d->w && d->y, "conv (upsample 4): bad args");
-    EOD_REQUIRE(conv_up4_bwd_ok(d), "conv: upsample = 4 needs a geometry for which eod_conv_up4_bwd_ok(d) == 1");
-    EOD_REQUIRE(eod_aligned16(d->x) && eod_aligned16(d->w), "conv: 16-byte alignment");
-    EOD_REQUIRE((long long)d->H * d->W * d->C0 * 2 < 0x7fffffffLL && 9LL * d->Cout * 4 * d->C0 * 2 < 0x7fffffffLL, "conv (upsample 4): operand exceeds the 2 GiB window");
-    IgemmP p = {};
-    p.a0 = (const char*)d->x; p.b = (const char*)d->w; p.bias = d->bias; p.bias_mode = d->bias ? 1 : 0;
-    p.cbias = d->cbias; p.cbias_stride = d->cbias_stride; p.res = (const char*)d->res; p.y = (char*)d->y;
-    p.N = d->N; p.H = d->Ho; p.W = d->Wo;  // the kernel works on the STORED (output) map; the gradient is (2H x 2W)
-    p.C0 = d->C0; p.C1 = 0; p.Cin = d->C0; p.Cout = d->Cout; p.KS = 3; p.stride = 1; p.pad = 1;
-    p.Ho = d->Ho; p.Wo = d->Wo; p.HoWo = d->Ho * d->Wo; p.Heff = d->Ho; p.Weff = d->Wo;
-    p.Hd = d->Ho; p.Wd = d->Wo; p.HWd = d->Ho * d->Wo;
-    p.M = (long long)d->N * d->Ho * d->Wo; p.Ncols = d->Cout; p.taps = 9; p.alpha = d->alpha; p.nb1 = 1; p.tapmajor_log2 = -1;
-    return launch_up4<half_t, false, true>(p, (hipStream_t)stream);
-}
-// 3x3 / stride 2 / pad 1 on conv_s2_halo_kernel (EOD_S2_HALO=0: the generic kernel, A/B): output maps that tile into 8 x 16 patches,
-// one source, 128-column tiles.  Only where the generic kernel runs unsplit in K, so both arms have the same workspace (none) and the
-// same statistics slots (8 x 16 tiles = the generic kernel's 128-row tiles, two wave rows each): the switch never changes a plan's
-// buffers.  (Odd input maps are covered: the plane positions outside the map are masked like the zero padding.)
-static int conv_splitk(const eod_conv_desc* d, int Ho, int Wo, bool halo);
+// 3x3 / stride 2 / pad 1 on conv_s2_halo_kernel: output maps that tile into 8 x 16 patches, one source, 128-column tiles.  (Odd input maps
+// are covered: the plane positions outside the map are masked like the zero padding.)
 static bool conv_s2_halo_ok(const eod_conv_desc* d, int Ho, int Wo) {
-    const bool store_ok = d->dtype == EOD_F16 || (d->dtype == EOD_F32 && d->w_split);
-    return opt(OPT_S2_HALO) != 0 && d->ksize == 3 && d->stride == 2 && d->pad == 1 && !d->pad_tl && !d->upsample && d->C1 == 0 && !d->x2 &&
-           d->Cout > 64 && d->Cout % 8 == 0 && d->C0 % 8 == 0 && Ho % 8 == 0 && Wo % 16 == 0 && !d->out_nchw_f32 && !d->w_tapmajor &&
-           !d->gn_scale_shift && !d->skip_x && !d->x_presplit && !d->y_presplit_bound && store_ok && conv_splitk(d, Ho, Wo, false) <= 1;
+    return d->ksize == 3 && d->stride == 2 && d->pad == 1 && !d->pad_tl && !d->upsample && d->C1 == 0 && !d->x2 && d->Cout > 64 &&
+           d->Cout % 8 == 0 && d->C0 % 8 == 0 && Ho % 8 == 0 && Wo % 16 == 0 && !d->out_nchw_f32 && !d->w_tapmajor && !d->gn_scale_shift &&
+           !d->skip_x && !d->x_presplit && !d->y_presplit_bound && conv_mma16(d);
 }
-// the UNet's output head on conv_head_kernel (EOD_HEAD=0: the 32-column halo instance, A/B)
 // the fp32x3 first conv (thin input, tap-major split weights) on conv_first_x3_kernel: 8 x 16 pixel tiles, 128-column workgroups
 static bool conv_first_ok(const eod_conv_desc* d, int Ho, int Wo) {
-    return opt(OPT_FIRST) != 0 && d->w_tapmajor && d->w_split && d->dtype == EOD_F32 && d->ksize == 3 && d->stride == 1 && d->pad == 1 && !d->pad_tl &&
-           !d->upsample && d->C1 == 0 && !d->x2 && (d->C0 == 4 || d->C0 == 8) && Ho % 8 == 0 && Wo % 16 == 0 && d->Cout % 4 == 0 && d->Cout > 64 && !d->out_nchw_f32 &&
+    return d->w_tapmajor && d->w_split && d->dtype == EOD_F32 && d->ksize == 3 && d->stride == 1 && d->pad == 1 && !d->pad_tl && !d->upsample &&
+           d->C1 == 0 && !d->x2 && (d->C0 == 4 || d->C0 == 8) && Ho % 8 == 0 && Wo % 16 == 0 && d->Cout % 4 == 0 && d->Cout > 64 && !d->out_nchw_f32 &&
            !d->gn_scale_shift && !d->skip_x && !d->x_presplit && !d->y_presplit_bound;
 }
-static bool conv_head_ok(const eod_conv_desc* d, bool halo_ok) {
-    const bool on = opt(OPT_HEAD) != 0;
-    const bool store_ok = d->dtype == EOD_F16 || (d->dtype == EOD_F32 && d->w_split);
-    return on && halo_ok && d->out_nchw_f32 && d->Cout <= 16 && d->gn_scale_shift && d->C1 == 0 && !d->x2 && !d->upsample && !d->res && !d->cbias &&
-           !d->stats && store_ok && d->C0 % 8 == 0 && d->C0 <= HEAD_MAX_C;
+// the UNet's output head on conv_head_kernel: GroupNorm + SiLU fused, <= 16 channels, NCHW fp32, on a halo geometry
+static bool conv_head_ok(const eod_conv_desc* d) {
+    return d->out_nchw_f32 && d->Cout <= 16 && d->gn_scale_shift && d->C1 == 0 && !d->x2 && !d->upsample && !d->res && !d->cbias && !d->stats &&
+           conv_mma16(d) && d->C0 % 8 == 0 && d->C0 <= HEAD_MAX_C;
 }
-// 256-column convs with a fused GroupNorm on the 8-wave instance that shares one patch between the two N-tiles (EOD_HALO_BN256=0: off, A/B).
-// (fp16 storage WITHOUT a fused GroupNorm -- the training step's convs -- measured on it in round 4: 128 x 128 maps -3 %, 32 x 32 +2 %: not used)
-static int conv_splitk(const eod_conv_desc* d, int Ho, int Wo, bool halo);
-static bool halo_bn256(const eod_conv_desc* d) {
-    const bool on = opt(OPT_HALO_BN256) != 0 && conv_splitk(d, d->H, d->W, true) <= 1;
-    // only where it still fills the chip: one 8-wave workgroup occupies a CU, so fewer than 256 of them leave CUs idle (32 x 32 maps at
-    // batch 8: 128 workgroups, measured -20 %; the choice never changes a result: same K order, same MFMAs)
-    const long long wgs = (long long)d->N * (d->H / 8) * ((d->W + 15) / 16) * (d->Cout / 256);
-    return on && d->Cout % 256 == 0 && !d->upsample && wgs >= 256;
-}
-// few pixel tiles (16 x 16 maps and smaller at batch 16): 64-column N-tiles double the workgroup count of a launch that cannot fill the
-// chip (a 384-column conv on a 16 x 16 map at batch 16 has 32 x 3 = 96 workgroups of 128 columns).  Decided from the PER-IMAGE geometry
-// at the nominal batch of 16, never from the actual batch -- and the choice never changes a result (same K order, same MFMA tiles).
-static bool halo_bn64(const eod_conv_desc* d) {
-    const long long wgs = 16LL * (d->H / 8) * ((d->W + 15) / 16) * ((d->Cout + 127) / 128);
-    return d->Cout > 64 && !d->upsample && wgs < 256 && conv_splitk(d, d->H, d->W, true) <= 1;
-}
-// 384, 640, ... columns: all but the last 128 on the 8-wave form, as a launch of its own
-static bool halo_bn256_plus128(const eod_conv_desc* d) {
-    const bool on = opt(OPT_HALO_BN256) != 0 && conv_splitk(d, d->H, d->W, true) <= 1;
-    const long long wgs = (long long)d->N * (d->H / 8) * ((d->W + 15) / 16) * ((d->Cout - 128) / 256);
-    return on && d->Cout > 256 && d->Cout % 256 == 128 && !d->upsample && wgs >= 256;
-}
-// ResBlock 1x1 skip conv fused behind the 3x3 K loop (conv3x3_halo_kernel<SKIP>; EOD_SKIP_FUSE=0: off, A/B)
+// ResBlock 1x1 skip conv fused behind the 3x3 K loop (conv3x3_halo_kernel<SKIP>), on a halo geometry
 static bool conv_skip_geom_ok(const eod_conv_desc* d) {
-    const bool on = opt(OPT_SKIP_FUSE) != 0;
-    if (!on || !d || d->ksize != 3 || d->stride != 1 || d->pad != 1 || d->upsample || d->pad_tl || d->C1 != 0 || d->x2 || d->res ||
-        d->out_nchw_f32 || d->w_tapmajor || d->Cout <= 64 || d->Cout % 8 || d->C0 % 8)
-        return false;
-    if (d->skip_C0 <= 0 || d->skip_C0 % 8 || d->skip_C1 < 0 || d->skip_C1 % 8) return false;
-    const int Ho = d->H, Wo = d->W;
-    if (!conv_uses_halo(d, Ho, Wo)) return false;
-    return d->dtype == EOD_F16 || (d->dtype == EOD_F32 && d->w_split);
-}
-extern "C" int eod_conv_skip_ok(const eod_conv_desc* d) { return conv_skip_geom_ok(d) ? 1 : 0; }
-extern "C" int eod_conv_split_ok(const eod_conv_desc* d) {
-    if (!d) return 0;
-    const int Heff = d->H * (d->upsample ? 2 : 1), Weff = d->W * (d->upsample ? 2 : 1);
-    const int Ho = (Heff + d->pad_tl + 2 * d->pad - d->ksize) / d->stride + 1;
-    const int Wo = (Weff + d->pad_tl + 2 * d->pad - d->ksize) / d->stride + 1;
-    return conv_split_ok(d, Ho, Wo) ? 1 : 0;
+    return d->ksize == 3 && d->stride == 1 && d->pad == 1 && !d->upsample && !d->pad_tl && d->C1 == 0 && !d->x2 && !d->res && !d->out_nchw_f32 &&
+           !d->w_tapmajor && d->Cout > 64 && d->Cout % 8 == 0 && d->C0 % 8 == 0 && d->skip_C0 > 0 && d->skip_C0 % 8 == 0 && d->skip_C1 >= 0 &&
+           d->skip_C1 % 8 == 0 && conv_mma16(d);
 }
 
-// 1 if eod_conv2d_igemm can apply GroupNorm(+SiLU) to the conv INPUT on the fly (gn_scale_shift) for this geometry.
-// The fused form re-normalises the halo patch once per N-tile (Cout / 128 times), so in fp16 storage it only pays while the conv has
-// few N-tiles (measured on MI355X: Cout <= 256, the separate apply pass wins beyond); in fp32 storage (split product) it pays at
-// every width the UNet has.
-extern "C" int eod_conv_gn_fusable(const eod_conv_desc* d) {
-    if (!d || d->upsample) return 0;
-    const int Ho = (d->H + d->pad_tl + 2 * d->pad - d->ksize) / d->stride + 1;
-    const int Wo = (d->W + d->pad_tl + 2 * d->pad - d->ksize) / d->stride + 1;
-    const int env_cout = opt(OPT_GN_FUSE_MAX_COUT);
-    // measured (same-box A/B of bench.py): fp32 storage with the split product pays for the fusion at every width (a separate pass
-    // moves 8 bytes per element; 384 / 512-wide layers: step -0.2 ms), fp16 storage up to 256 output channels
-    const int max_cout = env_cout >= 0 ? env_cout : (d->w_split ? 512 : 256);
-    if (d->Cout > max_cout) return 0;
-    return conv_uses_halo(d, Ho, Wo) ? 1 : 0;
-}
-
-// split-K factor of a conv that the generic kernel would run with too few workgroups to fill the chip (small maps)
 // K slices of a split halo conv: `s` slices of `per` channel chunks, the last one takes the rest + the fused skip phase.  The largest
 // s <= smax whose longest slice stays within 25 % of the mean (K-steps, the skip phase's included); per of that plan is returned.
 static int halo_split_plan(const eod_conv_desc* d, int smax, int* per_out) {
@@ -3323,14 +3218,16 @@ static int halo_split_plan(const eod_conv_desc* d, int smax, int* per_out) {
             if (per * (s - 1) >= kc) continue;  // the last slice keeps at least one chunk
             const int last = (kc - per * (s - 1)) * 9 + sk, longest = last > per * 9 ? last : per * 9;
             if ((long long)longest * s * 100 <= (long long)total * 125) {
-                if (per_out) *per_out = per;
+                *per_out = per;
                 return s;
             }
         }
     }
     return 1;
 }
-static int conv_splitk(const eod_conv_desc* d, int Ho, int Wo, bool halo) {
+static int generic_bn(int cout) { return cout <= 32 ? 32 : (cout <= 64 ? 64 : 128); }
+// split-K factor of a conv whose launch would have too few workgroups to fill the chip (small maps); halo_on = the halo_splitk option
+static int conv_splitk(const eod_conv_desc* d, int Ho, int Wo, bool halo, bool halo_on, int* per_out) {
     // the factor must NOT depend on the batch size: the K summation order of a sample has to be the same whether it is
     // computed alone or inside a larger batch (bit-exact batch-sharding invariance), so a nominal batch of 16 is used
     const int bk = 128 / eod_esize(d->dtype);
@@ -3338,52 +3235,205 @@ static int conv_splitk(const eod_conv_desc* d, int Ho, int Wo, bool halo) {
         // halo-patch kernel: 128-column tiles of 8 x 16 pixels; fewer than one workgroup per CU (16 x 16 maps at batch 16) -> the channel
         // chunks are split over gridDim.y workgroups (whole chunks: the nine taps of a chunk share its staged patch).  32 x 32 maps
         // (256 workgroups) measured SLOWER split in two: the reduce pass costs more than the second workgroup per CU gains.
-        if (!opt(OPT_HALO_SPLITK) || d->out_nchw_f32 || d->upsample || d->Cout <= 64 || d->Cout % 4) return 1;
+        if (!halo_on || d->out_nchw_f32 || d->upsample || d->Cout <= 64 || d->Cout % 4) return 1;
         const long long wgs = 16LL * (Ho / 8) * ((Wo + 15) / 16) * ((d->Cout + 127) / 128);
         const int kc = (d->C0 + bk - 1) / bk + (d->C1 + bk - 1) / bk;
         if (wgs >= 256 || kc < 4) return 1;
         int s = (int)((512 + wgs - 1) / wgs);
         if (s > kc / 2) s = kc / 2;  // at least two chunks (18 K-steps) per slice
         if (s > 8) s = 8;
-        return halo_split_plan(d, s, nullptr);
+        return halo_split_plan(d, s, per_out);
     }
     if (d->out_nchw_f32 || d->Cout % 4 || d->w_tapmajor) return 1;
     const long long M = 16LL * Ho * Wo;
-    const int bn = d->Cout <= 32 ? 32 : (d->Cout <= 64 ? 64 : 128);
+    const int bn = generic_bn(d->Cout);
     const long long tiles = ((M + 127) / 128) * ((d->Cout + bn - 1) / bn);
     const int kt = ((d->C0 + bk - 1) / bk + (d->C1 + bk - 1) / bk) * d->ksize * d->ksize;
-    if (tiles >= 128 || kt < 8) return 1;
+    if (tiles <= 0 || tiles >= 128 || kt < 8) return 1;
     int s = (int)(512 / tiles);  // two workgroups per CU (same-box A/B on the 64 x 64 configuration: 3.59 -> 3.47 ms per step against 256 / tiles)
     if (s > kt / 4) s = kt / 4;
     if (s > 16) s = 16;
     return s < 2 ? 1 : s;
 }
 
+// Every decision about a conv descriptor, taken ONCE: the geometry queries below and eod_conv2d_igemm read this plan, so a caller that
+// sizes its buffers from the queries and the launcher agree by construction.  conv_plan() is pure host arithmetic, evaluates the split-K
+// factor once and is the only place that reads a kernel-selection option for a conv: the launchers receive decisions.
+enum { FAM_UP4, FAM_UP4_BWD, FAM_FIRST, FAM_S2_HALO, FAM_HEAD, FAM_HALO, FAM_GENERIC, FAM_GENERIC_PARITY };
+struct ConvPlan {
+    int Heff, Weff, Ho, Wo;
+    bool halo;       // halo-patch geometry (conv_uses_halo)
+    int family;      // FAM_*
+    int bn;          // HALO / GENERIC: columns per workgroup (32, 64, 128, 256)
+    bool plus128;    // HALO, bn = 256: all but the last 128 columns on the 8-wave form, the rest as a 128-column launch of its own
+    bool direct;     // GENERIC split product: swapped-operand instance with the direct epilogue
+    int splitk, splitk_per;  // K slices over gridDim.y (1 = none); halo kernel: channel chunks per slice
+    int tpw, tpw_tail;       // HALO streaming instances / HEAD: pixel tiles per workgroup (tpw_tail: the plus128 form's last launch)
+    int64_t workspace_bytes;
+    int stats_slots;
+    bool gn_fusable, skip_ok;
+};
+static ConvPlan conv_plan(const eod_conv_desc* d) {
+    ConvPlan pl = {};
+    pl.bn = 128;
+    pl.splitk = pl.tpw = pl.tpw_tail = 1;
+    if (d->upsample == 4) {  // dX on the (H/2 x W/2) grid: no workspace, no statistics, nothing fused
+        pl.family = FAM_UP4_BWD;
+        pl.Heff = pl.Ho = d->H / 2;
+        pl.Weff = pl.Wo = d->W / 2;
+        return pl;
+    }
+    pl.Heff = d->H * (d->upsample ? 2 : 1);
+    pl.Weff = d->W * (d->upsample ? 2 : 1);
+    const int Ho = pl.Ho = conv_out_hw(d, pl.Heff), Wo = pl.Wo = conv_out_hw(d, pl.Weff);
+    const bool split = d->w_split, exact = !split && d->dtype != EOD_F16, gn = d->gn_scale_shift, skip = d->skip_x;
+    pl.halo = conv_uses_halo(d, Ho, Wo);
+    pl.splitk = conv_splitk(d, Ho, Wo, pl.halo, opt(OPT_HALO_SPLITK) != 0, &pl.splitk_per);
+    pl.workspace_bytes = pl.splitk > 1 ? (int64_t)pl.splitk * d->N * Ho * Wo * d->Cout * 4 : 0;
+
+    // GroupNorm partial sums of the output: statistics are accumulated on full 16-byte output chunks only
+    if (d->out_nchw_f32 || d->Cout % (16 / eod_esize(d->dtype))) pl.stats_slots = 0;
+    else if (d->upsample == 3) pl.stats_slots = (d->H / 8) * ((d->W + 15) / 16) * 8;  // parity-class form: (8 x 16 tile of the STORED map, class, wave row)
+    else if (pl.splitk > 1) pl.stats_slots = 1;  // split-K: the reduce pass takes the sums, one slot per image
+    else if (pl.halo) pl.stats_slots = (Ho / 8) * ((Wo + 15) / 16) * 2;  // 8 x 16 pixel tiles (8-wide maps: half of each tile masked), two wave rows each
+    else if ((Ho * Wo) % 128 != 0) pl.stats_slots = 0;  // 128-row tiles must not straddle images
+    else pl.stats_slots = (Ho * Wo / 128) * (d->Cout > 64 ? 2 : 4);  // (tile, wave row); conv_s2_halo_kernel / conv_first_x3_kernel count alike
+
+    // GroupNorm(+SiLU) of the conv INPUT applied in the patch staging (gn_scale_shift; gn_fuse_max_cout option).  The fused form
+    // re-normalises the halo patch once per N-tile (Cout / 128 times).  Measured (same-box A/B of bench.py): fp32 storage with the split
+    // product pays for the fusion at every width the UNet has (a separate pass moves 8 bytes per element; 384 / 512-wide layers: step
+    // -0.2 ms), fp16 storage only while the conv has few N-tiles (Cout <= 256, the separate apply pass wins beyond)
+    const int max_cout = opt(OPT_GN_FUSE_MAX_COUT) >= 0 ? opt(OPT_GN_FUSE_MAX_COUT) : (split ? 512 : 256);
+    pl.gn_fusable = !d->upsample && d->Cout <= max_cout && pl.halo;
+    pl.skip_ok = opt(OPT_SKIP_FUSE) != 0 && conv_skip_geom_ok(d) && pl.halo;  // (EOD_SKIP_FUSE=0: the skip conv as a launch of its own, A/B)
+
+    const long long tiles_pi = (long long)(Ho / 8) * ((Wo + 15) / 16);  // 8 x 16 pixel tiles per image
+    if (d->upsample == 3) {
+        pl.family = FAM_UP4;
+    } else if (opt(OPT_FIRST) != 0 && conv_first_ok(d, Ho, Wo)) {  // (EOD_FIRST=0: the generic kernel, A/B)
+        pl.family = FAM_FIRST;
+    } else if (opt(OPT_S2_HALO) != 0 && conv_s2_halo_ok(d, Ho, Wo) && pl.splitk <= 1) {
+        // (EOD_S2_HALO=0: the generic kernel, A/B.)  Only where the generic kernel runs unsplit in K, so both arms have the same workspace
+        // (none) and the same statistics slots (8 x 16 tiles = the generic kernel's 128-row tiles, two wave rows each): the switch never
+        // changes a plan's buffers.
+        pl.family = FAM_S2_HALO;
+    } else if (opt(OPT_HEAD) != 0 && pl.halo && conv_head_ok(d)) {  // (EOD_HEAD=0: the 32-column halo instance, A/B)
+        pl.family = FAM_HEAD;
+        // runs of tpw consecutive tiles of one image per workgroup (the kernel's chunk stream; head_tpw option, 0 = choose): the longest run
+        // that still leaves every CU its two workgroups.  A tile's result does not depend on the run it is computed in, so the choice may
+        // depend on the batch.
+        int tpw = opt(OPT_HEAD_TPW);
+        if (tpw <= 0) {
+            tpw = 16;
+            while (tpw > 1 && (tiles_pi % tpw || tiles_pi * d->N / tpw < 512)) tpw >>= 1;
+        }
+        while (tpw > 1 && tiles_pi % tpw) --tpw;
+        pl.tpw = tpw;
+    } else if (pl.halo) {
+        pl.family = FAM_HALO;
+        // Columns per workgroup.  None of these choices changes a result (same K order, same MFMA tiles); which storage type may take
+        // which form is measured, and stated here only:
+        const bool on256 = opt(OPT_HALO_BN256) != 0;  // (EOD_HALO_BN256=0: two 4-wave workgroups per pixel tile instead of one 8-wave one, A/B)
+        if (d->Cout <= 32) {
+            pl.bn = 32;  // the narrow NCHW-fp32 head conv
+        } else if (d->upsample || pl.splitk > 1) {
+            pl.bn = 128;  // the virtual nearest-2x instance and the K-slice instance exist at 128 columns only
+        } else if (!exact && 16 * tiles_pi * ((d->Cout + 127) / 128) < 256) {
+            // few pixel tiles (16 x 16 maps and smaller at batch 16): 64-column N-tiles double the workgroup count of a launch that cannot
+            // fill the chip (a 384-column conv on a 16 x 16 map at batch 16 has 32 x 3 = 96 workgroups of 128 columns).  Decided from the
+            // PER-IMAGE geometry at the nominal batch of 16, never from the actual batch.  Exact fp32 has no 64-column instance.
+            pl.bn = 64;
+        } else if (on256 && d->Cout % 256 == 0 && d->N * tiles_pi * (d->Cout / 256) >= 256 && ((gn && !exact) || (split && skip))) {
+            // 256-column convs on the 8-wave instance that shares one patch between the two N-tiles: with a fused GroupNorm, and the split
+            // product with a fused skip conv.  (fp16 storage WITHOUT a fused GroupNorm -- the training step's convs -- measured on it in
+            // round 4: 128 x 128 maps -3 %, 32 x 32 +2 %: not used.)  Only where it still fills the chip: one 8-wave workgroup occupies a CU,
+            // so fewer than 256 of them leave CUs idle (32 x 32 maps at batch 8: 128 workgroups, measured -20 %).
+            pl.bn = 256;
+        } else if (on256 && d->Cout > 256 && d->Cout % 256 == 128 && d->N * tiles_pi * ((d->Cout - 128) / 256) >= 256 && split && gn) {
+            pl.bn = 256;  // 384, 640, ... columns of the split product with a fused GroupNorm: 256 + 128
+            pl.plus128 = true;
+        }
+        // streaming instances (split product, 128 / 256 columns, no skip): runs of tpw consecutive pixel tiles of one image per workgroup
+        // (halo_tpw option; 0: chosen per launch).  Which workgroup computes a tile never changes its result (same K order, same MFMAs, its
+        // own statistics slot), so the choice may depend on the batch.
+        auto tpw_of = [&](int cols, int bn) {
+            const long long slots = bn == 256 ? 256 : 512;  // co-resident workgroups of the chip (8 / 4 waves each)
+            const long long wgs = d->N * tiles_pi * ((cols + bn - 1) / bn);
+            int want = opt(OPT_HALO_TPW);
+            if (want <= 0) {  // at least two rounds of workgroups stay (measured on 256 x 256 and 128 x 128 maps: 4 ... 8 tiles per run tie)
+                want = 1;
+                while (want < 8 && wgs / (2 * want) >= 2 * slots) want *= 2;
+            }
+            while (want > 1 && tiles_pi % want) --want;
+            return want;
+        };
+        if (split && !skip && !d->upsample && pl.bn >= 128 && pl.splitk <= 1) {
+            pl.tpw = tpw_of(pl.plus128 ? d->Cout - 128 : d->Cout, pl.bn);
+            if (pl.plus128) pl.tpw_tail = tpw_of(128, 128);
+        }
+    } else {
+        pl.family = pl.splitk <= 1 && !split && conv_parity_ok(d, Ho, Wo) ? FAM_GENERIC_PARITY : FAM_GENERIC;
+        pl.bn = generic_bn(d->Cout);
+        if (split && d->Cout > 64) {
+            // 256 columns per 8-wave workgroup: the pixel rows of a K-step are fetched and split once for two N-tiles (these launches are
+            // bound by that in-place split: four pieces per wave against 48 MFMAs) -- the qkv / proj 1x1 convs of the attention blocks
+            const long long M = (long long)d->N * Ho * Wo;
+            if (d->Cout % 256 == 0 && pl.splitk <= 1 && ((M + 127) / 128) * (d->Cout / 256) >= 256 && opt(OPT_HALO_BN256)) pl.bn = 256;
+            // whole tiles inside one image, no split-K, NHWC output: the instances with swapped MFMA operands and the direct epilogue
+            // (halo_epilogue_direct: no LDS transpose; fp32 or pre-split output)
+            pl.direct = pl.splitk <= 1 && !d->out_nchw_f32 && (Ho * Wo) % 128 == 0 && M % 128 == 0 && d->Cout % 4 == 0;
+        }
+    }
+    return pl;
+}
+
+extern "C" int eod_conv_skip_ok(const eod_conv_desc* d) { return d && conv_plan(d).skip_ok ? 1 : 0; }
+// 1 if eod_conv2d_igemm can apply GroupNorm(+SiLU) to the conv INPUT on the fly (gn_scale_shift) for this geometry
+extern "C" int eod_conv_gn_fusable(const eod_conv_desc* d) { return d && conv_plan(d).gn_fusable ? 1 : 0; }
 // bytes of caller-provided fp32 workspace eod_conv2d_igemm needs for this descriptor (0 = none)
-extern "C" int64_t eod_conv_workspace_size(const eod_conv_desc* d) {
-    if (!d || d->upsample == 4) return 0;
-    const int Heff = d->H * (d->upsample ? 2 : 1), Weff = d->W * (d->upsample ? 2 : 1);
-    const int Ho = (Heff + d->pad_tl + 2 * d->pad - d->ksize) / d->stride + 1;
-    const int Wo = (Weff + d->pad_tl + 2 * d->pad - d->ksize) / d->stride + 1;
-    const int s = conv_splitk(d, Ho, Wo, conv_uses_halo(d, Ho, Wo));
-    return s > 1 ? (int64_t)s * d->N * Ho * Wo * d->Cout * 4 : 0;
+extern "C" int64_t eod_conv_workspace_size(const eod_conv_desc* d) { return d ? conv_plan(d).workspace_bytes : 0; }
+extern "C" int eod_conv_stats_slots(const eod_conv_desc* d) { return d ? conv_plan(d).stats_slots : 0; }
+// the kernel family this descriptor runs on (bench.py's per-op tables, the per-family tolerances of the float64 pins)
+extern "C" const char* eod_conv_kernel_name(const eod_conv_desc* d) {
+    if (!d) return "";
+    const ConvPlan pl = conv_plan(d);
+    switch (pl.family) {
+        case FAM_UP4: case FAM_UP4_BWD: return "conv_up4_halo_kernel";
+        case FAM_FIRST: return "conv_first_x3_kernel";
+        case FAM_S2_HALO: return "conv_s2_halo_kernel";
+        case FAM_HEAD: return "conv_head_kernel";
+        case FAM_HALO: return pl.bn == 32 ? "conv3x3_halo_kernel<BN=32>" : "conv3x3_halo_kernel";
+        default: return "igemm_kernel";
+    }
 }
 
-extern "C" int eod_conv_stats_slots(const eod_conv_desc* d) {
-    if (!d || d->out_nchw_f32 || d->upsample == 4) return 0;
-    if (d->Cout % (16 / eod_esize(d->dtype))) return 0;  // statistics are accumulated on full 16-byte output chunks only
-    const int Heff = d->H * (d->upsample ? 2 : 1), Weff = d->W * (d->upsample ? 2 : 1);
-    const int Ho = (Heff + d->pad_tl + 2 * d->pad - d->ksize) / d->stride + 1;
-    const int Wo = (Weff + d->pad_tl + 2 * d->pad - d->ksize) / d->stride + 1;
-    if (d->upsample == 3) return (d->H / 8) * ((d->W + 15) / 16) * 8;  // parity-class form: (8 x 16 tile of the STORED map, class, wave row)
-    const bool halo = conv_uses_halo(d, Ho, Wo);
-    if (conv_splitk(d, Ho, Wo, halo) > 1) return 1;  // split-K: the reduce pass takes the sums, one slot per image
-    if (halo) return (Ho / 8) * ((Wo + 15) / 16) * 2;  // 8 x 16 pixel tiles (8-wide maps: half of each tile masked), two wave rows each
-    const int bm = conv_bm(d, halo);
-    if ((Ho * Wo) % bm != 0) return 0;  // tiles must not straddle images
-    return (Ho * Wo / bm) * conv_waves_m(d, halo);
+static int conv_up4_bwd(const eod_conv_desc* d, void* stream) {
+    EOD_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->C0 > 0 && d->Cout > 0 && d->x && d->w && d->y, "conv (upsample 4): bad args");
+    EOD_REQUIRE(conv_up4_bwd_ok(d), "conv: upsample = 4 needs a geometry for which eod_conv_up4_bwd_ok(d) == 1");
+    EOD_REQUIRE(eod_aligned16(d->x) && eod_aligned16(d->w), "conv: 16-byte alignment");
+    EOD_REQUIRE((long long)d->H * d->W * d->C0 * 2 < 0x7fffffffLL && 9LL * d->Cout * 4 * d->C0 * 2 < 0x7fffffffLL, "conv (upsample 4): operand exceeds the 2 GiB window");
+    const ConvPlan pl = conv_plan(d);
+    IgemmP p = {};
+    p.a0 = (const char*)d->x; p.b = (const char*)d->w; p.bias = d->bias; p.bias_mode = d->bias ? 1 : 0;
+    p.cbias = d->cbias; p.cbias_stride = d->cbias_stride; p.res = (const char*)d->res; p.y = (char*)d->y;
+    p.N = d->N; p.H = pl.Ho; p.W = pl.Wo;  // the kernel works on the STORED (output) map; the gradient is (2H x 2W)
+    p.C0 = d->C0; p.C1 = 0; p.Cin = d->C0; p.Cout = d->Cout; p.KS = 3; p.stride = 1; p.pad = 1;
+    p.Ho = pl.Ho; p.Wo = pl.Wo; p.HoWo = pl.Ho * pl.Wo; p.Heff = pl.Heff; p.Weff = pl.Weff;
+    p.Hd = pl.Ho; p.Wd = pl.Wo; p.HWd = pl.Ho * pl.Wo;
+    p.M = (long long)d->N * pl.Ho * pl.Wo; p.Ncols = d->Cout; p.taps = 9; p.alpha = d->alpha; p.nb1 = 1; p.tapmajor_log2 = -1;
+    return launch_up4<half_t, false, true>(p, (hipStream_t)stream);
 }
 
+// first pass of a split-K conv: the K slices write raw fp32 partial tiles to the caller's workspace, the epilogue is left to splitk_finish
+static IgemmP splitk_partial(const IgemmP& p, const eod_conv_desc* d, const ConvPlan& pl) {
+    IgemmP q = p;
+    q.stats = nullptr;
+    q.splitk = pl.splitk;
+    q.splitk_per = pl.splitk_per;
+    q.y = (char*)d->workspace;
+    q.bias = nullptr; q.bias_mode = 0; q.cbias = nullptr; q.res = nullptr; q.alpha = 1.0f;
+    return q;
+}
 // second pass of a split-K conv: sum the gridDim.y raw fp32 partial tiles of the workspace in their fixed order, apply alpha / bias /
 // per-sample bias / residual, store y (and the next GroupNorm's partial sums: one slot per image)
 static int splitk_finish(const eod_conv_desc* d, const IgemmP& p, int splitk, hipStream_t st) {
@@ -3405,8 +3455,50 @@ static int splitk_finish(const eod_conv_desc* d, const IgemmP& p, int splitk, hi
     EOD_CHECK_LAUNCH("splitk_reduce");
     return EOD_OK;
 }
+static int conv_require_workspace(const eod_conv_desc* d, const ConvPlan& pl) {
+    EOD_REQUIRE(d->workspace && d->workspace_bytes >= pl.workspace_bytes, "conv: workspace of %lld bytes required (eod_conv_workspace_size)", (long long)pl.workspace_bytes);
+    return EOD_OK;
+}
+
+// The ONE mapping from (storage, fused GroupNorm, fused skip, virtual 2x, bn) to a conv3x3_halo_kernel instance.  The if constexpr guards
+// name the instances that exist: 32 columns and the virtual nearest-2x without a fused skip; 64 and 256 columns on the fp16 MFMA only
+// (MS = 16), 256 with a fused GroupNorm or, for the split product, a fused skip.  conv_plan() never asks for another one.
+template <typename T, bool SPLIT, int MS, bool GN, bool SKIP>
+static int launch_halo_bn(IgemmP& p, const eod_conv_desc* d, const ConvPlan& pl, hipStream_t st) {
+    if constexpr (!SKIP) {
+        if (pl.bn == 32) return launch_halo<T, 32, 4, 1, false, 2, GN, SPLIT, MS>(p, st);
+    }
+    if constexpr (!SKIP && !GN) {
+        if (d->upsample) return launch_halo<T, 128, 2, 2, true, 2, false, SPLIT, MS>(p, st);
+    }
+    if constexpr (MS == 16) {
+        if (pl.bn == 64) return launch_halo<T, 64, 2, 2, false, 2, GN, SPLIT, MS, SKIP>(p, st);
+    }
+    if constexpr (MS == 16 && (GN || (SPLIT && SKIP))) {
+        if (pl.bn == 256 && pl.plus128) {  // 256-column tiles on the 8-wave form, the last 128 columns on the 4-wave one
+            IgemmP q = p;
+            q.Ncols = d->Cout - 128;
+            const int rc = launch_halo<T, 256, 2, 4, false, 2, GN, SPLIT, MS, SKIP>(q, st);
+            if (rc != EOD_OK) return rc;
+            p.n_base = d->Cout - 128;
+            p.tpw = pl.tpw_tail;
+            return launch_halo<T, 128, 2, 2, false, 2, GN, SPLIT, MS, SKIP>(p, st);
+        }
+        if (pl.bn == 256) return launch_halo<T, 256, 2, 4, false, 2, GN, SPLIT, MS, SKIP>(p, st);
+    }
+    if (pl.bn == 128) return launch_halo<T, 128, 2, 2, false, 2, GN, SPLIT, MS, SKIP>(p, st);
+    eod_set_error("conv_halo: no %d-column instance for this storage type", pl.bn);
+    return EOD_EINVAL;
+}
+template <typename T, bool SPLIT, int MS> static int launch_halo_T(IgemmP& p, const eod_conv_desc* d, const ConvPlan& pl, hipStream_t st) {
+    if constexpr (MS == 16) {  // (exact fp32 has no fused skip: eod_conv_skip_ok)
+        if (d->skip_x) return d->gn_scale_shift ? launch_halo_bn<T, SPLIT, MS, true, true>(p, d, pl, st) : launch_halo_bn<T, SPLIT, MS, false, true>(p, d, pl, st);
+    }
+    return d->gn_scale_shift ? launch_halo_bn<T, SPLIT, MS, true, false>(p, d, pl, st) : launch_halo_bn<T, SPLIT, MS, false, false>(p, d, pl, st);
+}
 
 extern "C" int eod_conv2d_igemm(const eod_conv_desc* d, void* stream) {
+    // ---- validate ----
     EOD_REQUIRE(d, "conv: null desc");
     EOD_REQUIRE(d->dtype == EOD_F32 || d->dtype == EOD_F16, "conv: bad dtype %d", d->dtype);
     const int es = eod_esize(d->dtype), epc = 16 / es;
@@ -3419,13 +3511,11 @@ extern "C" int eod_conv2d_igemm(const eod_conv_desc* d, void* stream) {
     EOD_REQUIRE(d->x && d->w && d->y, "conv: null pointer");
     EOD_REQUIRE((d->C1 == 0) == (d->x2 == nullptr), "conv: x2/C1 mismatch");
     EOD_REQUIRE(eod_aligned16(d->x) && eod_aligned16(d->w) && (!d->x2 || eod_aligned16(d->x2)), "conv: 16-byte alignment");
-    const int Heff = d->H * (d->upsample ? 2 : 1), Weff = d->W * (d->upsample ? 2 : 1);
-    const int Ho = (Heff + d->pad_tl + 2 * d->pad - d->ksize) / d->stride + 1;
-    const int Wo = (Weff + d->pad_tl + 2 * d->pad - d->ksize) / d->stride + 1;
+    // ---- plan ----
+    const ConvPlan pl = conv_plan(d);
+    const int Ho = pl.Ho, Wo = pl.Wo;
     EOD_REQUIRE(Ho == d->Ho && Wo == d->Wo, "conv: Ho/Wo mismatch: got %dx%d, geometry gives %dx%d", d->Ho, d->Wo, Ho, Wo);
     EOD_REQUIRE(!(d->out_nchw_f32 && d->res), "conv: residual not supported with NCHW output");
-    // per-lane source offsets are 32-bit pixel indices relative to the tile's first image; a 128-row tile spans
-    // at most 129 images (1x1 maps), so bound the pixel index range conservatively
     // per-lane source offsets are 32-bit BYTE offsets inside a 2 GiB window that starts at the tile's first image; a
     // 128-row tile touches at most 2 images once Ho*Wo >= 128 and at most 129 otherwise
     {
@@ -3435,6 +3525,7 @@ extern "C" int eod_conv2d_igemm(const eod_conv_desc* d, void* stream) {
         EOD_REQUIRE(img_bytes * span < 0x7fffffffLL, "conv: one image (%lld bytes) is too large for the 2 GiB tile window", img_bytes);
         EOD_REQUIRE((long long)d->ksize * d->ksize * d->Cout * (d->C0 + d->C1) * es < 0x7fffffffLL, "conv: weights exceed the 2 GiB window");
     }
+    // ---- kernel parameters ----
     IgemmP p = {};
     p.a0 = (const char*)d->x;
     p.a1 = (const char*)d->x2;
@@ -3447,7 +3538,7 @@ extern "C" int eod_conv2d_igemm(const eod_conv_desc* d, void* stream) {
     p.y = (char*)d->y;
     p.N = d->N; p.H = d->H; p.W = d->W; p.C0 = d->C0; p.C1 = d->C1; p.Cin = d->C0 + d->C1; p.Cout = d->Cout;
     p.KS = d->ksize; p.stride = d->stride; p.pad = d->pad; p.ups = d->upsample; p.pad_tl = d->pad_tl;
-    p.Ho = Ho; p.Wo = Wo; p.HoWo = Ho * Wo; p.Heff = Heff; p.Weff = Weff;
+    p.Ho = Ho; p.Wo = Wo; p.HoWo = Ho * Wo; p.Heff = pl.Heff; p.Weff = pl.Weff;
     p.Hd = Ho; p.Wd = Wo; p.HWd = Ho * Wo;
     p.M = (long long)d->N * Ho * Wo;
     p.Ncols = d->Cout;
@@ -3466,175 +3557,77 @@ extern "C" int eod_conv2d_igemm(const eod_conv_desc* d, void* stream) {
         p.ldk = eod_conv_tapmajor_ldk(d->C0, d->dtype);
     }
     hipStream_t st = (hipStream_t)stream;
-    // 3x3 / stride 1 / pad 1 on maps that tile into 8x16 patches: halo-patch kernel
-    const bool halo_ok = conv_uses_halo(d, Ho, Wo);
     if (d->stats) {
-        const int slots = eod_conv_stats_slots(d);
-        EOD_REQUIRE(slots > 0 && slots == d->stats_slots, "conv: stats_slots=%d but this geometry provides %d", d->stats_slots, slots);
+        EOD_REQUIRE(pl.stats_slots > 0 && pl.stats_slots == d->stats_slots, "conv: stats_slots=%d but this geometry provides %d", d->stats_slots, pl.stats_slots);
         p.stats = d->stats;
-        p.stats_P = slots;
-        p.tiles_per_image = Ho * Wo / conv_bm(d, halo_ok);
+        p.stats_P = pl.stats_slots;
+        p.tiles_per_image = Ho * Wo / 128;
     }
-    EOD_REQUIRE(!d->w_split || (conv_split_ok(d, Ho, Wo) && d->w_scale),
+    EOD_REQUIRE(!d->w_split || (conv_split_ok(d) && d->w_scale),
                 "conv: w_split needs a geometry for which eod_conv_split_ok(d) == 1 and the w_scale of eod_pack_conv_weight_split");
     p.w_scale = d->w_split ? d->w_scale : nullptr;
     p.w_rexp = d->w_split ? reinterpret_cast<const int*>(d->w_scale) + 4 : nullptr;  // (EOD_WSCALE_ROWS of csrc/misc.hip)
     p.w_row0 = 0;
     p.a_bound = d->w_split ? d->a_bound : nullptr;
-    EOD_REQUIRE(!d->x_presplit || (d->w_split && d->a_bound && !halo_ok && !d->upsample && !d->w_tapmajor && !d->gn_scale_shift),
+    EOD_REQUIRE(!d->x_presplit || (d->w_split && d->a_bound && !pl.halo && !d->upsample && !d->w_tapmajor && !d->gn_scale_shift),
                 "conv: x_presplit needs w_split with the producer's bound table, on the generic kernel (1x1 / stride-2 / small maps)");
     p.a_ps = d->x_presplit;
-    EOD_REQUIRE(!d->y_presplit_bound || (d->w_split && !halo_ok && !d->out_nchw_f32 && !d->stats && d->Cout % 8 == 0 && (Ho * Wo) % 128 == 0 &&
-                                         conv_splitk(d, Ho, Wo, false) <= 1),
+    EOD_REQUIRE(!d->y_presplit_bound || (d->w_split && !pl.halo && !d->out_nchw_f32 && !d->stats && d->Cout % 8 == 0 && (Ho * Wo) % 128 == 0 &&
+                                         pl.splitk <= 1),
                 "conv: y_presplit_bound needs w_split on the generic kernel, Cout %% 8 == 0, whole 128-row tiles per image, no statistics");
     p.y_ps_bound = d->y_presplit_bound;
     p.skip_bound = (d->w_split && d->skip_x) ? d->skip_bound : nullptr;
-    if (d->upsample == 3) {
-        EOD_REQUIRE(conv_up4_ok(d), "conv: upsample = 3 (parity-class form of the nearest-2x conv) needs a geometry for which eod_conv_up4_ok(d) == 1");
-        return d->dtype == EOD_F16 ? launch_up4<half_t, false>(p, st) : launch_up4<float, true>(p, st);
-    }
-    if (conv_first_ok(d, Ho, Wo)) return d->C0 == 4 ? launch_first<4>(p, st) : launch_first<8>(p, st);
-    if (conv_s2_halo_ok(d, Ho, Wo)) return d->dtype == EOD_F16 ? launch_s2<half_t, false>(p, st) : launch_s2<float, true>(p, st);
-    if (conv_head_ok(d, halo_ok)) {  // output head: GroupNorm + SiLU fused, <= 16 channels, NCHW fp32 (conv_head_kernel)
-        p.gn_ss = d->gn_scale_shift;
-        p.gn_silu = d->gn_silu;
-        p.tpw = opt(OPT_HEAD_TPW);
-        return d->dtype == EOD_F16 ? launch_head<half_t, false>(p, st) : launch_head<float, true>(p, st);
-    }
-    // ---- halo-patch kernels (3x3 / stride 1 / pad 1 on maps that tile into 8 x 16 patches), with or without the fused skip conv ----
-    constexpr int NOT_HALO = 1 << 20;
-    auto run_halo = [&](IgemmP& p) -> int {
-        if (d->skip_x) {  // ResBlock 1x1 skip conv fused behind the 3x3 K loop
-            EOD_REQUIRE(conv_skip_geom_ok(d) && halo_ok && d->skip_w, "conv: skip_x needs a geometry for which eod_conv_skip_ok(d) == 1, and skip_w");
-            EOD_REQUIRE((d->skip_C1 > 0) == (d->skip_x2 != nullptr), "conv: skip_x2 / skip_C1 mismatch");
-            EOD_REQUIRE(eod_aligned16(d->skip_x) && eod_aligned16(d->skip_x2) && eod_aligned16(d->skip_w), "conv: 16-byte alignment (skip operands)");
-            {
-                const int es = d->dtype == EOD_F16 ? 2 : 4;
-                const long long smax = d->skip_C0 > d->skip_C1 ? d->skip_C0 : d->skip_C1;
-                EOD_REQUIRE((long long)d->H * d->W * smax * es < 0x7fffffffLL && (long long)d->Cout * (d->skip_C0 + d->skip_C1) * es < 0x7fffffffLL,
-                            "conv: skip operand exceeds the 2 GiB window");
-            }
-            p.sx0 = (const char*)d->skip_x;
-            p.sx1 = (const char*)d->skip_x2;
-            p.b2 = (const char*)d->skip_w;
-            p.SC0 = d->skip_C0;
-            p.SC1 = d->skip_C1;
+    // ---- dispatch on the plan ----
+    const bool f16 = d->dtype == EOD_F16;
+    switch (pl.family) {
+        case FAM_UP4:
+            EOD_REQUIRE(conv_up4_ok(d), "conv: upsample = 3 (parity-class form of the nearest-2x conv) needs a geometry for which eod_conv_up4_ok(d) == 1");
+            return f16 ? launch_up4<half_t, false>(p, st) : launch_up4<float, true>(p, st);
+        case FAM_FIRST: return d->C0 == 4 ? launch_first<4>(p, st) : launch_first<8>(p, st);
+        case FAM_S2_HALO: return f16 ? launch_s2<half_t, false>(p, st) : launch_s2<float, true>(p, st);
+        case FAM_HEAD:
             p.gn_ss = d->gn_scale_shift;
             p.gn_silu = d->gn_silu;
-            if (halo_bn64(d)) {
-                if (d->w_split) return d->gn_scale_shift ? launch_halo<float, 64, 2, 2, false, 2, true, true, 16, true>(p, st)
-                                                         : launch_halo<float, 64, 2, 2, false, 2, false, true, 16, true>(p, st);
-                return d->gn_scale_shift ? launch_halo<half_t, 64, 2, 2, false, 2, true, false, 16, true>(p, st)
-                                         : launch_halo<half_t, 64, 2, 2, false, 2, false, false, 16, true>(p, st);
-            }
-            if (d->w_split && halo_bn256(d))
-                return d->gn_scale_shift ? launch_halo<float, 256, 2, 4, false, 2, true, true, 16, true>(p, st)
-                                         : launch_halo<float, 256, 2, 4, false, 2, false, true, 16, true>(p, st);
-            if (d->w_split && d->gn_scale_shift && halo_bn256_plus128(d)) {  // 256 columns on the 8-wave form, the last 128 on the 4-wave one
-                IgemmP q = p;
-                q.Ncols = d->Cout - 128;
-                const int rc = launch_halo<float, 256, 2, 4, false, 2, true, true, 16, true>(q, st);
-                if (rc != EOD_OK) return rc;
-                p.n_base = d->Cout - 128;
-                return launch_halo<float, 128, 2, 2, false, 2, true, true, 16, true>(p, st);
-            }
-            if (d->w_split) return d->gn_scale_shift ? launch_halo<float, 128, 2, 2, false, 2, true, true, 16, true>(p, st)
-                                                     : launch_halo<float, 128, 2, 2, false, 2, false, true, 16, true>(p, st);
-            if (d->gn_scale_shift && halo_bn256(d)) return launch_halo<half_t, 256, 2, 4, false, 2, true, false, 16, true>(p, st);
-            return d->gn_scale_shift ? launch_halo<half_t, 128, 2, 2, false, 2, true, false, 16, true>(p, st)
-                                     : launch_halo<half_t, 128, 2, 2, false, 2, false, false, 16, true>(p, st);
-        }
-        if (halo_ok && d->w_split) {
-            // fp32 storage, three fp16 MFMAs per product (weights pre-split and pre-scaled, activations split in LDS)
-            if (d->gn_scale_shift) {
-                EOD_REQUIRE(!d->upsample, "conv: fused input GroupNorm is not available together with upsample");
-                p.gn_ss = d->gn_scale_shift;
-                p.gn_silu = d->gn_silu;
-                if (d->Cout <= 32) return launch_halo<float, 32, 4, 1, false, 2, true, true, 16>(p, st);
-                if (halo_bn64(d)) return launch_halo<float, 64, 2, 2, false, 2, true, true, 16>(p, st);
-                if (halo_bn256(d)) return launch_halo<float, 256, 2, 4, false, 2, true, true, 16>(p, st);
-                if (halo_bn256_plus128(d)) {
-                    IgemmP q = p;
-                    q.Ncols = d->Cout - 128;
-                    const int rc = launch_halo<float, 256, 2, 4, false, 2, true, true, 16>(q, st);
-                    if (rc != EOD_OK) return rc;
-                    p.n_base = d->Cout - 128;
-                    return launch_halo<float, 128, 2, 2, false, 2, true, true, 16>(p, st);
-                }
-                return launch_halo<float, 128, 2, 2, false, 2, true, true, 16>(p, st);
-            }
-            if (d->Cout <= 32) return launch_halo<float, 32, 4, 1, false, 2, false, true, 16>(p, st);
-            if (d->upsample) return launch_halo<float, 128, 2, 2, true, 2, false, true, 16>(p, st);
-            if (halo_bn64(d)) return launch_halo<float, 64, 2, 2, false, 2, false, true, 16>(p, st);
-            return launch_halo<float, 128, 2, 2, false, 2, false, true, 16>(p, st);
-        }
-        if (halo_ok && d->dtype == EOD_F16) {
-            if (d->gn_scale_shift) {
-                EOD_REQUIRE(!d->upsample, "conv: fused input GroupNorm is not available together with upsample");
-                p.gn_ss = d->gn_scale_shift;
-                p.gn_silu = d->gn_silu;
-                if (d->Cout <= 32) return launch_halo<half_t, 32, 4, 1, false, 2, true, false, 16>(p, st);
-                if (halo_bn64(d)) return launch_halo<half_t, 64, 2, 2, false, 2, true, false, 16>(p, st);
-                if (halo_bn256(d)) return launch_halo<half_t, 256, 2, 4, false, 2, true, false, 16>(p, st);
-                return launch_halo<half_t, 128, 2, 2, false, 2, true, false, 16>(p, st);
-            }
-            if (d->Cout <= 32) return launch_halo<half_t, 32, 4, 1, false, 2, false, false, 16>(p, st);
-            if (d->upsample) return launch_halo<half_t, 128, 2, 2, true, 2, false, false, 16>(p, st);
-            if (halo_bn64(d)) return launch_halo<half_t, 64, 2, 2, false, 2, false, false, 16>(p, st);
-            return launch_halo<half_t, 128, 2, 2, false, 2, false, false, 16>(p, st);
-        }
-        if (halo_ok) {  // exact fp32 (v_mfma_f32_32x32x2_f32 on the same byte-oriented LDS image)
-            if (d->gn_scale_shift) {  // GroupNorm(+SiLU) of the input fused into the patch staging
-                EOD_REQUIRE(!d->upsample, "conv: fused input GroupNorm is not available together with upsample");
-                p.gn_ss = d->gn_scale_shift;
-                p.gn_silu = d->gn_silu;
-                return d->Cout <= 32 ? launch_halo<float, 32, 4, 1, false, 2, true>(p, st) : launch_halo<float, 128, 2, 2, false, 2, true>(p, st);
-            }
-            if (d->Cout <= 32) return launch_halo<float, 32, 4, 1, false, 2, false>(p, st);  // head conv (out_nchw_f32)
-            if (d->upsample) return launch_halo<float, 128, 2, 2, true, 2, false>(p, st);
-            return launch_halo<float, 128, 2, 2, false, 2, false>(p, st);
-        }
-        return NOT_HALO;
-    };
-    if (halo_ok) {
-        const int hsk = conv_splitk(d, Ho, Wo, true);
-        if (hsk > 1) {
-            // too few pixel tiles to fill the chip: K slices over gridDim.y workgroups (fp32 partial tiles in the caller's workspace),
-            // then the deterministic reduce + bias / residual (+ statistics) pass
-            EOD_REQUIRE(d->workspace && d->workspace_bytes >= eod_conv_workspace_size(d), "conv: workspace of %lld bytes required (eod_conv_workspace_size)", (long long)eod_conv_workspace_size(d));
-            IgemmP q = p;
-            q.stats = nullptr;
-            q.splitk = hsk;
-            (void)halo_split_plan(d, hsk, &q.splitk_per);
-            q.y = (char*)d->workspace;
-            q.bias = nullptr; q.bias_mode = 0; q.cbias = nullptr; q.res = nullptr; q.alpha = 1.0f;
-            const int rc = run_halo(q);
-            if (rc != EOD_OK) return rc == NOT_HALO ? EOD_EINVAL : rc;
-            return splitk_finish(d, p, hsk, st);
-        }
+            p.tpw = pl.tpw;
+            return f16 ? launch_head<half_t, false>(p, st) : launch_head<float, true>(p, st);
+        default: break;
     }
-    {
-        const int rc = run_halo(p);
-        if (rc != NOT_HALO) return rc;
+    // too few output tiles to fill the chip: K slices over gridDim.y workgroups (fp32 partial tiles in the caller's workspace), then the
+    // deterministic reduce + bias / residual (+ statistics) pass
+    const bool splitk = pl.splitk > 1;
+    if (pl.family == FAM_HALO && splitk) {
+        const int rc = conv_require_workspace(d, pl);
+        if (rc != EOD_OK) return rc;
+    }
+    if (d->skip_x) {  // ResBlock 1x1 skip conv fused behind the 3x3 K loop
+        EOD_REQUIRE(pl.skip_ok && d->skip_w, "conv: skip_x needs a geometry for which eod_conv_skip_ok(d) == 1, and skip_w");
+        EOD_REQUIRE((d->skip_C1 > 0) == (d->skip_x2 != nullptr), "conv: skip_x2 / skip_C1 mismatch");
+        EOD_REQUIRE(eod_aligned16(d->skip_x) && eod_aligned16(d->skip_x2) && eod_aligned16(d->skip_w), "conv: 16-byte alignment (skip operands)");
+        const long long smax = d->skip_C0 > d->skip_C1 ? d->skip_C0 : d->skip_C1;
+        EOD_REQUIRE((long long)d->H * d->W * smax * es < 0x7fffffffLL && (long long)d->Cout * (d->skip_C0 + d->skip_C1) * es < 0x7fffffffLL,
+                    "conv: skip operand exceeds the 2 GiB window");
+        p.sx0 = (const char*)d->skip_x;
+        p.sx1 = (const char*)d->skip_x2;
+        p.b2 = (const char*)d->skip_w;
+        p.SC0 = d->skip_C0;
+        p.SC1 = d->skip_C1;
+    }
+    if (pl.family == FAM_HALO) {
+        if (d->gn_scale_shift) {  // GroupNorm(+SiLU) of the input fused into the patch staging
+            EOD_REQUIRE(!d->upsample, "conv: fused input GroupNorm is not available together with upsample");
+            p.gn_ss = d->gn_scale_shift;
+            p.gn_silu = d->gn_silu;
+        }
+        p.tpw = pl.tpw;
+        IgemmP q = splitk ? splitk_partial(p, d, pl) : p;
+        // fp32 storage as three fp16 MFMAs per product (weights pre-split and pre-scaled, activations split in LDS); fp16; exact fp32
+        // (v_mfma_f32_32x32x2_f32 on the same byte-oriented LDS image)
+        const int rc = d->w_split ? launch_halo_T<float, true, 16>(q, d, pl, st)
+                                  : f16 ? launch_halo_T<half_t, false, 16>(q, d, pl, st) : launch_halo_T<float, false, 32>(q, d, pl, st);
+        return splitk && rc == EOD_OK ? splitk_finish(d, p, pl.splitk, st) : rc;
     }
     EOD_REQUIRE(!d->gn_scale_shift, "conv: fused input GroupNorm needs the halo-patch kernel (ask eod_conv_gn_fusable first)");
-    const int splitk = conv_splitk(d, Ho, Wo, false);
-    if (splitk > 1) {
-        // small maps: too few output tiles to fill 256 CUs -> split the K loop over gridDim.y workgroups (fp32 partial
-        // tiles in the caller's workspace), then one deterministic reduce + bias/residual pass
-        EOD_REQUIRE(d->workspace && d->workspace_bytes >= eod_conv_workspace_size(d), "conv: workspace of %lld bytes required (eod_conv_workspace_size)", (long long)eod_conv_workspace_size(d));
-        IgemmP q = p;
-        q.stats = nullptr;
-        q.splitk = splitk;
-        q.y = (char*)d->workspace;
-        q.bias = nullptr; q.bias_mode = 0; q.cbias = nullptr; q.res = nullptr; q.alpha = 1.0f;
-        const int rc = d->w_split ? launch_conv_split(q, splitk, st)
-                                  : d->dtype == EOD_F16 ? launch_T<half_t, true>(q, splitk, st) : launch_T<float, true>(q, splitk, st);
-        if (rc != EOD_OK) return rc;
-        return splitk_finish(d, p, splitk, st);
-    }
-    if (d->w_split) return launch_conv_split(p, 1, st);
-    if (conv_parity_ok(d, Ho, Wo)) {
+    if (pl.family == FAM_GENERIC_PARITY) {
         // zero-insertion upsampling (backward-data of a stride-2 conv): 3/4 of the (output position, tap) pairs meet an inserted zero,
         // and WHICH taps do depends only on the parity of the output position -> four launches, one per parity class, each over the
         // quarter grid with its 1 / 2 / 2 / 4 live taps (9 tap-visits per 4 outputs instead of 36)
@@ -3650,12 +3643,19 @@ extern "C" int eod_conv2d_igemm(const eod_conv_desc* d, void* stream) {
             q.taps = 0; q.taplist = 0;
             for (int a = 0; a < ndy; ++a)
                 for (int b = 0; b < ndx; ++b) q.taplist |= (unsigned)(dys[a] * 3 + dxs[b]) << (4 * q.taps++);
-            const int rc = d->dtype == EOD_F16 ? launch_T<half_t, true>(q, 1, st) : launch_T<float, true>(q, 1, st);
+            const int rc = f16 ? launch_T<half_t, true>(q, 1, st) : launch_T<float, true>(q, 1, st);
             if (rc != EOD_OK) return rc;
         }
         return EOD_OK;
     }
-    return d->dtype == EOD_F16 ? launch_T<half_t, true>(p, 1, st) : launch_T<float, true>(p, 1, st);
+    if (splitk) {
+        const int rc = conv_require_workspace(d, pl);
+        if (rc != EOD_OK) return rc;
+    }
+    IgemmP q = splitk ? splitk_partial(p, d, pl) : p;
+    const int rc = d->w_split ? launch_conv_split(q, pl.bn, pl.direct, pl.splitk, st)
+                              : f16 ? launch_T<half_t, true>(q, pl.splitk, st) : launch_T<float, true>(q, pl.splitk, st);
+    return splitk && rc == EOD_OK ? splitk_finish(d, p, pl.splitk, st) : rc;
 }
 
 extern "C" int eod_gemm_nt(const eod_gemm_desc* d, void* stream) {

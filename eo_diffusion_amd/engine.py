@@ -648,22 +648,9 @@ class Program:
                 fl = 2.0 * m * d.Cout * (cin_alg * d.ksize * d.ksize + sc)
                 by = es * (d.N * d.H * d.W * (cin + sc) + d.ksize * d.ksize * d.Cout * cin + d.Cout * sc + (0 if d.out_nchw_f32 else m * d.Cout)) \
                     + (4 * m * d.Cout if d.out_nchw_f32 else 0) + (es * m * d.Cout if d.res else 0)
-                geo = d.ksize == 3 and d.stride == 1 and d.pad == 1 and not d.pad_tl and (d.Wo % 16 == 0 or (d.Wo == 8 and d.Cout > 64 and not d.upsample)) and d.Ho % 8 == 0
-                halo = geo and d.Cout > 64 and not d.out_nchw_f32 and not d.w_tapmajor  # mirrors conv_uses_halo() in csrc/igemm.hip
-                head = geo and d.Cout <= 32 and d.out_nchw_f32 and not d.upsample  # 32-column instance (HBM-bound head conv)
-                headk = head and bool(d.gn_scale_shift) and d.Cout <= 16 and d.C1 == 0 and cin <= 384 and self.precision != "fp32" \
-                    and self.L.eod_get_option(b"head") != 0  # mirrors conv_head_ok()
-                first = geo and bool(d.w_tapmajor) and bool(d.w_split) and d.Wo % 16 == 0 and d.Cout > 64 and d.C0 in (4, 8) and not d.out_nchw_f32 \
-                    and self.L.eod_get_option(b"first") != 0  # mirrors conv_first_ok()
-                s2 = d.ksize == 3 and d.stride == 2 and d.pad == 1 and not d.pad_tl and not d.upsample and d.C1 == 0 and d.Cout > 64 \
-                    and d.Cout % 8 == 0 and d.Ho % 8 == 0 and d.Wo % 16 == 0 and not d.out_nchw_f32 and not d.w_tapmajor and not d.gn_scale_shift \
-                    and not d.skip_x and not d.x_presplit and not d.y_presplit_bound and self.precision != "fp32" and not d.workspace \
-                    and self.L.eod_get_option(b"s2_halo") != 0  # mirrors conv_s2_halo_ok() (no workspace: the generic kernel would run unsplit)
                 up4 = d.upsample == 3  # parity-class form of the nearest-2x conv: the algorithm's 9 taps are executed as 4 (pre-summed)
                 out.append(dict(kind="conv", flops=fl, bytes=by, exec_flops=fl * (4.0 / 9.0 if up4 else 1.0),
-                                kernel="conv_up4_halo_kernel" if up4 else "conv3x3_halo_kernel" if halo else
-                                       "conv_head_kernel" if headk else "conv3x3_halo_kernel<BN=32>" if head else
-                                       "conv_first_x3_kernel" if first else "conv_s2_halo_kernel" if s2 else "igemm_kernel",
+                                kernel=self.L.eod_conv_kernel_name(C.byref(d)).decode(),  # the family of the library's own plan
                                 label=f"conv{d.ksize}x{d.ksize}s{d.stride}{'u4' if up4 else 'u' if d.upsample else ''} {d.H}x{d.W} {cin}->{d.Cout}"
                                       + (f" +skip1x1 {sc}" if sc else "")))
             elif k == OP_GEMM:

@@ -35,12 +35,13 @@ const char* eod_last_error(void);
  * buffer of eod_pack_conv_weight_split, the 4-int state of eod_adamw_step_guarded).  eod_version() returns the value the library was built
  * with; a binding compares it with the header it mirrors at load time (eo_diffusion_amd/_lib.py does) instead of finding out by an
  * out-of-bounds device write. */
-#define EOD_ABI_VERSION 107
+#define EOD_ABI_VERSION 108
 int eod_version(void);
-/* Kernel-selection options ("skip_fuse", "head", "halo_bn256", "halo_splitk", "first": 1 / 0; "gn_fuse_max_cout": n, -1 = default; "halo_tpw":
- * pixel tiles per workgroup of the streaming halo instances, 1 = off = default, 0 = chosen per launch): every option has one
- * measured-best default, the other arm computes the same function on another kernel (same-box A/B runs, per-switch parity tests).
- * Read from the environment (EOD_SKIP_FUSE, EOD_HEAD, EOD_HALO_BN256, EOD_GN_FUSE_MAX_COUT, EOD_HALO_TPW, EOD_HALO_SPLITK, EOD_FIRST) at first use; returns the previous value,
+/* Kernel-selection options ("skip_fuse", "head", "halo_bn256", "halo_splitk", "first", "s2_halo": 1 / 0; "gn_fuse_max_cout": n, -1 = default;
+ * "halo_tpw": pixel tiles per workgroup of the streaming halo instances, 1 = off = default, 0 = chosen per launch; "head_tpw": the same of
+ * conv_head_kernel, 0 = chosen per launch = default): every option has one measured-best default, the other arm computes the same function
+ * on another kernel (same-box A/B runs, per-switch parity tests).  Read from the environment (EOD_SKIP_FUSE, EOD_HEAD, EOD_HALO_BN256,
+ * EOD_GN_FUSE_MAX_COUT, EOD_HALO_TPW, EOD_HALO_SPLITK, EOD_FIRST, EOD_HEAD_TPW, EOD_S2_HALO) at first use; returns the previous value,
  * or EOD_EINVAL for an unknown name.  Plans built before a change keep the kernels they were built with. */
 int eod_set_option(const char* name, int value);
 int eod_get_option(const char* name);
@@ -150,6 +151,9 @@ int eod_conv_up4_weights(const float* w_oihw, float* wc, int Cout, int Cin, void
  * eod_pack_conv_weight_dgrad (cout_pad = 4*C0) of the class-kernel tensor of eod_conv_up4_weights; Cout = channels of dX. */
 int eod_conv_up4_bwd_ok(const eod_conv_desc* d);
 int64_t eod_conv_workspace_size(const eod_conv_desc* d);
+/* the kernel family eod_conv2d_igemm runs this descriptor on under the current options (a static string): "conv3x3_halo_kernel",
+ * "conv3x3_halo_kernel<BN=32>", "conv_up4_halo_kernel", "conv_s2_halo_kernel", "conv_first_x3_kernel", "conv_head_kernel" or "igemm_kernel" */
+const char* eod_conv_kernel_name(const eod_conv_desc* d);
 
 /* ------------------------------------------------------------------------------------------
  * k3/k7/k8: batched GEMM on MFMA,  C[b][m][n] = alpha * sum_k A[b][m][k] * B[b][n][k] (+bias)(+res)

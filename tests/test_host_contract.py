@@ -105,6 +105,18 @@ def test_conv_geometry_queries_are_pure_host_predicates():
     assert ok(L.eod_conv_gn_fusable, Cout=256, dtype=_lib.EOD_F16, w_split=0)
     assert not ok(L.eod_conv_gn_fusable, Cout=512, dtype=_lib.EOD_F16, w_split=0)
     assert not ok(L.eod_conv_gn_fusable, stride=2, Ho=16, Wo=16)
+    # the kernel family of the plan the launcher itself follows, under the names of bench.py's per-op tables
+    name = lambda **kw: L.eod_conv_kernel_name(C.byref(desc(**kw))).decode()
+    assert name() == "conv3x3_halo_kernel"
+    assert name(upsample=3, Ho=64, Wo=64) == "conv_up4_halo_kernel"
+    assert name(H=64, W=64, stride=2) == "conv_s2_halo_kernel"
+    assert name(stride=2, Ho=16, Wo=16) == "igemm_kernel"              # 16 x 16 output map: split in K on the generic kernel
+    assert name(ksize=1, pad=0) == "igemm_kernel"
+    assert name(w_tapmajor=1, C0=8) == "conv_first_x3_kernel"
+    assert name(w_tapmajor=1, C0=8, dtype=_lib.EOD_F16, w_split=0) == "igemm_kernel"
+    assert name(Cout=3, out_nchw_f32=1, gn_scale_shift=1 << 20) == "conv_head_kernel"
+    assert name(Cout=3, out_nchw_f32=1, gn_scale_shift=1 << 20, w_split=0) == "conv3x3_halo_kernel<BN=32>"   # exact fp32 has no head kernel
+    assert name(W=24, Wo=24) == "igemm_kernel"                          # 24 columns do not tile
 
 
 def test_product_fails_loudly_without_gpu():

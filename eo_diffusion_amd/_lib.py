@@ -142,6 +142,10 @@ SYMBOLS = {
     "eod_ddim_step": (i32, [vp, vp, vp, f32, f32, f32, f32, f32, vp, vp, i64, vp]),
     "eod_cfg_combine": (i32, [vp, vp, f32, vp, i64, vp]),
     "eod_dpmpp_step": (i32, [vp, vp, vp, f32, f32, f32, f32, f32, f32, i32, vp, vp, i64, vp]),
+    "eod_ddim_step_obs": (i32, [vp, vp, vp, f32, f32, f32, f32, f32, vp, vp, f32, C.POINTER(i32), i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
+    "eod_dpmpp_step_obs": (i32, [vp, vp, vp, f32, f32, f32, f32, f32, f32, i32, vp, vp, f32, C.POINTER(i32), i32, i32, i32, i32, i32, i32, i32,
+                                 vp, vp, vp]),
+    "eod_block_mean": (i32, [vp, C.POINTER(i32), vp, i32, i32, i32, i32, vp]),
     "eod_ldm_p_sample": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, i32, i32, vp]),
     "eod_repaint_cond": (i32, [vp, vp, vp, i32, i32, i64, i32, vp]),
     "eod_postprocess": (i32, [vp, vp, i64, i32, vp]),
@@ -175,7 +179,7 @@ class EodError(RuntimeError):
     pass
 
 
-ABI_VERSION = 108  # EOD_ABI_VERSION of the include/eodiff.h this file mirrors
+ABI_VERSION = 109  # EOD_ABI_VERSION of the include/eodiff.h this file mirrors
 
 
 def lib():

@@ -448,6 +448,315 @@ extern "C" int eod_dpmpp_step(const float* x, const float* e_t, const float* d_p
     return EOD_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Observation consistency (no reference line): the data prediction of a DDIM / DPM-Solver++ step is moved towards
+// an observation of per-channel block means before the update uses it.  blk(i) = the f_c x f_c block of pixel i, anchored at the plane's
+// origin; per pixel, every operation rounded once (-ffp-contract=off):
+//   s     = p0 of the block's first pixel; then + p0 of every other pixel of the block, row by row, left to right (sequential fp32 adds)
+//   mean  = s / float(f_c * f_c)
+//   lm    = lambda * m                       (mask NULL: m = 1.0f)
+//   p0c   = p0 - (lm * (mean - values))
+// One thread owns one block and keeps its f^2 predictions (and the e_t / x the update needs) in registers; the lanes of a wave take
+// neighbouring blocks of a block-row, so a wave reads 64 f contiguous floats per image row.  One launch per factor that occurs among the
+// channels (registers sized to that factor), grid.y = (sample, channel with that factor).  VEC: 16-byte (f = 4, 8; quads of f = 1) or
+// 8-byte (f = 2, 6) accesses; otherwise, and always for odd f, element by element: same arithmetic, same order.  The order of the block
+// sum is a property of the block alone: it does not depend on B, on the launch geometry, on alignment, or on what the plane belongs to.
+// ---------------------------------------------------------------------------------------------
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+enum { OBS_DDIM = 0, OBS_DPMPP = 1, OBS_MEAN = 2 };
+
+struct ObsArgs {
+    const float *x, *e, *noise, *d_prev, *values, *mask;
+    float *out0, *out1;                // x_prev / x_next / the block means;  pred_x0
+    float a, s1m, lambda;              // a_t (a_s), sqrt(1 - a), the weight
+    float k0, k1, k2, k3;              // DDIM: a_prev, sigma_t, temperature, -;  DPM-Solver++: c_x, c_d, w_cur, w_prev
+    int clip, B, C, H, W;
+    int values_b1, mask_b1, mask_c1;   // broadcast: values [1, C, H, W]; mask [1, ., H, W]; mask [., 1, H, W]
+};
+struct ObsChannels {
+    unsigned char c[32];
+    int n;
+};
+struct ObsK {                          // what a step needs per pixel, computed once per thread
+    float sq_a, s1m, lambda, u0, u1, u2, u3;
+    bool clip, second, noisy;
+};
+
+template <int KIND>
+__device__ __forceinline__ ObsK obs_scalars(const ObsArgs& g) {
+    ObsK k;
+    k.s1m = g.s1m; k.lambda = g.lambda; k.clip = g.clip != 0; k.second = g.d_prev != nullptr; k.noisy = g.noise != nullptr;
+    k.sq_a = KIND == OBS_MEAN ? 1.0f : sqrtf(g.a);
+    k.u0 = g.k0; k.u1 = g.k1; k.u2 = g.k2; k.u3 = g.k3;
+    if (KIND == OBS_DDIM) {            // ddim_step_kernel's scalars
+        const float sig2 = g.k1 * g.k1;
+        k.u0 = sqrtf((1.0f - g.k0) - sig2);   // dcoef
+        k.u3 = sqrtf(g.k0);                   // sq_ap
+    }
+    return k;
+}
+
+// p0 as ddim_step_kernel / dpmpp_one form it (OBS_MEAN: the input itself)
+template <int KIND>
+__device__ __forceinline__ float obs_p0(float xv, float e, const ObsK& k) {
+    if (KIND == OBS_MEAN) return xv;
+    const float se = k.s1m * e;
+    float p0 = (xv - se) / k.sq_a;
+    if (KIND == OBS_DPMPP && k.clip) p0 = fminf(fmaxf(p0, -1.0f), 1.0f);
+    return p0;
+}
+
+// the projection and the update of one pixel; aux = e_t (DDIM: the direction) or x (DPM-Solver++: the state term)
+template <int KIND>
+__device__ __forceinline__ void obs_finish(float p0, float aux, float mean, float v, float m, float z, float d, const ObsK& k, float& o0,
+                                           float& o1) {
+    if (KIND == OBS_MEAN) { o0 = mean; o1 = 0.0f; return; }
+    const float lm = k.lambda * m;
+    const float df = mean - v;
+    const float t = lm * df;
+    const float p0c = p0 - t;
+    if (KIND == OBS_DDIM) {
+        const float dir = k.u0 * aux;
+        float nz;
+        if (k.noisy) {
+            const float sn = k.u1 * z;
+            nz = sn * k.u2;
+        } else {
+            nz = (k.u1 * 0.0f) * k.u2;
+        }
+        const float a = k.u3 * p0c;
+        const float b = a + dir;
+        o0 = b + nz;
+    } else {
+        float D = p0c;
+        if (k.second) {
+            const float u = k.u2 * p0c;
+            const float w = k.u3 * d;
+            D = u + w;
+        }
+        const float p = k.u0 * aux;
+        const float q = k.u1 * D;
+        o0 = p + q;
+    }
+    o1 = p0c;
+}
+
+template <int F, bool VEC> struct obs_width { static constexpr int v = !VEC || (F & 1) ? 1 : (F % 4 == 0 ? 4 : 2); };
+
+template <int N, int V>
+__device__ __forceinline__ void obs_load(const float* p, float* r) {
+#pragma unroll
+    for (int j = 0; j < N; j += V) {
+        if (V == 4) { const f32x4 t = *reinterpret_cast<const f32x4*>(p + j); r[j] = t[0]; r[j + 1] = t[1]; r[j + 2] = t[2]; r[j + 3] = t[3]; }
+        else if (V == 2) { const f32x2 t = *reinterpret_cast<const f32x2*>(p + j); r[j] = t[0]; r[j + 1] = t[1]; }
+        else r[j] = p[j];
+    }
+}
+template <int N, int V>
+__device__ __forceinline__ void obs_store(float* p, const float* r) {
+#pragma unroll
+    for (int j = 0; j < N; j += V) {
+        if (V == 4) { f32x4 t = {r[j], r[j + 1], r[j + 2], r[j + 3]}; *reinterpret_cast<f32x4*>(p + j) = t; }
+        else if (V == 2) { f32x2 t = {r[j], r[j + 1]}; *reinterpret_cast<f32x2*>(p + j) = t; }
+        else p[j] = r[j];
+    }
+}
+
+template <int KIND, int F, bool VEC>
+__global__ void __launch_bounds__(256) obs_kernel(ObsArgs g, ObsChannels ch) {
+    const int b = blockIdx.y / ch.n, c = ch.c[blockIdx.y % ch.n];
+    const long long hw = (long long)g.H * g.W;
+    const long long off = ((long long)b * g.C + c) * hw;                                           // x, e_t, noise, d_prev, outputs
+    const long long voff = ((long long)(g.values_b1 ? 0 : b) * g.C + c) * hw;
+    const long long moff = ((long long)(g.mask_b1 ? 0 : b) * (g.mask_c1 ? 1 : g.C) + (g.mask_c1 ? 0 : c)) * hw;
+    const ObsK k = obs_scalars<KIND>(g);
+    const bool masked = g.mask != nullptr;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    if (F == 1) {
+        // f = 1: the mean is p0 / 1.0f.  Quads of the plane; the last one is cut at the plane's end (VEC: hw % 4 == 0, checked by the host)
+        const long long quads = (hw + 3) / 4;
+        for (long long qd = (long long)blockIdx.x * blockDim.x + threadIdx.x; qd < quads; qd += stride) {
+            const long long i0 = qd * 4;
+            float xv[4] = {0.f, 0.f, 0.f, 0.f}, ev[4] = {0.f, 0.f, 0.f, 0.f}, vv[4] = {0.f, 0.f, 0.f, 0.f}, mv[4] = {1.0f, 1.0f, 1.0f, 1.0f};
+            float zv[4] = {0.f, 0.f, 0.f, 0.f}, dv[4] = {0.f, 0.f, 0.f, 0.f}, o0[4], o1[4];
+            if (VEC) {
+                obs_load<4, 4>(g.x + off + i0, xv);
+                if (KIND != OBS_MEAN) {
+                    obs_load<4, 4>(g.e + off + i0, ev);
+                    obs_load<4, 4>(g.values + voff + i0, vv);
+                    if (masked) obs_load<4, 4>(g.mask + moff + i0, mv);
+                    if (KIND == OBS_DDIM && k.noisy) obs_load<4, 4>(g.noise + off + i0, zv);
+                    if (KIND == OBS_DPMPP && k.second) obs_load<4, 4>(g.d_prev + off + i0, dv);
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (i0 + j < hw) {
+                        xv[j] = g.x[off + i0 + j];
+                        if (KIND != OBS_MEAN) {
+                            ev[j] = g.e[off + i0 + j];
+                            vv[j] = g.values[voff + i0 + j];
+                            if (masked) mv[j] = g.mask[moff + i0 + j];
+                            if (KIND == OBS_DDIM && k.noisy) zv[j] = g.noise[off + i0 + j];
+                            if (KIND == OBS_DPMPP && k.second) dv[j] = g.d_prev[off + i0 + j];
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float p0 = obs_p0<KIND>(xv[j], ev[j], k);
+                const float mean = p0 / 1.0f;
+                obs_finish<KIND>(p0, KIND == OBS_DDIM ? ev[j] : xv[j], mean, vv[j], mv[j], zv[j], dv[j], k, o0[j], o1[j]);
+            }
+            if (VEC) {
+                obs_store<4, 4>(g.out0 + off + i0, o0);
+                if (KIND != OBS_MEAN) obs_store<4, 4>(g.out1 + off + i0, o1);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (i0 + j < hw) {
+                        g.out0[off + i0 + j] = o0[j];
+                        if (KIND != OBS_MEAN) g.out1[off + i0 + j] = o1[j];
+                    }
+                }
+            }
+        }
+        return;
+    }
+    constexpr int V = obs_width<F, VEC>::v;
+    const int nbx = g.W / F;
+    const long long blocks = (long long)nbx * (g.H / F);
+    for (long long blk = (long long)blockIdx.x * blockDim.x + threadIdx.x; blk < blocks; blk += stride) {
+        const long long by = blk / nbx, bx = blk % nbx;
+        const long long at = by * F * g.W + bx * F;       // the block's first pixel in its plane; every row of it lies inside the plane
+        float P[F * F], A[KIND == OBS_MEAN ? 1 : F * F];
+#pragma unroll
+        for (int r = 0; r < F; ++r) {
+            float xr[F], er[F];
+            obs_load<F, V>(g.x + off + at + (long long)r * g.W, xr);
+            if (KIND != OBS_MEAN) obs_load<F, V>(g.e + off + at + (long long)r * g.W, er);
+#pragma unroll
+            for (int j = 0; j < F; ++j) {
+                P[r * F + j] = obs_p0<KIND>(xr[j], KIND == OBS_MEAN ? 0.0f : er[j], k);
+                if (KIND != OBS_MEAN) A[r * F + j] = KIND == OBS_DDIM ? er[j] : xr[j];
+            }
+        }
+        float s = P[0];
+#pragma unroll
+        for (int i = 1; i < F * F; ++i) s = s + P[i];     // row by row, left to right
+        const float mean = s / (float)(F * F);
+#pragma unroll
+        for (int r = 0; r < F; ++r) {
+            const long long row = at + (long long)r * g.W;
+            float vr[F], mr[F], zr[F], dr[F], o0[F], o1[F];
+#pragma unroll
+            for (int j = 0; j < F; ++j) { vr[j] = 0.0f; mr[j] = 1.0f; zr[j] = 0.0f; dr[j] = 0.0f; }
+            if (KIND != OBS_MEAN) {
+                obs_load<F, V>(g.values + voff + row, vr);
+                if (masked) obs_load<F, V>(g.mask + moff + row, mr);
+                if (KIND == OBS_DDIM && k.noisy) obs_load<F, V>(g.noise + off + row, zr);
+                if (KIND == OBS_DPMPP && k.second) obs_load<F, V>(g.d_prev + off + row, dr);
+            }
+#pragma unroll
+            for (int j = 0; j < F; ++j)
+                obs_finish<KIND>(P[r * F + j], KIND == OBS_MEAN ? 0.0f : A[r * F + j], mean, vr[j], mr[j], zr[j], dr[j], k, o0[j], o1[j]);
+            obs_store<F, V>(g.out0 + off + row, o0);
+            if (KIND != OBS_MEAN) obs_store<F, V>(g.out1 + off + row, o1);
+        }
+    }
+}
+
+static inline bool eod_overlap2(const float* a, long long na, const float* b, long long nb) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + (uintptr_t)nb * sizeof(float) && pb < pa + (uintptr_t)na * sizeof(float);
+}
+
+template <int KIND, int F>
+static void obs_launch_f(const ObsArgs& g, const ObsChannels& ch, bool vec, hipStream_t stream) {
+    const long long hw = (long long)g.H * g.W;
+    const long long units = F == 1 ? (hw + 3) / 4 : hw / (F * F);
+    const int planes = g.B * ch.n;
+    const dim3 grid(blocks_for(units, planes >= 4096 ? 1 : 4096 / planes), planes), block(256);
+    if (vec && (F != 1 || hw % 4 == 0))
+        hipLaunchKernelGGL((obs_kernel<KIND, F, true>), grid, block, 0, stream, g, ch);
+    else
+        hipLaunchKernelGGL((obs_kernel<KIND, F, false>), grid, block, 0, stream, g, ch);
+}
+
+// checks what the three entry points share, then one launch per factor that occurs
+template <int KIND>
+static int obs_launch(const char* what, ObsArgs g, const int32_t* factors, void* stream) {
+    EOD_REQUIRE(g.x && g.out0 && factors && g.B > 0 && g.C > 0 && g.H > 0 && g.W > 0, "%s: bad args", what);
+    EOD_REQUIRE(g.C <= 32, "%s: at most 32 channels (the factors travel by value), got %d", what, g.C);
+    EOD_REQUIRE((long long)g.B * g.C <= 65535, "%s: B * C = %lld planes exceed one launch", what, (long long)g.B * g.C);
+    for (int c = 0; c < g.C; ++c) {
+        EOD_REQUIRE(factors[c] >= 1 && factors[c] <= 8, "%s: factors[%d] = %d is outside 1..8", what, c, factors[c]);
+        EOD_REQUIRE(g.H % factors[c] == 0 && g.W % factors[c] == 0, "%s: factors[%d] = %d does not divide %d x %d", what, c, factors[c], g.H, g.W);
+    }
+    const long long n = (long long)g.B * g.C * g.H * g.W;
+    EOD_REQUIRE(KIND != OBS_MEAN || !eod_overlap2(g.out0, n, g.x, n), "%s: out overlaps x", what);
+    if (KIND != OBS_MEAN) {
+        EOD_REQUIRE(g.e && g.values && g.out1, "%s: bad args", what);
+        EOD_REQUIRE(g.a > 0.0f && g.a <= 1.0f, "%s: needs 0 < a <= 1, got %g", what, (double)g.a);
+        EOD_REQUIRE(g.lambda >= 0.0f && g.lambda <= 1.0f, "%s: the weight must lie in [0, 1], got %g", what, (double)g.lambda);
+        const long long nv = (long long)(g.values_b1 ? 1 : g.B) * g.C * g.H * g.W;
+        const long long nm = (long long)(g.mask_b1 ? 1 : g.B) * (g.mask_c1 ? 1 : g.C) * g.H * g.W;
+        EOD_REQUIRE(!eod_overlap2(g.out0, n, g.out1, n), "%s: the two outputs overlap", what);
+        float* const outs[2] = {g.out0, g.out1};
+        for (float* o : outs) {
+            EOD_REQUIRE(!eod_overlap2(o, n, g.values, nv), "%s: an output overlaps values", what);
+            EOD_REQUIRE(!g.mask || !eod_overlap2(o, n, g.mask, nm), "%s: an output overlaps mask", what);
+            EOD_REQUIRE(!g.d_prev || !eod_overlap2(o, n, g.d_prev, n), "%s: an output overlaps d_prev (the history is read while it is written)", what);
+        }
+    }
+    const bool vec = eod_aligned16(g.x) && eod_aligned16(g.out0) && (!g.e || eod_aligned16(g.e)) && (!g.noise || eod_aligned16(g.noise)) &&
+                     (!g.d_prev || eod_aligned16(g.d_prev)) && (!g.values || eod_aligned16(g.values)) && (!g.mask || eod_aligned16(g.mask)) &&
+                     (!g.out1 || eod_aligned16(g.out1));
+    for (int f = 1; f <= 8; ++f) {
+        ObsChannels ch;
+        ch.n = 0;
+        for (int c = 0; c < g.C; ++c)
+            if (factors[c] == f) ch.c[ch.n++] = (unsigned char)c;
+        if (!ch.n) continue;
+        switch (f) {
+            case 1: obs_launch_f<KIND, 1>(g, ch, vec, (hipStream_t)stream); break;
+            case 2: obs_launch_f<KIND, 2>(g, ch, vec, (hipStream_t)stream); break;
+            case 3: obs_launch_f<KIND, 3>(g, ch, vec, (hipStream_t)stream); break;
+            case 4: obs_launch_f<KIND, 4>(g, ch, vec, (hipStream_t)stream); break;
+            case 5: obs_launch_f<KIND, 5>(g, ch, vec, (hipStream_t)stream); break;
+            case 6: obs_launch_f<KIND, 6>(g, ch, vec, (hipStream_t)stream); break;
+            case 7: obs_launch_f<KIND, 7>(g, ch, vec, (hipStream_t)stream); break;
+            default: obs_launch_f<KIND, 8>(g, ch, vec, (hipStream_t)stream); break;
+        }
+        EOD_CHECK_LAUNCH(what);
+    }
+    return EOD_OK;
+}
+
+extern "C" int eod_ddim_step_obs(const float* x, const float* e_t, const float* noise, float a_t, float a_prev, float sigma_t,
+                                 float sqrt_1m_at, float temperature, const float* values, const float* mask, float lambda,
+                                 const int32_t* factors, int B, int C, int H, int W, int values_b1, int mask_b1, int mask_c1, float* x_prev,
+                                 float* pred_x0, void* stream) {
+    ObsArgs g = {x, e_t, noise, nullptr, values, mask, x_prev, pred_x0, a_t, sqrt_1m_at, lambda, a_prev, sigma_t, temperature, 0.0f,
+                 0, B, C, H, W, values_b1, mask_b1, mask_c1};
+    return obs_launch<OBS_DDIM>("ddim_step_obs", g, factors, stream);
+}
+
+extern "C" int eod_dpmpp_step_obs(const float* x, const float* e_t, const float* d_prev, float a_s, float sqrt_1m_as, float c_x, float c_d,
+                                  float w_cur, float w_prev, int clip, const float* values, const float* mask, float lambda,
+                                  const int32_t* factors, int B, int C, int H, int W, int values_b1, int mask_b1, int mask_c1, float* x_next,
+                                  float* pred_x0, void* stream) {
+    ObsArgs g = {x, e_t, nullptr, d_prev, values, mask, x_next, pred_x0, a_s, sqrt_1m_as, lambda, c_x, c_d, w_cur, w_prev,
+                 clip, B, C, H, W, values_b1, mask_b1, mask_c1};
+    return obs_launch<OBS_DPMPP>("dpmpp_step_obs", g, factors, stream);
+}
+
+extern "C" int eod_block_mean(const float* x, const int32_t* factors, float* out, int B, int C, int H, int W, void* stream) {
+    ObsArgs g = {x, nullptr, nullptr, nullptr, nullptr, nullptr, out, nullptr, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0, B, C, H, W, 0, 0, 0};
+    return obs_launch<OBS_MEAN>("block_mean", g, factors, stream);
+}
+
 extern "C" int eod_cfg_combine(const float* e_uncond, const float* e_cond, float scale, float* out, int64_t numel, void* stream) {
     EOD_REQUIRE(e_uncond && e_cond && out && numel > 0, "cfg_combine: bad args");
     hipLaunchKernelGGL(cfg_combine_kernel, dim3(blocks_for(numel, 4096)), dim3(256), 0, (hipStream_t)stream, e_uncond, e_cond, scale, out, (long long)numel);

@@ -11,13 +11,16 @@ in rng="torch" mode so that the global generator advances exactly as in the refe
 `sample_scene` (no counterpart in the reference) runs the same steps on a scene larger than the UNet's image size, tiled.
 `resample=(jump_length, jump_n_sample)` on sample / ddim_sampling / sample_scene: RePaint resampling over the INDICES of the DDIM
 steps (diffusion/util.py make_resample_schedule), the forward moves through eod_renoise with ddim_alphas at the two indices.
+`observation=` (a diffusion/consistency.py Observation) on sample / ddim_sampling / sample_scene: every step's data prediction is made
+consistent with an observation of per-channel block means, inside the step kernel (eod_ddim_step_obs).  With
+observation=None (the default) every call takes the launches it took before.
 """
 import numpy as np
 import torch
 
 from .. import _lib
 from ..engine import current_stream_ptr, f32c, require_gpu
-from . import chain
+from . import chain, consistency
 from .util import make_ddim_sampling_parameters, make_ddim_timesteps, noise_like, resample_plan
 
 
@@ -64,7 +67,7 @@ class DDIMSampler(object):
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
                quantize_x0=False, eta=0.0, mask=None, x0=None, temperature=1.0, noise_dropout=0.0, score_corrector=None,
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.0,
-               unconditional_conditioning=None, resample=None, jump_noises=None, **kwargs):
+               unconditional_conditioning=None, resample=None, jump_noises=None, observation=None, **kwargs):
         if conditioning is not None:
             cbs = (conditioning[list(conditioning.keys())[0]] if isinstance(conditioning, dict) else conditioning).shape[0]
             if cbs != batch_size:
@@ -77,18 +80,20 @@ class DDIMSampler(object):
                                   corrector_kwargs=corrector_kwargs, x_T=x_T, log_every_t=log_every_t,
                                   unconditional_guidance_scale=unconditional_guidance_scale,
                                   unconditional_conditioning=unconditional_conditioning, resample=resample,
-                                  jump_noises=jump_noises, **kwargs)
+                                  jump_noises=jump_noises, observation=observation, **kwargs)
 
     @torch.no_grad()
     def ddim_sampling(self, cond, shape, x_T=None, ddim_use_original_steps=False, callback=None, timesteps=None,
                       quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100, temperature=1.0,
                       noise_dropout=0.0, score_corrector=None, corrector_kwargs=None, unconditional_guidance_scale=1.0,
                       unconditional_conditioning=None, *, step_noises=None, mix_noises=None, progress=True, resample=None,
-                      jump_noises=None):
+                      jump_noises=None, observation=None):
         """resample=(jump_length, jump_n_sample): RePaint resampling over the indices 0 .. total_steps - 1 of the steps this call walks.
         After the listed evaluations the state (at ddim_alphas_prev[a + 1] = ddim_alphas[a]) is moved up to ddim_alphas[b] by
         eod_renoise; step_noises / mix_noises are then indexed by the evaluation's position in the walk, jump_noises by the jump's
-        ordinal (otherwise randn_like when the jump happens); callbacks and intermediates see every executed step."""
+        ordinal (otherwise randn_like when the jump happens); callbacks and intermediates see every executed step.
+        observation: an Observation (diffusion/consistency.py) for a state of `shape`; a per-evaluation `weight` is indexed like
+        step_noises.  It is independent of the RePaint mix (mask / x0), which is applied in front of the UNet as without it."""
         if ddim_use_original_steps:
             raise NotImplementedError("ddim_use_original_steps touches attributes the reference never defines (ddim.py:188-190)")
         device = self.model.betas.device
@@ -101,6 +106,7 @@ class DDIMSampler(object):
         total_steps = timesteps.shape[0]
         visits, jump_after = resample_plan("DDIMSampler.ddim_sampling", resample, total_steps,
                                            (("step_noises", step_noises), ("mix_noises", mix_noises)), jump_noises)
+        obs = consistency.bind(observation, "DDIMSampler.ddim_sampling", shape, len(visits), device)
         img = torch.randn(shape, device=device) if x_T is None else f32c(x_T.to(device))
         intermediates = {"x_inter": [img], "pred_x0": [img]}
         if mask is not None:
@@ -120,7 +126,8 @@ class DDIMSampler(object):
                                               score_corrector=score_corrector, corrector_kwargs=corrector_kwargs,
                                               unconditional_guidance_scale=unconditional_guidance_scale,
                                               unconditional_conditioning=unconditional_conditioning,
-                                              _noise=None if step_noises is None else step_noises[i])
+                                              _noise=None if step_noises is None else step_noises[i],
+                                              _obs=None if obs is None else (obs, i))
             return self._after_step(i, index, img, pred_x0, intermediates, callback, img_callback, log_every_t, total_steps)
 
         img = self._walk(img, visits, jump_after, step, jump_noises, lambda name, z: z.to(device), "DDIM Sampler" if progress else None)
@@ -159,9 +166,13 @@ class DDIMSampler(object):
                                               e_t.data_ptr(), e_t.numel(), current_stream_ptr(x.device)), "eod_cfg_combine")
         return e_t
 
-    def _ddim_update(self, x, e_t, noise, index, temperature):
-        """(x_prev, pred_x0) of step `index` in one pass; noise None: sigma_t is 0 and nothing is read"""
+    def _ddim_update(self, x, e_t, noise, index, temperature, obs=None):
+        """(x_prev, pred_x0) of step `index` in one pass; noise None: sigma_t is 0 and nothing is read.  obs = (BoundObservation, number
+        of the evaluation): the step with the data prediction made consistent with the observation (eod_ddim_step_obs)"""
         x = f32c(x)
+        if obs is not None:
+            return obs[0].ddim_step(obs[1], x, e_t, noise, self.ddim_alphas[index], self.ddim_alphas_prev[index], self.ddim_sigmas[index],
+                                    self.ddim_sqrt_one_minus_alphas[index], temperature)
         x_prev, pred_x0 = torch.empty_like(x), torch.empty_like(x)
         _lib.check(_lib.lib().eod_ddim_step(x.data_ptr(), e_t.data_ptr(), _lib.ptr(noise), float(self.ddim_alphas[index]),
                                             float(self.ddim_alphas_prev[index]), float(self.ddim_sigmas[index]),
@@ -173,7 +184,7 @@ class DDIMSampler(object):
     def sample_scene(self, S, scene_size, *, overlap=0, tile_batch=16, conditioning=None, mask=None, x0=None, eta=0.0, x_T=None,
                      temperature=1.0, unconditional_guidance_scale=1.0, unconditional_conditioning=None, step_noises=None,
                      mix_noises=None, callback=None, img_callback=None, log_every_t=100, verbose=False, progress=True, resample=None,
-                     jump_noises=None, skip_known=False, n_scenes=1):
+                     jump_noises=None, skip_known=False, n_scenes=1, observation=None):
         """DDIM over ONE scene [1, C, H, W] larger than the UNet's image size (see EODiffusion.sampling_scene and
         eo_diffusion_amd/tiling.py): per step the RePaint mix (mask / x0 scene-sized), the UNet on overlapping tiles in chunks of
         tile_batch, the blend of the noise estimates, ONE scene-level eod_ddim_step.  Classifier-free guidance runs per chunk through
@@ -193,7 +204,10 @@ class DDIMSampler(object):
         ([S, B, C, H, W]) have leading dimension B, or 1 for one scene that stands for every member; mask broadcasts against
         [B, C, H, W] as it does against [1, C, H, W] today.  The tiles of the whole stack go through the UNet in chunks of tile_batch
         (a chunk may hold tiles of several scenes); skip_known classifies per scene.  With injected draws member b equals the
-        single-scene call on scene b's inputs and draws, bit for bit."""
+        single-scene call on scene b's inputs and draws, bit for bit.
+        observation: an Observation with scene-sized values / mask (leading dimension n_scenes or 1); its blocks are anchored at the
+        scene's origin and the projection is part of the ONE scene-level step, so it is seamless across tile borders.  Refused together
+        with skip_known: a block may straddle estimated and non-estimated pixels, and skip_known's bit equality could not hold."""
         from ..tiling import keep_known
         what = "DDIMSampler.sample_scene"
         m = self.model
@@ -201,7 +215,7 @@ class DDIMSampler(object):
         walk = lambda: resample_plan(what, resample, make_ddim_timesteps("uniform", S, m.timesteps, verbose=False).shape[0],
                                      (("step_noises", step_noises), ("mix_noises", mix_noises)), jump_noises)
         sc = self._scene_setup(what, scene_size, overlap, tile_batch, n_scenes, walk, mask, x0, skip_known, conditioning,
-                               unconditional_conditioning, unconditional_guidance_scale, x_T)
+                               unconditional_conditioning, unconditional_guidance_scale, x_T, observation)
         if sc.known is not None:
             return sc.known, {"x_inter": [sc.known], "pred_x0": [sc.known]}
         img, x0, mask, B, device = sc.img, sc.x0, sc.mask, sc.B, sc.device
@@ -220,7 +234,7 @@ class DDIMSampler(object):
                 noise = sc.as_scene("step_noises[i]", step_noises[i])
             else:
                 noise = torch.randn_like(img) if float(self.ddim_sigmas[index]) != 0.0 else None
-            img, pred_x0 = self._ddim_update(img, e_t, noise, index, temperature)
+            img, pred_x0 = self._ddim_update(img, e_t, noise, index, temperature, None if sc.obs is None else (sc.obs, i))
             return self._after_step(i, index, img, pred_x0, intermediates, callback, img_callback, log_every_t, total_steps)
 
         img = self._walk(img, sc.visits, sc.jump_after, step, jump_noises, sc.as_scene, "DDIM Sampler (scene)" if progress else None)
@@ -228,7 +242,7 @@ class DDIMSampler(object):
 
     # ------------------------------------------------------------------ what the scene samplers (this one and DPMSolverSampler's) share
     def _scene_setup(self, what, scene_size, overlap, tile_batch, n_scenes, walk, mask, x0, skip_known, conditioning,
-                     unconditional_conditioning, unconditional_guidance_scale, x_T):
+                     unconditional_conditioning, unconditional_guidance_scale, x_T, observation=None):
         """Everything of a scene call in front of its first step: the plan, every refusal (walk() -> (visits, jump_after) fixes the walk and
         counts the injected draws, before anything is launched), mask / x0 scene-sized, the tiles to evaluate, the conditioning cut into
         them, the start state.  Returns a namespace; `known` is not None when no tile is active (the call returns it, no UNet call)."""
@@ -241,6 +255,10 @@ class DDIMSampler(object):
         B = m._scene_count(what, n_scenes)
         visits, jump_after = walk()
         tile_slots(plan, tile_batch)  # (refuses a bad tile_batch)
+        if observation is not None and skip_known:
+            raise _lib.EodError(f"{what}: skip_known and observation do not go together (a block of the observation may straddle "
+                                "estimated and non-estimated pixels)")
+        obs = consistency.bind(observation, what, (B, C, plan.H, plan.W), len(visits), device)
         if (mask is None) != (x0 is None):
             raise _lib.EodError(f"{what}: mask and x0 go together (RePaint mix of the known region)")
         full = plan if B == 1 else TileStack(plan, B)  # (plan: the tiles that go through the UNet -- with skip_known the active ones only)
@@ -260,7 +278,7 @@ class DDIMSampler(object):
         if mask is not None and B > 1:
             x0, mask = (z.expand(B, *z.shape[1:]).contiguous() for z in (x0, mask))
         sc = SimpleNamespace(plan=plan, full=full, B=B, device=device, tile_batch=tile_batch, x0=x0, mask=mask, visits=visits,
-                             jump_after=jump_after, known=None, c_tiles=None, uc_tiles=None)
+                             jump_after=jump_after, known=None, c_tiles=None, uc_tiles=None, obs=obs)
         if plan is None:
             sc.known = x0.clone()
             return sc
@@ -288,7 +306,7 @@ class DDIMSampler(object):
     @torch.no_grad()
     def p_sample_ddim(self, x, c, t, index, repeat_noise=False, use_original_steps=False, quantize_denoised=False,
                       temperature=1.0, noise_dropout=0.0, score_corrector=None, corrector_kwargs=None,
-                      unconditional_guidance_scale=1.0, unconditional_conditioning=None, *, _noise=None):
+                      unconditional_guidance_scale=1.0, unconditional_conditioning=None, *, _noise=None, _obs=None):
         require_gpu(x, "DDIMSampler.p_sample_ddim")
         if use_original_steps:
             raise NotImplementedError("use_original_steps (ddim.py:188-190) is not available in the reference either")
@@ -298,4 +316,4 @@ class DDIMSampler(object):
             _unused = torch.randn_like(x)  # ddim.py:171 draws a tensor that is never used; keep the RNG stream aligned
         e_t = self._eps(x, t, c, unconditional_guidance_scale, unconditional_conditioning)
         noise = f32c(_noise.to(x.device)) if _noise is not None else noise_like(x.shape, x.device, repeat_noise)
-        return self._ddim_update(x, e_t, noise, index, temperature)
+        return self._ddim_update(x, e_t, noise, index, temperature, _obs)

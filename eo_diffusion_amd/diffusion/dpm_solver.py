@@ -13,12 +13,16 @@ first evaluation, on the evaluation right after a resampling jump (the history b
 last step (index 0: lower-order final) and everywhere with order=1; the step body decides from the index of the evaluation before it,
 so chain.walk does not know about the history.  Draw policy: DDIMSampler's minus the eta noise -- x_T, the mix noise when a mask is
 given, one draw per jump.
+`observation=` (a diffusion/consistency.py Observation) on sample / sample_scene: the prediction of every evaluation is made consistent
+with an observation of per-channel block means inside the step kernel (eod_dpmpp_step_obs: after the clamp, before the multistep
+combination; the history the next evaluation reads is the projected prediction).  DESIGN.md section 9.5.
 """
 import numpy as np
 import torch
 
 from .. import _lib
 from ..engine import current_stream_ptr, f32c, require_gpu
+from . import consistency
 from .ddim import DDIMSampler
 from .util import dpm_coefficients, dpm_lambda, make_dpm_timesteps, resample_plan
 
@@ -57,12 +61,16 @@ class DPMSolverSampler(DDIMSampler):
         return resample_plan(what, resample, n, (("mix_noises", mix_noises),), jump_noises)
 
     # ------------------------------------------------------------------ the step
-    def _dpm_update(self, x, e_t, hist, index, clip):
-        """(x_next, pred_x0) of the evaluation at step `index`; hist = (index, pred_x0) of the evaluation before it, or None"""
+    def _dpm_update(self, x, e_t, hist, index, clip, obs=None):
+        """(x_next, pred_x0) of the evaluation at step `index`; hist = (index, pred_x0) of the evaluation before it, or None; obs =
+        (BoundObservation, number of the evaluation): eod_dpmpp_step_obs in place of eod_dpmpp_step"""
         second = self.dpm_second[index] if hist is not None and hist[0] == index + 1 else None
         c_x, c_d, w_cur, w_prev = self.dpm_first[index] if second is None else second
         x, e_t = f32c(x), f32c(e_t)
         d_prev = None if second is None else hist[1]
+        if obs is not None:
+            return obs[0].dpmpp_step(obs[1], x, e_t, d_prev, self.ddim_alphas[index], self.dpm_sqrt_one_minus_alphas[index], c_x, c_d, w_cur,
+                                     w_prev, clip)
         x_next, pred_x0 = torch.empty_like(x), torch.empty_like(x)
         _lib.check(_lib.lib().eod_dpmpp_step(x.data_ptr(), e_t.data_ptr(), _lib.ptr(d_prev), float(self.ddim_alphas[index]),
                                              float(self.dpm_sqrt_one_minus_alphas[index]), float(c_x), float(c_d), float(w_cur),
@@ -73,16 +81,18 @@ class DPMSolverSampler(DDIMSampler):
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, *, order=2, discretize="logsnr", t_start=None, clip_denoised=False,
                mask=None, x0=None, x_T=None, unconditional_guidance_scale=1.0, unconditional_conditioning=None, mix_noises=None,
-               resample=None, jump_noises=None, callback=None, img_callback=None, log_every_t=100, progress=True):
+               resample=None, jump_noises=None, callback=None, img_callback=None, log_every_t=100, progress=True, observation=None):
         """`S` steps (self.num_evaluations <= S UNet evaluations: duplicate levels of the logsnr grid are removed) from x_T to an image
         batch [batch_size, *shape].  Returns (samples, {"x_inter", "pred_x0"}) like DDIMSampler.sample.  mask / x0: the RePaint mix at
         every evaluation (mix_noises[i]: its q_sample noise, indexed by the evaluation's position in the walk).  resample /
-        jump_noises: RePaint resampling over the indices of the levels, as in DDIMSampler.ddim_sampling."""
+        jump_noises: RePaint resampling over the indices of the levels, as in DDIMSampler.ddim_sampling.  observation: an Observation for a
+        state [batch_size, *shape]; a per-evaluation `weight` is indexed like mix_noises."""
         what = "DPMSolverSampler.sample"
         visits, jump_after = self._plan(what, S, order, discretize, t_start, resample, mix_noises, jump_noises, mask, x0)
         device = self.model.betas.device
         C, H, W = shape
         b = batch_size
+        obs = consistency.bind(observation, what, (b, C, H, W), len(visits), device)
         if conditioning is not None and conditioning.shape[0] != b:
             print(f"Warning: Got {conditioning.shape[0]} conditionings but batch-size is {b}")
         img = torch.randn((b, C, H, W), device=device) if x_T is None else f32c(x_T.to(device))
@@ -100,7 +110,7 @@ class DPMSolverSampler(DDIMSampler):
                 nz = mix_noises[i].to(device) if mix_noises is not None else torch.randn_like(x0)
                 img = self.model._repaint_mix(img, x0, mask, ts, nz)
             e_t = self._eps(img, ts, conditioning, unconditional_guidance_scale, unconditional_conditioning)
-            img, pred_x0 = self._dpm_update(img, e_t, hist[0], index, clip_denoised)
+            img, pred_x0 = self._dpm_update(img, e_t, hist[0], index, clip_denoised, None if obs is None else (obs, i))
             hist[0] = (index, pred_x0)
             return self._after_step(i, index, img, pred_x0, intermediates, callback, img_callback, log_every_t, total_steps)
 
@@ -111,19 +121,20 @@ class DPMSolverSampler(DDIMSampler):
     def sample_scene(self, S, scene_size, *, overlap=0, tile_batch=16, conditioning=None, mask=None, x0=None, order=2, discretize="logsnr",
                      t_start=None, clip_denoised=False, x_T=None, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
                      mix_noises=None, callback=None, img_callback=None, log_every_t=100, progress=True, resample=None, jump_noises=None,
-                     skip_known=False, n_scenes=1):
+                     skip_known=False, n_scenes=1, observation=None):
         """The solver over a scene (or a stack of n_scenes) larger than the UNet's image size: DDIMSampler.sample_scene's arguments with
         the solver's keywords in place of `eta` / `step_noises`.  One scene-level state, one scene-level history tensor and ONE
         eod_dpmpp_step on [B, C, H, W] per evaluation; tiles, blending, guidance per chunk, conditioning, skip_known (keep_known at the
         end) and n_scenes as there.  With overlap = 0 and injected draws the result equals sample() on the tiles, bit for bit; with
         skip_known it equals the skip_known=False scene at every estimated pixel and is `x0` elsewhere (at a pixel that is not
-        estimated the zero estimate keeps state and history finite; at an estimated pixel pred_x0 depends on that pixel's x and e only)."""
+        estimated the zero estimate keeps state and history finite; at an estimated pixel pred_x0 depends on that pixel's x and e only).
+        observation: as in DDIMSampler.sample_scene (scene-sized, blocks anchored at the scene's origin, refused with skip_known)."""
         from ..tiling import keep_known
         what = "DPMSolverSampler.sample_scene"
         m = self.model
         walk = lambda: self._plan(what, S, order, discretize, t_start, resample, mix_noises, jump_noises, mask, x0)
         sc = self._scene_setup(what, scene_size, overlap, tile_batch, n_scenes, walk, mask, x0, skip_known, conditioning,
-                               unconditional_conditioning, unconditional_guidance_scale, x_T)
+                               unconditional_conditioning, unconditional_guidance_scale, x_T, observation)
         if sc.known is not None:
             return sc.known, {"x_inter": [sc.known], "pred_x0": [sc.known]}
         img, x0, mask, B, device = sc.img, sc.x0, sc.mask, sc.B, sc.device
@@ -137,7 +148,7 @@ class DPMSolverSampler(DDIMSampler):
                 nz = sc.as_scene("mix_noises[i]", mix_noises[i]) if mix_noises is not None else torch.randn_like(x0)
                 img = m._repaint_mix(img, x0, mask, torch.full((B,), t, device=device, dtype=torch.long), nz)
             e_t = self._scene_eps(sc, img, t, unconditional_guidance_scale)
-            img, pred_x0 = self._dpm_update(img, e_t, hist[0], index, clip_denoised)
+            img, pred_x0 = self._dpm_update(img, e_t, hist[0], index, clip_denoised, None if sc.obs is None else (sc.obs, i))
             hist[0] = (index, pred_x0)
             return self._after_step(i, index, img, pred_x0, intermediates, callback, img_callback, log_every_t, total_steps)
 

@@ -35,7 +35,7 @@ const char* eod_last_error(void);
  * buffer of eod_pack_conv_weight_split, the 4-int state of eod_adamw_step_guarded).  eod_version() returns the value the library was built
  * with; a binding compares it with the header it mirrors at load time (eo_diffusion_amd/_lib.py does) instead of finding out by an
  * out-of-bounds device write. */
-#define EOD_ABI_VERSION 108
+#define EOD_ABI_VERSION 109
 int eod_version(void);
 /* Kernel-selection options ("skip_fuse", "head", "halo_bn256", "halo_splitk", "first", "s2_halo": 1 / 0; "gn_fuse_max_cout": n, -1 = default;
  * "halo_tpw": pixel tiles per workgroup of the streaming halo instances, 1 = off = default, 0 = chosen per launch; "head_tpw": the same of
@@ -331,6 +331,35 @@ int eod_ddim_step(const float* x, const float* e_t, const float* noise, float a_
  * by element otherwise: same arithmetic. */
 int eod_dpmpp_step(const float* x, const float* e_t, const float* d_prev, float a_s, float sqrt_1m_as, float c_x, float c_d,
                    float w_cur, float w_prev, int clip, float* x_next, float* pred_x0, int64_t numel, void* stream);
+/* Observation consistency (no reference line): eod_ddim_step / eod_dpmpp_step with the data prediction moved towards
+ * an observation of per-channel block means (the range / null-space projection of DDNM for A = masked per-channel block mean, A+ =
+ * replication) before the update uses it.  The tensors are [B][C][H][W] fp32; factors is a HOST array of C <= 32 ints in 1..8 (the block
+ * edge per channel, 1 = observed at full resolution), read during the call and handed to the kernels by value: nothing is allocated,
+ * copied or synchronised.  blk(i) = the f_c x f_c block of pixel i, anchored at the plane's origin.  Per pixel, every operation rounded
+ * once in fp32, in this order:
+ *   p0    as eod_ddim_step / eod_dpmpp_step form it (the same bits), for dpmpp with clip != 0 clamped as there
+ *   s     = p0 of the block's first pixel, then + p0 of each further pixel of the block ROW BY ROW, LEFT TO RIGHT (sequential adds)
+ *   mean  = s / (float)(f_c * f_c)                 -- f_c = 1: p0 / 1.0f
+ *   lm    = lambda * m                             -- m = mask at the pixel, 1.0f with mask NULL
+ *   p0c   = p0 - (lm * (mean - values))
+ *   ddim:  x_prev = ((sqrtf(a_prev) * p0c) + dir_xt) + nz, dir_xt and nz as in eod_ddim_step (from e_t and noise);  pred_x0 = p0c
+ *   dpmpp: D = d_prev ? (w_cur * p0c) + (w_prev * d_prev) : p0c;  x_next = (c_x * x) + (c_d * D);  pred_x0 = p0c (the next step's d_prev)
+ * The order of the block sum is part of the contract: it does not depend on B, on pointer alignment, on the launch geometry or on whether
+ * the tensor is a batch or a scene.  values is the observation on the full-resolution grid ([B or 1][C][H][W], values_b1 != 0: one for all
+ * samples); mask NULL or [B or 1][C or 1][H][W] (mask_b1 / mask_c1 != 0: broadcast), 1 = observed, 0 = free.  With values and mask constant
+ * on every block and mask in {0, 1}, lambda = 1 this is the projection: afterwards the block means of pred_x0 are values (to rounding).
+ * EOD_EINVAL with nothing launched: a null x / e_t / values / output / factors, C > 32, a factor outside 1..8 or one that does not divide
+ * H and W, a outside (0, 1], lambda outside [0, 1] (NaN included), an output overlapping values, mask, d_prev or the other output.
+ * One launch per factor that occurs.  16-byte accesses (f = 4, 8, and f = 1 where H * W % 4 == 0) or 8-byte ones (f = 2, 6) where every
+ * pointer is 16-byte aligned, element by element otherwise and for odd f: same arithmetic.  Nothing is read or written outside a plane. */
+int eod_ddim_step_obs(const float* x, const float* e_t, const float* noise, float a_t, float a_prev, float sigma_t, float sqrt_1m_at,
+                      float temperature, const float* values, const float* mask, float lambda, const int32_t* factors, int B, int C,
+                      int H, int W, int values_b1, int mask_b1, int mask_c1, float* x_prev, float* pred_x0, void* stream);
+int eod_dpmpp_step_obs(const float* x, const float* e_t, const float* d_prev, float a_s, float sqrt_1m_as, float c_x, float c_d,
+                       float w_cur, float w_prev, int clip, const float* values, const float* mask, float lambda, const int32_t* factors,
+                       int B, int C, int H, int W, int values_b1, int mask_b1, int mask_c1, float* x_next, float* pred_x0, void* stream);
+/* the operator alone: out = A+ A x, every pixel replaced by its block's mean (s and mean as above, of x itself); out must not overlap x */
+int eod_block_mean(const float* x, const int32_t* factors, float* out, int B, int C, int H, int W, void* stream);
 /* classifier-free guidance of p_sample_ddim (ddim.py:177-181): out = e_uncond + scale * (e_cond - e_uncond) */
 int eod_cfg_combine(const float* e_uncond, const float* e_cond, float scale, float* out, int64_t numel, void* stream);
 /* table-driven DDPM step of the LDM-derived sampler: DDPM.p_sample ddpm.py:248-255 with predict_start_from_noise :221-225,

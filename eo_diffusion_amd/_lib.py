@@ -146,6 +146,16 @@ SYMBOLS = {
     "eod_dpmpp_step_obs": (i32, [vp, vp, vp, f32, f32, f32, f32, f32, f32, i32, vp, vp, f32, C.POINTER(i32), i32, i32, i32, i32, i32, i32, i32,
                                  vp, vp, vp]),
     "eod_block_mean": (i32, [vp, C.POINTER(i32), vp, i32, i32, i32, i32, vp]),
+    "eod_obs_project": (i32, [vp, vp, vp, f32, C.POINTER(i32), i32, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "eod_ddim_step_spec": (i32, [vp, vp, vp, f32, f32, f32, f32, f32, vp, vp, f32, C.POINTER(f32), C.POINTER(f32), i32, i32, i32, i32, i32, i32,
+                                 i32, i32, vp, vp, vp]),
+    "eod_dpmpp_step_spec": (i32, [vp, vp, vp, f32, f32, f32, f32, f32, f32, i32, vp, vp, f32, C.POINTER(f32), C.POINTER(f32), i32, i32, i32, i32,
+                                  i32, i32, i32, i32, vp, vp, vp]),
+    "eod_spec_project": (i32, [vp, vp, vp, f32, C.POINTER(f32), C.POINTER(f32), i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "eod_spec_apply": (i32, [vp, C.POINTER(f32), i32, i32, vp, i32, i32, i32, i32, vp]),
+    "eod_pred_x0": (i32, [vp, vp, f32, f32, i32, vp, i64, vp]),
+    "eod_ddim_step_p0": (i32, [vp, vp, vp, f32, f32, f32, vp, i64, vp]),
+    "eod_dpmpp_step_p0": (i32, [vp, vp, vp, f32, f32, f32, f32, vp, i64, vp]),
     "eod_ldm_p_sample": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, i32, i32, vp]),
     "eod_repaint_cond": (i32, [vp, vp, vp, i32, i32, i64, i32, vp]),
     "eod_postprocess": (i32, [vp, vp, i64, i32, vp]),
@@ -179,7 +189,8 @@ class EodError(RuntimeError):
     pass
 
 
-ABI_VERSION = 109  # EOD_ABI_VERSION of the include/eodiff.h this file mirrors
+ABI_VERSION = 110  # EOD_ABI_VERSION of the include/eodiff.h this file mirrors
+SPEC_GRID_BLOCKS = 4096  # EOD_SPEC_GRID_BLOCKS there
 
 
 def lib():

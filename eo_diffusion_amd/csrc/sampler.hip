@@ -463,7 +463,8 @@ extern "C" int eod_dpmpp_step(const float* x, const float* e_t, const float* d_p
 // sum is a property of the block alone: it does not depend on B, on the launch geometry, on alignment, or on what the plane belongs to.
 // ---------------------------------------------------------------------------------------------
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-enum { OBS_DDIM = 0, OBS_DPMPP = 1, OBS_MEAN = 2 };
+enum { OBS_DDIM = 0, OBS_DPMPP = 1, OBS_MEAN = 2, OBS_PROJECT = 3, OBS_APPLY = 4 };   // PROJECT: the projection of a given p; APPLY: spec_kernel's
+#define OBS_STEP(KIND) ((KIND) == OBS_DDIM || (KIND) == OBS_DPMPP)                       // the kinds that form p0 from (x, e_t) and finish a step
 
 struct ObsArgs {
     const float *x, *e, *noise, *d_prev, *values, *mask;
@@ -486,7 +487,7 @@ template <int KIND>
 __device__ __forceinline__ ObsK obs_scalars(const ObsArgs& g) {
     ObsK k;
     k.s1m = g.s1m; k.lambda = g.lambda; k.clip = g.clip != 0; k.second = g.d_prev != nullptr; k.noisy = g.noise != nullptr;
-    k.sq_a = KIND == OBS_MEAN ? 1.0f : sqrtf(g.a);
+    k.sq_a = OBS_STEP(KIND) ? sqrtf(g.a) : 1.0f;
     k.u0 = g.k0; k.u1 = g.k1; k.u2 = g.k2; k.u3 = g.k3;
     if (KIND == OBS_DDIM) {            // ddim_step_kernel's scalars
         const float sig2 = g.k1 * g.k1;
@@ -496,25 +497,19 @@ __device__ __forceinline__ ObsK obs_scalars(const ObsArgs& g) {
     return k;
 }
 
-// p0 as ddim_step_kernel / dpmpp_one form it (OBS_MEAN: the input itself)
+// p0 as ddim_step_kernel / dpmpp_one form it (no step kind: the input itself)
 template <int KIND>
 __device__ __forceinline__ float obs_p0(float xv, float e, const ObsK& k) {
-    if (KIND == OBS_MEAN) return xv;
+    if (!OBS_STEP(KIND)) return xv;
     const float se = k.s1m * e;
     float p0 = (xv - se) / k.sq_a;
     if (KIND == OBS_DPMPP && k.clip) p0 = fminf(fmaxf(p0, -1.0f), 1.0f);
     return p0;
 }
 
-// the projection and the update of one pixel; aux = e_t (DDIM: the direction) or x (DPM-Solver++: the state term)
+// the update of one pixel from its projected prediction; aux = e_t (DDIM: the direction) or x (DPM-Solver++: the state term)
 template <int KIND>
-__device__ __forceinline__ void obs_finish(float p0, float aux, float mean, float v, float m, float z, float d, const ObsK& k, float& o0,
-                                           float& o1) {
-    if (KIND == OBS_MEAN) { o0 = mean; o1 = 0.0f; return; }
-    const float lm = k.lambda * m;
-    const float df = mean - v;
-    const float t = lm * df;
-    const float p0c = p0 - t;
+__device__ __forceinline__ void obs_update(float p0c, float aux, float z, float d, const ObsK& k, float& o0, float& o1) {
     if (KIND == OBS_DDIM) {
         const float dir = k.u0 * aux;
         float nz;
@@ -539,6 +534,19 @@ __device__ __forceinline__ void obs_finish(float p0, float aux, float mean, floa
         o0 = p + q;
     }
     o1 = p0c;
+}
+
+// the projection and the update of one pixel (OBS_PROJECT: the projection alone)
+template <int KIND>
+__device__ __forceinline__ void obs_finish(float p0, float aux, float mean, float v, float m, float z, float d, const ObsK& k, float& o0,
+                                           float& o1) {
+    if (KIND == OBS_MEAN) { o0 = mean; o1 = 0.0f; return; }
+    const float lm = k.lambda * m;
+    const float df = mean - v;
+    const float t = lm * df;
+    const float p0c = p0 - t;
+    if (KIND == OBS_PROJECT) { o0 = p0c; o1 = 0.0f; return; }
+    obs_update<KIND>(p0c, aux, z, d, k, o0, o1);
 }
 
 template <int F, bool VEC> struct obs_width { static constexpr int v = !VEC || (F & 1) ? 1 : (F % 4 == 0 ? 4 : 2); };
@@ -582,7 +590,7 @@ __global__ void __launch_bounds__(256) obs_kernel(ObsArgs g, ObsChannels ch) {
             if (VEC) {
                 obs_load<4, 4>(g.x + off + i0, xv);
                 if (KIND != OBS_MEAN) {
-                    obs_load<4, 4>(g.e + off + i0, ev);
+                    if (OBS_STEP(KIND)) obs_load<4, 4>(g.e + off + i0, ev);
                     obs_load<4, 4>(g.values + voff + i0, vv);
                     if (masked) obs_load<4, 4>(g.mask + moff + i0, mv);
                     if (KIND == OBS_DDIM && k.noisy) obs_load<4, 4>(g.noise + off + i0, zv);
@@ -594,7 +602,7 @@ __global__ void __launch_bounds__(256) obs_kernel(ObsArgs g, ObsChannels ch) {
                     if (i0 + j < hw) {
                         xv[j] = g.x[off + i0 + j];
                         if (KIND != OBS_MEAN) {
-                            ev[j] = g.e[off + i0 + j];
+                            if (OBS_STEP(KIND)) ev[j] = g.e[off + i0 + j];
                             vv[j] = g.values[voff + i0 + j];
                             if (masked) mv[j] = g.mask[moff + i0 + j];
                             if (KIND == OBS_DDIM && k.noisy) zv[j] = g.noise[off + i0 + j];
@@ -611,13 +619,13 @@ __global__ void __launch_bounds__(256) obs_kernel(ObsArgs g, ObsChannels ch) {
             }
             if (VEC) {
                 obs_store<4, 4>(g.out0 + off + i0, o0);
-                if (KIND != OBS_MEAN) obs_store<4, 4>(g.out1 + off + i0, o1);
+                if (OBS_STEP(KIND)) obs_store<4, 4>(g.out1 + off + i0, o1);
             } else {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     if (i0 + j < hw) {
                         g.out0[off + i0 + j] = o0[j];
-                        if (KIND != OBS_MEAN) g.out1[off + i0 + j] = o1[j];
+                        if (OBS_STEP(KIND)) g.out1[off + i0 + j] = o1[j];
                     }
                 }
             }
@@ -630,16 +638,16 @@ __global__ void __launch_bounds__(256) obs_kernel(ObsArgs g, ObsChannels ch) {
     for (long long blk = (long long)blockIdx.x * blockDim.x + threadIdx.x; blk < blocks; blk += stride) {
         const long long by = blk / nbx, bx = blk % nbx;
         const long long at = by * F * g.W + bx * F;       // the block's first pixel in its plane; every row of it lies inside the plane
-        float P[F * F], A[KIND == OBS_MEAN ? 1 : F * F];
+        float P[F * F], A[OBS_STEP(KIND) ? F * F : 1];
 #pragma unroll
         for (int r = 0; r < F; ++r) {
             float xr[F], er[F];
             obs_load<F, V>(g.x + off + at + (long long)r * g.W, xr);
-            if (KIND != OBS_MEAN) obs_load<F, V>(g.e + off + at + (long long)r * g.W, er);
+            if (OBS_STEP(KIND)) obs_load<F, V>(g.e + off + at + (long long)r * g.W, er);
 #pragma unroll
             for (int j = 0; j < F; ++j) {
-                P[r * F + j] = obs_p0<KIND>(xr[j], KIND == OBS_MEAN ? 0.0f : er[j], k);
-                if (KIND != OBS_MEAN) A[r * F + j] = KIND == OBS_DDIM ? er[j] : xr[j];
+                P[r * F + j] = obs_p0<KIND>(xr[j], OBS_STEP(KIND) ? er[j] : 0.0f, k);
+                if (OBS_STEP(KIND)) A[r * F + j] = KIND == OBS_DDIM ? er[j] : xr[j];
             }
         }
         float s = P[0];
@@ -660,9 +668,9 @@ __global__ void __launch_bounds__(256) obs_kernel(ObsArgs g, ObsChannels ch) {
             }
 #pragma unroll
             for (int j = 0; j < F; ++j)
-                obs_finish<KIND>(P[r * F + j], KIND == OBS_MEAN ? 0.0f : A[r * F + j], mean, vr[j], mr[j], zr[j], dr[j], k, o0[j], o1[j]);
+                obs_finish<KIND>(P[r * F + j], OBS_STEP(KIND) ? A[r * F + j] : 0.0f, mean, vr[j], mr[j], zr[j], dr[j], k, o0[j], o1[j]);
             obs_store<F, V>(g.out0 + off + row, o0);
-            if (KIND != OBS_MEAN) obs_store<F, V>(g.out1 + off + row, o1);
+            if (OBS_STEP(KIND)) obs_store<F, V>(g.out1 + off + row, o1);
         }
     }
 }
@@ -695,16 +703,17 @@ static int obs_launch(const char* what, ObsArgs g, const int32_t* factors, void*
         EOD_REQUIRE(g.H % factors[c] == 0 && g.W % factors[c] == 0, "%s: factors[%d] = %d does not divide %d x %d", what, c, factors[c], g.H, g.W);
     }
     const long long n = (long long)g.B * g.C * g.H * g.W;
-    EOD_REQUIRE(KIND != OBS_MEAN || !eod_overlap2(g.out0, n, g.x, n), "%s: out overlaps x", what);
+    EOD_REQUIRE(OBS_STEP(KIND) || !eod_overlap2(g.out0, n, g.x, n), "%s: out overlaps %s", what, KIND == OBS_MEAN ? "x" : "p");
     if (KIND != OBS_MEAN) {
-        EOD_REQUIRE(g.e && g.values && g.out1, "%s: bad args", what);
-        EOD_REQUIRE(g.a > 0.0f && g.a <= 1.0f, "%s: needs 0 < a <= 1, got %g", what, (double)g.a);
+        EOD_REQUIRE(g.values && (!OBS_STEP(KIND) || (g.e && g.out1)), "%s: bad args", what);
+        EOD_REQUIRE(!OBS_STEP(KIND) || (g.a > 0.0f && g.a <= 1.0f), "%s: needs 0 < a <= 1, got %g", what, (double)g.a);
         EOD_REQUIRE(g.lambda >= 0.0f && g.lambda <= 1.0f, "%s: the weight must lie in [0, 1], got %g", what, (double)g.lambda);
         const long long nv = (long long)(g.values_b1 ? 1 : g.B) * g.C * g.H * g.W;
         const long long nm = (long long)(g.mask_b1 ? 1 : g.B) * (g.mask_c1 ? 1 : g.C) * g.H * g.W;
-        EOD_REQUIRE(!eod_overlap2(g.out0, n, g.out1, n), "%s: the two outputs overlap", what);
+        EOD_REQUIRE(!g.out1 || !eod_overlap2(g.out0, n, g.out1, n), "%s: the two outputs overlap", what);
         float* const outs[2] = {g.out0, g.out1};
         for (float* o : outs) {
+            if (!o) continue;
             EOD_REQUIRE(!eod_overlap2(o, n, g.values, nv), "%s: an output overlaps values", what);
             EOD_REQUIRE(!g.mask || !eod_overlap2(o, n, g.mask, nm), "%s: an output overlaps mask", what);
             EOD_REQUIRE(!g.d_prev || !eod_overlap2(o, n, g.d_prev, n), "%s: an output overlaps d_prev (the history is read while it is written)", what);
@@ -755,6 +764,353 @@ extern "C" int eod_dpmpp_step_obs(const float* x, const float* e_t, const float*
 extern "C" int eod_block_mean(const float* x, const int32_t* factors, float* out, int B, int C, int H, int W, void* stream) {
     ObsArgs g = {x, nullptr, nullptr, nullptr, nullptr, nullptr, out, nullptr, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0, B, C, H, W, 0, 0, 0};
     return obs_launch<OBS_MEAN>("block_mean", g, factors, stream);
+}
+
+extern "C" int eod_obs_project(const float* p, const float* values, const float* mask, float lambda, const int32_t* factors, int B, int C,
+                               int H, int W, int values_b1, int mask_b1, int mask_c1, float* out, void* stream) {
+    ObsArgs g = {p, nullptr, nullptr, nullptr, values, mask, out, nullptr, 1.0f, 0.0f, lambda, 0.0f, 0.0f, 0.0f, 0.0f,
+                 0, B, C, H, W, values_b1, mask_b1, mask_c1};
+    return obs_launch<OBS_PROJECT>("obs_project", g, factors, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Cross-band observations (no reference line): A = R (x) D_f, R [K][C] mixing the channels' f x f block means into
+// K observed bands, A+ = G (x) replication with G = pinv(R) [C][K].  Per pixel i, every operation rounded once (-ffp-contract=off):
+//   mean_c = the block mean of section 9.5 for channel c and blk(i)           (f = 1: p0 / 1.0f)
+//   d_k    = R[k][0] * mean_0;  then for c = 1 .. C-1 in order  d_k = d_k + (R[k][c] * mean_c)
+//   r_k    = d_k - values_k(i)
+//   t_c    = G[c][0] * r_0;     then for k = 1 .. K-1 in order  t_c = t_c + (G[c][k] * r_k)
+//   lm     = lambda * m(i)                                                     (mask NULL: m = 1.0f)
+//   p0c_c  = p0_c - (lm * t_c)
+// One launch, grid.y = sample.  A thread owns one f x f block across all channels (f = 1: a quad of pixels, four blocks).  Pass 1 walks
+// the channels, forms p0 and folds each block mean into K running dots (a statically indexed register array; the loop over k is
+// unrolled to 8 and guarded by the wave-uniform k < K: no zero padding, a + 0 * r term would turn a non-finite r into NaN and flip the
+// sign of a zero).  Pass 2 walks the block's rows: the K residuals of the row's pixels, then per channel the row of x / e_t again (the
+// same wave fetched it moments ago), the same p0 bits, t_c, the update.  R and G stay in the kernel arguments: indexed by the
+// wave-uniform channel they are scalar loads.  The access widths are obs_kernel's.
+// ---------------------------------------------------------------------------------------------
+#define EOD_SPEC_MAXK 8
+struct SpecMat {
+    float R[EOD_SPEC_MAXK][32];
+    float G[32][EOD_SPEC_MAXK];
+};
+
+// N floats of a row, the first nv of them valid (V > 1: all are); the others keep what r holds
+template <int N, int V>
+__device__ __forceinline__ void spec_load(const float* p, float* r, int nv) {
+    if (V > 1) { obs_load<N, V>(p, r); return; }
+#pragma unroll
+    for (int j = 0; j < N; ++j)
+        if (j < nv) r[j] = p[j];
+}
+template <int N, int V>
+__device__ __forceinline__ void spec_store(float* p, const float* r, int nv) {
+    if (V > 1) { obs_store<N, V>(p, r); return; }
+#pragma unroll
+    for (int j = 0; j < N; ++j)
+        if (j < nv) p[j] = r[j];
+}
+
+template <int KIND, int F, bool VEC>
+__global__ void __launch_bounds__(256) spec_kernel(ObsArgs g, int K, SpecMat m) {
+    constexpr bool STEP = OBS_STEP(KIND);
+    constexpr int WID = F == 1 ? 4 : F;        // the floats of an image row this thread owns
+    constexpr int NB = F == 1 ? 4 : 1;         // the blocks they belong to
+    constexpr int V = F == 1 ? (VEC ? 4 : 1) : obs_width<F, VEC>::v;
+    const int b = blockIdx.y;
+    const long long hw = (long long)g.H * g.W;
+    const long long off = (long long)b * g.C * hw;                                  // x, e_t, noise, d_prev, the step's outputs
+    const long long voff = (long long)(g.values_b1 ? 0 : b) * K * hw;
+    const long long moff = (long long)(g.mask_b1 ? 0 : b) * hw;
+    const ObsK k = obs_scalars<KIND>(g);
+    const bool masked = g.mask != nullptr;
+    const int nbx = g.W / F;
+    const long long units = F == 1 ? (hw + 3) / 4 : (long long)nbx * (g.H / F);
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long u = (long long)blockIdx.x * blockDim.x + threadIdx.x; u < units; u += stride) {
+        long long at;                          // the first pixel in its plane; every row read below lies inside the plane
+        int nv = WID;                          // f = 1: the last quad is cut at the plane's end (VEC: hw % 4 == 0, checked by the host)
+        if (F == 1) {
+            at = u * 4;
+            if (!VEC && hw - at < 4) nv = (int)(hw - at);
+        } else {
+            at = (u / nbx) * F * g.W + (u % nbx) * F;
+        }
+        float d[EOD_SPEC_MAXK][NB];
+#pragma unroll
+        for (int kk = 0; kk < EOD_SPEC_MAXK; ++kk)
+#pragma unroll
+            for (int n = 0; n < NB; ++n) d[kk][n] = 0.0f;
+        // pass 1: the block means of every channel, folded into the K dots
+        for (int c = 0; c < g.C; ++c) {
+            const long long pc = off + (long long)c * hw + at;
+            float s[NB];
+#pragma unroll
+            for (int n = 0; n < NB; ++n) s[n] = 0.0f;
+#pragma unroll
+            for (int r = 0; r < F; ++r) {
+                float xr[WID], er[WID];
+#pragma unroll
+                for (int j = 0; j < WID; ++j) { xr[j] = 0.0f; er[j] = 0.0f; }
+                spec_load<WID, V>(g.x + pc + (long long)r * g.W, xr, nv);
+                if (STEP) spec_load<WID, V>(g.e + pc + (long long)r * g.W, er, nv);
+#pragma unroll
+                for (int j = 0; j < WID; ++j) {
+                    const float p0 = obs_p0<KIND>(xr[j], er[j], k);
+                    if (F == 1) s[j] = p0;
+                    else s[0] = (r == 0 && j == 0) ? p0 : s[0] + p0;      // row by row, left to right
+                }
+            }
+#pragma unroll
+            for (int n = 0; n < NB; ++n) {
+                const float mean = s[n] / (float)(F * F);
+#pragma unroll
+                for (int kk = 0; kk < EOD_SPEC_MAXK; ++kk) {
+                    if (kk < K) {
+                        const float pr = m.R[kk][c] * mean;
+                        d[kk][n] = c == 0 ? pr : d[kk][n] + pr;
+                    }
+                }
+            }
+        }
+        if (KIND == OBS_APPLY) {               // the operator alone: d_k on the full-resolution grid
+            const long long ooff = (long long)b * K * hw;
+            for (int r = 0; r < F; ++r) {
+#pragma unroll
+                for (int kk = 0; kk < EOD_SPEC_MAXK; ++kk) {
+                    if (kk < K) {
+                        float o[WID];
+#pragma unroll
+                        for (int j = 0; j < WID; ++j) o[j] = d[kk][F == 1 ? j : 0];
+                        spec_store<WID, V>(g.out0 + ooff + (long long)kk * hw + at + (long long)r * g.W, o, nv);
+                    }
+                }
+            }
+            continue;
+        }
+        // pass 2: row by row the residuals of the row's pixels, then every channel's projection and update
+        for (int r = 0; r < F; ++r) {
+            const long long row = at + (long long)r * g.W;
+            float rk[EOD_SPEC_MAXK][WID], lm[WID];
+#pragma unroll
+            for (int kk = 0; kk < EOD_SPEC_MAXK; ++kk) {
+                if (kk < K) {
+                    float vr[WID];
+#pragma unroll
+                    for (int j = 0; j < WID; ++j) vr[j] = 0.0f;
+                    spec_load<WID, V>(g.values + voff + (long long)kk * hw + row, vr, nv);
+#pragma unroll
+                    for (int j = 0; j < WID; ++j) rk[kk][j] = d[kk][F == 1 ? j : 0] - vr[j];
+                } else {
+#pragma unroll
+                    for (int j = 0; j < WID; ++j) rk[kk][j] = 0.0f;     // (never read: the sums below are guarded alike)
+                }
+            }
+            {
+                float mr[WID];
+#pragma unroll
+                for (int j = 0; j < WID; ++j) mr[j] = 1.0f;
+                if (masked) spec_load<WID, V>(g.mask + moff + row, mr, nv);
+#pragma unroll
+                for (int j = 0; j < WID; ++j) lm[j] = k.lambda * mr[j];
+            }
+            for (int c = 0; c < g.C; ++c) {
+                const long long pc = off + (long long)c * hw + row;
+                float xr[WID], er[WID], zr[WID], dr[WID], o0[WID], o1[WID];
+#pragma unroll
+                for (int j = 0; j < WID; ++j) { xr[j] = 0.0f; er[j] = 0.0f; zr[j] = 0.0f; dr[j] = 0.0f; }
+                spec_load<WID, V>(g.x + pc, xr, nv);
+                if (STEP) spec_load<WID, V>(g.e + pc, er, nv);
+                if (KIND == OBS_DDIM && k.noisy) spec_load<WID, V>(g.noise + pc, zr, nv);
+                if (KIND == OBS_DPMPP && k.second) spec_load<WID, V>(g.d_prev + pc, dr, nv);
+#pragma unroll
+                for (int j = 0; j < WID; ++j) {
+                    const float p0 = obs_p0<KIND>(xr[j], er[j], k);
+                    float t = m.G[c][0] * rk[0][j];
+#pragma unroll
+                    for (int kk = 1; kk < EOD_SPEC_MAXK; ++kk) {
+                        if (kk < K) {
+                            const float pr = m.G[c][kk] * rk[kk][j];
+                            t = t + pr;
+                        }
+                    }
+                    const float q = lm[j] * t;
+                    const float p0c = p0 - q;
+                    if (STEP) obs_update<KIND>(p0c, KIND == OBS_DDIM ? er[j] : xr[j], zr[j], dr[j], k, o0[j], o1[j]);
+                    else o0[j] = p0c;
+                }
+                spec_store<WID, V>(g.out0 + pc, o0, nv);
+                if (STEP) spec_store<WID, V>(g.out1 + pc, o1, nv);
+            }
+        }
+    }
+}
+
+// the blocks of 256 threads of one spec_kernel launch, over all samples (EOD_SPEC_GRID_BLOCKS of include/eodiff.h): beyond it the
+// threads stride over the plane
+template <int KIND, int F>
+static void spec_launch_f(const ObsArgs& g, int K, const SpecMat& m, bool vec, hipStream_t stream) {
+    const long long hw = (long long)g.H * g.W;
+    const long long units = F == 1 ? (hw + 3) / 4 : hw / (F * F);
+    const dim3 grid(blocks_for(units, g.B >= EOD_SPEC_GRID_BLOCKS ? 1 : EOD_SPEC_GRID_BLOCKS / g.B), g.B), block(256);
+    if (vec && (F != 1 || hw % 4 == 0))
+        hipLaunchKernelGGL((spec_kernel<KIND, F, true>), grid, block, 0, stream, g, K, m);
+    else
+        hipLaunchKernelGGL((spec_kernel<KIND, F, false>), grid, block, 0, stream, g, K, m);
+}
+
+// checks what the four cross-band entry points share, then the one launch.  OBS_APPLY: out0 is [B][K][H][W] and G is not read.
+template <int KIND>
+static int spec_launch(const char* what, ObsArgs g, const float* R, const float* G, int K, int f, void* stream) {
+    EOD_REQUIRE(g.x && g.out0 && R && g.B > 0 && g.C > 0 && g.H > 0 && g.W > 0, "%s: bad args", what);
+    EOD_REQUIRE(g.C <= 32, "%s: at most 32 channels (the matrices travel by value), got %d", what, g.C);
+    EOD_REQUIRE(K >= 1 && K <= EOD_SPEC_MAXK && K <= g.C, "%s: needs 1 <= K <= min(C, %d), got K = %d, C = %d", what, EOD_SPEC_MAXK, K, g.C);
+    EOD_REQUIRE(g.B <= 65535, "%s: B = %d samples exceed one launch", what, g.B);
+    EOD_REQUIRE(f >= 1 && f <= 8, "%s: f = %d is outside 1..8", what, f);
+    EOD_REQUIRE(g.H % f == 0 && g.W % f == 0, "%s: f = %d does not divide %d x %d", what, f, g.H, g.W);
+    const long long hw = (long long)g.H * g.W, n = (long long)g.B * g.C * hw;
+    const long long n0 = KIND == OBS_APPLY ? (long long)g.B * K * hw : n;
+    EOD_REQUIRE(KIND != OBS_APPLY || !eod_overlap2(g.out0, n0, g.x, n), "%s: out overlaps x", what);
+    if (KIND != OBS_APPLY) {
+        EOD_REQUIRE(G && g.values && (!OBS_STEP(KIND) || (g.e && g.out1)), "%s: bad args", what);
+        EOD_REQUIRE(!OBS_STEP(KIND) || (g.a > 0.0f && g.a <= 1.0f), "%s: needs 0 < a <= 1, got %g", what, (double)g.a);
+        EOD_REQUIRE(g.lambda >= 0.0f && g.lambda <= 1.0f, "%s: the weight must lie in [0, 1], got %g", what, (double)g.lambda);
+        const long long nv = (long long)(g.values_b1 ? 1 : g.B) * K * hw, nm = (long long)(g.mask_b1 ? 1 : g.B) * hw;
+        EOD_REQUIRE(!g.out1 || !eod_overlap2(g.out0, n, g.out1, n), "%s: the two outputs overlap", what);
+        float* const outs[2] = {g.out0, g.out1};
+        for (float* o : outs) {
+            if (!o) continue;
+            EOD_REQUIRE(!eod_overlap2(o, n, g.x, n), "%s: an output overlaps %s", what, (KIND == OBS_PROJECT ? "p" : "x"));
+            EOD_REQUIRE(!g.e || !eod_overlap2(o, n, g.e, n), "%s: an output overlaps e_t", what);
+            EOD_REQUIRE(!g.noise || !eod_overlap2(o, n, g.noise, n), "%s: an output overlaps noise", what);
+            EOD_REQUIRE(!g.d_prev || !eod_overlap2(o, n, g.d_prev, n), "%s: an output overlaps d_prev", what);
+            EOD_REQUIRE(!eod_overlap2(o, n, g.values, nv), "%s: an output overlaps values", what);
+            EOD_REQUIRE(!g.mask || !eod_overlap2(o, n, g.mask, nm), "%s: an output overlaps mask", what);
+        }
+    }
+    SpecMat m;
+    memset(&m, 0, sizeof m);
+    for (int kk = 0; kk < K; ++kk)
+        for (int c = 0; c < g.C; ++c) {
+            m.R[kk][c] = R[kk * g.C + c];
+            if (KIND != OBS_APPLY) m.G[c][kk] = G[c * K + kk];
+        }
+    const bool vec = eod_aligned16(g.x) && eod_aligned16(g.out0) && (!g.e || eod_aligned16(g.e)) && (!g.noise || eod_aligned16(g.noise)) &&
+                     (!g.d_prev || eod_aligned16(g.d_prev)) && (!g.values || eod_aligned16(g.values)) && (!g.mask || eod_aligned16(g.mask)) &&
+                     (!g.out1 || eod_aligned16(g.out1));
+    switch (f) {
+        case 1: spec_launch_f<KIND, 1>(g, K, m, vec, (hipStream_t)stream); break;
+        case 2: spec_launch_f<KIND, 2>(g, K, m, vec, (hipStream_t)stream); break;
+        case 3: spec_launch_f<KIND, 3>(g, K, m, vec, (hipStream_t)stream); break;
+        case 4: spec_launch_f<KIND, 4>(g, K, m, vec, (hipStream_t)stream); break;
+        case 5: spec_launch_f<KIND, 5>(g, K, m, vec, (hipStream_t)stream); break;
+        case 6: spec_launch_f<KIND, 6>(g, K, m, vec, (hipStream_t)stream); break;
+        case 7: spec_launch_f<KIND, 7>(g, K, m, vec, (hipStream_t)stream); break;
+        default: spec_launch_f<KIND, 8>(g, K, m, vec, (hipStream_t)stream); break;
+    }
+    EOD_CHECK_LAUNCH(what);
+    return EOD_OK;
+}
+
+extern "C" int eod_ddim_step_spec(const float* x, const float* e_t, const float* noise, float a_t, float a_prev, float sigma_t,
+                                  float sqrt_1m_at, float temperature, const float* values, const float* mask, float lambda, const float* R,
+                                  const float* G, int K, int f, int B, int C, int H, int W, int values_b1, int mask_b1, float* x_prev,
+                                  float* pred_x0, void* stream) {
+    ObsArgs g = {x, e_t, noise, nullptr, values, mask, x_prev, pred_x0, a_t, sqrt_1m_at, lambda, a_prev, sigma_t, temperature, 0.0f,
+                 0, B, C, H, W, values_b1, mask_b1, 1};
+    return spec_launch<OBS_DDIM>("ddim_step_spec", g, R, G, K, f, stream);
+}
+
+extern "C" int eod_dpmpp_step_spec(const float* x, const float* e_t, const float* d_prev, float a_s, float sqrt_1m_as, float c_x, float c_d,
+                                   float w_cur, float w_prev, int clip, const float* values, const float* mask, float lambda, const float* R,
+                                   const float* G, int K, int f, int B, int C, int H, int W, int values_b1, int mask_b1, float* x_next,
+                                   float* pred_x0, void* stream) {
+    ObsArgs g = {x, e_t, nullptr, d_prev, values, mask, x_next, pred_x0, a_s, sqrt_1m_as, lambda, c_x, c_d, w_cur, w_prev,
+                 clip, B, C, H, W, values_b1, mask_b1, 1};
+    return spec_launch<OBS_DPMPP>("dpmpp_step_spec", g, R, G, K, f, stream);
+}
+
+extern "C" int eod_spec_project(const float* p, const float* values, const float* mask, float lambda, const float* R, const float* G, int K,
+                                int f, int B, int C, int H, int W, int values_b1, int mask_b1, float* out, void* stream) {
+    ObsArgs g = {p, nullptr, nullptr, nullptr, values, mask, out, nullptr, 1.0f, 0.0f, lambda, 0.0f, 0.0f, 0.0f, 0.0f,
+                 0, B, C, H, W, values_b1, mask_b1, 1};
+    return spec_launch<OBS_PROJECT>("spec_project", g, R, G, K, f, stream);
+}
+
+extern "C" int eod_spec_apply(const float* x, const float* R, int K, int f, float* out, int B, int C, int H, int W, void* stream) {
+    ObsArgs g = {x, nullptr, nullptr, nullptr, nullptr, nullptr, out, nullptr, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0, B, C, H, W, 0, 0, 1};
+    return spec_launch<OBS_APPLY>("spec_apply", g, R, nullptr, K, f, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The ends of a chain of observations: the prediction alone (obs_p0's operations), and the update from a given
+// projected prediction (obs_update's operations).  pred_x0 -> projections -> step_p0 has the bits of the fused kernels.  Quads of the
+// tensor, 16-byte accesses where numel % 4 == 0 and every pointer is aligned, element by element otherwise.
+// ---------------------------------------------------------------------------------------------
+enum { END_P0 = 0, END_DDIM = 1, END_DPMPP = 2 };
+
+template <int END, bool VEC>
+__global__ void __launch_bounds__(256) chain_end_kernel(ObsArgs g, long long numel) {
+    constexpr int KIND = END == END_DDIM ? OBS_DDIM : OBS_DPMPP;
+    const ObsK k = obs_scalars<KIND>(g);
+    const long long quads = (numel + 3) / 4;
+    for (long long qd = (long long)blockIdx.x * blockDim.x + threadIdx.x; qd < quads; qd += (long long)gridDim.x * blockDim.x) {
+        const long long i0 = qd * 4;
+        const int nv = VEC || numel - i0 >= 4 ? 4 : (int)(numel - i0);
+        float xv[4] = {0.f, 0.f, 0.f, 0.f}, ev[4] = {0.f, 0.f, 0.f, 0.f}, pv[4] = {0.f, 0.f, 0.f, 0.f}, zv[4] = {0.f, 0.f, 0.f, 0.f};
+        float dv[4] = {0.f, 0.f, 0.f, 0.f}, o0[4], o1[4];
+        constexpr int V = VEC ? 4 : 1;
+        if (END != END_DDIM) spec_load<4, V>(g.x + i0, xv, nv);
+        if (END != END_DPMPP) spec_load<4, V>(g.e + i0, ev, nv);
+        if (END != END_P0) spec_load<4, V>(g.values + i0, pv, nv);           // (values: the given p0c)
+        if (END == END_DDIM && k.noisy) spec_load<4, V>(g.noise + i0, zv, nv);
+        if (END == END_DPMPP && k.second) spec_load<4, V>(g.d_prev + i0, dv, nv);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (END == END_P0) o0[j] = obs_p0<OBS_DPMPP>(xv[j], ev[j], k);
+            else obs_update<KIND>(pv[j], END == END_DDIM ? ev[j] : xv[j], zv[j], dv[j], k, o0[j], o1[j]);
+        }
+        spec_store<4, V>(g.out0 + i0, o0, nv);
+    }
+}
+
+template <int END>
+static int chain_end_launch(const char* what, const ObsArgs& g, int64_t numel, void* stream) {
+    EOD_REQUIRE(g.out0 && numel > 0, "%s: bad args", what);
+    const float* const ins[5] = {g.x, g.e, g.values, g.noise, g.d_prev};
+    bool vec = numel % 4 == 0 && eod_aligned16(g.out0);
+    for (const float* p : ins) {
+        if (!p) continue;
+        EOD_REQUIRE(!eod_overlap(g.out0, p, numel), "%s: the output overlaps an input", what);
+        vec = vec && eod_aligned16(p);
+    }
+    const dim3 grid(blocks_for((numel + 3) / 4, 2048)), block(256);
+    if (vec) hipLaunchKernelGGL((chain_end_kernel<END, true>), grid, block, 0, (hipStream_t)stream, g, (long long)numel);
+    else hipLaunchKernelGGL((chain_end_kernel<END, false>), grid, block, 0, (hipStream_t)stream, g, (long long)numel);
+    EOD_CHECK_LAUNCH(what);
+    return EOD_OK;
+}
+
+extern "C" int eod_pred_x0(const float* x, const float* e_t, float a, float sqrt_1m_a, int clip, float* p0, int64_t numel, void* stream) {
+    EOD_REQUIRE(x && e_t, "pred_x0: bad args");
+    EOD_REQUIRE(a > 0.0f && a <= 1.0f, "pred_x0: needs 0 < a <= 1, got %g", (double)a);
+    ObsArgs g = {x, e_t, nullptr, nullptr, nullptr, nullptr, p0, nullptr, a, sqrt_1m_a, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, clip, 1, 1, 1, 1, 0, 0, 0};
+    return chain_end_launch<END_P0>("pred_x0", g, numel, stream);
+}
+
+extern "C" int eod_ddim_step_p0(const float* e_t, const float* p0c, const float* noise, float a_prev, float sigma_t, float temperature,
+                                float* x_prev, int64_t numel, void* stream) {
+    EOD_REQUIRE(e_t && p0c, "ddim_step_p0: bad args");
+    ObsArgs g = {nullptr, e_t, noise, nullptr, p0c, nullptr, x_prev, nullptr, 1.0f, 0.0f, 0.0f, a_prev, sigma_t, temperature, 0.0f,
+                 0, 1, 1, 1, 1, 0, 0, 0};
+    return chain_end_launch<END_DDIM>("ddim_step_p0", g, numel, stream);
+}
+
+extern "C" int eod_dpmpp_step_p0(const float* x, const float* p0c, const float* d_prev, float c_x, float c_d, float w_cur, float w_prev,
+                                 float* x_next, int64_t numel, void* stream) {
+    EOD_REQUIRE(x && p0c, "dpmpp_step_p0: bad args");
+    ObsArgs g = {x, nullptr, nullptr, d_prev, p0c, nullptr, x_next, nullptr, 1.0f, 0.0f, 0.0f, c_x, c_d, w_cur, w_prev, 0, 1, 1, 1, 1, 0, 0, 0};
+    return chain_end_launch<END_DPMPP>("dpmpp_step_p0", g, numel, stream);
 }
 
 extern "C" int eod_cfg_combine(const float* e_uncond, const float* e_cond, float scale, float* out, int64_t numel, void* stream) {

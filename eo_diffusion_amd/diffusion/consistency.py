@@ -6,6 +6,12 @@ With A = masked per-channel block mean and A+ = replication, every evaluation of
 prediction p0 by p0 - weight * mask * (A+ A p0 - values) before the update uses it: the range / null-space projection of DDNM
 (Wang et al. 2022) fused into the step kernel.  Per pixel, what the kernel computes for ANY values / mask is stated in include/eodiff.h;
 it is the projection when values and mask are constant on every block and the mask is 0 or 1.
+
+SpectralObservation is the observation that mixes bands: K known linear mixes `response` [K, C] of the channels'
+f x f block means (a panchromatic band, a second sensor's broad bands), A = R (x) D_f, A+ = pinv(R) (x) replication, imposed by
+eod_ddim_step_spec / eod_dpmpp_step_spec.  `observation=` also takes a list of 1 .. 4 observations of either kind, a chain: every
+evaluation forms its prediction (eod_pred_x0), projects it by one link after the other (eod_spec_project / eod_obs_project, each with its
+own weight) and finishes the step from the result (eod_ddim_step_p0 / eod_dpmpp_step_p0).  A list of one takes the fused kernel.
 """
 import ctypes
 import math
@@ -19,6 +25,10 @@ from ..engine import current_stream_ptr, f32c, require_gpu
 
 MAX_FACTOR = 8
 MAX_CHANNELS = 32
+MAX_ROWS = 8            # rows of a response matrix (EOD_SPEC_MAXK of csrc/sampler.hip)
+MAX_LINKS = 4           # observations in one chain
+MIN_RCOND = 1e-3        # sigma_min / sigma_max of a response matrix below which it is refused (the fp32 residual
+                        # of the projection grows with the conditioning, 0.55 eps at cond 45 and 11.6 eps at cond 268)
 
 
 def _factors(what, factors):
@@ -42,6 +52,54 @@ def _divides(what, factors, H, W):
 
 def _c_factors(factors):
     return (ctypes.c_int32 * len(factors))(*factors)
+
+
+def _weights(what, weight):
+    """([fp32-rounded weights], one per evaluation?) of a `weight` argument: a float in [0, 1] or a sequence of them"""
+    if isinstance(weight, (numbers.Real, np.floating)) and not isinstance(weight, bool):
+        ws, per_evaluation = [weight], False
+    else:
+        try:
+            ws = list(weight)
+        except TypeError:
+            raise _lib.EodError(f"{what}: `weight` is a float or a sequence of floats, got {weight!r}") from None
+        per_evaluation = True
+    for w in ws:
+        if isinstance(w, bool) or not isinstance(w, (numbers.Real, np.floating)) or not math.isfinite(float(w)):
+            raise _lib.EodError(f"{what}: a weight is a finite float, got {w!r}")
+        if not 0.0 <= float(np.float32(w)) <= 1.0:
+            raise _lib.EodError(f"{what}: a weight lies in [0, 1], got {w!r}")
+    return [float(np.float32(w)) for w in ws], per_evaluation
+
+
+def _response(what, response):
+    """the response matrix [K, C] as the fp32 array the kernels use; shape, dtype, limits and finiteness refused here"""
+    try:
+        R = np.asarray(response.detach().cpu().numpy() if torch.is_tensor(response) else response)
+    except Exception:
+        raise _lib.EodError(f"{what}: `response` is array-like [K, C], got {type(response).__name__}") from None
+    if R.dtype == np.bool_ or not (np.issubdtype(R.dtype, np.floating) or np.issubdtype(R.dtype, np.integer)):
+        raise _lib.EodError(f"{what}: `response` must hold real numbers, got dtype {R.dtype}")
+    if R.ndim != 2 or 0 in R.shape:
+        raise _lib.EodError(f"{what}: `response` is [K, C] (K observed bands as mixes of C channels), got shape {R.shape}")
+    K, C = R.shape
+    if C > MAX_CHANNELS or K > MAX_ROWS or K > C:
+        raise _lib.EodError(f"{what}: `response` [K, C] needs K <= min(C, {MAX_ROWS}) and C <= {MAX_CHANNELS}, got {K} x {C}")
+    with np.errstate(over="ignore"):
+        R = np.ascontiguousarray(R, dtype=np.float32)
+    if not np.isfinite(R).all():
+        raise _lib.EodError(f"{what}: `response` has a non-finite entry (as float32)")
+    return R
+
+
+def _factor(what, factor):
+    if isinstance(factor, bool) or not isinstance(factor, numbers.Integral) or not 1 <= factor <= MAX_FACTOR:
+        raise _lib.EodError(f"{what}: `factor` is an integer in 1 .. {MAX_FACTOR}, got {factor!r}")
+    return int(factor)
+
+
+def _c_floats(a):
+    return (ctypes.c_float * a.size)(*a.ravel().tolist())
 
 
 class Observation:
@@ -69,20 +127,7 @@ class Observation:
                 raise _lib.EodError(f"{what}: `mask` must be [B or 1, {C} or 1, {H}, {W}], got {tuple(mask.shape)}")
             if 1 not in (v.shape[0], mask.shape[0]) and v.shape[0] != mask.shape[0]:
                 raise _lib.EodError(f"{what}: `values` is for {v.shape[0]} samples, `mask` for {mask.shape[0]}")
-        if isinstance(weight, (numbers.Real, np.floating)) and not isinstance(weight, bool):
-            ws, self.per_evaluation = [weight], False
-        else:
-            try:
-                ws = list(weight)
-            except TypeError:
-                raise _lib.EodError(f"{what}: `weight` is a float or a sequence of floats, got {weight!r}") from None
-            self.per_evaluation = True
-        for w in ws:
-            if isinstance(w, bool) or not isinstance(w, (numbers.Real, np.floating)) or not math.isfinite(float(w)):
-                raise _lib.EodError(f"{what}: a weight is a finite float, got {w!r}")
-            if not 0.0 <= float(np.float32(w)) <= 1.0:
-                raise _lib.EodError(f"{what}: a weight lies in [0, 1], got {w!r}")
-        self.weights = [float(np.float32(w)) for w in ws]
+        self.weights, self.per_evaluation = _weights(what, weight)
         self.values, self.mask = v, mask
 
     def bind(self, what, shape, n_evaluations, device):
@@ -137,13 +182,159 @@ class BoundObservation:
         return x_next, pred_x0
 
 
+    def project(self, i, p):
+        """the projection of a given prediction p at evaluation number i (a link of a chain): eod_obs_project"""
+        out = torch.empty_like(p)
+        _lib.check(_lib.lib().eod_obs_project(p.data_ptr(), *self._tail(p, i), out.data_ptr(), current_stream_ptr(p.device)), "eod_obs_project")
+        return out
+
+
+class SpectralObservation:
+    """K observed bands that are known linear mixes of the state's C channels, on a grid `factor` times coarser.  values [B or 1, K, H, W]
+    fp32: what the other sensor saw, replicated onto the full-resolution grid; response: array-like [K, C], K <= min(C, 8), C <= 32, finite,
+    of full row rank with sigma_min >= 1e-3 sigma_max (float64 SVD of the fp32 entries the kernels use); factor: the block edge, 1 .. 8;
+    mask None or [B or 1, 1, H, W] fp32 (ONE mask for all K bands: per-band masks change the pseudo-inverse); weight as for Observation.
+    `pinv` [C, K] is the float64 pseudo-inverse rounded once to fp32."""
+
+    def __init__(self, values, response, factor=1, mask=None, weight=1.0):
+        what = "SpectralObservation"
+        self.response = _response(what, response)
+        K, C = self.response.shape
+        sv = np.linalg.svd(self.response.astype(np.float64), compute_uv=False)
+        if not (sv[0] > 0.0 and sv[-1] >= MIN_RCOND * sv[0]):
+            raise _lib.EodError(f"{what}: `response` is too badly conditioned to project with in fp32 (sigma_min {sv[-1]:.3g} < "
+                                f"{MIN_RCOND:g} * sigma_max {sv[0]:.3g}); rows must be linearly independent")
+        self.pinv = np.ascontiguousarray(np.linalg.pinv(self.response.astype(np.float64)), dtype=np.float32)
+        self.factor = _factor(what, factor)
+        v = torch.as_tensor(values)
+        if v.dtype != torch.float32:
+            raise _lib.EodError(f"{what}: `values` must be float32, got {v.dtype}")
+        if v.dim() != 4 or v.shape[1] != K:
+            raise _lib.EodError(f"{what}: `values` must be [B or 1, {K}, H, W] (`response` has {K} rows), got {tuple(v.shape)}")
+        H, W = int(v.shape[2]), int(v.shape[3])
+        if H % self.factor or W % self.factor:
+            raise _lib.EodError(f"{what}: factor = {self.factor} does not divide {H} x {W}")
+        if mask is not None:
+            mask = torch.as_tensor(mask)
+            if mask.dtype != torch.float32:
+                raise _lib.EodError(f"{what}: `mask` must be float32, got {mask.dtype}")
+            if mask.dim() != 4 or mask.shape[1] != 1 or tuple(mask.shape[2:]) != (H, W):
+                raise _lib.EodError(f"{what}: `mask` must be [B or 1, 1, {H}, {W}] (one mask for all {K} bands), got {tuple(mask.shape)}")
+            if 1 not in (v.shape[0], mask.shape[0]) and v.shape[0] != mask.shape[0]:
+                raise _lib.EodError(f"{what}: `values` is for {v.shape[0]} samples, `mask` for {mask.shape[0]}")
+        self.weights, self.per_evaluation = _weights(what, weight)
+        self.values, self.mask = v, mask
+
+    def bind(self, what, shape, n_evaluations, device):
+        B, C, H, W = (int(s) for s in shape)
+        if self.response.shape[1] != C:
+            raise _lib.EodError(f"{what}: the observation's `response` mixes {self.response.shape[1]} channels, the state has {C}")
+        if tuple(self.values.shape[2:]) != (H, W):
+            raise _lib.EodError(f"{what}: the observation is {tuple(self.values.shape[2:])}, the state is {(H, W)}")
+        for name, t in (("values", self.values), ("mask", self.mask)):
+            if t is not None and t.shape[0] not in (1, B):
+                raise _lib.EodError(f"{what}: the observation's `{name}` has leading dimension {t.shape[0]}; the call needs {B} or 1")
+        if self.per_evaluation and len(self.weights) != n_evaluations:
+            raise _lib.EodError(f"{what}: the call evaluates the UNet {n_evaluations} times, the observation's `weight` has {len(self.weights)} entries")
+        return BoundSpectral(self, (B, C, H, W), n_evaluations, device)
+
+
+class BoundSpectral:
+    def __init__(self, obs, shape, n_evaluations, device):
+        self.shape, self.factor, self.K = shape, obs.factor, obs.response.shape[0]
+        self.c_R, self.c_G = _c_floats(obs.response), _c_floats(obs.pinv)
+        self.values = f32c(obs.values.to(device))
+        self.mask = None if obs.mask is None else f32c(obs.mask.to(device))
+        self.weights = obs.weights if obs.per_evaluation else obs.weights * n_evaluations
+
+    def _tail(self, x, i):
+        """the arguments the three entry points share, from `values` to the broadcast flags"""
+        if tuple(x.shape) != self.shape:
+            raise _lib.EodError(f"observation bound to a state of shape {self.shape}, the step got {tuple(x.shape)}")
+        B, C, H, W = self.shape
+        m = self.mask
+        return (self.values.data_ptr(), _lib.ptr(m), self.weights[i], self.c_R, self.c_G, self.K, self.factor, B, C, H, W,
+                int(self.values.shape[0] != B), int(m is not None and m.shape[0] != B))
+
+    def ddim_step(self, i, x, e_t, noise, a_t, a_prev, sigma_t, sqrt_1m_at, temperature):
+        """(x_prev, pred_x0) of evaluation number i: eod_ddim_step_spec"""
+        x, e_t = f32c(x), f32c(e_t)
+        x_prev, pred_x0 = torch.empty_like(x), torch.empty_like(x)
+        _lib.check(_lib.lib().eod_ddim_step_spec(x.data_ptr(), e_t.data_ptr(), _lib.ptr(noise), float(a_t), float(a_prev), float(sigma_t),
+                                                 float(sqrt_1m_at), float(temperature), *self._tail(x, i), x_prev.data_ptr(),
+                                                 pred_x0.data_ptr(), current_stream_ptr(x.device)), "eod_ddim_step_spec")
+        return x_prev, pred_x0
+
+    def dpmpp_step(self, i, x, e_t, d_prev, a_s, sqrt_1m_as, c_x, c_d, w_cur, w_prev, clip):
+        """(x_next, pred_x0) of evaluation number i: eod_dpmpp_step_spec"""
+        x, e_t = f32c(x), f32c(e_t)
+        x_next, pred_x0 = torch.empty_like(x), torch.empty_like(x)
+        _lib.check(_lib.lib().eod_dpmpp_step_spec(x.data_ptr(), e_t.data_ptr(), _lib.ptr(d_prev), float(a_s), float(sqrt_1m_as), float(c_x),
+                                                  float(c_d), float(w_cur), float(w_prev), int(bool(clip)), *self._tail(x, i),
+                                                  x_next.data_ptr(), pred_x0.data_ptr(), current_stream_ptr(x.device)), "eod_dpmpp_step_spec")
+        return x_next, pred_x0
+
+    def project(self, i, p):
+        """the projection of a given prediction p at evaluation number i (a link of a chain): eod_spec_project"""
+        out = torch.empty_like(p)
+        _lib.check(_lib.lib().eod_spec_project(p.data_ptr(), *self._tail(p, i), out.data_ptr(), current_stream_ptr(p.device)), "eod_spec_project")
+        return out
+
+
+class BoundChain:
+    """2 .. 4 bound observations applied in order to every evaluation's prediction, each link to the previous link's result and with its own
+    weight: eod_pred_x0, one projection launch per link, eod_ddim_step_p0 / eod_dpmpp_step_p0.  The bits are those the fused kernel of
+    every link would give on the same prediction.  pred_x0 (for DPM-Solver++: the next evaluation's history) is the last link's result."""
+
+    def __init__(self, links):
+        self.links = links
+
+    def _project(self, i, p):
+        for link in self.links:
+            p = link.project(i, p)
+        return p
+
+    @staticmethod
+    def _pred_x0(x, e_t, a, sqrt_1m_a, clip):
+        p0 = torch.empty_like(x)
+        _lib.check(_lib.lib().eod_pred_x0(x.data_ptr(), e_t.data_ptr(), float(a), float(sqrt_1m_a), int(bool(clip)), p0.data_ptr(), x.numel(),
+                                          current_stream_ptr(x.device)), "eod_pred_x0")
+        return p0
+
+    def ddim_step(self, i, x, e_t, noise, a_t, a_prev, sigma_t, sqrt_1m_at, temperature):
+        x, e_t = f32c(x), f32c(e_t)
+        pred_x0 = self._project(i, self._pred_x0(x, e_t, a_t, sqrt_1m_at, False))
+        x_prev = torch.empty_like(x)
+        _lib.check(_lib.lib().eod_ddim_step_p0(e_t.data_ptr(), pred_x0.data_ptr(), _lib.ptr(noise), float(a_prev), float(sigma_t),
+                                               float(temperature), x_prev.data_ptr(), x.numel(), current_stream_ptr(x.device)), "eod_ddim_step_p0")
+        return x_prev, pred_x0
+
+    def dpmpp_step(self, i, x, e_t, d_prev, a_s, sqrt_1m_as, c_x, c_d, w_cur, w_prev, clip):
+        x, e_t = f32c(x), f32c(e_t)
+        pred_x0 = self._project(i, self._pred_x0(x, e_t, a_s, sqrt_1m_as, clip))
+        x_next = torch.empty_like(x)
+        _lib.check(_lib.lib().eod_dpmpp_step_p0(x.data_ptr(), pred_x0.data_ptr(), _lib.ptr(d_prev), float(c_x), float(c_d), float(w_cur),
+                                                float(w_prev), x_next.data_ptr(), x.numel(), current_stream_ptr(x.device)), "eod_dpmpp_step_p0")
+        return x_next, pred_x0
+
+
 def bind(observation, what, shape, n_evaluations, device):
-    """None, or the observation bound to the call (every refusal before anything is launched)"""
+    """None, or the observation bound to the call (every refusal before anything is launched).  An Observation or a SpectralObservation, or
+    a list / tuple of 1 .. 4 of them: one takes its fused step kernel, more become a BoundChain."""
     if observation is None:
         return None
-    if not isinstance(observation, Observation):
-        raise _lib.EodError(f"{what}: `observation` is an Observation, got {type(observation).__name__}")
-    return observation.bind(what, shape, n_evaluations, device)
+    kinds = (Observation, SpectralObservation)
+    if isinstance(observation, kinds):
+        return observation.bind(what, shape, n_evaluations, device)
+    if not isinstance(observation, (list, tuple)):
+        raise _lib.EodError(f"{what}: `observation` is an Observation, a SpectralObservation or a list of them, got {type(observation).__name__}")
+    if not 1 <= len(observation) <= MAX_LINKS:
+        raise _lib.EodError(f"{what}: a chain of observations has 1 .. {MAX_LINKS} links, got {len(observation)}")
+    for link in observation:
+        if not isinstance(link, kinds):
+            raise _lib.EodError(f"{what}: a link of `observation` is an Observation or a SpectralObservation, got {type(link).__name__}")
+    links = [link.bind(what, shape, n_evaluations, device) for link in observation]
+    return links[0] if len(links) == 1 else BoundChain(links)
 
 
 def block_mean(x, factors):
@@ -159,4 +350,24 @@ def block_mean(x, factors):
     x = f32c(x)
     out = torch.empty_like(x)
     _lib.check(_lib.lib().eod_block_mean(x.data_ptr(), _c_factors(fs), out.data_ptr(), B, C, H, W, current_stream_ptr(x.device)), "eod_block_mean")
+    return out
+
+
+def spectral_response(x, response, factor=1):
+    """R (x) D_f of x on the GPU (eod_spec_apply): [B, K, H, W], band k = sum_c response[k][c] * (the factor x factor block mean of channel c),
+    replicated onto the full-resolution grid.  Makes a SpectralObservation's `values` out of an image, and measures how far a result is
+    from one."""
+    what = "spectral_response"
+    R = _response(what, response)
+    f = _factor(what, factor)
+    K, C = R.shape
+    if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != C:
+        raise _lib.EodError(f"{what}: x must be a tensor [B, {C}, H, W] (`response` mixes {C} channels)")
+    B, _, H, W = x.shape
+    if H % f or W % f:
+        raise _lib.EodError(f"{what}: factor = {f} does not divide {H} x {W}")
+    require_gpu(x, what)
+    x = f32c(x)
+    out = torch.empty((B, K, H, W), device=x.device, dtype=torch.float32)
+    _lib.check(_lib.lib().eod_spec_apply(x.data_ptr(), _c_floats(R), K, f, out.data_ptr(), B, C, H, W, current_stream_ptr(x.device)), "eod_spec_apply")
     return out

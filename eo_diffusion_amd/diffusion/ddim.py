@@ -14,6 +14,8 @@ steps (diffusion/util.py make_resample_schedule), the forward moves through eod_
 `observation=` (a diffusion/consistency.py Observation) on sample / ddim_sampling / sample_scene: every step's data prediction is made
 consistent with an observation of per-channel block means, inside the step kernel (eod_ddim_step_obs).  With
 observation=None (the default) every call takes the launches it took before.
+`observation=` also takes a SpectralObservation (K known mixes of the bands' block means: eod_ddim_step_spec) or a list of 1 .. 4
+observations applied in order to every prediction (eod_pred_x0, one projection per link, eod_ddim_step_p0); DESIGN.md section 9.6.
 """
 import numpy as np
 import torch
@@ -92,8 +94,8 @@ class DDIMSampler(object):
         After the listed evaluations the state (at ddim_alphas_prev[a + 1] = ddim_alphas[a]) is moved up to ddim_alphas[b] by
         eod_renoise; step_noises / mix_noises are then indexed by the evaluation's position in the walk, jump_noises by the jump's
         ordinal (otherwise randn_like when the jump happens); callbacks and intermediates see every executed step.
-        observation: an Observation (diffusion/consistency.py) for a state of `shape`; a per-evaluation `weight` is indexed like
-        step_noises.  It is independent of the RePaint mix (mask / x0), which is applied in front of the UNet as without it."""
+        observation: an Observation or a SpectralObservation (diffusion/consistency.py) for a state of `shape`, or a list of 1 .. 4 of
+        them, applied in order; a per-evaluation `weight` is indexed like step_noises.  It is independent of the RePaint mix (mask / x0), which is applied in front of the UNet as without it."""
         if ddim_use_original_steps:
             raise NotImplementedError("ddim_use_original_steps touches attributes the reference never defines (ddim.py:188-190)")
         device = self.model.betas.device
@@ -205,7 +207,7 @@ class DDIMSampler(object):
         [B, C, H, W] as it does against [1, C, H, W] today.  The tiles of the whole stack go through the UNet in chunks of tile_batch
         (a chunk may hold tiles of several scenes); skip_known classifies per scene.  With injected draws member b equals the
         single-scene call on scene b's inputs and draws, bit for bit.
-        observation: an Observation with scene-sized values / mask (leading dimension n_scenes or 1); its blocks are anchored at the
+        observation: an Observation / SpectralObservation (or a list of 1 .. 4, applied in order) with scene-sized values / mask (leading dimension n_scenes or 1); its blocks are anchored at the
         scene's origin and the projection is part of the ONE scene-level step, so it is seamless across tile borders.  Refused together
         with skip_known: a block may straddle estimated and non-estimated pixels, and skip_known's bit equality could not hold."""
         from ..tiling import keep_known

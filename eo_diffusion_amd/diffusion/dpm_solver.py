@@ -16,6 +16,8 @@ given, one draw per jump.
 `observation=` (a diffusion/consistency.py Observation) on sample / sample_scene: the prediction of every evaluation is made consistent
 with an observation of per-channel block means inside the step kernel (eod_dpmpp_step_obs: after the clamp, before the multistep
 combination; the history the next evaluation reads is the projected prediction).  DESIGN.md section 9.5.
+A SpectralObservation (eod_dpmpp_step_spec) or a list of 1 .. 4 observations (eod_pred_x0, one projection per link, eod_dpmpp_step_p0: the
+history is the last link's result) goes the same way; DESIGN.md section 9.6.
 """
 import numpy as np
 import torch
@@ -85,8 +87,9 @@ class DPMSolverSampler(DDIMSampler):
         """`S` steps (self.num_evaluations <= S UNet evaluations: duplicate levels of the logsnr grid are removed) from x_T to an image
         batch [batch_size, *shape].  Returns (samples, {"x_inter", "pred_x0"}) like DDIMSampler.sample.  mask / x0: the RePaint mix at
         every evaluation (mix_noises[i]: its q_sample noise, indexed by the evaluation's position in the walk).  resample /
-        jump_noises: RePaint resampling over the indices of the levels, as in DDIMSampler.ddim_sampling.  observation: an Observation for a
-        state [batch_size, *shape]; a per-evaluation `weight` is indexed like mix_noises."""
+        jump_noises: RePaint resampling over the indices of the levels, as in DDIMSampler.ddim_sampling.  observation: an Observation or a
+        SpectralObservation for a state [batch_size, *shape], or a list of 1 .. 4 of them applied in order; a per-evaluation `weight` is
+        indexed like mix_noises."""
         what = "DPMSolverSampler.sample"
         visits, jump_after = self._plan(what, S, order, discretize, t_start, resample, mix_noises, jump_noises, mask, x0)
         device = self.model.betas.device

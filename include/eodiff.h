@@ -35,7 +35,7 @@ const char* eod_last_error(void);
  * buffer of eod_pack_conv_weight_split, the 4-int state of eod_adamw_step_guarded).  eod_version() returns the value the library was built
  * with; a binding compares it with the header it mirrors at load time (eo_diffusion_amd/_lib.py does) instead of finding out by an
  * out-of-bounds device write. */
-#define EOD_ABI_VERSION 109
+#define EOD_ABI_VERSION 110
 int eod_version(void);
 /* Kernel-selection options ("skip_fuse", "head", "halo_bn256", "halo_splitk", "first", "s2_halo": 1 / 0; "gn_fuse_max_cout": n, -1 = default;
  * "halo_tpw": pixel tiles per workgroup of the streaming halo instances, 1 = off = default, 0 = chosen per launch; "head_tpw": the same of
@@ -360,6 +360,56 @@ int eod_dpmpp_step_obs(const float* x, const float* e_t, const float* d_prev, fl
                        int B, int C, int H, int W, int values_b1, int mask_b1, int mask_c1, float* x_next, float* pred_x0, void* stream);
 /* the operator alone: out = A+ A x, every pixel replaced by its block's mean (s and mean as above, of x itself); out must not overlap x */
 int eod_block_mean(const float* x, const int32_t* factors, float* out, int B, int C, int H, int W, void* stream);
+/* section 9.5's projection of a GIVEN prediction p [B][C][H][W] (a link of a chain of observations): s, mean, lm as above with p in place
+ * of p0, out = p - (lm * (mean - values)).  Refusals as above; out must not overlap p, values or mask. */
+int eod_obs_project(const float* p, const float* values, const float* mask, float lambda, const int32_t* factors, int B, int C, int H, int W,
+                    int values_b1, int mask_b1, int mask_c1, float* out, void* stream);
+/* Cross-band observations (no reference line): what is observed is K linear mixes of the C channels' f x f block
+ * means, A = R (x) D_f: D_f the mean over f x f blocks anchored at the plane's origin, R [K][C] of full row rank.  A+ = G (x) replication
+ * with G = pinv(R) [C][K].  R and G are HOST arrays (row-major fp32, the values the arithmetic uses: G is computed by the caller in float64
+ * and rounded once), read during the call and handed to the kernel by value: nothing is allocated, copied or synchronised, the calls can be
+ * captured in a graph.  Per pixel i, every operation rounded once in fp32, in this order:
+ *   p0_c   as eod_ddim_step / eod_dpmpp_step form it (the same bits), for dpmpp with clip != 0 clamped as there
+ *   mean_c = the block mean of section 9.5 of channel c over blk(i): the same first pixel, the same ROW BY ROW, LEFT TO RIGHT order of the
+ *            sequential adds, / (float)(f * f)      -- f = 1: p0_c / 1.0f
+ *   d_k    = R[k][0] * mean_0;  then for c = 1 .. C-1 in order:  d_k = d_k + (R[k][c] * mean_c)           (k = 0 .. K-1)
+ *   r_k    = d_k - values_k(i)
+ *   t_c    = G[c][0] * r_0;     then for k = 1 .. K-1 in order:  t_c = t_c + (G[c][k] * r_k)
+ *   lm     = lambda * m(i)                          -- m = mask at the pixel, 1.0f with mask NULL
+ *   p0c_c  = p0_c - (lm * t_c)
+ *   the update from p0c as in eod_ddim_step_obs / eod_dpmpp_step_obs;  pred_x0 = p0c
+ * Only the K rows of R and the K columns of G take part: there is no term for k >= K.  This is a property of the block alone: it does not
+ * depend on B, on pointer alignment, on the launch geometry or on whether the tensor is a batch or a scene.  values [B or 1][K][H][W]
+ * (values_b1 != 0: one for all samples) is what the other sensor saw, replicated onto the full-resolution grid; mask NULL or
+ * [B or 1][1][H][W] (mask_b1 != 0: one for all samples), one mask for all K rows.  The formula is computed for ANY values and mask; with
+ * both constant on every block, mask in {0, 1} and lambda = 1 it is the range / null-space projection of DDNM: afterwards R times the block
+ * means of pred_x0 is values (to rounding) on the observed blocks.
+ * EOD_EINVAL with nothing launched: a null x / e_t / values / R / G / output, K outside 1 .. min(C, 8), C > 32, f outside 1..8 or not
+ * dividing H and W, a outside (0, 1], lambda outside [0, 1] (NaN included), an output overlapping ANY input or the other output.
+ * ONE launch.  Access widths as for eod_ddim_step_obs; beyond EOD_SPEC_GRID_BLOCKS blocks of 256 threads the threads stride over the plane. */
+#define EOD_SPEC_GRID_BLOCKS 4096
+int eod_ddim_step_spec(const float* x, const float* e_t, const float* noise, float a_t, float a_prev, float sigma_t, float sqrt_1m_at,
+                       float temperature, const float* values, const float* mask, float lambda, const float* R, const float* G, int K, int f,
+                       int B, int C, int H, int W, int values_b1, int mask_b1, float* x_prev, float* pred_x0, void* stream);
+int eod_dpmpp_step_spec(const float* x, const float* e_t, const float* d_prev, float a_s, float sqrt_1m_as, float c_x, float c_d, float w_cur,
+                        float w_prev, int clip, const float* values, const float* mask, float lambda, const float* R, const float* G, int K,
+                        int f, int B, int C, int H, int W, int values_b1, int mask_b1, float* x_next, float* pred_x0, void* stream);
+/* the same projection of a GIVEN prediction p [B][C][H][W] (mean_c of p itself): out = p0c.  out must not overlap p, values or mask. */
+int eod_spec_project(const float* p, const float* values, const float* mask, float lambda, const float* R, const float* G, int K, int f, int B,
+                     int C, int H, int W, int values_b1, int mask_b1, float* out, void* stream);
+/* the operator alone: out [B][K][H][W] = d_k of x [B][C][H][W] on the full-resolution grid (mean_c of x itself); out must not overlap x */
+int eod_spec_apply(const float* x, const float* R, int K, int f, float* out, int B, int C, int H, int W, void* stream);
+/* The ends of a chain of observations: a prediction is formed, projected by one link after the other (eod_spec_project, eod_obs_project),
+ * and the update uses the result.  eod_pred_x0: p0 = (x - (sqrt_1m_a * e_t)) / sqrtf(a), clip != 0: clamped to [-1, 1] -- the p0 of
+ * eod_ddim_step (clip = 0) / eod_dpmpp_step.  eod_ddim_step_p0: x_prev = ((sqrtf(a_prev) * p0c) + dir_xt) + nz as in eod_ddim_step (which
+ * reads e_t and noise, not x).  eod_dpmpp_step_p0: D = d_prev ? (w_cur * p0c) + (w_prev * d_prev) : p0c; x_next = (c_x * x) + (c_d * D).
+ * pred_x0 -> ONE projection -> step_p0 has the bits of the fused kernel (_obs / _spec) on the same inputs.  [numel] fp32 tensors.
+ * EOD_EINVAL with nothing launched: a null tensor (noise / d_prev may be NULL), numel <= 0, a outside (0, 1], the output overlapping an input. */
+int eod_pred_x0(const float* x, const float* e_t, float a, float sqrt_1m_a, int clip, float* p0, int64_t numel, void* stream);
+int eod_ddim_step_p0(const float* e_t, const float* p0c, const float* noise, float a_prev, float sigma_t, float temperature, float* x_prev,
+                     int64_t numel, void* stream);
+int eod_dpmpp_step_p0(const float* x, const float* p0c, const float* d_prev, float c_x, float c_d, float w_cur, float w_prev, float* x_next,
+                      int64_t numel, void* stream);
 /* classifier-free guidance of p_sample_ddim (ddim.py:177-181): out = e_uncond + scale * (e_cond - e_uncond) */
 int eod_cfg_combine(const float* e_uncond, const float* e_cond, float scale, float* out, int64_t numel, void* stream);
 /* table-driven DDPM step of the LDM-derived sampler: DDPM.p_sample ddpm.py:248-255 with predict_start_from_noise :221-225,

@@ -153,6 +153,9 @@ SYMBOLS = {
                                   i32, i32, i32, i32, vp, vp, vp]),
     "eod_spec_project": (i32, [vp, vp, vp, f32, C.POINTER(f32), C.POINTER(f32), i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
     "eod_spec_apply": (i32, [vp, C.POINTER(f32), i32, i32, vp, i32, i32, i32, i32, vp]),
+    "eod_psf_residual": (i32, [vp, vp, vp, f32, C.POINTER(f32), i32, i32, C.POINTER(i32), i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "eod_psf_apply": (i32, [vp, C.POINTER(f32), i32, i32, C.POINTER(i32), i32, vp, i32, i32, i32, i32, vp]),
+    "eod_psf_update": (i32, [vp, vp, f32, C.POINTER(f32), i32, i32, C.POINTER(i32), i32, i32, i32, i32, i32, vp, vp]),
     "eod_pred_x0": (i32, [vp, vp, f32, f32, i32, vp, i64, vp]),
     "eod_ddim_step_p0": (i32, [vp, vp, vp, f32, f32, f32, vp, i64, vp]),
     "eod_dpmpp_step_p0": (i32, [vp, vp, vp, f32, f32, f32, f32, vp, i64, vp]),
@@ -189,7 +192,7 @@ class EodError(RuntimeError):
     pass
 
 
-ABI_VERSION = 110  # EOD_ABI_VERSION of the include/eodiff.h this file mirrors
+ABI_VERSION = 111  # EOD_ABI_VERSION of the include/eodiff.h this file mirrors
 SPEC_GRID_BLOCKS = 4096  # EOD_SPEC_GRID_BLOCKS there
 
 

@@ -1,0 +1,152 @@
+// PSF-aware observations (no reference line): A = D_f N^-1 B0, B0 the zero-padded separable convolution with the
+// symmetric taps h[0 .. 2r] (horizontal, then vertical), N = diag(B0 1), D_f the f x f block mean of section 9.5.  One Landweber step of
+// data consistency is two launches: eod_psf_residual (q = lm * (A p - values), on the coarse grid) and eod_psf_update (out = p - A^T q
+// scaled by step).  The per-pixel contract is in include/eodiff.h; this file is built with -ffp-contract=off, every operation is rounded
+// once.  The bodies live in psf_body.h (one phase of one tile for one thread), so that a host program can run them as well.
+//
+// A workgroup of 256 threads owns a tile of tc x tc coarse pixels = ft x ft pixels, ft = tc * f <= 32 (psf_tile_coarse: tc a multiple of
+// 4, so a tile starts at a quad of both grids).  It stages the tile and its halo of r pixels in LDS with out-of-plane lanes zero, runs
+// the horizontal pass into a second buffer, then the vertical pass.  Work items (plane, tile) beyond EOD_PSF_GRID_BLOCKS are taken by
+// striding.  Taps, the channel list and its inverse travel by value in the kernel arguments; nothing is allocated, copied or
+// synchronised.  VEC: 16-byte accesses of the full-resolution tensors (W % 4 == 0, pointers aligned); VECQ: of the coarse ones
+// (W / f % 4 == 0, pointers aligned); the element-wise forms run the same arithmetic.
+#include "common.h"
+
+#define PSF_FN __device__ __host__ __forceinline__
+#include "psf_body.h"
+
+template <bool VEC, bool VECQ>
+__global__ void __launch_bounds__(PSF_THREADS) psf_residual_kernel(PsfArgs g, PsfTaps t, long long items) {
+    __shared__ PsfResLds s;
+    for (long long item = blockIdx.x; item < items; item += gridDim.x) {
+        psf_residual_phase<VEC, VECQ>(0, g, t, s, item, threadIdx.x);
+        __syncthreads();
+        psf_residual_phase<VEC, VECQ>(1, g, t, s, item, threadIdx.x);
+        __syncthreads();
+        psf_residual_phase<VEC, VECQ>(2, g, t, s, item, threadIdx.x);
+        __syncthreads();
+        psf_residual_phase<VEC, VECQ>(3, g, t, s, item, threadIdx.x);
+        __syncthreads();
+    }
+}
+
+template <bool VEC, bool VECQ>
+__global__ void __launch_bounds__(PSF_THREADS) psf_update_kernel(PsfArgs g, PsfTaps t, long long items) {
+    __shared__ PsfUpdLds s;
+    for (long long item = blockIdx.x; item < items; item += gridDim.x) {
+        psf_update_phase<VEC, VECQ>(0, g, t, s, item, threadIdx.x);
+        __syncthreads();
+        psf_update_phase<VEC, VECQ>(1, g, t, s, item, threadIdx.x);
+        __syncthreads();
+        psf_update_phase<VEC, VECQ>(2, g, t, s, item, threadIdx.x);
+        __syncthreads();
+        psf_update_phase<VEC, VECQ>(3, g, t, s, item, threadIdx.x);
+        __syncthreads();
+        psf_update_phase<VEC, VECQ>(4, g, t, s, item, threadIdx.x);
+        __syncthreads();
+    }
+}
+
+static inline bool psf_overlap(const float* a, long long na, const float* b, long long nb) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + (uintptr_t)nb * sizeof(float) && pb < pa + (uintptr_t)na * sizeof(float);
+}
+
+// what the three entry points share: the geometry, the taps and the channel list into g / t
+static int psf_common(const char* what, PsfArgs& g, PsfTaps& t, const float* taps, const int32_t* channels) {
+    EOD_REQUIRE(g.p && g.out && taps && channels && g.B > 0 && g.C > 0 && g.H > 0 && g.W > 0, "%s: bad args", what);
+    EOD_REQUIRE(g.C <= PSF_MAXC, "%s: at most %d channels (the channel list travels by value), got %d", what, PSF_MAXC, g.C);
+    EOD_REQUIRE(g.K >= 1 && g.K <= g.C, "%s: K = %d observed channels is outside 1 .. C = %d", what, g.K, g.C);
+    EOD_REQUIRE(g.r >= 0 && g.r <= PSF_MAXR, "%s: the tap radius r = %d is outside 0 .. %d", what, g.r, PSF_MAXR);
+    EOD_REQUIRE(g.f >= 1 && g.f <= 8, "%s: f = %d is outside 1..8", what, g.f);
+    EOD_REQUIRE(g.H % g.f == 0 && g.W % g.f == 0, "%s: f = %d does not divide %d x %d", what, g.f, g.H, g.W);
+    for (int c = 0; c < PSF_MAXC; ++c) g.kof[c] = -1;
+    for (int k = 0; k < g.K; ++k) {
+        EOD_REQUIRE(channels[k] >= 0 && channels[k] < g.C, "%s: channels[%d] = %d is outside 0 .. %d", what, k, channels[k], g.C - 1);
+        EOD_REQUIRE(k == 0 || channels[k] > channels[k - 1], "%s: channels must be strictly increasing", what);
+        g.ch[k] = (unsigned char)channels[k];
+        g.kof[channels[k]] = (signed char)k;
+    }
+    for (int k = g.K; k < PSF_MAXC; ++k) g.ch[k] = 0;
+    const int n = 2 * g.r + 1;
+    for (int i = 0; i < n; ++i) {
+        const float h = taps[i];
+        EOD_REQUIRE(h == h && h - h == 0.0f && h >= 0.0f && !__builtin_signbit(h), "%s: taps[%d] = %g is not a finite non-negative number", what, i, (double)h);
+        EOD_REQUIRE(memcmp(&taps[i], &taps[n - 1 - i], sizeof(float)) == 0, "%s: the taps are not symmetric (taps[%d] != taps[%d])", what, i, n - 1 - i);
+        t.h[i] = h;
+    }
+    for (int i = n; i < 2 * PSF_MAXR + 1; ++i) t.h[i] = 0.0f;
+    EOD_REQUIRE(taps[g.r] > 0.0f, "%s: the centre tap must be positive", what);
+    g.tc = psf_tile_coarse(g.f);
+    const int ft = g.tc * g.f;
+    g.tiles_x = (g.W + ft - 1) / ft;
+    g.tiles_y = (g.H + ft - 1) / ft;
+    return EOD_OK;
+}
+
+static inline int psf_grid(long long items) { return (int)(items < EOD_PSF_GRID_BLOCKS ? items : EOD_PSF_GRID_BLOCKS); }
+
+static int psf_residual_launch(const char* what, PsfArgs g, const float* taps, const int32_t* channels, void* stream) {
+    PsfTaps t;
+    const int rc = psf_common(what, g, t, taps, channels);
+    if (rc != EOD_OK) return rc;
+    const long long hw = (long long)g.H * g.W, chw = hw / (g.f * g.f);
+    const long long np = (long long)g.B * g.C * hw, nq = (long long)g.B * g.K * chw;
+    EOD_REQUIRE(!psf_overlap(g.out, nq, g.p, np), "%s: the output overlaps %s", what, g.values ? "p" : "x");
+    if (g.values) {
+        EOD_REQUIRE(g.lambda >= 0.0f && g.lambda <= 1.0f, "%s: the weight must lie in [0, 1], got %g", what, (double)g.lambda);
+        EOD_REQUIRE(!psf_overlap(g.out, nq, g.values, (long long)(g.values_b1 ? 1 : g.B) * g.K * chw), "%s: q overlaps values", what);
+        EOD_REQUIRE(!g.mask || !psf_overlap(g.out, nq, g.mask, (long long)(g.mask_b1 ? 1 : g.B) * (g.mask_c1 ? 1 : g.K) * chw), "%s: q overlaps mask", what);
+    }
+    const bool vec = g.W % 4 == 0 && eod_aligned16(g.p);
+    const bool vecq = (g.W / g.f) % 4 == 0 && eod_aligned16(g.out) && (!g.values || eod_aligned16(g.values)) && (!g.mask || eod_aligned16(g.mask));
+    const long long items = (long long)g.B * g.K * g.tiles_x * g.tiles_y;
+    const dim3 grid(psf_grid(items)), block(PSF_THREADS);
+    hipStream_t st = (hipStream_t)stream;
+    if (vec && vecq) hipLaunchKernelGGL((psf_residual_kernel<true, true>), grid, block, 0, st, g, t, items);
+    else if (vec) hipLaunchKernelGGL((psf_residual_kernel<true, false>), grid, block, 0, st, g, t, items);
+    else if (vecq) hipLaunchKernelGGL((psf_residual_kernel<false, true>), grid, block, 0, st, g, t, items);
+    else hipLaunchKernelGGL((psf_residual_kernel<false, false>), grid, block, 0, st, g, t, items);
+    EOD_CHECK_LAUNCH(what);
+    return EOD_OK;
+}
+
+extern "C" int eod_psf_residual(const float* p, const float* values, const float* mask, float lambda, const float* taps, int r, int f,
+                                const int32_t* channels, int K, int B, int C, int H, int W, int values_b1, int mask_b1, int mask_c1, float* q,
+                                void* stream) {
+    EOD_REQUIRE(values, "psf_residual: bad args");
+    PsfArgs g = {p, values, mask, nullptr, q, lambda, 0.0f, r, f, K, B, C, H, W, values_b1, mask_b1, mask_c1, 0, 0, 0, {0}, {0}};
+    return psf_residual_launch("psf_residual", g, taps, channels, stream);
+}
+
+extern "C" int eod_psf_apply(const float* x, const float* taps, int r, int f, const int32_t* channels, int K, float* out, int B, int C, int H,
+                             int W, void* stream) {
+    PsfArgs g = {x, nullptr, nullptr, nullptr, out, 0.0f, 0.0f, r, f, K, B, C, H, W, 0, 0, 0, 0, 0, 0, {0}, {0}};
+    return psf_residual_launch("psf_apply", g, taps, channels, stream);
+}
+
+extern "C" int eod_psf_update(const float* p, const float* q, float step, const float* taps, int r, int f, const int32_t* channels, int K,
+                              int B, int C, int H, int W, float* out, void* stream) {
+    const char* what = "psf_update";
+    EOD_REQUIRE(q, "%s: bad args", what);
+    PsfArgs g = {p, nullptr, nullptr, q, out, 0.0f, step, r, f, K, B, C, H, W, 0, 0, 0, 0, 0, 0, {0}, {0}};
+    PsfTaps t;
+    const int rc = psf_common(what, g, t, taps, channels);
+    if (rc != EOD_OK) return rc;
+    EOD_REQUIRE(step - step == 0.0f && step > 0.0f, "%s: step must be finite and positive, got %g", what, (double)step);
+    const long long hw = (long long)H * W, chw = hw / (f * f);
+    const long long np = (long long)B * C * hw, nq = (long long)B * K * chw;
+    EOD_REQUIRE(!psf_overlap(out, np, p, np), "%s: out overlaps p (a tile's halo is read after its neighbours have written)", what);
+    EOD_REQUIRE(!psf_overlap(out, np, q, nq), "%s: out overlaps q", what);
+    const bool vec = W % 4 == 0 && eod_aligned16(p) && eod_aligned16(out);
+    const bool vecq = (W / f) % 4 == 0 && eod_aligned16(q);
+    const long long items = (long long)B * C * g.tiles_x * g.tiles_y;
+    const dim3 grid(psf_grid(items)), block(PSF_THREADS);
+    hipStream_t st = (hipStream_t)stream;
+    if (vec && vecq) hipLaunchKernelGGL((psf_update_kernel<true, true>), grid, block, 0, st, g, t, items);
+    else if (vec) hipLaunchKernelGGL((psf_update_kernel<true, false>), grid, block, 0, st, g, t, items);
+    else if (vecq) hipLaunchKernelGGL((psf_update_kernel<false, true>), grid, block, 0, st, g, t, items);
+    else hipLaunchKernelGGL((psf_update_kernel<false, false>), grid, block, 0, st, g, t, items);
+    EOD_CHECK_LAUNCH(what);
+    return EOD_OK;
+}

@@ -12,6 +12,11 @@ f x f block means (a panchromatic band, a second sensor's broad bands), A = R (x
 eod_ddim_step_spec / eod_dpmpp_step_spec.  `observation=` also takes a list of 1 .. 4 observations of either kind, a chain: every
 evaluation forms its prediction (eod_pred_x0), projects it by one link after the other (eod_spec_project / eod_obs_project, each with its
 own weight) and finishes the step from the result (eod_ddim_step_p0 / eod_dpmpp_step_p0).  A list of one takes the fused kernel.
+
+PsfObservation is the observation through a sensor's point spread function: A = D_f N^-1 B0, a renormalised
+zero-padded separable blur followed by the f x f block mean, with values and mask on the COARSE grid.  A+ has no local form, so the link
+takes `iters` Landweber steps p <- p - weight * tau * A^T(mask * (A p - values)) per evaluation (eod_psf_residual, eod_psf_update;
+csrc/psf.hip).  It is a link like the others; alone it runs as a chain of one through the unfused ends.
 """
 import ctypes
 import math
@@ -27,6 +32,8 @@ MAX_FACTOR = 8
 MAX_CHANNELS = 32
 MAX_ROWS = 8            # rows of a response matrix (EOD_SPEC_MAXK of csrc/sampler.hip)
 MAX_LINKS = 4           # observations in one chain
+MAX_RADIUS = 12         # of a PSF's taps (PSF_MAXR of csrc/psf_body.h)
+MAX_ITERS = 8           # Landweber steps of a PsfObservation per evaluation
 MIN_RCOND = 1e-3        # sigma_min / sigma_max of a response matrix below which it is refused (the fp32 residual
                         # of the projection grows with the conditioning, 0.55 eps at cond 45 and 11.6 eps at cond 268)
 
@@ -281,8 +288,197 @@ class BoundSpectral:
         return out
 
 
+def _taps(what, psf):
+    """the 1-D taps h[0 .. 2r] as the fp32 array the kernels use: finite, non-negative, bitwise symmetric, centre tap positive"""
+    try:
+        h = np.asarray(psf.detach().cpu().numpy() if torch.is_tensor(psf) else psf)
+    except Exception:
+        raise _lib.EodError(f"{what}: `psf` is array-like, the 1-D taps h[0 .. 2r], got {type(psf).__name__}") from None
+    if h.dtype == np.bool_ or not (np.issubdtype(h.dtype, np.floating) or np.issubdtype(h.dtype, np.integer)):
+        raise _lib.EodError(f"{what}: `psf` must hold real numbers, got dtype {h.dtype}")
+    if h.ndim != 1 or h.size % 2 != 1 or h.size > 2 * MAX_RADIUS + 1:
+        raise _lib.EodError(f"{what}: `psf` is the 1-D taps h[0 .. 2r] of a separable PSF, r = 0 .. {MAX_RADIUS} (an odd number of them, "
+                            f"at most {2 * MAX_RADIUS + 1}), got shape {h.shape}")
+    with np.errstate(over="ignore"):
+        h = np.ascontiguousarray(h, dtype=np.float32)
+    if not np.isfinite(h).all() or np.signbit(h).any():
+        raise _lib.EodError(f"{what}: the taps of `psf` must be finite and non-negative (as float32)")
+    if h.view(np.uint32).tolist() != h[::-1].view(np.uint32).tolist():
+        raise _lib.EodError(f"{what}: the taps of `psf` must be symmetric bit for bit (as float32): A^T is computed with the same stencil")
+    if not h[h.size // 2] > 0.0:
+        raise _lib.EodError(f"{what}: the centre tap of `psf` must be positive")
+    return h
+
+
+def _channels(what, channels):
+    try:
+        cs = list(channels)
+    except TypeError:
+        raise _lib.EodError(f"{what}: `channels` is None (all) or a sequence of channel numbers, got {channels!r}") from None
+    if not 1 <= len(cs) <= MAX_CHANNELS:
+        raise _lib.EodError(f"{what}: `channels` lists 1 .. {MAX_CHANNELS} channels, got {len(cs)}")
+    for c in cs:
+        if isinstance(c, bool) or not isinstance(c, numbers.Integral) or not 0 <= c < MAX_CHANNELS:
+            raise _lib.EodError(f"{what}: a channel is an integer in 0 .. {MAX_CHANNELS - 1}, got {c!r}")
+    if any(b <= a for a, b in zip(cs, cs[1:])):
+        raise _lib.EodError(f"{what}: `channels` must be strictly increasing, got {cs}")
+    return tuple(int(c) for c in cs)
+
+
+def _c_ints(a):
+    return (ctypes.c_int32 * len(a))(*a)
+
+
+def psf_cmax(taps, L):
+    """max_j sum_i h[i - j + r] / n_i over a line of length L, n = B0 1 (float64 of the fp32 taps): the largest column sum of the
+    renormalised 1-D blur N^-1 B0"""
+    h = np.asarray(taps, np.float32).astype(np.float64)
+    r, idx = h.size // 2, np.arange(int(L))
+    n, col = np.zeros(int(L)), np.zeros(int(L))
+    for t in range(h.size):
+        ok = (idx + t - r >= 0) & (idx + t - r < L)
+        n[ok] += h[t]
+    for t in range(h.size):
+        ok = (idx + t - r >= 0) & (idx + t - r < L)          # row i, column i + t - r holds h[t]
+        col[idx[ok] + t - r] += h[t] / n[ok]
+    return float(col.max())
+
+
+def psf_tau(taps, factor, H, W):
+    """the Landweber step size f^2 / (cmax(H) cmax(W)) <= 1 / ||A||^2 (||A||^2 <= ||A||_1 ||A||_inf = cmax(H) cmax(W) / f^2), float64"""
+    return float(factor * factor) / (psf_cmax(taps, H) * psf_cmax(taps, W))
+
+
+def gaussian_sigma(factor, mtf_nyquist=0.3):
+    """sigma in fine pixels of the Gaussian whose MTF exp(-2 pi^2 sigma^2 nu^2) is mtf_nyquist at the coarse grid's Nyquist frequency 1 / (2 f)"""
+    what = "gaussian_psf"
+    f = _factor(what, factor)
+    if isinstance(mtf_nyquist, bool) or not isinstance(mtf_nyquist, (numbers.Real, np.floating)) or not 0.0 < float(mtf_nyquist) <= 1.0:
+        raise _lib.EodError(f"{what}: `mtf_nyquist` is a float in (0, 1], got {mtf_nyquist!r}")
+    return f * math.sqrt(-2.0 * math.log(float(mtf_nyquist))) / math.pi
+
+
+def gaussian_psf(factor, mtf_nyquist=0.3, radius=None):
+    """The taps of a Gaussian PSF for a sensor `factor` times coarser whose MTF at its Nyquist frequency is mtf_nyquist: sigma =
+    f sqrt(-2 ln mtf) / pi, taps on -r .. r with r = min(ceil(3 sigma), 12) (or `radius`), normalised in float64, rounded to fp32,
+    symmetric bit for bit.  float32 [2r + 1]."""
+    what = "gaussian_psf"
+    sigma = gaussian_sigma(factor, mtf_nyquist)
+    if radius is None:
+        r = min(int(math.ceil(3.0 * sigma)), MAX_RADIUS)
+    else:
+        if isinstance(radius, bool) or not isinstance(radius, numbers.Integral) or not 0 <= radius <= MAX_RADIUS:
+            raise _lib.EodError(f"{what}: `radius` is an integer in 0 .. {MAX_RADIUS}, got {radius!r}")
+        r = int(radius)
+    k = np.arange(-r, r + 1, dtype=np.float64)
+    g = np.exp(-(k * k) / (2.0 * sigma * sigma)) if sigma > 0.0 else (k == 0).astype(np.float64)
+    h = (g / g.sum()).astype(np.float32)
+    h[r + 1:] = h[:r][::-1]
+    return h
+
+
+class PsfObservation:
+    """K channels seen through a sensor's PSF on a grid `factor` times coarser: A = D_f N^-1 B0 per observed channel (B0 the zero-padded
+    separable convolution with the 1-D taps `psf`, horizontally then vertically; N = diag(B0 1); D_f the factor x factor block mean).
+    values [B or 1, K, H / f, W / f] fp32 on the COARSE grid: what the sensor delivered; psf: array-like [2r + 1], r = 0 .. 12, finite,
+    non-negative, symmetric bit for bit as float32, centre tap positive; factor 1 .. 8; channels None (all C, C = K) or K strictly
+    increasing channel numbers; mask None or [B or 1, K or 1, H / f, W / f] fp32; weight as for Observation; iters 1 .. 8 Landweber steps
+    per evaluation."""
+
+    def __init__(self, values, psf, factor, channels=None, mask=None, weight=1.0, iters=1):
+        what = "PsfObservation"
+        self.taps = _taps(what, psf)
+        self.factor = _factor(what, factor)
+        self.channels = None if channels is None else _channels(what, channels)
+        if isinstance(iters, bool) or not isinstance(iters, numbers.Integral) or not 1 <= iters <= MAX_ITERS:
+            raise _lib.EodError(f"{what}: `iters` is an integer in 1 .. {MAX_ITERS}, got {iters!r}")
+        self.iters = int(iters)
+        v = torch.as_tensor(values)
+        if v.dtype != torch.float32:
+            raise _lib.EodError(f"{what}: `values` must be float32, got {v.dtype}")
+        if v.dim() != 4 or 0 in v.shape or v.shape[1] > MAX_CHANNELS or (self.channels is not None and v.shape[1] != len(self.channels)):
+            want = "K <= 32" if self.channels is None else str(len(self.channels))
+            raise _lib.EodError(f"{what}: `values` must be [B or 1, {want}, H / f, W / f] on the coarse grid, got {tuple(v.shape)}")
+        K, Hc, Wc = (int(d) for d in v.shape[1:])
+        if mask is not None:
+            mask = torch.as_tensor(mask)
+            if mask.dtype != torch.float32:
+                raise _lib.EodError(f"{what}: `mask` must be float32, got {mask.dtype}")
+            if mask.dim() != 4 or mask.shape[1] not in (1, K) or tuple(mask.shape[2:]) != (Hc, Wc):
+                raise _lib.EodError(f"{what}: `mask` must be [B or 1, {K} or 1, {Hc}, {Wc}] on the coarse grid, got {tuple(mask.shape)}")
+            if 1 not in (v.shape[0], mask.shape[0]) and v.shape[0] != mask.shape[0]:
+                raise _lib.EodError(f"{what}: `values` is for {v.shape[0]} samples, `mask` for {mask.shape[0]}")
+        self.weights, self.per_evaluation = _weights(what, weight)
+        self.values, self.mask = v, mask
+
+    def bind(self, what, shape, n_evaluations, device):
+        B, C, H, W = (int(s) for s in shape)
+        K, f = int(self.values.shape[1]), self.factor
+        if C > MAX_CHANNELS:
+            raise _lib.EodError(f"{what}: a PsfObservation takes a state of at most {MAX_CHANNELS} channels, got {C}")
+        if self.channels is None:
+            if K != C:
+                raise _lib.EodError(f"{what}: the PsfObservation observes all channels (`channels` is None) and has {K}, the state has {C}")
+            channels = tuple(range(C))
+        else:
+            channels = self.channels
+            if channels[-1] >= C:
+                raise _lib.EodError(f"{what}: the PsfObservation observes channel {channels[-1]}, the state has {C}")
+        if H % f or W % f or tuple(self.values.shape[2:]) != (H // f, W // f):
+            raise _lib.EodError(f"{what}: the PsfObservation is {tuple(self.values.shape[2:])} at factor {f}, the state is {(H, W)}")
+        for name, t in (("values", self.values), ("mask", self.mask)):
+            if t is not None and t.shape[0] not in (1, B):
+                raise _lib.EodError(f"{what}: the observation's `{name}` has leading dimension {t.shape[0]}; the call needs {B} or 1")
+        if self.per_evaluation and len(self.weights) != n_evaluations:
+            raise _lib.EodError(f"{what}: the call evaluates the UNet {n_evaluations} times, the observation's `weight` has {len(self.weights)} entries")
+        return BoundPsf(self, (B, C, H, W), channels, n_evaluations, device)
+
+
+class BoundPsf:
+    def __init__(self, obs, shape, channels, n_evaluations, device):
+        B, C, H, W = shape
+        self.shape, self.factor, self.iters, self.channels = shape, obs.factor, obs.iters, channels
+        self.K, self.r = len(channels), obs.taps.size // 2
+        self.tau = psf_tau(obs.taps, obs.factor, H, W)
+        self.step = float(np.float32(self.tau / (obs.factor * obs.factor)))
+        self.c_taps, self.c_channels = _c_floats(obs.taps), _c_ints(channels)
+        self.values = f32c(obs.values.to(device))
+        self.mask = None if obs.mask is None else f32c(obs.mask.to(device))
+        self.weights = obs.weights if obs.per_evaluation else obs.weights * n_evaluations
+
+    def residual(self, i, p, q):
+        """q = weight_i * mask * (A p - values) on the coarse grid: eod_psf_residual"""
+        if tuple(p.shape) != self.shape:
+            raise _lib.EodError(f"observation bound to a state of shape {self.shape}, the step got {tuple(p.shape)}")
+        B, C, H, W = self.shape
+        m = self.mask
+        _lib.check(_lib.lib().eod_psf_residual(p.data_ptr(), self.values.data_ptr(), _lib.ptr(m), self.weights[i], self.c_taps, self.r, self.factor,
+                                               self.c_channels, self.K, B, C, H, W, int(self.values.shape[0] != B),
+                                               int(m is not None and m.shape[0] != B), int(m is not None and m.shape[1] != self.K),
+                                               q.data_ptr(), current_stream_ptr(p.device)), "eod_psf_residual")
+        return q
+
+    def update(self, p, q, out):
+        """out = p - tau A^T q: eod_psf_update"""
+        B, C, H, W = self.shape
+        _lib.check(_lib.lib().eod_psf_update(p.data_ptr(), q.data_ptr(), self.step, self.c_taps, self.r, self.factor, self.c_channels, self.K,
+                                             B, C, H, W, out.data_ptr(), current_stream_ptr(p.device)), "eod_psf_update")
+        return out
+
+    def project(self, i, p):
+        """`iters` Landweber steps from the prediction p at evaluation number i (a link of a chain): iters x (residual, update), ping-pong
+        between two buffers (eod_psf_update's out must not be its p)"""
+        B, C, H, W = self.shape
+        p = f32c(p)
+        q = torch.empty((B, self.K, H // self.factor, W // self.factor), device=p.device, dtype=torch.float32)
+        bufs = [torch.empty_like(p) for _ in range(min(self.iters, 2))]
+        for it in range(self.iters):
+            p = self.update(p, self.residual(i, p, q), bufs[it % 2])
+        return p
+
+
 class BoundChain:
-    """2 .. 4 bound observations applied in order to every evaluation's prediction, each link to the previous link's result and with its own
+    """1 .. 4 bound observations (one: a PsfObservation, which has no fused kernel) applied in order to every evaluation's prediction, each link to the previous link's result and with its own
     weight: eod_pred_x0, one projection launch per link, eod_ddim_step_p0 / eod_dpmpp_step_p0.  The bits are those the fused kernel of
     every link would give on the same prediction.  pred_x0 (for DPM-Solver++: the next evaluation's history) is the last link's result."""
 
@@ -319,22 +515,27 @@ class BoundChain:
 
 
 def bind(observation, what, shape, n_evaluations, device):
-    """None, or the observation bound to the call (every refusal before anything is launched).  An Observation or a SpectralObservation, or
-    a list / tuple of 1 .. 4 of them: one takes its fused step kernel, more become a BoundChain."""
+    """None, or the observation bound to the call (every refusal before anything is launched).  An Observation, a SpectralObservation or a
+    PsfObservation, or a list / tuple of 1 .. 4 of them: one takes its fused step kernel (a PsfObservation has none: a BoundChain of
+    one), more become a BoundChain."""
     if observation is None:
         return None
-    kinds = (Observation, SpectralObservation)
+    kinds = (Observation, SpectralObservation, PsfObservation)
+    if isinstance(observation, PsfObservation):
+        return BoundChain([observation.bind(what, shape, n_evaluations, device)])
     if isinstance(observation, kinds):
         return observation.bind(what, shape, n_evaluations, device)
     if not isinstance(observation, (list, tuple)):
-        raise _lib.EodError(f"{what}: `observation` is an Observation, a SpectralObservation or a list of them, got {type(observation).__name__}")
+        raise _lib.EodError(f"{what}: `observation` is an Observation, a SpectralObservation, a PsfObservation or a list of them, got "
+                            f"{type(observation).__name__}")
     if not 1 <= len(observation) <= MAX_LINKS:
         raise _lib.EodError(f"{what}: a chain of observations has 1 .. {MAX_LINKS} links, got {len(observation)}")
     for link in observation:
         if not isinstance(link, kinds):
-            raise _lib.EodError(f"{what}: a link of `observation` is an Observation or a SpectralObservation, got {type(link).__name__}")
+            raise _lib.EodError(f"{what}: a link of `observation` is an Observation, a SpectralObservation or a PsfObservation, got "
+                                f"{type(link).__name__}")
     links = [link.bind(what, shape, n_evaluations, device) for link in observation]
-    return links[0] if len(links) == 1 else BoundChain(links)
+    return links[0] if len(links) == 1 and not isinstance(links[0], BoundPsf) else BoundChain(links)
 
 
 def block_mean(x, factors):
@@ -370,4 +571,27 @@ def spectral_response(x, response, factor=1):
     x = f32c(x)
     out = torch.empty((B, K, H, W), device=x.device, dtype=torch.float32)
     _lib.check(_lib.lib().eod_spec_apply(x.data_ptr(), _c_floats(R), K, f, out.data_ptr(), B, C, H, W, current_stream_ptr(x.device)), "eod_spec_apply")
+    return out
+
+
+def psf_observe(x, psf, factor, channels=None):
+    """A x on the GPU (eod_psf_apply): [B, K, H / f, W / f], the channels `channels` (None: all) of x [B, C, H, W] blurred by the
+    renormalised zero-padded separable PSF and averaged over factor x factor blocks.  Makes a PsfObservation's `values` out of an image,
+    and measures how far a result is from one."""
+    what = "psf_observe"
+    h = _taps(what, psf)
+    f = _factor(what, factor)
+    if not torch.is_tensor(x) or x.dim() != 4 or not 1 <= x.shape[1] <= MAX_CHANNELS:
+        raise _lib.EodError(f"{what}: x must be a tensor [B, C <= {MAX_CHANNELS}, H, W]")
+    B, C, H, W = (int(d) for d in x.shape)
+    cs = tuple(range(C)) if channels is None else _channels(what, channels)
+    if cs[-1] >= C:
+        raise _lib.EodError(f"{what}: channel {cs[-1]} of an x with {C} channels")
+    if H % f or W % f:
+        raise _lib.EodError(f"{what}: factor = {f} does not divide {H} x {W}")
+    require_gpu(x, what)
+    x = f32c(x)
+    out = torch.empty((B, len(cs), H // f, W // f), device=x.device, dtype=torch.float32)
+    _lib.check(_lib.lib().eod_psf_apply(x.data_ptr(), _c_floats(h), h.size // 2, f, _c_ints(cs), len(cs), out.data_ptr(), B, C, H, W,
+                                        current_stream_ptr(x.device)), "eod_psf_apply")
     return out

@@ -16,6 +16,8 @@ consistent with an observation of per-channel block means, inside the step kerne
 observation=None (the default) every call takes the launches it took before.
 `observation=` also takes a SpectralObservation (K known mixes of the bands' block means: eod_ddim_step_spec) or a list of 1 .. 4
 observations applied in order to every prediction (eod_pred_x0, one projection per link, eod_ddim_step_p0); DESIGN.md section 9.6.
+A PsfObservation (the bands seen through the sensor's point spread function on a coarser grid: eod_psf_residual / eod_psf_update,
+DESIGN.md section 9.7) is a link like the others; alone it runs as a chain of one.
 """
 import numpy as np
 import torch

@@ -18,6 +18,7 @@ with an observation of per-channel block means inside the step kernel (eod_dpmpp
 combination; the history the next evaluation reads is the projected prediction).  DESIGN.md section 9.5.
 A SpectralObservation (eod_dpmpp_step_spec) or a list of 1 .. 4 observations (eod_pred_x0, one projection per link, eod_dpmpp_step_p0: the
 history is the last link's result) goes the same way; DESIGN.md section 9.6.
+A PsfObservation is a link like the others; alone it runs as a chain of one.
 """
 import numpy as np
 import torch

@@ -35,7 +35,7 @@ const char* eod_last_error(void);
  * buffer of eod_pack_conv_weight_split, the 4-int state of eod_adamw_step_guarded).  eod_version() returns the value the library was built
  * with; a binding compares it with the header it mirrors at load time (eo_diffusion_amd/_lib.py does) instead of finding out by an
  * out-of-bounds device write. */
-#define EOD_ABI_VERSION 110
+#define EOD_ABI_VERSION 111
 int eod_version(void);
 /* Kernel-selection options ("skip_fuse", "head", "halo_bn256", "halo_splitk", "first", "s2_halo": 1 / 0; "gn_fuse_max_cout": n, -1 = default;
  * "halo_tpw": pixel tiles per workgroup of the streaming halo instances, 1 = off = default, 0 = chosen per launch; "head_tpw": the same of
@@ -410,6 +410,39 @@ int eod_ddim_step_p0(const float* e_t, const float* p0c, const float* noise, flo
                      int64_t numel, void* stream);
 int eod_dpmpp_step_p0(const float* x, const float* p0c, const float* d_prev, float c_x, float c_d, float w_cur, float w_prev, float* x_next,
                       int64_t numel, void* stream);
+/* PSF-aware observations (no reference line): the K channels `channels` (strictly increasing) of p [B][C][H][W] are
+ * observed through A = D_f N^-1 B0 -- B0 the zero-padded separable convolution with the 1-D taps h[0 .. 2r] (r = 0 .. 12; fp32, finite,
+ * non-negative, bitwise symmetric, h[r] > 0), horizontally, then vertically; N = diag(B0 1); D_f the f x f block mean of section 9.5 -- on
+ * the COARSE grid [H / f][W / f].  taps and channels are HOST arrays read during the call and handed to the kernels by value: nothing is
+ * allocated, copied or synchronised, the calls can be captured in a graph.  Per pixel, every operation rounded once in fp32 (u outside the
+ * plane is +0.0f, and its product is formed and added like any other):
+ *   conv_h(u)[y][x] = (((h[0] * u[y][x-r]) + h[1] * u[y][x-r+1]) + ...) + h[2r] * u[y][x+r]       taps in ascending order
+ *   conv_v likewise along y;   blur(u) = conv_v(conv_h(u))                                        horizontal first, always
+ *   nh[x] = conv_h of a row of 1.0f;  nv[y] likewise;  n[y][x] = nv[y] * nh[x]
+ *   b       = blur(p_c) / n
+ *   mean    = section 9.5's block sum of b (first pixel, then row by row, left to right) / (float)(f * f)
+ *   q       = lm * (mean - values),   lm = lambda * m   (mask NULL: m = 1.0f)                     coarse grid
+ *   w[y][x] = (q[y / f][x / f] * step) / n[y][x]
+ *   out_c   = p_c - blur(w)                              channels not listed: out_c = p_c
+ * The order is a property of the pixel alone: it does not depend on B, on pointer alignment, on the tile or the launch geometry or on
+ * whether the tensor is a batch or a scene.  With h = {1.0f} and step = 1.0f, values / mask being what section 9.5 replicates, out has
+ * the bits of eod_obs_project.  With lambda = 0 or mask = 0 a finite p gives out = p.  A^T q = B0((replicate(q) / f^2) / n) because h is
+ * symmetric; with step = tau / f^2, tau <= 1 / ||A||^2, residual + update is one non-expansive Landweber step p - lambda tau A^T(m (A p - y)).
+ * eod_psf_residual: q [B][K][H/f][W/f] from p, values [B or 1][K][H/f][W/f] and mask NULL or [B or 1][K or 1][H/f][W/f] (the _b1 / _c1
+ * flags != 0: broadcast).  eod_psf_apply: out [B][K][H/f][W/f] = mean, the operator alone.  eod_psf_update: out [B][C][H][W] from p and q.
+ * EOD_EINVAL with nothing launched: a null pointer (mask may be NULL), C > 32, K outside 1 .. C, channels not strictly increasing or out of
+ * range, r outside 0 .. 12, f outside 1 .. 8 or not dividing H and W, taps breaking the rules above, lambda outside [0, 1] (NaN included),
+ * step not finite or <= 0, an output overlapping any input (eod_psf_update reads a tile's halo of p after the neighbours have written).
+ * One launch each; 16-byte accesses of the full-resolution tensors where W % 4 == 0 and their pointers are 16-byte aligned, of the coarse
+ * ones where W / f % 4 == 0 and theirs are, element by element otherwise: same arithmetic.  Beyond EOD_PSF_GRID_BLOCKS workgroups the
+ * workgroups stride over the (plane, tile) pairs.  Nothing is read or written outside a plane. */
+#define EOD_PSF_GRID_BLOCKS 4096
+int eod_psf_residual(const float* p, const float* values, const float* mask, float lambda, const float* taps, int r, int f,
+                     const int32_t* channels, int K, int B, int C, int H, int W, int values_b1, int mask_b1, int mask_c1, float* q, void* stream);
+int eod_psf_apply(const float* x, const float* taps, int r, int f, const int32_t* channels, int K, float* out, int B, int C, int H, int W,
+                  void* stream);
+int eod_psf_update(const float* p, const float* q, float step, const float* taps, int r, int f, const int32_t* channels, int K, int B, int C,
+                   int H, int W, float* out, void* stream);
 /* classifier-free guidance of p_sample_ddim (ddim.py:177-181): out = e_uncond + scale * (e_cond - e_uncond) */
 int eod_cfg_combine(const float* e_uncond, const float* e_cond, float scale, float* out, int64_t numel, void* stream);
 /* table-driven DDPM step of the LDM-derived sampler: DDPM.p_sample ddpm.py:248-255 with predict_start_from_noise :221-225,

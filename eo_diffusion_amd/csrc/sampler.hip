@@ -1113,6 +1113,57 @@ extern "C" int eod_dpmpp_step_p0(const float* x, const float* p0c, const float* 
     return chain_end_launch<END_DPMPP>("dpmpp_step_p0", g, numel, stream);
 }
 
+// ---------------------------------------------------------------------------------------------
+// The clipped DDPM step cut where its data prediction is complete: ddpm_step_kernel<true>'s operations up to x0
+// (eod_ddpm_pred_x0) and from x0 on (eod_ddpm_step_p0), so that the links of an observation can project the prediction in between.  The
+// bodies are ddpm_p0_body.h (a host program compiles them, too).  grid (blocks, N) as ddpm_step_kernel; quads of a sample, 16-byte
+// accesses where chw % 4 == 0 and every pointer is aligned, element by element otherwise.
+// ---------------------------------------------------------------------------------------------
+#define DDPM_P0_FN __device__ __host__ __forceinline__
+#include "ddpm_p0_body.h"
+
+template <bool STEP, bool VEC>
+__global__ void __launch_bounds__(256) ddpm_p0_kernel(DdpmP0Args g) {
+    const long long first = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
+    if (STEP) ddpm_step_p0_thread<VEC>(g, blockIdx.y, first, stride);
+    else ddpm_pred_x0_thread<VEC>(g, blockIdx.y, first, stride);
+}
+
+template <bool STEP>
+static int ddpm_p0_launch(const char* what, const DdpmP0Args& g, void* stream) {
+    EOD_REQUIRE(g.x && g.t && g.acp && g.out && g.N > 0 && g.chw > 0 && g.T > 0, "%s: bad args", what);
+    const long long n = (long long)g.N * g.chw;
+    const float* const tensors[4] = {g.x, g.e, g.p0c, g.z};
+    const float* const tables[3] = {g.betas, g.alphas, g.acp};
+    bool vec = g.chw % 4 == 0 && eod_aligned16(g.out);
+    for (const float* p : tensors) {
+        if (!p) continue;
+        EOD_REQUIRE(!eod_overlap2(g.out, n, p, n), "%s: the output overlaps an input", what);
+        vec = vec && eod_aligned16(p);
+    }
+    for (const float* p : tables) EOD_REQUIRE(!p || !eod_overlap2(g.out, n, p, g.T), "%s: the output overlaps a schedule table", what);
+    EOD_REQUIRE(!eod_overlap2(g.out, n, reinterpret_cast<const float*>(g.t), 2LL * g.N), "%s: the output overlaps t", what);
+    const dim3 grid(blocks_for((g.chw + 3) / 4, 2048), g.N), block(256);
+    if (vec) hipLaunchKernelGGL((ddpm_p0_kernel<STEP, true>), grid, block, 0, (hipStream_t)stream, g);
+    else hipLaunchKernelGGL((ddpm_p0_kernel<STEP, false>), grid, block, 0, (hipStream_t)stream, g);
+    EOD_CHECK_LAUNCH(what);
+    return EOD_OK;
+}
+
+extern "C" int eod_ddpm_pred_x0(const float* x_t, const float* pred, const int64_t* t, const float* acp, float* p0, int N, int64_t chw, int T,
+                                int clip, void* stream) {
+    EOD_REQUIRE(pred, "ddpm_pred_x0: bad args");
+    DdpmP0Args g = {x_t, pred, nullptr, nullptr, (const long long*)t, nullptr, nullptr, acp, p0, N, (long long)chw, T, clip};
+    return ddpm_p0_launch<false>("ddpm_pred_x0", g, stream);
+}
+
+extern "C" int eod_ddpm_step_p0(const float* x_t, const float* p0c, const float* noise, const int64_t* t, const float* betas,
+                                const float* alphas, const float* acp, float* out, int N, int64_t chw, int T, void* stream) {
+    EOD_REQUIRE(p0c && noise && betas && alphas, "ddpm_step_p0: bad args");
+    DdpmP0Args g = {x_t, nullptr, p0c, noise, (const long long*)t, betas, alphas, acp, out, N, (long long)chw, T, 0};
+    return ddpm_p0_launch<true>("ddpm_step_p0", g, stream);
+}
+
 extern "C" int eod_cfg_combine(const float* e_uncond, const float* e_cond, float scale, float* out, int64_t numel, void* stream) {
     EOD_REQUIRE(e_uncond && e_cond && out && numel > 0, "cfg_combine: bad args");
     hipLaunchKernelGGL(cfg_combine_kernel, dim3(blocks_for(numel, 4096)), dim3(256), 0, (hipStream_t)stream, e_uncond, e_cond, scale, out, (long long)numel);

@@ -17,7 +17,13 @@ PsfObservation is the observation through a sensor's poi
 zero-padded separable blur followed by the f x f block mean, with values and mask on the COARSE grid.  A+ has no local form, so the link
 takes `iters` Landweber steps p <- p - weight * tau * A^T(mask * (A p - values)) per evaluation (eod_psf_residual, eod_psf_update;
 csrc/psf.hip).  It is a link like the others; alone it runs as a chain of one through the unfused ends.
+
+The ancestral samplers (EODiffusion.sampling / sampling_scene) take the same observations through ddpm_step below:
+eod_ddpm_pred_x0, every link's project(k, p) in order, eod_ddpm_step_p0 -- the clipped DDPM step cut where its prediction is complete.
+There is no fused kernel on that route; a single link is a chain of one.  shard(n_total, lo, hi) of the three classes cuts an observation
+of a batch to the samples [lo, hi) (dist.sharded_sampling / sharded_sampling_scene).
 """
+import copy
 import ctypes
 import math
 import numbers
@@ -109,6 +115,26 @@ def _c_floats(a):
     return (ctypes.c_float * a.size)(*a.ravel().tolist())
 
 
+def _shard(obs, n_total, lo, hi):
+    """a copy of `obs` with every tensor whose leading dimension is n_total cut to [lo:hi]; leading dimension 1 is kept.  Host only."""
+    what = f"{type(obs).__name__}.shard"
+    for v in (n_total, lo, hi):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+            raise _lib.EodError(f"{what}: n_total, lo and hi are integers, got {(n_total, lo, hi)!r}")
+    if not 0 <= lo <= hi <= n_total or n_total < 1:
+        raise _lib.EodError(f"{what}: needs 0 <= lo <= hi <= n_total and n_total >= 1, got n_total = {n_total}, [{lo}, {hi})")
+    out = copy.copy(obs)
+    for name in ("values", "mask"):
+        t = getattr(obs, name)
+        if t is None:
+            continue
+        if t.shape[0] not in (1, n_total):
+            raise _lib.EodError(f"{what}: `{name}` has leading dimension {t.shape[0]}, not {n_total} or 1")
+        if t.shape[0] == n_total:                      # (n_total == 1: [0:1] or the empty shard, like every other size)
+            setattr(out, name, t[lo:hi])
+    return out
+
+
 class Observation:
     """values [B or 1, C, H, W] fp32: the observation on the full-resolution grid (a coarse one replicated over its blocks, i.e. A+ y);
     factors: C integers in 1 .. 8, the block edge per channel; mask None or [B or 1, C or 1, H, W] fp32, 1 = observed, 0 = free (soft values
@@ -150,7 +176,13 @@ class Observation:
                 raise _lib.EodError(f"{what}: the observation's `{name}` has leading dimension {t.shape[0]}; the call needs {B} or 1")
         if self.per_evaluation and len(self.weights) != n_evaluations:
             raise _lib.EodError(f"{what}: the call evaluates the UNet {n_evaluations} times, the observation's `weight` has {len(self.weights)} entries")
+        if device is None:                             # (check(): the refusals alone, nothing copied)
+            return None
         return BoundObservation(self, (B, C, H, W), n_evaluations, device)
+
+    def shard(self, n_total, lo, hi):
+        """the observation of samples [lo, hi) of a batch of n_total: tensors with leading dimension n_total cut, leading dimension 1 kept"""
+        return _shard(self, n_total, lo, hi)
 
 
 class BoundObservation:
@@ -243,7 +275,13 @@ class SpectralObservation:
                 raise _lib.EodError(f"{what}: the observation's `{name}` has leading dimension {t.shape[0]}; the call needs {B} or 1")
         if self.per_evaluation and len(self.weights) != n_evaluations:
             raise _lib.EodError(f"{what}: the call evaluates the UNet {n_evaluations} times, the observation's `weight` has {len(self.weights)} entries")
+        if device is None:                             # (check(): the refusals alone, nothing copied)
+            return None
         return BoundSpectral(self, (B, C, H, W), n_evaluations, device)
+
+    def shard(self, n_total, lo, hi):
+        """the observation of samples [lo, hi) of a batch of n_total: tensors with leading dimension n_total cut, leading dimension 1 kept"""
+        return _shard(self, n_total, lo, hi)
 
 
 class BoundSpectral:
@@ -431,7 +469,13 @@ class PsfObservation:
                 raise _lib.EodError(f"{what}: the observation's `{name}` has leading dimension {t.shape[0]}; the call needs {B} or 1")
         if self.per_evaluation and len(self.weights) != n_evaluations:
             raise _lib.EodError(f"{what}: the call evaluates the UNet {n_evaluations} times, the observation's `weight` has {len(self.weights)} entries")
+        if device is None:                             # (check(): the refusals alone, nothing copied)
+            return None
         return BoundPsf(self, (B, C, H, W), channels, n_evaluations, device)
+
+    def shard(self, n_total, lo, hi):
+        """the observation of samples [lo, hi) of a batch of n_total: tensors with leading dimension n_total cut, leading dimension 1 kept"""
+        return _shard(self, n_total, lo, hi)
 
 
 class BoundPsf:
@@ -522,7 +566,8 @@ def bind(observation, what, shape, n_evaluations, device):
         return None
     kinds = (Observation, SpectralObservation, PsfObservation)
     if isinstance(observation, PsfObservation):
-        return BoundChain([observation.bind(what, shape, n_evaluations, device)])
+        link = observation.bind(what, shape, n_evaluations, device)
+        return None if device is None else BoundChain([link])
     if isinstance(observation, kinds):
         return observation.bind(what, shape, n_evaluations, device)
     if not isinstance(observation, (list, tuple)):
@@ -535,7 +580,39 @@ def bind(observation, what, shape, n_evaluations, device):
             raise _lib.EodError(f"{what}: a link of `observation` is an Observation, a SpectralObservation or a PsfObservation, got "
                                 f"{type(link).__name__}")
     links = [link.bind(what, shape, n_evaluations, device) for link in observation]
+    if device is None:
+        return None
     return links[0] if len(links) == 1 and not isinstance(links[0], BoundPsf) else BoundChain(links)
+
+
+def check(observation, what, shape, n_evaluations):
+    """every refusal of bind() with nothing copied or launched (EODiffusion.check_scene_args)"""
+    bind(observation, what, shape, n_evaluations, None)
+
+
+def shard(observation, n_total, lo, hi):
+    """None, an observation's shard(n_total, lo, hi), or every link's when it is a list / tuple (anything else: left for bind() to refuse)"""
+    if isinstance(observation, (list, tuple)):
+        return [link.shard(n_total, lo, hi) if hasattr(link, "shard") else link for link in observation]
+    return observation.shard(n_total, lo, hi) if hasattr(observation, "shard") else observation
+
+
+def ddpm_step(bound, k, x_t, pred, noise, t, betas, alphas, acp, clip):
+    """One ancestral (DDPM) update with an observation: eod_ddpm_pred_x0 -> each link's project(k, p) in order -> eod_ddpm_step_p0.
+    bound: a BoundObservation, BoundSpectral, BoundPsf or BoundChain (a single link is a chain of one); k: the evaluation's number in the
+    walk (what `weight` sequences are indexed by; not the timestep); t int64 [N] and the schedule tables [T] on the device.  clip False:
+    the same posterior form without the clamp (algebraically the reference's epsilon form, not its bits)."""
+    x, e, z = f32c(x_t), f32c(pred), f32c(noise)
+    n, T, stream = x.shape[0], acp.numel(), current_stream_ptr(x.device)
+    p = torch.empty_like(x)
+    _lib.check(_lib.lib().eod_ddpm_pred_x0(x.data_ptr(), e.data_ptr(), t.data_ptr(), acp.data_ptr(), p.data_ptr(), n, x.numel() // n, T,
+                                           int(bool(clip)), stream), "eod_ddpm_pred_x0")
+    for link in (bound.links if isinstance(bound, BoundChain) else (bound,)):
+        p = link.project(k, p)
+    out = torch.empty_like(x)
+    _lib.check(_lib.lib().eod_ddpm_step_p0(x.data_ptr(), p.data_ptr(), z.data_ptr(), t.data_ptr(), betas.data_ptr(), alphas.data_ptr(),
+                                           acp.data_ptr(), out.data_ptr(), n, x.numel() // n, T, stream), "eod_ddpm_step_p0")
+    return out
 
 
 def block_mean(x, factors):

@@ -13,7 +13,9 @@ Differences from the reference that are deliberate (and documented in DESIGN.md)
     counter-based Philox noise source keyed by the GLOBAL sample index (multi-GPU sharding);
   * `sampling_scene`: the same chain on a scene larger than the UNet's image size, tiled (eo_diffusion_amd/tiling.py);
   * `resample=(jump_length, jump_n_sample)` on both: RePaint resampling, the chain walks diffusion/util.py's make_resample_schedule
-    and moves up it with eod_renoise.
+    and moves up it with eod_renoise (DESIGN.md section 9);
+  * `observation=` on both: every evaluation's data prediction is projected onto what a sensor delivered before the posterior step uses
+    it (diffusion/consistency.py ddpm_step: eod_ddpm_pred_x0 -> the links -> eod_ddpm_step_p0).
 """
 import math
 import os
@@ -24,7 +26,7 @@ import torch.nn as nn
 from .. import _lib
 from ..backbones.unet_openai import *  # noqa: F401,F403  (the reference re-exports these, model.py:5)
 from ..engine import current_stream_ptr, f32c, require_gpu
-from . import chain
+from . import chain, consistency
 from .util import resample_plan
 
 
@@ -173,14 +175,17 @@ class EODiffusion(nn.Module):
         return out
 
     # ------------------------------------------------------------------ the chain sampling() and sampling_scene() share
-    def _ddpm_step(self, x_t, i, noise, estimate, clip, gt=None, mask=None, on_mixed=None):
-        """one evaluation at timestep i: [RePaint mix with `noise`] -> estimate(x_t, t, i) -> eod_ddpm_step with the same `noise`"""
+    def _ddpm_step(self, x_t, i, noise, estimate, clip, gt=None, mask=None, on_mixed=None, bound=None, k=None):
+        """one evaluation at timestep i: [RePaint mix with `noise`] -> estimate(x_t, t, i) -> eod_ddpm_step with the same `noise`; with a
+        bound observation the update is consistency.ddpm_step at evaluation number k of the walk (prediction -> links -> posterior step)"""
         t = torch.full((x_t.shape[0],), i, dtype=torch.int64, device=x_t.device)
         if gt is not None:
             x_t = self._repaint_mix(x_t, gt, mask, t, noise)
         if on_mixed is not None:
             on_mixed(x_t, i)
-        return self._ddpm_update(x_t, estimate(x_t, t, i), noise, t, clip=clip)
+        if bound is None:
+            return self._ddpm_update(x_t, estimate(x_t, t, i), noise, t, clip=clip)
+        return consistency.ddpm_step(bound, k, x_t, estimate(x_t, t, i), noise, t, self.betas, self.alphas, self.alphas_cumprod, clip)
 
     def _x_T(self, shape, dev, rng, seed, sample0):
         """the start of a chain that was not given one: Philox, or the reference's draw on the CPU generator (model.py:48)"""
@@ -189,10 +194,10 @@ class EODiffusion(nn.Module):
         return torch.randn(shape).to(dev)
 
     def _ddpm_chain(self, x_T, visits, jump_after, estimate, clip, gt, mask, *, noises, jump_noises, as_draw, rng, seed, sample0, desc,
-                    on_mixed=None):
+                    on_mixed=None, bound=None):
         """x_T down resample_plan's walk.  Draws: injected (`noises` / `jump_noises`, brought into shape by as_draw(name, tensor)),
         rng="philox" (chain.py's keys, samples sample0 ...) or the device generator in loop order: one randn_like per evaluation for
-        BOTH the mix and the update, one per jump."""
+        BOTH the mix and the update, one per jump.  bound: consistency.bind's result for this state and len(visits) evaluations, or None."""
         shape, dev = tuple(x_T.shape), x_T.device
         acp = self.alphas_cumprod.tolist() if jump_after else None  # ONE host copy of the buffer for the whole call
 
@@ -203,7 +208,7 @@ class EODiffusion(nn.Module):
                 noise = self._philox(shape, dev, seed, sample0, i, chain.step_stream(visit))
             else:
                 noise = torch.randn_like(x_t)
-            return self._ddpm_step(x_t, i, noise, estimate, clip, gt, mask, on_mixed)
+            return self._ddpm_step(x_t, i, noise, estimate, clip, gt, mask, on_mixed, bound, k)
 
         def jump(x_t, j, a, b, visits_of_b):
             if jump_noises is not None:
@@ -217,7 +222,8 @@ class EODiffusion(nn.Module):
     # ------------------------------------------------------------------ sampling loop (model.py:46-75)
     @torch.no_grad()
     def sampling(self, n_samples, clipped_reverse_diffusion=True, device="cpu", cond=None, y=None, idx=0, save=False,
-                 *, x_T=None, noises=None, rng="torch", seed=0, sample_offset=0, progress=True, resample=None, jump_noises=None):
+                 *, x_T=None, noises=None, rng="torch", seed=0, sample_offset=0, progress=True, resample=None, jump_noises=None,
+                 observation=None):
         """Reverse chain t = T-1 ... 0.  RNG order of the reference is kept: x_T is drawn on the CPU
         generator (model.py:48), one `randn_like` per step on the device generator (:55) used for BOTH the
         RePaint q_sample of gt (:59) and the reverse step (:69).
@@ -228,13 +234,20 @@ class EODiffusion(nn.Module):
         the landing timestep replaces the known region as on every visit.  `noises` is then indexed by the evaluation's position in
         the walk and `jump_noises` by the jump's ordinal; rng="philox": visit v = 0, 1, ... of timestep i draws with (step i, stream
         1 + 2 v), the jump landing on b in front of visit v >= 1 of b with (step b, stream 2 v); rng="torch": randn_like in loop
-        order.  None: the single descent, today's bits."""
+        order.  None: the single descent, today's bits.
+        observation: an Observation, SpectralObservation or PsfObservation of diffusion/consistency.py, or a list of 1 .. 4 of them
+        (tensors with leading dimension n_samples or 1; a `weight` sequence has one entry per evaluation of the walk).  Every
+        evaluation's prediction of x_0 is projected by the links in order and the posterior step uses the result (DESIGN.md section
+        9.8); at t = 0 that step returns the prediction, so with weight 1 the returned sample meets a block-mean observation to
+        rounding.  The mix stays in front of the UNet.  With clipped_reverse_diffusion=False the same posterior form runs without the
+        clamp: the reference's epsilon form algebraically, not bit for bit.  None: today's launches and bits."""
         dev = torch.device(device)
         if dev.type != "cuda":
             raise _lib.EodError("EODiffusion.sampling: device must be a HIP GPU ('cuda[:i]'); there is no CPU path")
         self._tables_on(dev)
         visits, jump_after = resample_plan("EODiffusion.sampling", resample, self.timesteps, (("noises", noises),), jump_noises)
         shape = (n_samples, self.in_channels, self.image_size, self.image_size)
+        bound = consistency.bind(observation, "EODiffusion.sampling", shape, len(visits), dev)
         x_t = f32c(x_T.to(dev)) if x_T is not None else self._x_T(shape, dev, rng, seed, sample_offset)
         gt = mask = None
         if cond is not None and self.cond_type == "sum":
@@ -248,7 +261,7 @@ class EODiffusion(nn.Module):
 
         return self._ddpm_chain(x_t, visits, jump_after, lambda x, t, i: self.model(x, t, cond=cond, y=y), clipped_reverse_diffusion, gt, mask,
                                 noises=noises, jump_noises=jump_noises, as_draw=lambda name, z: f32c(z.to(dev)), rng=rng, seed=seed,
-                                sample0=sample_offset, desc="Sampling" if progress else None, on_mixed=save_grid if save else None)
+                                sample0=sample_offset, desc="Sampling" if progress else None, on_mixed=save_grid if save else None, bound=bound)
 
     # ------------------------------------------------------------------ whole-scene sampling (no counterpart in the reference)
     def _scene_args(self, what, scene_size, overlap, device):
@@ -320,7 +333,7 @@ class EODiffusion(nn.Module):
     @torch.no_grad()
     def sampling_scene(self, scene_size, clipped_reverse_diffusion=True, device="cpu", cond=None, y=None, *, overlap=0, tile_batch=16,
                        x_T=None, noises=None, rng="philox", seed=0, progress=True, resample=None, jump_noises=None, skip_known=False,
-                       n_scenes=1, sample_offset=0):
+                       n_scenes=1, sample_offset=0, observation=None):
         """Reverse chain over ONE scene [1, C, H, W], H, W >= image_size, with the UNet applied to overlapping image_size tiles
         (eo_diffusion_amd/tiling.py).  Per step: RePaint mix on the scene (cond_type == "sum"; cond [1, C+1, H, W] split as in
         sampling()) -> gather the tiles -> UNet on chunks of tile_batch tiles (same t, y broadcast, concatenated cond cut into the
@@ -348,19 +361,25 @@ class EODiffusion(nn.Module):
         the stack and however the stack is split over calls (dist.sharded_sampling_scene).  skip_known classifies per scene (a mask
         with leading dimension 1 once): scene b comes back as keep_known of its own estimated pixels, a scene with no active tile as
         its known image; no active tile in the whole stack: the known images, no UNet call.  Returns [B, C, H, W].
-        n_scenes=1 (default): everything above, unchanged; sample_offset then picks which Philox sample the one scene is."""
+        n_scenes=1 (default): everything above, unchanged; sample_offset then picks which Philox sample the one scene is.
+        observation: as in sampling(), on the SCENE: tensors are scene-sized (a PsfObservation's on its coarse grid) with leading
+        dimension n_scenes or 1, blocks and PSFs are anchored at the scene origin and the links are part of the one scene-level step, so
+        a block or a PSF footprint that a tile edge cuts is handled as anywhere else.  Refused together with skip_known=True (the
+        skipped tiles have no estimate to project)."""
         from ..tiling import gather_padded, keep_known, tile_slots, tiles_to_evaluate
         what = "EODiffusion.sampling_scene"
         plan, dev = self._scene_args(what, scene_size, overlap, device)
         if rng not in ("philox", "torch"):
             raise _lib.EodError(f"{what}: rng is 'philox' or 'torch', got {rng!r}")
+        self._no_skip_with_observation(what, skip_known, observation)
         if self._scene_count(what, n_scenes) > 1:
             return self._sampling_stack(what, plan, dev, n_scenes, clipped_reverse_diffusion, cond, y, tile_batch, x_T, noises, rng, seed,
-                                        sample_offset, progress, resample, jump_noises, skip_known)
+                                        sample_offset, progress, resample, jump_noises, skip_known, observation=observation)
         self._tables_on(dev)
         visits, jump_after = resample_plan(what, resample, self.timesteps, (("noises", noises),), jump_noises)
         shape = (1, self.in_channels, plan.H, plan.W)
         tile_slots(plan, tile_batch)  # (refuses a bad tile_batch)
+        bound = consistency.bind(observation, what, shape, len(visits), dev)
         gt = mask = cond_tiles = None
         if cond is not None and self.cond_type == "sum":
             cond = self._scene_tensor(what, "cond", cond, None, plan, dev)
@@ -379,22 +398,31 @@ class EODiffusion(nn.Module):
         x_t = as_scene("x_T", x_T) if x_T is not None else self._x_T(shape, dev, rng, seed, sample_offset)
         estimate = self._scene_estimate(tiles, tile_batch, cond_tiles, self._scene_labels(y, tile_slots(tiles, tile_batch)[0], dev))
         x_t = self._ddpm_chain(x_t, visits, jump_after, estimate, clipped_reverse_diffusion, gt, mask, noises=noises, jump_noises=jump_noises,
-                               as_draw=as_scene, rng=rng, seed=seed, sample0=sample_offset, desc="Sampling scene" if progress else None)
+                               as_draw=as_scene, rng=rng, seed=seed, sample0=sample_offset, desc="Sampling scene" if progress else None, bound=bound)
         return x_t if tiles is plan else keep_known(x_t, gt, tiles)
 
+    @staticmethod
+    def _no_skip_with_observation(what, skip_known, observation):
+        if skip_known and observation is not None:
+            raise _lib.EodError(f"{what}: skip_known=True cannot be combined with `observation`: a skipped tile has no estimate whose "
+                                "prediction could be projected")
+
     def check_scene_args(self, scene_size, device, *, n_scenes=1, cond=None, y=None, overlap=0, tile_batch=16, x_T=None, rng="philox",
-                         resample=None, noises=None, jump_noises=None, skip_known=False):
+                         resample=None, noises=None, jump_noises=None, skip_known=False, observation=None):
         """Everything sampling_scene refuses from its arguments alone (scene size, overlap, tile_batch, rng, n_scenes, the shapes of
-        cond / x_T, the label count, the resampling walk, skip_known without a known region), with nothing copied or launched.
+        cond / x_T, the label count, the resampling walk, skip_known without a known region or with an observation, an observation that
+        does not fit the scene, the stack or the walk), with nothing copied or launched.
         dist.sharded_sampling_scene runs it on the GLOBAL arguments on every rank, so that all ranks refuse together."""
         from ..tiling import TilePlan, tile_slots
         what = "EODiffusion.sampling_scene"
         plan, dev = self._scene_args(what, scene_size, overlap, device)
         if rng not in ("philox", "torch"):
             raise _lib.EodError(f"{what}: rng is 'philox' or 'torch', got {rng!r}")
+        self._no_skip_with_observation(what, skip_known, observation)
         B = self._scene_count(what, n_scenes)
-        resample_plan(what, resample, self.timesteps, (("noises", noises),), jump_noises)
+        visits, _ = resample_plan(what, resample, self.timesteps, (("noises", noises),), jump_noises)
         tile_slots(plan, tile_batch)
+        consistency.check(observation, what, (B, self.in_channels, plan.H, plan.W), len(visits))
         for name, z, channels in (("x_T", x_T, self.in_channels), ("cond", cond, None)):
             if z is not None:
                 self._scene_shape(what, name, z, channels, plan, B)
@@ -408,7 +436,7 @@ class EODiffusion(nn.Module):
             raise _lib.EodError(f"{what}: a stack of {B} scenes takes one class label, or one per scene; got {torch.as_tensor(y).numel()}")
 
     def _sampling_stack(self, what, plan, dev, B, clip, cond, y, tile_batch, x_T, noises, rng, seed, sample0, progress, resample, jump_noises,
-                        skip_known):
+                        skip_known, *, observation=None):
         """sampling_scene for n_scenes = B > 1: the same chain on the state [B, C, H, W] and a tiling.TileStack"""
         from ..tiling import TileStack, gather_padded, keep_known, tile_slots, tiles_to_evaluate
         self._tables_on(dev)
@@ -416,10 +444,12 @@ class EODiffusion(nn.Module):
         stack = TileStack(plan, B)
         tile_slots(stack, tile_batch)  # (refuses a bad tile_batch)
         y = self._stack_labels_arg(what, y, B)
+        self._no_skip_with_observation(what, skip_known, observation)
         as_stack = lambda name, z, channels=self.in_channels, expand=True: self._scene_tensor(what, name, z, channels, plan, dev, B, expand)
         for name, z, channels in (("x_T", x_T, self.in_channels), ("cond", cond, None)):  # (every shape, before anything is launched)
             if z is not None:
                 self._scene_shape(what, name, z, channels, plan, B)
+        bound = consistency.bind(observation, what, (B, self.in_channels, plan.H, plan.W), len(visits), dev)
         gt = mask = cond_tiles = None
         if cond is not None:
             cond = as_stack("cond", cond, None, False)  # [1 or B, ...]: a broadcast known scene is classified and cut once
@@ -440,7 +470,7 @@ class EODiffusion(nn.Module):
         x_t = as_stack("x_T", x_T) if x_T is not None else self._x_T((B, self.in_channels, plan.H, plan.W), dev, rng, seed, sample0)
         estimate = self._scene_estimate(tiles, tile_batch, cond_tiles, None, self._stack_labels(y, tiles, tile_batch, dev))
         x_t = self._ddpm_chain(x_t, visits, jump_after, estimate, clip, gt, mask, noises=noises, jump_noises=jump_noises,
-                               as_draw=as_stack, rng=rng, seed=seed, sample0=sample0, desc="Sampling scenes" if progress else None)
+                               as_draw=as_stack, rng=rng, seed=seed, sample0=sample0, desc="Sampling scenes" if progress else None, bound=bound)
         return x_t if tiles is stack else keep_known(x_t, gt, tiles)
 
     def _scene_estimate(self, plan, tile_batch, cond_tiles, y_chunk, y_slots=None):

@@ -3,11 +3,14 @@
 
     python examples/sharpen_bands.py                                   # 384 x 576, bands observed at 1x, 2x and 4x coarser grids
     python examples/sharpen_bands.py --factors 1 2 6 --height 384 --width 576 --steps 25
+    python examples/sharpen_bands.py --ancestral --timesteps 250       # the reference's own sampler: model.sampling_scene(..., observation=...)
 
 Channel c of a synthetic scene is "observed" as its mean over every f_c x f_c block (f_c = 1: the band itself, at full resolution) --
 what a 20 m or 60 m Sentinel-2 band is next to a 10 m one.  `DPMSolverSampler.sample_scene(..., observation=Observation(values,
 factors))` makes the data prediction of every evaluation consistent with that observation; the script prints
-how far the block means of the result are from the observation.  The network is untrained unless --ckpt is given: the script shows the
+how far the block means of the result are from the observation.  With --ancestral the call is the ancestral chain over all `--timesteps`
+levels, `EODiffusion.sampling_scene(..., observation=...)`: there the RETURNED scene itself, not only the last
+prediction, has the observation's block means for weight 1.  The network is untrained unless --ckpt is given: the script shows the
 mechanics and the constraint, not image quality.
 """
 import argparse
@@ -47,6 +50,7 @@ def main():
     ap.add_argument("--overlap", type=int, default=16)
     ap.add_argument("--timesteps", type=int, default=1000)
     ap.add_argument("--steps", type=int, default=25)
+    ap.add_argument("--ancestral", action="store_true", help="the ancestral sampler over all --timesteps levels instead of DPM-Solver++ over --steps")
     ap.add_argument("--weight", type=float, default=1.0, help="1: the block means are imposed; below 1: pulled towards (a noisy observation)")
     ap.add_argument("--precision", default="fp32x3", choices=["fp32", "fp32x3", "fp16"])
     ap.add_argument("--seed", type=int, default=0)
@@ -68,15 +72,21 @@ def main():
     model = model.to(device).eval()
     truth = synthetic_scene(args.height, args.width, args.seed).to(device) * 2.0 - 1.0
     values = block_mean(truth, args.factors)                         # A+ A x: what the coarse bands show, on the full-resolution grid
+    observation = Observation(values, args.factors, weight=args.weight)
     sampler = DPMSolverSampler(model)
     t0 = time.perf_counter()
-    scene, _ = sampler.sample_scene(args.steps, (args.height, args.width), overlap=args.overlap, clip_denoised=True, progress=False,
-                                    observation=Observation(values, args.factors, weight=args.weight))
+    if args.ancestral:
+        scene = model.sampling_scene((args.height, args.width), True, device, overlap=args.overlap, seed=args.seed, progress=False,
+                                     observation=observation)
+    else:
+        scene, _ = sampler.sample_scene(args.steps, (args.height, args.width), overlap=args.overlap, clip_denoised=True, progress=False,
+                                        observation=observation)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    evaluations = args.timesteps if args.ancestral else sampler.num_evaluations
     np.save(args.out, ((scene + 1.0) / 2.0)[0].cpu().numpy())
     res = (block_mean(scene, args.factors) - values).abs().amax(dim=(0, 2, 3)).tolist()
-    print(f"{args.height} x {args.width}, factors {tuple(args.factors)}, weight {args.weight}: {sampler.num_evaluations} evaluations in {dt:.2f} s; "
+    print(f"{args.height} x {args.width}, factors {tuple(args.factors)}, weight {args.weight}: {evaluations} evaluations in {dt:.2f} s; "
           f"max |block mean of the result - observation| per band: " + ", ".join(f"{r:.2e}" for r in res) + f"; wrote {args.out}")
 
 

@@ -35,7 +35,7 @@ const char* eod_last_error(void);
  * buffer of eod_pack_conv_weight_split, the 4-int state of eod_adamw_step_guarded).  eod_version() returns the value the library was built
  * with; a binding compares it with the header it mirrors at load time (eo_diffusion_amd/_lib.py does) instead of finding out by an
  * out-of-bounds device write. */
-#define EOD_ABI_VERSION 111
+#define EOD_ABI_VERSION 112
 int eod_version(void);
 /* Kernel-selection options ("skip_fuse", "head", "halo_bn256", "halo_splitk", "first", "s2_halo": 1 / 0; "gn_fuse_max_cout": n, -1 = default;
  * "halo_tpw": pixel tiles per workgroup of the streaming halo instances, 1 = off = default, 0 = chosen per launch; "head_tpw": the same of
@@ -410,6 +410,29 @@ int eod_ddim_step_p0(const float* e_t, const float* p0c, const float* noise, flo
                      int64_t numel, void* stream);
 int eod_dpmpp_step_p0(const float* x, const float* p0c, const float* d_prev, float c_x, float c_d, float w_cur, float w_prev, float* x_next,
                       int64_t numel, void* stream);
+/* The clipped DDPM step of eod_ddpm_step cut where its data prediction is complete (no reference line for the cut):
+ * the ancestral samplers form the prediction, project it by the links of an observation (eod_obs_project, eod_spec_project, eod_psf_*) and
+ * finish the posterior step from the result.  Tensors [N][chw] fp32, t int64 [N] and the tables [T] on the device as for eod_ddpm_step; a
+ * timestep outside [0, T) fills that sample's output with NaN.  Per element, every operation rounded once in fp32, in this order:
+ *   eod_ddpm_pred_x0:
+ *     c_x0 = sqrtf(1.0f / acp_t);  c_pred = sqrtf(1.0f / acp_t - 1.0f)
+ *     u = c_x0 * x;  v = c_pred * e;  p0 = u - v
+ *     clip != 0:  p0 = fminf(fmaxf(p0, -1), 1)                               -- eod_ddpm_step's clamp (a NaN becomes -1)
+ *   eod_ddpm_step_p0:
+ *     all_pos = (min over the batch of t) > 0                                -- the reference's batch-wide branch, as eod_ddpm_step
+ *     all_pos:  m_x0 = beta_t * sqrtf(acp_prev) / (1 - acp_t);  m_xt = (1 - acp_prev) * sqrtf(alpha_t) / (1 - acp_t)
+ *               std  = sqrtf(beta_t * (1 - acp_prev) / (1 - acp_t));         mean = (m_x0 * p0c) + (m_xt * x)
+ *     else:     m_x0 = beta_t / (1 - acp_t);  std = 0;                       mean = m_x0 * p0c
+ *     out = mean + (std * z)
+ * eod_ddpm_step_p0(eod_ddpm_pred_x0(x, e, clip = 1)) has the bits of eod_ddpm_step(clip = 1).  With clip = 0 the pair is the same posterior
+ * form without the clamp: algebraically the reference's epsilon form (model.py:101-122), NOT bit-equal to eod_ddpm_step(clip = 0).
+ * EOD_EINVAL with nothing launched: a null pointer, N, chw or T <= 0, the output overlapping an input (a tensor, t or a table).  16-byte
+ * accesses where chw % 4 == 0 and every tensor pointer is 16-byte aligned, element by element otherwise: same arithmetic.  Nothing is
+ * allocated, copied or synchronised: the calls can be captured in a graph.  The bodies are csrc/ddpm_p0_body.h. */
+int eod_ddpm_pred_x0(const float* x_t, const float* pred, const int64_t* t, const float* acp, float* p0, int N, int64_t chw, int T, int clip,
+                     void* stream);
+int eod_ddpm_step_p0(const float* x_t, const float* p0c, const float* noise, const int64_t* t, const float* betas, const float* alphas,
+                     const float* acp, float* out, int N, int64_t chw, int T, void* stream);
 /* PSF-aware observations (no reference line): the K channels `channels` (strictly increasing) of p [B][C][H][W] are
  * observed through A = D_f N^-1 B0 -- B0 the zero-padded separable convolution with the 1-D taps h[0 .. 2r] (r = 0 .. 12; fp32, finite,
  * non-negative, bitwise symmetric, h[r] > 0), horizontally, then vertically; N = diag(B0 1); D_f the f x f block mean of section 9.5 -- on

@@ -16,7 +16,9 @@ own weight) and finishes the step from the result (eod_ddim_step_p0 / eod_dpmpp_
 PsfObservation is the observation through a sensor's point spread function: A = D_f N^-1 B0, a renormalised
 zero-padded separable blur followed by the f x f block mean, with values and mask on the COARSE grid.  A+ has no local form, so the link
 takes `iters` Landweber steps p <- p - weight * tau * A^T(mask * (A p - values)) per evaluation (eod_psf_residual, eod_psf_update;
-csrc/psf.hip).  It is a link like the others; alone it runs as a chain of one through the unfused ends.
+csrc/psf.hip).  It is a link like the others; alone it runs as a chain of one through the unfused ends.  With solver="cg" (DESIGN.md
+section 9.9) the link lands on its constraint instead: p - weight * A^T z with (M A A^T M + damping I) z = mask * (A p - values) solved by
+`iters` conjugate-gradient iterations on the coarse grid (eod_psf_cg; csrc/psf_cg.hip), where A A^T is a separable banded stencil (psf_gram).
 
 The ancestral samplers (EODiffusion.sampling / sampling_scene) take the same observations through ddpm_step below:
 eod_ddpm_pred_x0, every link's project(k, p) in order, eod_ddpm_step_p0 -- the clipped DDPM step cut where its prediction is complete.
@@ -40,6 +42,8 @@ MAX_ROWS = 8            # rows of a response matrix (EOD_SPEC_MAXK of csrc/sampl
 MAX_LINKS = 4           # observations in one chain
 MAX_RADIUS = 12         # of a PSF's taps (PSF_MAXR of csrc/psf_body.h)
 MAX_ITERS = 8           # Landweber steps of a PsfObservation per evaluation
+MAX_CG_ITERS = 64       # conjugate-gradient iterations of a PsfObservation(solver="cg") per evaluation (CG_MAX_ITERS of csrc/psf_cg_body.h)
+SOLVERS = ("landweber", "cg")
 MIN_RCOND = 1e-3        # sigma_min / sigma_max of a response matrix below which it is refused (the fp32 residual
                         # of the projection grows with the conditioning, 0.55 eps at cond 45 and 11.6 eps at cond 268)
 
@@ -387,6 +391,55 @@ def psf_tau(taps, factor, H, W):
     return float(factor * factor) / (psf_cmax(taps, H) * psf_cmax(taps, W))
 
 
+def psf_gram(taps, factor, L):
+    """(bands, b): the 1-D Gram matrix G_L = A1(L) A1(L)^T of the operator A1 = D_f N^-1 B0 on a line of length L (renormalised zero padding,
+    block mean) as its band: bands float32 [L / f, 2b + 1], bands[i][j] = G_L[i][i - b + j], zero where the column lies outside the line;
+    b = ceil(2r / f).  float64 of the fp32 taps, band by band (no dense matrix: L may be a scene's width); the upper band is computed and
+    mirrored, so G_L is symmetric bit for bit.  A A^T = G(H) (x) G(W)."""
+    what = "psf_gram"
+    h = _taps(what, taps).astype(np.float64)
+    f = _factor(what, factor)
+    if isinstance(L, bool) or not isinstance(L, numbers.Integral) or L < 1 or L % f:
+        raise _lib.EodError(f"{what}: L is a positive multiple of factor = {f}, got {L!r}")
+    L = int(L)
+    r, Lc = h.size // 2, L // f
+    b = -((-2 * r) // f)
+    n = np.convolve(np.ones(L), h)[r:r + L]                  # N = diag(B0 1)
+    w = f + 2 * r                                            # row i of A1 lives on x = i f - r .. i f + f - 1 + r
+    rows = np.zeros((Lc, w))
+    for a in range(f):                                       # the block's pixel y = i f + a sees x = y - r + t through h[t] / n[y]
+        inv = 1.0 / n[a::f]
+        for t in range(h.size):
+            rows[:, a + t] += h[t] * inv
+    x = np.arange(Lc)[:, None] * f - r + np.arange(w)[None, :]
+    rows[(x < 0) | (x >= L)] = 0.0
+    rows /= f
+    bands = np.zeros((Lc, 2 * b + 1))
+    for k in range(min(b, Lc - 1) + 1):                      # G[i][i + k]: the two rows overlap on w - k f columns
+        g = (rows[:Lc - k, k * f:] * rows[k:, :w - k * f]).sum(axis=1)
+        bands[np.arange(Lc - k), b + k] = g
+        bands[np.arange(k, Lc), b - k] = g
+    return bands.astype(np.float32), b
+
+
+def _dampings(what, damping):
+    """([fp32-rounded dampings], one per evaluation?) of a `damping` argument: a finite float >= 0 or a sequence of them"""
+    if isinstance(damping, (numbers.Real, np.floating)) and not isinstance(damping, bool):
+        ds, per_evaluation = [damping], False
+    else:
+        try:
+            ds = list(damping)
+        except TypeError:
+            raise _lib.EodError(f"{what}: `damping` is a float or a sequence of floats, got {damping!r}") from None
+        per_evaluation = True
+    for d in ds:
+        if isinstance(d, bool) or not isinstance(d, (numbers.Real, np.floating)) or not math.isfinite(float(d)):
+            raise _lib.EodError(f"{what}: a damping is a finite float, got {d!r}")
+        if not 0.0 <= float(d) or not math.isfinite(float(np.float32(d))):
+            raise _lib.EodError(f"{what}: a damping is >= 0 (and finite as float32), got {d!r}")
+    return [float(np.float32(d)) for d in ds], per_evaluation
+
+
 def gaussian_sigma(factor, mtf_nyquist=0.3):
     """sigma in fine pixels of the Gaussian whose MTF exp(-2 pi^2 sigma^2 nu^2) is mtf_nyquist at the coarse grid's Nyquist frequency 1 / (2 f)"""
     what = "gaussian_psf"
@@ -420,17 +473,26 @@ class PsfObservation:
     separable convolution with the 1-D taps `psf`, horizontally then vertically; N = diag(B0 1); D_f the factor x factor block mean).
     values [B or 1, K, H / f, W / f] fp32 on the COARSE grid: what the sensor delivered; psf: array-like [2r + 1], r = 0 .. 12, finite,
     non-negative, symmetric bit for bit as float32, centre tap positive; factor 1 .. 8; channels None (all C, C = K) or K strictly
-    increasing channel numbers; mask None or [B or 1, K or 1, H / f, W / f] fp32; weight as for Observation; iters 1 .. 8 Landweber steps
-    per evaluation."""
+    increasing channel numbers; mask None or [B or 1, K or 1, H / f, W / f] fp32; weight as for Observation.  solver "landweber" (the
+    default): iters 1 .. 8 Landweber steps per evaluation, which approach the constraint set.  solver "cg": iters 1 .. 64 conjugate-gradient
+    iterations of the exact projection per evaluation, p - weight * A^T (M A A^T M + damping I)^-1 mask (A p - values); the mask must then
+    be 0 or 1 exactly, and damping (a float >= 0, or one per evaluation) is the Tikhonov term for noisy values."""
 
-    def __init__(self, values, psf, factor, channels=None, mask=None, weight=1.0, iters=1):
+    def __init__(self, values, psf, factor, channels=None, mask=None, weight=1.0, iters=1, solver="landweber", damping=0.0):
         what = "PsfObservation"
         self.taps = _taps(what, psf)
         self.factor = _factor(what, factor)
         self.channels = None if channels is None else _channels(what, channels)
-        if isinstance(iters, bool) or not isinstance(iters, numbers.Integral) or not 1 <= iters <= MAX_ITERS:
-            raise _lib.EodError(f"{what}: `iters` is an integer in 1 .. {MAX_ITERS}, got {iters!r}")
+        if not isinstance(solver, str) or solver not in SOLVERS:
+            raise _lib.EodError(f"{what}: `solver` is one of {SOLVERS}, got {solver!r}")
+        self.solver = solver
+        most = MAX_CG_ITERS if solver == "cg" else MAX_ITERS
+        if isinstance(iters, bool) or not isinstance(iters, numbers.Integral) or not 1 <= iters <= most:
+            raise _lib.EodError(f"{what}: `iters` is an integer in 1 .. {most} with solver={solver!r}, got {iters!r}")
         self.iters = int(iters)
+        self.dampings, self.damping_per_evaluation = _dampings(what, damping)
+        if solver != "cg" and any(d != 0.0 for d in self.dampings):
+            raise _lib.EodError(f"{what}: `damping` belongs to solver=\"cg\" (the Landweber steps have no regularised form), got {damping!r}")
         v = torch.as_tensor(values)
         if v.dtype != torch.float32:
             raise _lib.EodError(f"{what}: `values` must be float32, got {v.dtype}")
@@ -446,6 +508,9 @@ class PsfObservation:
                 raise _lib.EodError(f"{what}: `mask` must be [B or 1, {K} or 1, {Hc}, {Wc}] on the coarse grid, got {tuple(mask.shape)}")
             if 1 not in (v.shape[0], mask.shape[0]) and v.shape[0] != mask.shape[0]:
                 raise _lib.EodError(f"{what}: `values` is for {v.shape[0]} samples, `mask` for {mask.shape[0]}")
+            if solver == "cg" and not bool(((mask == 0.0) | (mask == 1.0)).all()):
+                raise _lib.EodError(f"{what}: with solver=\"cg\" the `mask` must be 0 or 1 exactly (a soft mask inside M A A^T M destroys the "
+                                    f"system's conditioning); express soft knowledge with `weight` and `damping`")
         self.weights, self.per_evaluation = _weights(what, weight)
         self.values, self.mask = v, mask
 
@@ -469,6 +534,8 @@ class PsfObservation:
                 raise _lib.EodError(f"{what}: the observation's `{name}` has leading dimension {t.shape[0]}; the call needs {B} or 1")
         if self.per_evaluation and len(self.weights) != n_evaluations:
             raise _lib.EodError(f"{what}: the call evaluates the UNet {n_evaluations} times, the observation's `weight` has {len(self.weights)} entries")
+        if self.damping_per_evaluation and len(self.dampings) != n_evaluations:
+            raise _lib.EodError(f"{what}: the call evaluates the UNet {n_evaluations} times, the observation's `damping` has {len(self.dampings)} entries")
         if device is None:                             # (check(): the refusals alone, nothing copied)
             return None
         return BoundPsf(self, (B, C, H, W), channels, n_evaluations, device)
@@ -489,29 +556,40 @@ class BoundPsf:
         self.values = f32c(obs.values.to(device))
         self.mask = None if obs.mask is None else f32c(obs.mask.to(device))
         self.weights = obs.weights if obs.per_evaluation else obs.weights * n_evaluations
+        self.solver = obs.solver
+        if self.solver == "cg":                        # the two Gram tables beside `values`; workspace and coarse buffers at the first project
+            self.dampings = obs.dampings if obs.damping_per_evaluation else obs.dampings * n_evaluations
+            self.unit_step = float(np.float32(1.0 / (obs.factor * obs.factor)))
+            gy, self.band = psf_gram(obs.taps, obs.factor, H)
+            gx, _ = psf_gram(obs.taps, obs.factor, W)
+            self.gy, self.gx = torch.from_numpy(gy).to(device), torch.from_numpy(gx).to(device)
+            self._cg = self._coarse = None
 
-    def residual(self, i, p, q):
+    def residual(self, i, p, q, weight=None):
         """q = weight_i * mask * (A p - values) on the coarse grid: eod_psf_residual"""
         if tuple(p.shape) != self.shape:
             raise _lib.EodError(f"observation bound to a state of shape {self.shape}, the step got {tuple(p.shape)}")
         B, C, H, W = self.shape
         m = self.mask
-        _lib.check(_lib.lib().eod_psf_residual(p.data_ptr(), self.values.data_ptr(), _lib.ptr(m), self.weights[i], self.c_taps, self.r, self.factor,
+        _lib.check(_lib.lib().eod_psf_residual(p.data_ptr(), self.values.data_ptr(), _lib.ptr(m), self.weights[i] if weight is None else weight,
+                                               self.c_taps, self.r, self.factor,
                                                self.c_channels, self.K, B, C, H, W, int(self.values.shape[0] != B),
                                                int(m is not None and m.shape[0] != B), int(m is not None and m.shape[1] != self.K),
                                                q.data_ptr(), current_stream_ptr(p.device)), "eod_psf_residual")
         return q
 
-    def update(self, p, q, out):
+    def update(self, p, q, out, step=None):
         """out = p - tau A^T q: eod_psf_update"""
         B, C, H, W = self.shape
-        _lib.check(_lib.lib().eod_psf_update(p.data_ptr(), q.data_ptr(), self.step, self.c_taps, self.r, self.factor, self.c_channels, self.K,
+        _lib.check(_lib.lib().eod_psf_update(p.data_ptr(), q.data_ptr(), self.step if step is None else step, self.c_taps, self.r, self.factor, self.c_channels, self.K,
                                              B, C, H, W, out.data_ptr(), current_stream_ptr(p.device)), "eod_psf_update")
         return out
 
     def project(self, i, p):
         """`iters` Landweber steps from the prediction p at evaluation number i (a link of a chain): iters x (residual, update), ping-pong
         between two buffers (eod_psf_update's out must not be its p)"""
+        if self.solver == "cg":
+            return self.project_cg(i, p)
         B, C, H, W = self.shape
         p = f32c(p)
         q = torch.empty((B, self.K, H // self.factor, W // self.factor), device=p.device, dtype=torch.float32)
@@ -519,6 +597,33 @@ class BoundPsf:
         for it in range(self.iters):
             p = self.update(p, self.residual(i, p, q), bufs[it % 2])
         return p
+
+
+    def solve(self, i, c, q):
+        """q = weight_i * mask * z, (M A A^T M + damping_i I) z = c by `iters` conjugate-gradient iterations on the coarse grid: eod_psf_cg.
+        The workspace belongs to the link: allocated at the first call, reused by every later one."""
+        B, C, H, W = self.shape
+        Hc, Wc = H // self.factor, W // self.factor
+        L = _lib.lib()
+        if self._cg is None or self._cg.device != c.device:
+            self._cg = torch.empty(int(L.eod_psf_cg_workspace_size(B, self.K, Hc, Wc)), device=c.device, dtype=torch.uint8)
+        m = self.mask
+        _lib.check(L.eod_psf_cg(c.data_ptr(), _lib.ptr(m), self.dampings[i], self.weights[i], self.gy.data_ptr(), self.gx.data_ptr(), self.band,
+                                self.iters, B, self.K, Hc, Wc, int(m is not None and m.shape[0] != B),
+                                int(m is not None and m.shape[1] != self.K), q.data_ptr(), self._cg.data_ptr(), self._cg.numel(),
+                                current_stream_ptr(c.device)), "eod_psf_cg")
+        return q
+
+    def project_cg(self, i, p):
+        """the exact projection of the prediction p at evaluation number i: eod_psf_residual (weight 1) -> eod_psf_cg -> eod_psf_update
+        (step 1 / f^2).  The two coarse buffers belong to the link; the result is a fresh tensor (a sampler keeps it as its history)."""
+        B, C, H, W = self.shape
+        p = f32c(p)
+        if self._coarse is None or self._coarse[0].device != p.device:
+            self._coarse = [torch.empty((B, self.K, H // self.factor, W // self.factor), device=p.device, dtype=torch.float32) for _ in range(2)]
+        c, q = self._coarse
+        self.solve(i, self.residual(i, p, c, 1.0), q)
+        return self.update(p, q, torch.empty_like(p), self.unit_step)
 
 
 class BoundChain:

@@ -4,12 +4,14 @@ PSF-aware observations.
 
     python examples/sharpen_psf.py                                     # 384 x 576, 13 bands, MTF 0.3 at Nyquist
     python examples/sharpen_psf.py --mtf 0.2 --iters 4 --steps 25
+    python examples/sharpen_psf.py --solver cg --iters 16                # the exact projection: the residuals fall to rounding
+    python examples/sharpen_psf.py --solver cg --iters 8 --damping 0.05  # the regularised solve for noisy observations
 
 A synthetic 13-band truth is "observed" the way the instrument does it: the six 20 m bands (B5, B6, B7, B8A, B11, B12) blurred by a Gaussian
 PSF and sampled on a 2x coarser grid, the three 60 m bands (B1, B9, B10) on a 6x coarser one, each group with the PSF of its own grid
 (gaussian_psf: the MTF at that grid's Nyquist frequency).  `observation=[PsfObservation(20 m group), PsfObservation(60 m group)]` takes
-`iters` Landweber steps toward each constraint set after every evaluation's prediction; the 10 m bands are left to
-the network.  The script prints both residuals, max |A x - y| on the coarse grids, of the last prediction and of the returned scene, next to
+`iters` Landweber steps toward each constraint set after every evaluation's prediction, or with --solver cg `iters`
+conjugate-gradient iterations of the exact projection onto it (section 9.9); the 10 m bands are left to the network.  The script prints both residuals, max |A x - y| on the coarse grids, of the last prediction and of the returned scene, next to
 those of the same call without an observation.  The network is UNTRAINED unless --ckpt is given: the script shows the mechanics and the
 constraints, not image quality.
 """
@@ -50,7 +52,9 @@ def main():
     ap.add_argument("--height", type=int, default=384)
     ap.add_argument("--width", type=int, default=576)
     ap.add_argument("--mtf", type=float, default=0.3, help="the PSF's MTF at each coarse grid's Nyquist frequency")
-    ap.add_argument("--iters", type=int, default=2, help="Landweber steps per evaluation and link (1 .. 8)")
+    ap.add_argument("--iters", type=int, default=2, help="Landweber steps (1 .. 8) or cg iterations (1 .. 64) per evaluation and link")
+    ap.add_argument("--solver", default="landweber", choices=["landweber", "cg"])
+    ap.add_argument("--damping", type=float, default=0.0, help="--solver cg: the Tikhonov term mu of (A A^T + mu I)")
     ap.add_argument("--image-size", type=int, default=64, help="the UNet's tile size")
     ap.add_argument("--overlap", type=int, default=16)
     ap.add_argument("--timesteps", type=int, default=1000)
@@ -76,7 +80,7 @@ def main():
     truth = synthetic_scene(args.height, args.width, args.seed).to(device) * 2.0 - 1.0
     seen = {name: (cs, f, gaussian_psf(f, args.mtf)) for name, (cs, f) in GROUPS.items()}
     values = {name: psf_observe(truth, h, f, cs) for name, (cs, f, h) in seen.items()}          # what the sensor delivered, on the coarse grids
-    links = [PsfObservation(values[name], h, f, cs, iters=args.iters) for name, (cs, f, h) in seen.items()]
+    links = [PsfObservation(values[name], h, f, cs, iters=args.iters, solver=args.solver, damping=args.damping) for name, (cs, f, h) in seen.items()]
     sampler = DPMSolverSampler(model)
     x_T = torch.randn((1, BANDS, args.height, args.width), device=device)
     call = lambda **kw: sampler.sample_scene(args.steps, (args.height, args.width), overlap=args.overlap, clip_denoised=False, progress=False,
@@ -88,7 +92,9 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     np.save(args.out, ((scene + 1.0) / 2.0)[0].cpu().numpy())
-    print(f"{args.height} x {args.width}, {BANDS} bands, MTF {args.mtf} at Nyquist, {args.iters} Landweber step(s) per evaluation: "
+    print(f"{args.height} x {args.width}, {BANDS} bands, MTF {args.mtf} at Nyquist, {args.iters} "
+          f"{'cg iteration(s)' if args.solver == 'cg' else 'Landweber step(s)'} per evaluation"
+          f"{f', damping {args.damping}' if args.damping else ''}: "
           f"{sampler.num_evaluations} evaluations in {dt:.2f} s (the network is {'the checkpoint' if args.ckpt else 'UNTRAINED'})")
     for name, (cs, f, h) in seen.items():
         print(f"  {name} group: channels {list(cs)} at f = {f}, {h.size} taps")

@@ -35,7 +35,7 @@ const char* eod_last_error(void);
  * buffer of eod_pack_conv_weight_split, the 4-int state of eod_adamw_step_guarded).  eod_version() returns the value the library was built
  * with; a binding compares it with the header it mirrors at load time (eo_diffusion_amd/_lib.py does) instead of finding out by an
  * out-of-bounds device write. */
-#define EOD_ABI_VERSION 112
+#define EOD_ABI_VERSION 113
 int eod_version(void);
 /* Kernel-selection options ("skip_fuse", "head", "halo_bn256", "halo_splitk", "first", "s2_halo": 1 / 0; "gn_fuse_max_cout": n, -1 = default;
  * "halo_tpw": pixel tiles per workgroup of the streaming halo instances, 1 = off = default, 0 = chosen per launch; "head_tpw": the same of
@@ -466,6 +466,36 @@ int eod_psf_apply(const float* x, const float* taps, int r, int f, const int32_t
                   void* stream);
 int eod_psf_update(const float* p, const float* q, float step, const float* taps, int r, int f, const int32_t* channels, int K, int B, int C,
                    int H, int W, float* out, void* stream);
+/* The exact PSF data consistency (no reference line): conjugate gradients on the COARSE grid [Hc][Wc] = [H / f][W / f],
+ * one independent system per plane (sample b, observed channel k):
+ *   S z = c,   S = M G M + mu I,   M = diag(m), m in {0, 1} (mask NULL: 1),   G = A A^T = G_H (x) G_W
+ * gy [Hc][2b + 1] and gx [Wc][2b + 1] are DEVICE fp32 tables of the banded symmetric 1-D Gram matrices G_L = A1(L) A1(L)^T, entry [i][j] =
+ * G_L[i][i - b + j], zero where the column lies outside the line; b = 0 .. 24.  One application, every operation rounded once in fp32 (u
+ * outside the plane is +0.0f, and its product is formed and added like any other):
+ *   u       = m * d                                                               (mask NULL: u = d)
+ *   t[y][x] = (((gx[x][0] * u[y][x-b]) + gx[x][1] * u[y][x-b+1]) + ...) + gx[x][2b] * u[y][x+b]
+ *   v[y][x] = (((gy[y][0] * t[y-b][x]) + gy[y][1] * t[y-b+1][x]) + ...) + gy[y][2b] * t[y+b][x]
+ *   q       = (m * v) + (mu * d)                                                  (mask NULL: v + (mu * d))
+ * q is a function of the pixel alone.  sigma[plane] = <d, q>: the fp32 x fp32 products are exact in float64 and are added in float64, each
+ * tile of 32 x 32 in a fixed order into a slot indexed by (plane, tile), the slots of a plane in a fixed tree over the tile index -- a plane's
+ * total depends on that plane's data and on Hc, Wc alone, not on B, K, the alignment, the grid or the other planes of the launch.
+ * eod_psf_cg runs `iters` = 1 .. 64 iterations from z = 0, r = d = c, rho = <r, r>:
+ *   q = S d;  sigma = <d, q>;  alpha = fp32(rho / sigma);  z = z + (alpha * d);  r = r - (alpha * q);  rho' = <r, r>;
+ *   beta = fp32(rho' / rho);  d = r + (beta * d);  rho = rho'
+ * with alpha = beta = 0 for a plane whose rho is 0, whose sigma is <= 0 or where either is not finite (and beta = 0 where rho' is not
+ * finite), and writes q_out = lambda * (m * z), ready for eod_psf_update with step = fp32(1 / f^2).  A plane with c = 0 keeps z = 0.
+ * ws: caller-owned DEVICE workspace of at least eod_psf_cg_workspace_size(B, K, Hc, Wc) bytes, any alignment, private layout.
+ * eod_psf_gram: q [B][K][Hc][Wc] and sigma (double [B * K], 8-byte aligned) from d.  eod_psf_cg: 4 iters + 2 launches in one call.
+ * EOD_EINVAL with nothing launched: a null pointer (mask may be NULL), B, K, Hc or Wc <= 0, b outside 0 .. 24, iters outside 1 .. 64, mu
+ * negative or not finite, lambda outside [0, 1] (NaN included), a workspace that is too small, an output or the workspace overlapping an
+ * input or each other.  Nothing is allocated, copied or synchronised: the calls can be captured in a graph.  16-byte accesses where
+ * Wc % 4 == 0 and the pointers are 16-byte aligned, element by element otherwise: same bits.  Beyond EOD_PSF_GRID_BLOCKS workgroups the
+ * workgroups stride over the (plane, tile) pairs. */
+int64_t eod_psf_cg_workspace_size(int B, int K, int Hc, int Wc);
+int eod_psf_gram(const float* d, const float* mask, float mu, const float* gy, const float* gx, int b, int B, int K, int Hc, int Wc,
+                 int mask_b1, int mask_c1, float* q, double* sigma, void* ws, int64_t ws_bytes, void* stream);
+int eod_psf_cg(const float* c, const float* mask, float mu, float lambda, const float* gy, const float* gx, int b, int iters, int B, int K,
+               int Hc, int Wc, int mask_b1, int mask_c1, float* q_out, void* ws, int64_t ws_bytes, void* stream);
 /* classifier-free guidance of p_sample_ddim (ddim.py:177-181): out = e_uncond + scale * (e_cond - e_uncond) */
 int eod_cfg_combine(const float* e_uncond, const float* e_cond, float scale, float* out, int64_t numel, void* stream);
 /* table-driven DDPM step of the LDM-derived sampler: DDPM.p_sample ddpm.py:248-255 with predict_start_from_noise :221-225,

@@ -1149,6 +1149,12 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void igemm_kernel(const 
 //   * DMA schedule per K-step (chunk cc, tap t), per wave: [4 weight-tile pieces for step+1][1 patch piece of chunk cc+1
 //     (taps 0..5)].  vmcnt retires in order, so the wait for step s's weights is vmcnt(1) when a patch piece was
 //     issued after them and vmcnt(0) otherwise: every patch piece gets two full K-steps to land.
+//   * 16x16x32 paths: the taps of a chunk run dx-MAJOR (K-step t = tap (dy, dx) = (t % 3, t / 3), weight slot 3 dy + dx).  The A fragment
+//     of row block i for tap row dy is patch row i + dy of the wave's window, so the three steps of one dx keep a rotating window of TM
+//     fragments per half and a step with dy > 0 reads ONE new row per half: 36 A reads per chunk instead of 72 (108 ds_read_b128 per
+//     chunk with the weights, 12 per 48 MFMAs).  On the 8-wave instance the new rows of steps 1..8 are read one step early, where the
+//     registers they replace die (the chunk's patch buffer is read-only for the chunk): behind a step's barrier it reads only the
+//     weight fragments.  The first step of a chunk reads its rows behind its barrier.  (STREAM instances: the tap order only.)
 //   * everything else (MFMA tiling, buffer-descriptor OOB zero fill, concat sources, epilogue) is shared with igemm.
 // Requirements (checked by the launcher, otherwise the generic kernel runs): ksize 3, stride 1, pad 1, Wo % 16 == 0 (or Wo == 8, half tiles),
 // Ho % 8 == 0 (with or without the virtual nearest-2x upsampling of the input).
@@ -1463,7 +1469,29 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
     // (v = 0 / 1: [8 x hi] / [8 x lo] chunk of the lane's pair in split mode, sub-step 0 / 1 in fp16 storage); the (i, dy) part is a
     // compile-time offset of the ds_read, and the buffer flip at a chunk boundary is one add per register.
     int acur[2][3] = {{0, 0, 0}, {0, 0, 0}};
-    auto aimm = [](int i, int dy) { return (UPS ? ((i + dy + 1) >> 1) : (i + dy)) * PW * BKB; };
+    // The (i, dy) part depends on r = i + dy alone: the fragment of (i, dy + 1) IS the fragment of (i + 1, dy).  The 16x16x32 paths
+    // therefore run the taps of a chunk dx-MAJOR (step t = tap (dy, dx) = (t % 3, t / 3), weight slot 3 dy + dx) and keep a ROTATING
+    // WINDOW of TM fragments per half across the three steps of one dx: window row r lives in aw[v][r % TM]; a step with dy > 0 reads
+    // the ONE new row TM - 1 + dy into the registers of row dy - 1, which died with the step before.  6 rows per dx and half instead of
+    // 12: 36 A reads per chunk instead of 72.  The tap loop is fully unrolled, so every index below is a compile-time constant.
+    auto aoff = [](int r) { return (UPS ? ((r + 1) >> 1) : r) * PW * BKB; };
+    i32x4 aw[2][TM];
+    // (STREAM instances sit at the 256-register limit with spills: they take the tap order -- their outputs are the bits of the
+    //  single-tile instances -- but re-read all TM rows every step, as before, and read nothing early)
+    constexpr bool WINDOW = !STREAM;
+    auto a_load = [&](int v, int dx, int dy) {  // window rows a step (dy, dx) adds: all TM at dy = 0, else row TM - 1 + dy
+#pragma unroll
+        for (int r = 0; r < TM + 2; ++r)
+            if (dy == 0 || !WINDOW ? (r >= dy && r < TM + dy) : r == TM - 1 + dy) aw[v][r % TM] = *reinterpret_cast<const i32x4*>(sA + acur[v][dx] + aoff(r));
+    };
+    // The current chunk's patch buffer is read-only for the whole chunk (DMA and the in-place rewrite target the OTHER buffer), so only
+    // the weight tile needs a step's barrier.  The 8-wave instance (256 columns: eight waves leave one barrier together and issue their
+    // reads at once) gets the new A rows of steps 1..8 of a chunk one step EARLY, each half where the registers it replaces die
+    // (a_early); the first step of a chunk reads all of its rows behind its barrier: the other waves' rewritten pieces of that chunk
+    // are visible only there.  Measured: 256-column layers -1.7 ... -2.6 %, the 4-wave instances and conv_up4_halo_kernel within their
+    // repeat spread for 14-34 more registers, so those read behind the barrier (DESIGN_HISTORY.md 10.20).
+    constexpr bool EARLY = WINDOW && MS == 16 && WAVES_N == 4;
+    auto tap_slot = [](int t) { return MS == 16 ? 3 * (t % 3) + t / 3 : t; };
     if constexpr (MS == 16) {
         constexpr int LROW = WM / 16;  // tile rows per wave (even)
         static_assert(LROW % 2 == 0, "the UPS row split needs an even first tile row per wave");
@@ -1541,7 +1569,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
             EOD_TSTAMP_AT(4 * t + 1);
             // DMA for the next step: weights first, then (taps 0..LAH-1) one piece of the next chunk's patch
             if (step + 1 < TSTEP) {
-                if (t < 8) issue_weights_at(t + 1, cur, bve, sB + ((step + 1) & 1) * BSTAGE);
+                if (t < 8) issue_weights_at(tap_slot(t + 1), cur, bve, sB + ((step + 1) & 1) * BSTAGE);
                 else issue_weights(0, nxt, sB + ((step + 1) & 1) * BSTAGE);
             }
             pp1 = 0;
@@ -1557,7 +1585,9 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
             }
             EOD_TSTAMP_AT(4 * t + 2);
             // ---- MFMAs of tap t: A fragments = patch rows shifted by (dy, dx) ----
-            const int dy = t / 3, dx = t - dy * 3;
+            const int dy = MS == 16 ? t % 3 : t / 3, dx = MS == 16 ? t / 3 : t % 3;  // (16x16x32 paths: dx-major, see `aw`)
+            const int ndy = (t + 1) % 3, ndx = (t + 1) / 3;                          // tap of the next step of this chunk (t < 8)
+            const bool a_here = !EARLY || t == 0, a_early = EARLY && t < 8;
             const char* bst = sB + (step & 1) * BSTAGE;
             int arow[TM], asw[TM];  // (32x32x16 paths; the 16x16x32 ones read through acur)
 #pragma unroll
@@ -1572,48 +1602,49 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
                 // permutation keeps every ds_read_b128 lane group on 16 distinct 16-byte slots; A and B use the same one, so the
                 // contraction is unchanged).  [8 x hi] at chunk 2 pi, [8 x lo] behind it; 3 x 16 MFMAs, smallest terms first.
                 const int ch = 2 * ((0x2130 >> (4 * lh)) & 3);
-                i32x4 ah[TM], al[TM], bh[TN], bl[TN];
-#pragma unroll
-                for (int i = 0; i < TM; ++i) al[i] = *reinterpret_cast<const i32x4*>(sA + acur[1][dx] + aimm(i, dy));
+                // A: the window aw[0] = hi, aw[1] = lo; row block i of this step is window row i + dy
+                i32x4 bh[TN], bl[TN];
+                if (a_here) a_load(1, dx, dy);
 #pragma unroll
                 for (int j = 0; j < TN; ++j) bh[j] = *reinterpret_cast<const i32x4*>(bst + b_rd + j * MS * BKB + ((ch ^ bsw) << 4));
-#pragma unroll
-                for (int i = 0; i < TM; ++i) ah[i] = *reinterpret_cast<const i32x4*>(sA + acur[0][dx] + aimm(i, dy));
+                if (a_here) a_load(0, dx, dy);
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
                     for (int j = 0; j < TN; ++j)
-                        acc[i][j] = DIRECT ? __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, bh[j]), __builtin_bit_cast(half8, al[i]), acc[i][j], 0, 0, 0)
-                                           : __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, al[i]), __builtin_bit_cast(half8, bh[j]), acc[i][j], 0, 0, 0);
+                        acc[i][j] = DIRECT ? __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, bh[j]), __builtin_bit_cast(half8, aw[1][(i + dy) % TM]), acc[i][j], 0, 0, 0)
+                                           : __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, aw[1][(i + dy) % TM]), __builtin_bit_cast(half8, bh[j]), acc[i][j], 0, 0, 0);
 #pragma unroll
                 for (int j = 0; j < TN; ++j) bl[j] = *reinterpret_cast<const i32x4*>(bst + b_rd + j * MS * BKB + (((ch + 1) ^ bsw) << 4));
+                if (a_early) a_load(1, ndx, ndy);  // the lo rows of this step are dead
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
                     for (int j = 0; j < TN; ++j)
-                        acc[i][j] = DIRECT ? __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, bl[j]), __builtin_bit_cast(half8, ah[i]), acc[i][j], 0, 0, 0)
-                                           : __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, ah[i]), __builtin_bit_cast(half8, bl[j]), acc[i][j], 0, 0, 0);
+                        acc[i][j] = DIRECT ? __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, bl[j]), __builtin_bit_cast(half8, aw[0][(i + dy) % TM]), acc[i][j], 0, 0, 0)
+                                           : __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, aw[0][(i + dy) % TM]), __builtin_bit_cast(half8, bl[j]), acc[i][j], 0, 0, 0);
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
                     for (int j = 0; j < TN; ++j)
-                        acc[i][j] = DIRECT ? __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, bh[j]), __builtin_bit_cast(half8, ah[i]), acc[i][j], 0, 0, 0)
-                                           : __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, ah[i]), __builtin_bit_cast(half8, bh[j]), acc[i][j], 0, 0, 0);
+                        acc[i][j] = DIRECT ? __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, bh[j]), __builtin_bit_cast(half8, aw[0][(i + dy) % TM]), acc[i][j], 0, 0, 0)
+                                           : __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, aw[0][(i + dy) % TM]), __builtin_bit_cast(half8, bh[j]), acc[i][j], 0, 0, 0);
+                if (a_early) a_load(0, ndx, ndy);  // and now the hi rows
             } else if constexpr (MS == 16) {
                 // fp16 storage: the K-step's 64 k are two 16x16x32 sub-steps; lane quarter lh of sub-step s reads chunk 4 s + lh
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
                     const int ch = 4 * s + lh;
-                    i32x4 fa16[TM], fb16[TN];
-#pragma unroll
-                    for (int i = 0; i < TM; ++i) fa16[i] = *reinterpret_cast<const i32x4*>(sA + acur[s][dx] + aimm(i, dy));
+                    i32x4 fb16[TN];  // (A: the window aw[s], row block i = window row i + dy)
+                    if (a_here) a_load(s, dx, dy);
 #pragma unroll
                     for (int j = 0; j < TN; ++j) fb16[j] = *reinterpret_cast<const i32x4*>(bst + b_rd + j * MS * BKB + ((ch ^ bsw) << 4));
 #pragma unroll
                     for (int i = 0; i < TM; ++i)
 #pragma unroll
                         for (int j = 0; j < TN; ++j)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, fa16[i]), __builtin_bit_cast(half8, fb16[j]), acc[i][j], 0, 0, 0);
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, aw[s][(i + dy) % TM]), __builtin_bit_cast(half8, fb16[j]), acc[i][j], 0, 0, 0);
+                    if (a_early) a_load(s, ndx, ndy);  // this sub-step's rows are dead
                 }
             } else {
             // fragments are read ONE sub-step ahead of the MFMAs that consume them (two register sets), and the order
@@ -1940,10 +1971,10 @@ __global__ __launch_bounds__(256, 2) void conv_up4_halo_kernel(const IgemmP p) {
         const f32x4 f = *reinterpret_cast<const f32x4*>(ptr);
         *reinterpret_cast<i32x4*>(ptr) = split_pair_exchange_scaled(f, asc.s, (pchunk_of(i) & 1) != 0);
     };
-    // tap slot of K-step s (a = s >> 1, b = s & 1) of the 3x3 frame: forward (par_y + a, par_x + b); backward (1 - p + a, 1 - q + b)
+    // tap slot of K-step s (row a = s & 1 runs inner, column b = s >> 1) of the 3x3 frame: forward (par_y + a, par_x + b); backward (1 - p + a, 1 - q + b)
     auto issue_weights = [&](int s, const Chunk& c, char* bst) {
         const int oy = BWD ? 1 - (c.cls >> 1) : par_y, ox = BWD ? 1 - (c.cls & 1) : par_x;
-        const int tap = (oy + (s >> 1)) * 3 + ox + (s & 1);
+        const int tap = (oy + (s & 1)) * 3 + ox + (s >> 1);
         const unsigned soff = (unsigned)(tap * tapstride) + (unsigned)((c.kin + (BWD ? c.cls * p.C0 : 0)) * ES);
 #pragma unroll
         for (int i = 0; i < LB; ++i) {
@@ -1991,6 +2022,14 @@ __global__ __launch_bounds__(256, 2) void conv_up4_halo_kernel(const IgemmP p) {
     const int b_rd = (wn * WN + lr) * BKB;
     const int boff0 = b_rd + ((c0 ^ bsw) << 4), boff1 = b_rd + ((c1 ^ bsw) << 4);
 
+    // rotating row window of the A fragments (see conv3x3_halo_kernel): the two steps of a column tap b read window rows a .. a + TM - 1,
+    // row r in aw[v][r % TM]; the step a = 1 adds row TM only -- 20 A reads per chunk instead of 32
+    i32x4 aw[2][TM];
+    auto a_load = [&](int v, int b, int a) {
+#pragma unroll
+        for (int r = 0; r < TM + 1; ++r)
+            if (a == 0 ? r < TM : r == TM) aw[v][r % TM] = *reinterpret_cast<const i32x4*>(sA + acur[v][b] + r * PW * BKB);
+    };
     const int KC = BWD ? 4 * p.kc0 : p.kc0, NSTEP = KC * 4;  // backward: (chunk, class) pairs
     {  // prologue: whole patch of chunk 0 + weights of step 0
         const Chunk ch0 = chunk_of(0);
@@ -2029,49 +2068,46 @@ __global__ __launch_bounds__(256, 2) void conv_up4_halo_kernel(const IgemmP p) {
                     }
             }
             // ---- MFMAs of tap (a, b) ----
-            const int a = s >> 1, b = s & 1;
+            const int a = s & 1, b = s >> 1;
             const char* bst = sB + (step & 1) * BSTAGE;
             if constexpr (SPLIT) {
-                i32x4 ah[TM], al[TM], bh[TN], bl[TN];
-#pragma unroll
-                for (int i = 0; i < TM; ++i) al[i] = *reinterpret_cast<const i32x4*>(sA + acur[1][b] + (i + a) * PW * BKB);
+                i32x4 bh[TN], bl[TN];  // (A: the window aw[0] = hi, aw[1] = lo; row block i = window row i + a)
+                a_load(1, b, a);
 #pragma unroll
                 for (int j = 0; j < TN; ++j) bh[j] = *reinterpret_cast<const i32x4*>(bst + boff0 + j * MS * BKB);
-#pragma unroll
-                for (int i = 0; i < TM; ++i) ah[i] = *reinterpret_cast<const i32x4*>(sA + acur[0][b] + (i + a) * PW * BKB);
+                a_load(0, b, a);
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
                     for (int j = 0; j < TN; ++j)
-                        acc[i][j] = DIRECT ? __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, bh[j]), __builtin_bit_cast(half8, al[i]), acc[i][j], 0, 0, 0)
-                                           : __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, al[i]), __builtin_bit_cast(half8, bh[j]), acc[i][j], 0, 0, 0);
+                        acc[i][j] = DIRECT ? __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, bh[j]), __builtin_bit_cast(half8, aw[1][(i + a) % TM]), acc[i][j], 0, 0, 0)
+                                           : __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, aw[1][(i + a) % TM]), __builtin_bit_cast(half8, bh[j]), acc[i][j], 0, 0, 0);
 #pragma unroll
                 for (int j = 0; j < TN; ++j) bl[j] = *reinterpret_cast<const i32x4*>(bst + boff1 + j * MS * BKB);
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
                     for (int j = 0; j < TN; ++j)
-                        acc[i][j] = DIRECT ? __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, bl[j]), __builtin_bit_cast(half8, ah[i]), acc[i][j], 0, 0, 0)
-                                           : __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, ah[i]), __builtin_bit_cast(half8, bl[j]), acc[i][j], 0, 0, 0);
+                        acc[i][j] = DIRECT ? __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, bl[j]), __builtin_bit_cast(half8, aw[0][(i + a) % TM]), acc[i][j], 0, 0, 0)
+                                           : __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, aw[0][(i + a) % TM]), __builtin_bit_cast(half8, bl[j]), acc[i][j], 0, 0, 0);
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
                     for (int j = 0; j < TN; ++j)
-                        acc[i][j] = DIRECT ? __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, bh[j]), __builtin_bit_cast(half8, ah[i]), acc[i][j], 0, 0, 0)
-                                           : __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, ah[i]), __builtin_bit_cast(half8, bh[j]), acc[i][j], 0, 0, 0);
+                        acc[i][j] = DIRECT ? __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, bh[j]), __builtin_bit_cast(half8, aw[0][(i + a) % TM]), acc[i][j], 0, 0, 0)
+                                           : __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, aw[0][(i + a) % TM]), __builtin_bit_cast(half8, bh[j]), acc[i][j], 0, 0, 0);
             } else {
 #pragma unroll
                 for (int v = 0; v < 2; ++v) {  // fp16 storage: two 32-k sub-steps per 64-channel chunk
-                    i32x4 fa16[TM], fb16[TN];
-#pragma unroll
-                    for (int i = 0; i < TM; ++i) fa16[i] = *reinterpret_cast<const i32x4*>(sA + acur[v][b] + (i + a) * PW * BKB);
+                    i32x4 fb16[TN];
+                    a_load(v, b, a);
 #pragma unroll
                     for (int j = 0; j < TN; ++j) fb16[j] = *reinterpret_cast<const i32x4*>(bst + (v ? boff1 : boff0) + j * MS * BKB);
 #pragma unroll
                     for (int i = 0; i < TM; ++i)
 #pragma unroll
                         for (int j = 0; j < TN; ++j)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, fa16[i]), __builtin_bit_cast(half8, fb16[j]), acc[i][j], 0, 0, 0);
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, aw[v][(i + a) % TM]), __builtin_bit_cast(half8, fb16[j]), acc[i][j], 0, 0, 0);
                 }
             }
             if constexpr (SPLIT) {

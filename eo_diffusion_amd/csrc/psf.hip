@@ -47,6 +47,38 @@ __global__ void __launch_bounds__(PSF_THREADS) psf_update_kernel(PsfArgs g, PsfT
     }
 }
 
+template <bool VEC, bool VECQ>
+__global__ void __launch_bounds__(PSF_THREADS) psf_residual_mix_kernel(PsfArgs g, PsfTaps t, PsfMix mx, long long items) {
+    __shared__ PsfResLds s;
+    for (long long item = blockIdx.x; item < items; item += gridDim.x) {
+        psf_residual_mix_phase<VEC, VECQ>(0, g, t, mx, s, item, threadIdx.x);
+        __syncthreads();
+        psf_residual_mix_phase<VEC, VECQ>(1, g, t, mx, s, item, threadIdx.x);
+        __syncthreads();
+        psf_residual_mix_phase<VEC, VECQ>(2, g, t, mx, s, item, threadIdx.x);
+        __syncthreads();
+        psf_residual_mix_phase<VEC, VECQ>(3, g, t, mx, s, item, threadIdx.x);
+        __syncthreads();
+    }
+}
+
+template <bool VEC, bool VECQ>
+__global__ void __launch_bounds__(PSF_THREADS) psf_update_mix_kernel(PsfArgs g, PsfTaps t, PsfMix mx, long long items) {
+    __shared__ PsfUpdLds s;
+    for (long long item = blockIdx.x; item < items; item += gridDim.x) {
+        psf_update_mix_phase<VEC, VECQ>(0, g, t, mx, s, item, threadIdx.x);
+        __syncthreads();
+        psf_update_mix_phase<VEC, VECQ>(1, g, t, mx, s, item, threadIdx.x);
+        __syncthreads();
+        psf_update_mix_phase<VEC, VECQ>(2, g, t, mx, s, item, threadIdx.x);
+        __syncthreads();
+        psf_update_mix_phase<VEC, VECQ>(3, g, t, mx, s, item, threadIdx.x);
+        __syncthreads();
+        psf_update_mix_phase<VEC, VECQ>(4, g, t, mx, s, item, threadIdx.x);
+        __syncthreads();
+    }
+}
+
 static inline bool psf_overlap(const float* a, long long na, const float* b, long long nb) {
     const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
     return pa < pb + (uintptr_t)nb * sizeof(float) && pb < pa + (uintptr_t)na * sizeof(float);
@@ -147,6 +179,94 @@ extern "C" int eod_psf_update(const float* p, const float* q, float step, const 
     else if (vec) hipLaunchKernelGGL((psf_update_kernel<true, false>), grid, block, 0, st, g, t, items);
     else if (vecq) hipLaunchKernelGGL((psf_update_kernel<false, true>), grid, block, 0, st, g, t, items);
     else hipLaunchKernelGGL((psf_update_kernel<false, false>), grid, block, 0, st, g, t, items);
+    EOD_CHECK_LAUNCH(what);
+    return EOD_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ through a band mix
+// what the three mixed entry points share: psf_common's refusals with the bands 0 .. K - 1 in the place of a channel list, K <= PSF_MAXK,
+// and the matrix (rows x cols, row pitch `pitch` inside PsfMix) by value
+static int psf_common_mix(const char* what, PsfArgs& g, PsfTaps& t, PsfMix& mx, const float* taps, const float* M, int rows, int cols, int pitch) {
+    EOD_REQUIRE(M, "%s: bad args", what);
+    EOD_REQUIRE(g.K >= 1 && g.K <= PSF_MAXK && g.K <= g.C, "%s: needs 1 <= K <= min(C, %d), got K = %d, C = %d", what, PSF_MAXK, g.K, g.C);
+    EOD_REQUIRE(g.C <= PSF_MAXC, "%s: at most %d channels (the matrix travels by value), got %d", what, PSF_MAXC, g.C);
+    int32_t bands[PSF_MAXK];
+    for (int k = 0; k < PSF_MAXK; ++k) bands[k] = k;
+    const int rc = psf_common(what, g, t, taps, bands);
+    if (rc != EOD_OK) return rc;
+    for (int c = 0; c < PSF_MAXC; ++c) g.kof[c] = 0;         // update: no copied plane, every channel takes its mix
+    for (int i = 0; i < PSF_MAXK * PSF_MAXC; ++i) mx.m[i] = 0.0f;
+    for (int i = 0; i < rows; ++i)
+        for (int j = 0; j < cols; ++j) {
+            const float v = M[i * cols + j];
+            EOD_REQUIRE(v - v == 0.0f, "%s: entry [%d][%d] = %g of the matrix is not finite", what, i, j, (double)v);
+            mx.m[i * pitch + j] = v;
+        }
+    return EOD_OK;
+}
+
+static int psf_residual_mix_launch(const char* what, PsfArgs g, const float* taps, const float* R, void* stream) {
+    PsfTaps t;
+    PsfMix mx;
+    const int rc = psf_common_mix(what, g, t, mx, taps, R, g.K, g.C, PSF_MAXC);
+    if (rc != EOD_OK) return rc;
+    const long long hw = (long long)g.H * g.W, chw = hw / (g.f * g.f);
+    const long long np = (long long)g.B * g.C * hw, nq = (long long)g.B * g.K * chw;
+    EOD_REQUIRE(!psf_overlap(g.out, nq, g.p, np), "%s: the output overlaps %s", what, g.values ? "p" : "x");
+    if (g.values) {
+        EOD_REQUIRE(g.lambda >= 0.0f && g.lambda <= 1.0f, "%s: the weight must lie in [0, 1], got %g", what, (double)g.lambda);
+        EOD_REQUIRE(!psf_overlap(g.out, nq, g.values, (long long)(g.values_b1 ? 1 : g.B) * g.K * chw), "%s: q overlaps values", what);
+        EOD_REQUIRE(!g.mask || !psf_overlap(g.out, nq, g.mask, (long long)(g.mask_b1 ? 1 : g.B) * chw), "%s: q overlaps mask", what);
+    }
+    const bool vec = g.W % 4 == 0 && eod_aligned16(g.p);
+    const bool vecq = (g.W / g.f) % 4 == 0 && eod_aligned16(g.out) && (!g.values || eod_aligned16(g.values)) && (!g.mask || eod_aligned16(g.mask));
+    const long long items = (long long)g.B * g.K * g.tiles_x * g.tiles_y;
+    const dim3 grid(psf_grid(items)), block(PSF_THREADS);
+    hipStream_t st = (hipStream_t)stream;
+    if (vec && vecq) hipLaunchKernelGGL((psf_residual_mix_kernel<true, true>), grid, block, 0, st, g, t, mx, items);
+    else if (vec) hipLaunchKernelGGL((psf_residual_mix_kernel<true, false>), grid, block, 0, st, g, t, mx, items);
+    else if (vecq) hipLaunchKernelGGL((psf_residual_mix_kernel<false, true>), grid, block, 0, st, g, t, mx, items);
+    else hipLaunchKernelGGL((psf_residual_mix_kernel<false, false>), grid, block, 0, st, g, t, mx, items);
+    EOD_CHECK_LAUNCH(what);
+    return EOD_OK;
+}
+
+extern "C" int eod_psf_residual_mix(const float* p, const float* values, const float* mask, float lambda, const float* taps, int r, int f,
+                                    const float* R, int K, int B, int C, int H, int W, int values_b1, int mask_b1, float* q, void* stream) {
+    EOD_REQUIRE(values, "psf_residual_mix: bad args");
+    PsfArgs g = {p, values, mask, nullptr, q, lambda, 0.0f, r, f, K, B, C, H, W, values_b1, mask_b1, 1, 0, 0, 0, {0}, {0}};
+    return psf_residual_mix_launch("psf_residual_mix", g, taps, R, stream);
+}
+
+extern "C" int eod_psf_apply_mix(const float* x, const float* taps, int r, int f, const float* R, int K, float* out, int B, int C, int H, int W,
+                                 void* stream) {
+    PsfArgs g = {x, nullptr, nullptr, nullptr, out, 0.0f, 0.0f, r, f, K, B, C, H, W, 0, 0, 1, 0, 0, 0, {0}, {0}};
+    return psf_residual_mix_launch("psf_apply_mix", g, taps, R, stream);
+}
+
+extern "C" int eod_psf_update_mix(const float* p, const float* q, float step, const float* taps, int r, int f, const float* G, int K, int B,
+                                  int C, int H, int W, float* out, void* stream) {
+    const char* what = "psf_update_mix";
+    EOD_REQUIRE(q, "%s: bad args", what);
+    PsfArgs g = {p, nullptr, nullptr, q, out, 0.0f, step, r, f, K, B, C, H, W, 0, 0, 0, 0, 0, 0, {0}, {0}};
+    PsfTaps t;
+    PsfMix mx;
+    const int rc = psf_common_mix(what, g, t, mx, taps, G, C, K, PSF_MAXK);
+    if (rc != EOD_OK) return rc;
+    EOD_REQUIRE(step - step == 0.0f && step > 0.0f, "%s: step must be finite and positive, got %g", what, (double)step);
+    const long long hw = (long long)H * W, chw = hw / (f * f);
+    const long long np = (long long)B * C * hw, nq = (long long)B * K * chw;
+    EOD_REQUIRE(!psf_overlap(out, np, p, np), "%s: out overlaps p (a tile's halo is read after its neighbours have written)", what);
+    EOD_REQUIRE(!psf_overlap(out, np, q, nq), "%s: out overlaps q", what);
+    const bool vec = W % 4 == 0 && eod_aligned16(p) && eod_aligned16(out);
+    const bool vecq = (W / f) % 4 == 0 && eod_aligned16(q);
+    const long long items = (long long)B * C * g.tiles_x * g.tiles_y;
+    const dim3 grid(psf_grid(items)), block(PSF_THREADS);
+    hipStream_t st = (hipStream_t)stream;
+    if (vec && vecq) hipLaunchKernelGGL((psf_update_mix_kernel<true, true>), grid, block, 0, st, g, t, mx, items);
+    else if (vec) hipLaunchKernelGGL((psf_update_mix_kernel<true, false>), grid, block, 0, st, g, t, mx, items);
+    else if (vecq) hipLaunchKernelGGL((psf_update_mix_kernel<false, true>), grid, block, 0, st, g, t, mx, items);
+    else hipLaunchKernelGGL((psf_update_mix_kernel<false, false>), grid, block, 0, st, g, t, mx, items);
     EOD_CHECK_LAUNCH(what);
     return EOD_OK;
 }

@@ -13,6 +13,7 @@
 #define PSF_THREADS 256
 #define PSF_MAXT 32                        // the largest tile edge in full-resolution pixels
 #define PSF_ROWS (PSF_MAXT + 2 * PSF_MAXR)  // 56: a tile with its halo
+#define PSF_MAXK 8                         // observed bands of a mixed observation (EOD_SPEC_MAXK of csrc/sampler.hip)
 #define PSF_PITCH 64                       // row pitch of a buffer filled by aligned quads: 56 + up to 3 leading columns, rounded up to a quad
 
 typedef float psf_f4 __attribute__((ext_vector_type(4)));
@@ -49,6 +50,11 @@ struct PsfUpdLds {
     float w[PSF_ROWS * PSF_ROWS];       // w over the tile and its halo, out-of-plane 0
     float hbuf[PSF_ROWS * PSF_MAXT];
     float nh[PSF_ROWS], nv[PSF_ROWS];
+};
+
+// the mixing matrix of eod_psf_*_mix, by value: R[k][c] at m[k * PSF_MAXC + c] (residual), G[c][k] at m[c * PSF_MAXK + k] (update)
+struct PsfMix {
+    float m[PSF_MAXK * PSF_MAXC];
 };
 
 // conv of a line of ones of length L at position x: the contract's nh / nv
@@ -290,4 +296,120 @@ PSF_FN void psf_update_phase(int phase, const PsfArgs& g, const PsfTaps& t, PsfU
             }
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------------ the same through a band mix (section 9.10)
+// (m[0] * x_0) + (m[1] * x_1) + ... over n planes `stride` apart, a quad at a time, the adds in index order.  The planes are taken four
+// at a time with the four loads issued before the first of them is used (the tests on n are wave-uniform): one plane per trip leaves a
+// single load in flight per thread, and the staging loop is then bound by the latency of n dependent round trips.
+PSF_FN psf_f4 psf_mix_quads(const float* base, long long stride, const float* m, int n) {
+    psf_f4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+    for (int i = 0; i < n; i += 4) {
+        const int left = n - i;
+        const psf_f4 z = {0.0f, 0.0f, 0.0f, 0.0f};
+        const psf_f4 a = *reinterpret_cast<const psf_f4*>(base + i * stride);
+        const psf_f4 b = left > 1 ? *reinterpret_cast<const psf_f4*>(base + (i + 1) * stride) : z;
+        const psf_f4 c = left > 2 ? *reinterpret_cast<const psf_f4*>(base + (i + 2) * stride) : z;
+        const psf_f4 d = left > 3 ? *reinterpret_cast<const psf_f4*>(base + (i + 3) * stride) : z;
+        const float ma = m[i];
+        const psf_f4 pa = {ma * a[0], ma * a[1], ma * a[2], ma * a[3]};
+        if (i == 0) v = pa;
+        else { v[0] = v[0] + pa[0]; v[1] = v[1] + pa[1]; v[2] = v[2] + pa[2]; v[3] = v[3] + pa[3]; }
+        if (left > 1) { const float mb = m[i + 1]; const psf_f4 pb = {mb * b[0], mb * b[1], mb * b[2], mb * b[3]};
+                        v[0] = v[0] + pb[0]; v[1] = v[1] + pb[1]; v[2] = v[2] + pb[2]; v[3] = v[3] + pb[3]; }
+        if (left > 2) { const float mc = m[i + 2]; const psf_f4 pc = {mc * c[0], mc * c[1], mc * c[2], mc * c[3]};
+                        v[0] = v[0] + pc[0]; v[1] = v[1] + pc[1]; v[2] = v[2] + pc[2]; v[3] = v[3] + pc[3]; }
+        if (left > 3) { const float md = m[i + 3]; const psf_f4 pd = {md * d[0], md * d[1], md * d[2], md * d[3]};
+                        v[0] = v[0] + pd[0]; v[1] = v[1] + pd[1]; v[2] = v[2] + pd[2]; v[3] = v[3] + pd[3]; }
+    }
+    return v;
+}
+
+// q_k = lm * (D_f (blur(u_k) / n) - values_k), u_k = sum_c R[k][c] * p_c: phase 0 stages u_k (the channel planes quad by quad, the running
+// sum in registers, LDS written once); phases 1 .. 3 are psf_residual_phase's on the staged patch.  g.K bands, g.mask_c1 = 1.
+template <bool VEC, bool VECQ>
+PSF_FN void psf_residual_mix_phase(int phase, const PsfArgs& g, const PsfTaps& t, const PsfMix& mx, PsfResLds& s, long long item, int tid) {
+    if (phase != 0) {
+        psf_residual_phase<VEC, VECQ>(phase, g, t, s, item, tid);
+        return;
+    }
+    const PsfTile tl = psf_tile_of(g, item);
+    const int r = g.r, ft = tl.ft, y0 = tl.y0, x0 = tl.x0;
+    const int b = (int)(tl.plane / g.K), k = (int)(tl.plane % g.K);
+    const int rows = ft + 2 * r;
+    const int xs = (x0 - r) & ~3;
+    const int lead = x0 - r - xs;
+    const long long hw = (long long)g.H * g.W;
+    const float* src = g.p + (long long)b * g.C * hw;
+    const float* R = mx.m + k * PSF_MAXC;
+    const int nq = (lead + ft + 2 * r + 3) / 4;
+    for (int idx = tid; idx < rows * nq; idx += PSF_THREADS) {
+        const int row = idx / nq, qd = idx % nq;
+        const int gy = y0 - r + row, gx = xs + 4 * qd;
+        psf_f4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (gy >= 0 && gy < g.H) {
+            const long long at = (long long)gy * g.W + gx;
+            if (VEC) {
+                if (gx >= 0 && gx < g.W) v = psf_mix_quads(src + at, hw, R, g.C);   // W % 4 == 0: a whole quad
+            } else {
+                for (int j = 0; j < 4; ++j)
+                    if (gx + j >= 0 && gx + j < g.W) {
+                        float u = R[0] * src[at + j];
+                        for (int c = 1; c < g.C; ++c) {
+                            const float pr = R[c] * src[c * hw + at + j];
+                            u = u + pr;
+                        }
+                        v[j] = u;
+                    }
+            }
+        }
+        *reinterpret_cast<psf_f4*>(s.patch + row * PSF_PITCH + 4 * qd) = v;
+    }
+    if (tid < ft) s.nh[tid] = psf_norm(t, r, x0 + tid, g.W);
+    else if (tid >= 64 && tid < 64 + ft) s.nv[tid - 64] = psf_norm(t, r, y0 + tid - 64, g.H);
+}
+
+// out_c = p_c - blur((replicate(s_c) * step) / n), s_c = sum_k G[c][k] * q_k: phase 0 stages s_c over the tile's coarse pixels and their
+// halo; phases 1 .. 4 are psf_update_phase's.  Every channel is written (g.kof[c] = 0 for all c: no copied plane).
+template <bool VEC, bool VECQ>
+PSF_FN void psf_update_mix_phase(int phase, const PsfArgs& g, const PsfTaps& t, const PsfMix& mx, PsfUpdLds& s, long long item, int tid) {
+    if (phase != 0) {
+        psf_update_phase<VEC, VECQ>(phase, g, t, s, item, tid);
+        return;
+    }
+    const PsfTile tl = psf_tile_of(g, item);
+    const int c = (int)(tl.plane % g.C), b = (int)(tl.plane / g.C);
+    const int r = g.r, f = g.f, ft = tl.ft, y0 = tl.y0, x0 = tl.x0;
+    const int rows = ft + 2 * r;
+    const int Hc = g.H / f, Wc = g.W / f;
+    const int ylo = y0 - r < 0 ? 0 : y0 - r, xlo = x0 - r < 0 ? 0 : x0 - r;
+    const int yhi = y0 + ft + r > g.H ? g.H : y0 + ft + r, xhi = x0 + ft + r > g.W ? g.W : x0 + ft + r;
+    const int cy0 = ylo / f, cx0 = xlo / f, cy1 = (yhi - 1) / f, cx1 = (xhi - 1) / f;
+    const int cxs = cx0 & ~3;
+    const long long chw = (long long)Hc * Wc;
+    const float* src = g.q + (long long)b * g.K * chw;
+    const float* G = mx.m + c * PSF_MAXK;
+    const int nq = (cx1 - cxs) / 4 + 1, qrows = cy1 - cy0 + 1;
+    for (int idx = tid; idx < qrows * nq; idx += PSF_THREADS) {
+        const int row = idx / nq, qd = idx % nq;
+        const int gy = cy0 + row, gx = cxs + 4 * qd;
+        const long long at = (long long)gy * Wc + gx;
+        psf_f4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (VECQ) {                                             // gx <= cx1 < Wc, Wc % 4 == 0: a whole quad
+            v = psf_mix_quads(src + at, chw, G, g.K);
+        } else {
+            for (int j = 0; j < 4; ++j)
+                if (gx + j < Wc) {
+                    float u = G[0] * src[at + j];
+                    for (int k = 1; k < g.K; ++k) {
+                        const float pr = G[k] * src[k * chw + at + j];
+                        u = u + pr;
+                    }
+                    v[j] = u;
+                }
+        }
+        *reinterpret_cast<psf_f4*>(s.qs + row * PSF_PITCH + 4 * qd) = v;
+    }
+    if (tid < rows) s.nh[tid] = psf_norm(t, r, x0 - r + tid, g.W);
+    else if (tid >= 64 && tid < 64 + rows) s.nv[tid - 64] = psf_norm(t, r, y0 - r + tid - 64, g.H);
 }

@@ -19,6 +19,9 @@ takes `iters` Landweber steps p <- p - weight * tau * A^T(mask * (A p - values))
 csrc/psf.hip).  It is a link like the others; alone it runs as a chain of one through the unfused ends.  With solver="cg" (DESIGN.md
 section 9.9) the link lands on its constraint instead: p - weight * A^T z with (M A A^T M + damping I) z = mask * (A p - values) solved by
 `iters` conjugate-gradient iterations on the coarse grid (eod_psf_cg; csrc/psf_cg.hip), where A A^T is a separable banded stencil (psf_gram).
+With `response=` [K, C] the link observes K band mixes through the PSF, A = R (x) A_s: a panchromatic band with its
+own MTF, a second sensor's broad bands on that sensor's grid (eod_psf_residual_mix, eod_psf_update_mix; M A A^T M = (R R^T) (x) (M_s G M_s), so
+the exact projection stays K independent plane solves of the unchanged eod_psf_cg).
 
 The ancestral samplers (EODiffusion.sampling / sampling_scene) take the same observations through ddpm_step below:
 eod_ddpm_pred_x0, every link's project(k, p) in order, eod_ddpm_step_p0 -- the clipped DDPM step cut where its prediction is complete.
@@ -107,6 +110,17 @@ def _response(what, response):
     if not np.isfinite(R).all():
         raise _lib.EodError(f"{what}: `response` has a non-finite entry (as float32)")
     return R
+
+
+def _conditioned(what, response):
+    """(R, pinv): _response's fp32 [K, C] under the conditioning rule (sigma_min >= MIN_RCOND sigma_max, float64 SVD of the fp32 entries) and
+    its float64 pseudo-inverse [C, K] rounded once to fp32"""
+    R = _response(what, response)
+    sv = np.linalg.svd(R.astype(np.float64), compute_uv=False)
+    if not (sv[0] > 0.0 and sv[-1] >= MIN_RCOND * sv[0]):
+        raise _lib.EodError(f"{what}: `response` is too badly conditioned to project with in fp32 (sigma_min {sv[-1]:.3g} < "
+                            f"{MIN_RCOND:g} * sigma_max {sv[0]:.3g}); rows must be linearly independent")
+    return R, np.ascontiguousarray(np.linalg.pinv(R.astype(np.float64)), dtype=np.float32)
 
 
 def _factor(what, factor):
@@ -241,13 +255,8 @@ class SpectralObservation:
 
     def __init__(self, values, response, factor=1, mask=None, weight=1.0):
         what = "SpectralObservation"
-        self.response = _response(what, response)
+        self.response, self.pinv = _conditioned(what, response)
         K, C = self.response.shape
-        sv = np.linalg.svd(self.response.astype(np.float64), compute_uv=False)
-        if not (sv[0] > 0.0 and sv[-1] >= MIN_RCOND * sv[0]):
-            raise _lib.EodError(f"{what}: `response` is too badly conditioned to project with in fp32 (sigma_min {sv[-1]:.3g} < "
-                                f"{MIN_RCOND:g} * sigma_max {sv[0]:.3g}); rows must be linearly independent")
-        self.pinv = np.ascontiguousarray(np.linalg.pinv(self.response.astype(np.float64)), dtype=np.float32)
         self.factor = _factor(what, factor)
         v = torch.as_tensor(values)
         if v.dtype != torch.float32:
@@ -476,13 +485,27 @@ class PsfObservation:
     increasing channel numbers; mask None or [B or 1, K or 1, H / f, W / f] fp32; weight as for Observation.  solver "landweber" (the
     default): iters 1 .. 8 Landweber steps per evaluation, which approach the constraint set.  solver "cg": iters 1 .. 64 conjugate-gradient
     iterations of the exact projection per evaluation, p - weight * A^T (M A A^T M + damping I)^-1 mask (A p - values); the mask must then
-    be 0 or 1 exactly, and damping (a float >= 0, or one per evaluation) is the Tikhonov term for noisy values."""
+    be 0 or 1 exactly, and damping (a float >= 0, or one per evaluation) is the Tikhonov term for noisy values.
 
-    def __init__(self, values, psf, factor, channels=None, mask=None, weight=1.0, iters=1, solver="landweber", damping=0.0):
+    response: None, or array-like [K, C] under SpectralObservation's rules (K <= min(C, 8), C <= 32, finite, sigma_min >= 1e-3 sigma_max):
+    the K observed bands are the mixes sum_c response[k][c] * channel c seen through the ONE operator above, A = R (x) A_s (a panchromatic
+    band with its own MTF; another sensor's broad bands on its grid).  Not together with `channels`; values then has K planes and the mask
+    is [B or 1, 1, H / f, W / f], one for all bands.  `pinv` [C, K] is the float64 pseudo-inverse rounded once to fp32.  solver "cg":
+    M A A^T M = (R R^T) (x) (M_s G M_s), so the projection is p - weight * (pinv(R) (x) A_s^T (M_s G M_s + damping I)^-1) mask (A p - values),
+    K independent plane solves.  The damped system is therefore (R R^T) (x) (M_s G M_s + damping I): the Tikhonov term is scaled by each
+    band's response energy -- for orthonormal rows it is the unmixed form, for one band it is damping * |r|^2.  solver "landweber": the
+    step size is psf_tau / sigma_max(R)^2 (float64 SVD of the fp32 entries), soft masks allowed as before."""
+
+    def __init__(self, values, psf, factor, channels=None, mask=None, weight=1.0, iters=1, solver="landweber", damping=0.0, response=None):
         what = "PsfObservation"
         self.taps = _taps(what, psf)
         self.factor = _factor(what, factor)
         self.channels = None if channels is None else _channels(what, channels)
+        self.response = self.pinv = None
+        if response is not None:
+            if channels is not None:
+                raise _lib.EodError(f"{what}: `response` mixes all channels of the state; it cannot be given together with `channels`")
+            self.response, self.pinv = _conditioned(what, response)
         if not isinstance(solver, str) or solver not in SOLVERS:
             raise _lib.EodError(f"{what}: `solver` is one of {SOLVERS}, got {solver!r}")
         self.solver = solver
@@ -496,6 +519,9 @@ class PsfObservation:
         v = torch.as_tensor(values)
         if v.dtype != torch.float32:
             raise _lib.EodError(f"{what}: `values` must be float32, got {v.dtype}")
+        if self.response is not None and (v.dim() != 4 or 0 in v.shape or v.shape[1] != self.response.shape[0]):
+            raise _lib.EodError(f"{what}: `values` must be [B or 1, {self.response.shape[0]}, H / f, W / f] (`response` has "
+                                f"{self.response.shape[0]} rows), got {tuple(v.shape)}")
         if v.dim() != 4 or 0 in v.shape or v.shape[1] > MAX_CHANNELS or (self.channels is not None and v.shape[1] != len(self.channels)):
             want = "K <= 32" if self.channels is None else str(len(self.channels))
             raise _lib.EodError(f"{what}: `values` must be [B or 1, {want}, H / f, W / f] on the coarse grid, got {tuple(v.shape)}")
@@ -506,6 +532,9 @@ class PsfObservation:
                 raise _lib.EodError(f"{what}: `mask` must be float32, got {mask.dtype}")
             if mask.dim() != 4 or mask.shape[1] not in (1, K) or tuple(mask.shape[2:]) != (Hc, Wc):
                 raise _lib.EodError(f"{what}: `mask` must be [B or 1, {K} or 1, {Hc}, {Wc}] on the coarse grid, got {tuple(mask.shape)}")
+            if self.response is not None and mask.shape[1] != 1:
+                raise _lib.EodError(f"{what}: with `response` the `mask` must be [B or 1, 1, {Hc}, {Wc}] (one mask for all {K} bands: per-band "
+                                    f"masks break the factorisation of A A^T), got {tuple(mask.shape)}")
             if 1 not in (v.shape[0], mask.shape[0]) and v.shape[0] != mask.shape[0]:
                 raise _lib.EodError(f"{what}: `values` is for {v.shape[0]} samples, `mask` for {mask.shape[0]}")
             if solver == "cg" and not bool(((mask == 0.0) | (mask == 1.0)).all()):
@@ -519,7 +548,11 @@ class PsfObservation:
         K, f = int(self.values.shape[1]), self.factor
         if C > MAX_CHANNELS:
             raise _lib.EodError(f"{what}: a PsfObservation takes a state of at most {MAX_CHANNELS} channels, got {C}")
-        if self.channels is None:
+        if self.response is not None:
+            if self.response.shape[1] != C:
+                raise _lib.EodError(f"{what}: the PsfObservation's `response` mixes {self.response.shape[1]} channels, the state has {C}")
+            channels = None
+        elif self.channels is None:
             if K != C:
                 raise _lib.EodError(f"{what}: the PsfObservation observes all channels (`channels` is None) and has {K}, the state has {C}")
             channels = tuple(range(C))
@@ -549,10 +582,18 @@ class BoundPsf:
     def __init__(self, obs, shape, channels, n_evaluations, device):
         B, C, H, W = shape
         self.shape, self.factor, self.iters, self.channels = shape, obs.factor, obs.iters, channels
-        self.K, self.r = len(channels), obs.taps.size // 2
+        self.r = obs.taps.size // 2
         self.tau = psf_tau(obs.taps, obs.factor, H, W)
+        self.mixed = obs.response is not None
+        if self.mixed:                                 # A = R (x) A_s: ||A|| = sigma_max(R) ||A_s||; the Landweber adjoint mixes by R^T, cg by pinv(R)
+            self.K = obs.response.shape[0]
+            self.tau /= float(np.linalg.svd(obs.response.astype(np.float64), compute_uv=False)[0]) ** 2
+            self.c_R = _c_floats(obs.response)
+            self.c_G = _c_floats(obs.pinv if obs.solver == "cg" else np.ascontiguousarray(obs.response.T))
+        else:
+            self.K, self.c_channels = len(channels), _c_ints(channels)
         self.step = float(np.float32(self.tau / (obs.factor * obs.factor)))
-        self.c_taps, self.c_channels = _c_floats(obs.taps), _c_ints(channels)
+        self.c_taps = _c_floats(obs.taps)
         self.values = f32c(obs.values.to(device))
         self.mask = None if obs.mask is None else f32c(obs.mask.to(device))
         self.weights = obs.weights if obs.per_evaluation else obs.weights * n_evaluations
@@ -571,6 +612,12 @@ class BoundPsf:
             raise _lib.EodError(f"observation bound to a state of shape {self.shape}, the step got {tuple(p.shape)}")
         B, C, H, W = self.shape
         m = self.mask
+        if self.mixed:
+            _lib.check(_lib.lib().eod_psf_residual_mix(p.data_ptr(), self.values.data_ptr(), _lib.ptr(m), self.weights[i] if weight is None else weight,
+                                                       self.c_taps, self.r, self.factor, self.c_R, self.K, B, C, H, W,
+                                                       int(self.values.shape[0] != B), int(m is not None and m.shape[0] != B),
+                                                       q.data_ptr(), current_stream_ptr(p.device)), "eod_psf_residual_mix")
+            return q
         _lib.check(_lib.lib().eod_psf_residual(p.data_ptr(), self.values.data_ptr(), _lib.ptr(m), self.weights[i] if weight is None else weight,
                                                self.c_taps, self.r, self.factor,
                                                self.c_channels, self.K, B, C, H, W, int(self.values.shape[0] != B),
@@ -579,8 +626,12 @@ class BoundPsf:
         return q
 
     def update(self, p, q, out, step=None):
-        """out = p - tau A^T q: eod_psf_update"""
+        """out = p - tau A^T q: eod_psf_update (with a response: eod_psf_update_mix, the coarse planes mixed by R^T or, under cg, pinv(R))"""
         B, C, H, W = self.shape
+        if self.mixed:
+            _lib.check(_lib.lib().eod_psf_update_mix(p.data_ptr(), q.data_ptr(), self.step if step is None else step, self.c_taps, self.r, self.factor,
+                                                     self.c_G, self.K, B, C, H, W, out.data_ptr(), current_stream_ptr(p.device)), "eod_psf_update_mix")
+            return out
         _lib.check(_lib.lib().eod_psf_update(p.data_ptr(), q.data_ptr(), self.step if step is None else step, self.c_taps, self.r, self.factor, self.c_channels, self.K,
                                              B, C, H, W, out.data_ptr(), current_stream_ptr(p.device)), "eod_psf_update")
         return out
@@ -610,7 +661,7 @@ class BoundPsf:
         m = self.mask
         _lib.check(L.eod_psf_cg(c.data_ptr(), _lib.ptr(m), self.dampings[i], self.weights[i], self.gy.data_ptr(), self.gx.data_ptr(), self.band,
                                 self.iters, B, self.K, Hc, Wc, int(m is not None and m.shape[0] != B),
-                                int(m is not None and m.shape[1] != self.K), q.data_ptr(), self._cg.data_ptr(), self._cg.numel(),
+                                int(m is not None and (self.mixed or m.shape[1] != self.K)), q.data_ptr(), self._cg.data_ptr(), self._cg.numel(),
                                 current_stream_ptr(c.device)), "eod_psf_cg")
         return q
 
@@ -756,16 +807,31 @@ def spectral_response(x, response, factor=1):
     return out
 
 
-def psf_observe(x, psf, factor, channels=None):
+def psf_observe(x, psf, factor, channels=None, response=None):
     """A x on the GPU (eod_psf_apply): [B, K, H / f, W / f], the channels `channels` (None: all) of x [B, C, H, W] blurred by the
     renormalised zero-padded separable PSF and averaged over factor x factor blocks.  Makes a PsfObservation's `values` out of an image,
-    and measures how far a result is from one."""
+    and measures how far a result is from one.  With `response` [K, C] (not together with `channels`): the K band mixes of x seen that
+    way (eod_psf_apply_mix)."""
     what = "psf_observe"
     h = _taps(what, psf)
     f = _factor(what, factor)
     if not torch.is_tensor(x) or x.dim() != 4 or not 1 <= x.shape[1] <= MAX_CHANNELS:
         raise _lib.EodError(f"{what}: x must be a tensor [B, C <= {MAX_CHANNELS}, H, W]")
     B, C, H, W = (int(d) for d in x.shape)
+    if response is not None:
+        if channels is not None:
+            raise _lib.EodError(f"{what}: `response` mixes all channels of x; it cannot be given together with `channels`")
+        R = _response(what, response)
+        if R.shape[1] != C:
+            raise _lib.EodError(f"{what}: `response` mixes {R.shape[1]} channels, x has {C}")
+        if H % f or W % f:
+            raise _lib.EodError(f"{what}: factor = {f} does not divide {H} x {W}")
+        require_gpu(x, what)
+        x = f32c(x)
+        out = torch.empty((B, R.shape[0], H // f, W // f), device=x.device, dtype=torch.float32)
+        _lib.check(_lib.lib().eod_psf_apply_mix(x.data_ptr(), _c_floats(h), h.size // 2, f, _c_floats(R), R.shape[0], out.data_ptr(), B, C, H, W,
+                                                current_stream_ptr(x.device)), "eod_psf_apply_mix")
+        return out
     cs = tuple(range(C)) if channels is None else _channels(what, channels)
     if cs[-1] >= C:
         raise _lib.EodError(f"{what}: channel {cs[-1]} of an x with {C} channels")

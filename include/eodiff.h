@@ -35,7 +35,7 @@ const char* eod_last_error(void);
  * buffer of eod_pack_conv_weight_split, the 4-int state of eod_adamw_step_guarded).  eod_version() returns the value the library was built
  * with; a binding compares it with the header it mirrors at load time (eo_diffusion_amd/_lib.py does) instead of finding out by an
  * out-of-bounds device write. */
-#define EOD_ABI_VERSION 113
+#define EOD_ABI_VERSION 114
 int eod_version(void);
 /* Kernel-selection options ("skip_fuse", "head", "halo_bn256", "halo_splitk", "first", "s2_halo": 1 / 0; "gn_fuse_max_cout": n, -1 = default;
  * "halo_tpw": pixel tiles per workgroup of the streaming halo instances, 1 = off = default, 0 = chosen per launch; "head_tpw": the same of
@@ -466,6 +466,29 @@ int eod_psf_apply(const float* x, const float* taps, int r, int f, const int32_t
                   void* stream);
 int eod_psf_update(const float* p, const float* q, float step, const float* taps, int r, int f, const int32_t* channels, int K, int B, int C,
                    int H, int W, float* out, void* stream);
+/* Cross-band PSF observations (no reference line): K bands, each a known linear mix R [K][C] of the C channels of
+ * p [B][C][H][W], seen through ONE operator A_s = D_f N^-1 B0 (the taps, f and contract of the block above) under ONE coarse mask:
+ * A = R (x) A_s.  R [K][C] and G [C][K] are HOST arrays of finite fp32 read during the call and handed to the kernels by value like the
+ * taps: nothing is allocated, copied or synchronised, the calls can be captured in a graph.  Per pixel, every operation rounded once in
+ * fp32, the order a property of the pixel alone (not of B, the alignment, the tile, the launch geometry, batch or scene):
+ *   u_k[y][x] = R[k][0] * p_0[y][x];  then for c = 1 .. C-1 in order:  u_k = u_k + (R[k][c] * p_c[y][x])     in-plane; outside the plane +0.0f
+ *   b = blur(u_k) / n;  mean = block sum of b / (float)(f * f);  q_k = lm * (mean - values_k),  lm = lambda * m      (the lines above, unchanged)
+ *   s_c[Y][X] = G[c][0] * q_0[Y][X];  then for k = 1 .. K-1 in order:  s_c = s_c + (G[c][k] * q_k[Y][X])     coarse grid
+ *   w[y][x]   = (s_c[y / f][x / f] * step) / n[y][x];   out_c = p_c - blur(w)                                 (the lines above, unchanged)
+ * Every product is formed, zeros of R or G included; eod_psf_update_mix writes every channel (a zero row of G: out_c = p_c - blur(0) = p_c
+ * for finite q).  With the rows of R rows of the identity and G = R^T the pair has the bits of eod_psf_residual / eod_psf_update with that
+ * channel list.  eod_psf_residual_mix: q [B][K][H/f][W/f] from p, values [B or 1][K][H/f][W/f], mask NULL or [B or 1][1][H/f][W/f] (one mask
+ * for all K bands).  eod_psf_apply_mix: out [B][K][H/f][W/f] = mean, the operator alone.  eod_psf_update_mix: out [B][C][H][W] from p and
+ * q [B][K][H/f][W/f].  With G = pinv(R), q the result of eod_psf_cg on the K residual planes (shared mask) and step = fp32(1 / f^2) the
+ * triple is the exact projection onto {M A p = M values}: M A A^T M = (R R^T) (x) (M_s G_s M_s) factorises plane by plane.
+ * EOD_EINVAL with nothing launched: the refusals of eod_psf_residual / eod_psf_update, K outside 1 .. min(C, 8), C > 32, R / G null or
+ * with a non-finite entry.  One launch each; the access forms and the striding are those of the block above. */
+int eod_psf_residual_mix(const float* p, const float* values, const float* mask, float lambda, const float* taps, int r, int f,
+                         const float* R, int K, int B, int C, int H, int W, int values_b1, int mask_b1, float* q, void* stream);
+int eod_psf_apply_mix(const float* x, const float* taps, int r, int f, const float* R, int K, float* out, int B, int C, int H, int W,
+                      void* stream);
+int eod_psf_update_mix(const float* p, const float* q, float step, const float* taps, int r, int f, const float* G, int K, int B, int C,
+                       int H, int W, float* out, void* stream);
 /* The exact PSF data consistency (no reference line): conjugate gradients on the COARSE grid [Hc][Wc] = [H / f][W / f],
  * one independent system per plane (sample b, observed channel k):
  *   S z = c,   S = M G M + mu I,   M = diag(m), m in {0, 1} (mask NULL: 1),   G = A A^T = G_H (x) G_W

@@ -159,6 +159,11 @@ SYMBOLS = {
     "eod_psf_residual_mix": (i32, [vp, vp, vp, f32, C.POINTER(f32), i32, i32, C.POINTER(f32), i32, i32, i32, i32, i32, i32, i32, vp, vp]),
     "eod_psf_apply_mix": (i32, [vp, C.POINTER(f32), i32, i32, C.POINTER(f32), i32, vp, i32, i32, i32, i32, vp]),
     "eod_psf_update_mix": (i32, [vp, vp, f32, C.POINTER(f32), i32, i32, C.POINTER(f32), i32, i32, i32, i32, i32, vp, vp]),
+    "eod_psf_residual_xy": (i32, [vp, vp, vp, f32, C.POINTER(f32), i32, C.POINTER(f32), i32, i32, C.POINTER(i32), C.POINTER(f32), i32, i32, i32, i32, i32,
+                                  i32, i32, i32, vp, vp]),
+    "eod_psf_apply_xy": (i32, [vp, C.POINTER(f32), i32, C.POINTER(f32), i32, i32, C.POINTER(i32), C.POINTER(f32), i32, vp, i32, i32, i32, i32, vp]),
+    "eod_psf_update_xy": (i32, [vp, vp, f32, C.POINTER(f32), i32, C.POINTER(f32), i32, i32, C.POINTER(i32), C.POINTER(f32), i32, i32, i32, i32, i32,
+                                vp, vp]),
     "eod_psf_cg_workspace_size": (i64, [i32, i32, i32, i32]),
     "eod_psf_gram": (i32, [vp, vp, f32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i64, vp]),
     "eod_psf_cg": (i32, [vp, vp, f32, f32, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i64, vp]),
@@ -200,7 +205,7 @@ class EodError(RuntimeError):
     pass
 
 
-ABI_VERSION = 114  # EOD_ABI_VERSION of the include/eodiff.h this file mirrors
+ABI_VERSION = 115  # EOD_ABI_VERSION of the include/eodiff.h this file mirrors
 SPEC_GRID_BLOCKS = 4096  # EOD_SPEC_GRID_BLOCKS there
 
 

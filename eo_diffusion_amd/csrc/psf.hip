@@ -9,7 +9,8 @@
 // the horizontal pass into a second buffer, then the vertical pass.  Work items (plane, tile) beyond EOD_PSF_GRID_BLOCKS are taken by
 // striding.  Taps, the channel list and its inverse travel by value in the kernel arguments; nothing is allocated, copied or
 // synchronised.  VEC: 16-byte accesses of the full-resolution tensors (W % 4 == 0, pointers aligned); VECQ: of the coarse ones
-// (W / f % 4 == 0, pointers aligned); the element-wise forms run the same arithmetic.
+// (W / f % 4 == 0, pointers aligned); the element-wise forms run the same arithmetic.  The last block of the file is the general form of
+// section 9.11: one tap vector per axis, asymmetric taps allowed, a halo of ry rows and rx columns (eod_psf_*_xy).
 #include "common.h"
 
 #define PSF_FN __device__ __host__ __forceinline__
@@ -267,6 +268,164 @@ extern "C" int eod_psf_update_mix(const float* p, const float* q, float step, co
     else if (vec) hipLaunchKernelGGL((psf_update_mix_kernel<true, false>), grid, block, 0, st, g, t, mx, items);
     else if (vecq) hipLaunchKernelGGL((psf_update_mix_kernel<false, true>), grid, block, 0, st, g, t, mx, items);
     else hipLaunchKernelGGL((psf_update_mix_kernel<false, false>), grid, block, 0, st, g, t, mx, items);
+    EOD_CHECK_LAUNCH(what);
+    return EOD_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ one tap vector per axis
+// The same tile, access forms and stride loop; the halo is ry rows and rx columns.  One kernel per pair serves the plain and the mixed form
+// (MIX: the matrix by value, as above; the plain form passes it zeroed and never reads it).  That costs the plain launches a 1 KB kernel
+// argument nobody reads (about 1.4 KB in all, well inside the 4 KB limit, still by value and so graph-capturable) and 256 host stores
+// per call: noise next to a launch, and the price of one signature for both forms instead of a second set of launch lines.
+template <bool VEC, bool VECQ, bool MIX>
+__global__ void __launch_bounds__(PSF_THREADS) psf_residual_xy_kernel(PsfArgs g, PsfTapsXy tt, PsfMix mx, long long items) {
+    __shared__ PsfResLds s;
+    for (long long item = blockIdx.x; item < items; item += gridDim.x) {
+        psf_residual_xy_phase<VEC, VECQ, MIX>(0, g, tt, &mx, s, item, threadIdx.x);
+        __syncthreads();
+        psf_residual_xy_phase<VEC, VECQ, MIX>(1, g, tt, &mx, s, item, threadIdx.x);
+        __syncthreads();
+        psf_residual_xy_phase<VEC, VECQ, MIX>(2, g, tt, &mx, s, item, threadIdx.x);
+        __syncthreads();
+        psf_residual_xy_phase<VEC, VECQ, MIX>(3, g, tt, &mx, s, item, threadIdx.x);
+        __syncthreads();
+    }
+}
+
+template <bool VEC, bool VECQ, bool MIX>
+__global__ void __launch_bounds__(PSF_THREADS) psf_update_xy_kernel(PsfArgs g, PsfTapsXy tt, PsfMix mx, long long items) {
+    __shared__ PsfUpdLds s;
+    for (long long item = blockIdx.x; item < items; item += gridDim.x) {
+        psf_update_xy_phase<VEC, VECQ, MIX>(0, g, tt, &mx, s, item, threadIdx.x);
+        __syncthreads();
+        psf_update_xy_phase<VEC, VECQ, MIX>(1, g, tt, &mx, s, item, threadIdx.x);
+        __syncthreads();
+        psf_update_xy_phase<VEC, VECQ, MIX>(2, g, tt, &mx, s, item, threadIdx.x);
+        __syncthreads();
+        psf_update_xy_phase<VEC, VECQ, MIX>(3, g, tt, &mx, s, item, threadIdx.x);
+        __syncthreads();
+        psf_update_xy_phase<VEC, VECQ, MIX>(4, g, tt, &mx, s, item, threadIdx.x);
+        __syncthreads();
+    }
+}
+
+// one axis' taps into t, forward or reversed: psf_common's rules without the symmetry
+static int psf_axis_taps(const char* what, const char* axis, PsfTaps& t, const float* taps, int r, bool reversed) {
+    EOD_REQUIRE(taps, "%s: bad args", what);
+    EOD_REQUIRE(r >= 0 && r <= PSF_MAXR, "%s: the tap radius r%s = %d is outside 0 .. %d", what, axis, r, PSF_MAXR);
+    const int n = 2 * r + 1;
+    for (int i = 0; i < n; ++i) {
+        const float h = taps[i];
+        EOD_REQUIRE(h == h && h - h == 0.0f && h >= 0.0f && !__builtin_signbit(h), "%s: taps_%s[%d] = %g is not a finite non-negative number", what, axis, i, (double)h);
+        t.h[reversed ? n - 1 - i : i] = h;
+    }
+    for (int i = n; i < 2 * PSF_MAXR + 1; ++i) t.h[i] = 0.0f;
+    EOD_REQUIRE(taps[r] > 0.0f, "%s: the centre tap of taps_%s must be positive", what, axis);
+    return EOD_OK;
+}
+
+// what the three _xy entry points share: exactly one of channels / M, then psf_common's (psf_common_mix's) refusals of everything but the
+// taps (it is handed the identity tap), then the two tap vectors
+static int psf_common_xy(const char* what, PsfArgs& g, PsfTapsXy& tt, PsfMix& mx, const float* taps_y, int ry, const float* taps_x, int rx,
+                         const int32_t* channels, const float* M, int rows, int cols, int pitch, bool reversed) {
+    EOD_REQUIRE((channels != nullptr) != (M != nullptr), "%s: exactly one of the channel list and the matrix must be given", what);
+    static const float one[1] = {1.0f};
+    PsfTaps unused;
+    g.r = 0;
+    int rc;
+    if (M) {
+        rc = psf_common_mix(what, g, unused, mx, one, M, rows, cols, pitch);
+    } else {
+        for (int i = 0; i < PSF_MAXK * PSF_MAXC; ++i) mx.m[i] = 0.0f;
+        rc = psf_common(what, g, unused, one, channels);
+    }
+    if (rc != EOD_OK) return rc;
+    rc = psf_axis_taps(what, "y", tt.y, taps_y, ry, reversed);
+    if (rc != EOD_OK) return rc;
+    rc = psf_axis_taps(what, "x", tt.x, taps_x, rx, reversed);
+    if (rc != EOD_OK) return rc;
+    tt.ry = ry;
+    tt.rx = rx;
+    g.r = ry > rx ? ry : rx;
+    return EOD_OK;
+}
+
+#define PSF_XY_LAUNCH(kernel)                                                                                          \
+    do {                                                                                                               \
+        if (mixed) {                                                                                                   \
+            if (vec && vecq) hipLaunchKernelGGL((kernel<true, true, true>), grid, block, 0, st, g, tt, mx, items);      \
+            else if (vec) hipLaunchKernelGGL((kernel<true, false, true>), grid, block, 0, st, g, tt, mx, items);        \
+            else if (vecq) hipLaunchKernelGGL((kernel<false, true, true>), grid, block, 0, st, g, tt, mx, items);       \
+            else hipLaunchKernelGGL((kernel<false, false, true>), grid, block, 0, st, g, tt, mx, items);                \
+        } else {                                                                                                       \
+            if (vec && vecq) hipLaunchKernelGGL((kernel<true, true, false>), grid, block, 0, st, g, tt, mx, items);     \
+            else if (vec) hipLaunchKernelGGL((kernel<true, false, false>), grid, block, 0, st, g, tt, mx, items);       \
+            else if (vecq) hipLaunchKernelGGL((kernel<false, true, false>), grid, block, 0, st, g, tt, mx, items);      \
+            else hipLaunchKernelGGL((kernel<false, false, false>), grid, block, 0, st, g, tt, mx, items);               \
+        }                                                                                                              \
+    } while (0)
+
+static int psf_residual_xy_launch(const char* what, PsfArgs g, const float* taps_y, int ry, const float* taps_x, int rx, const int32_t* channels,
+                                  const float* R, void* stream) {
+    PsfTapsXy tt;
+    PsfMix mx;
+    const bool mixed = R != nullptr;
+    const int rc = psf_common_xy(what, g, tt, mx, taps_y, ry, taps_x, rx, channels, R, g.K, g.C, PSF_MAXC, false);
+    if (rc != EOD_OK) return rc;
+    EOD_REQUIRE(!mixed || !g.values || g.mask_c1, "%s: with a matrix the mask is one plane for all bands (mask_c1 != 0)", what);
+    const long long hw = (long long)g.H * g.W, chw = hw / (g.f * g.f);
+    const long long np = (long long)g.B * g.C * hw, nq = (long long)g.B * g.K * chw;
+    EOD_REQUIRE(!psf_overlap(g.out, nq, g.p, np), "%s: the output overlaps %s", what, g.values ? "p" : "x");
+    if (g.values) {
+        EOD_REQUIRE(g.lambda >= 0.0f && g.lambda <= 1.0f, "%s: the weight must lie in [0, 1], got %g", what, (double)g.lambda);
+        EOD_REQUIRE(!psf_overlap(g.out, nq, g.values, (long long)(g.values_b1 ? 1 : g.B) * g.K * chw), "%s: q overlaps values", what);
+        EOD_REQUIRE(!g.mask || !psf_overlap(g.out, nq, g.mask, (long long)(g.mask_b1 ? 1 : g.B) * (g.mask_c1 ? 1 : g.K) * chw), "%s: q overlaps mask", what);
+    }
+    const bool vec = g.W % 4 == 0 && eod_aligned16(g.p);
+    const bool vecq = (g.W / g.f) % 4 == 0 && eod_aligned16(g.out) && (!g.values || eod_aligned16(g.values)) && (!g.mask || eod_aligned16(g.mask));
+    const long long items = (long long)g.B * g.K * g.tiles_x * g.tiles_y;
+    const dim3 grid(psf_grid(items)), block(PSF_THREADS);
+    hipStream_t st = (hipStream_t)stream;
+    PSF_XY_LAUNCH(psf_residual_xy_kernel);
+    EOD_CHECK_LAUNCH(what);
+    return EOD_OK;
+}
+
+extern "C" int eod_psf_residual_xy(const float* p, const float* values, const float* mask, float lambda, const float* taps_y, int ry,
+                                   const float* taps_x, int rx, int f, const int32_t* channels, const float* R, int K, int B, int C, int H, int W,
+                                   int values_b1, int mask_b1, int mask_c1, float* q, void* stream) {
+    EOD_REQUIRE(values, "psf_residual_xy: bad args");
+    PsfArgs g = {p, values, mask, nullptr, q, lambda, 0.0f, 0, f, K, B, C, H, W, values_b1, mask_b1, mask_c1, 0, 0, 0, {0}, {0}};
+    return psf_residual_xy_launch("psf_residual_xy", g, taps_y, ry, taps_x, rx, channels, R, stream);
+}
+
+extern "C" int eod_psf_apply_xy(const float* x, const float* taps_y, int ry, const float* taps_x, int rx, int f, const int32_t* channels,
+                                const float* R, int K, float* out, int B, int C, int H, int W, void* stream) {
+    PsfArgs g = {x, nullptr, nullptr, nullptr, out, 0.0f, 0.0f, 0, f, K, B, C, H, W, 0, 0, R ? 1 : 0, 0, 0, 0, {0}, {0}};
+    return psf_residual_xy_launch("psf_apply_xy", g, taps_y, ry, taps_x, rx, channels, R, stream);
+}
+
+extern "C" int eod_psf_update_xy(const float* p, const float* q, float step, const float* taps_y, int ry, const float* taps_x, int rx, int f,
+                                 const int32_t* channels, const float* G, int K, int B, int C, int H, int W, float* out, void* stream) {
+    const char* what = "psf_update_xy";
+    EOD_REQUIRE(q, "%s: bad args", what);
+    PsfArgs g = {p, nullptr, nullptr, q, out, 0.0f, step, 0, f, K, B, C, H, W, 0, 0, 0, 0, 0, 0, {0}, {0}};
+    PsfTapsXy tt;
+    PsfMix mx;
+    const bool mixed = G != nullptr;
+    const int rc = psf_common_xy(what, g, tt, mx, taps_y, ry, taps_x, rx, channels, G, C, K, PSF_MAXK, true);
+    if (rc != EOD_OK) return rc;
+    EOD_REQUIRE(step - step == 0.0f && step > 0.0f, "%s: step must be finite and positive, got %g", what, (double)step);
+    const long long hw = (long long)H * W, chw = hw / (f * f);
+    const long long np = (long long)B * C * hw, nq = (long long)B * K * chw;
+    EOD_REQUIRE(!psf_overlap(out, np, p, np), "%s: out overlaps p (a tile's halo is read after its neighbours have written)", what);
+    EOD_REQUIRE(!psf_overlap(out, np, q, nq), "%s: out overlaps q", what);
+    const bool vec = W % 4 == 0 && eod_aligned16(p) && eod_aligned16(out);
+    const bool vecq = (W / f) % 4 == 0 && eod_aligned16(q);
+    const long long items = (long long)B * C * g.tiles_x * g.tiles_y;
+    const dim3 grid(psf_grid(items)), block(PSF_THREADS);
+    hipStream_t st = (hipStream_t)stream;
+    PSF_XY_LAUNCH(psf_update_xy_kernel);
     EOD_CHECK_LAUNCH(what);
     return EOD_OK;
 }

@@ -413,3 +413,170 @@ PSF_FN void psf_update_mix_phase(int phase, const PsfArgs& g, const PsfTaps& t, 
     if (tid < rows) s.nh[tid] = psf_norm(t, r, x0 - r + tid, g.W);
     else if (tid >= 64 && tid < 64 + rows) s.nv[tid - 64] = psf_norm(t, r, y0 - r + tid - 64, g.H);
 }
+
+// ------------------------------------------------------------------------------------------------ one tap vector per axis (section 9.11)
+// hx[0 .. 2 rx] along x and hy[0 .. 2 ry] along y, not necessarily symmetric, the radii independent.  The residual carries the forward
+// taps; the update carries them REVERSED (h~[t] = h[2r - t]: B0^T is the correlation with the reversed taps), so both run the one
+// convolution routine.  n is the conv of a line of ones with the FORWARD taps in both: psf_norm_rev reads a reversed array backwards.
+struct PsfTapsXy {
+    PsfTaps y, x;
+    int ry, rx;
+};
+
+PSF_FN float psf_norm_rev(const PsfTaps& t, int r, int x, int L) {
+    float acc = t.h[2 * r] * ((x - r >= 0 && x - r < L) ? 1.0f : 0.0f);
+    for (int i = 1; i <= 2 * r; ++i) {
+        const int xi = x - r + i;
+        const float pr = t.h[2 * r - i] * ((xi >= 0 && xi < L) ? 1.0f : 0.0f);
+        acc = acc + pr;
+    }
+    return acc;
+}
+
+// The residual of a tile: ft + 2 ry rows of lead + ft + 2 rx columns are staged (PSF_PITCH holds 3 + 32 + 24 columns rounded up to a
+// quad, PsfResLds 56 rows: the maxima; the loops run over the real extents, no zero tap is ever multiplied).  phase 0: the patch (MIX: the
+// band mix of section 9.10, mx->m = R) and nh / nv;  1: horizontal with hx;  2: vertical with hy and / n;  3: psf_residual_phase's.
+template <bool VEC, bool VECQ, bool MIX>
+PSF_FN void psf_residual_xy_phase(int phase, const PsfArgs& g, const PsfTapsXy& tt, const PsfMix* mx, PsfResLds& s, long long item, int tid) {
+    if (phase == 3) {
+        psf_residual_phase<VEC, VECQ>(3, g, tt.x, s, item, tid);
+        return;
+    }
+    const PsfTile tl = psf_tile_of(g, item);
+    const int ry = tt.ry, rx = tt.rx, ft = tl.ft, y0 = tl.y0, x0 = tl.x0;
+    const int b = (int)(tl.plane / g.K), k = (int)(tl.plane % g.K);
+    const int rows = ft + 2 * ry;
+    const int xs = (x0 - rx) & ~3;         // the patch starts at a quad boundary at or left of x0 - rx
+    const int lead = x0 - rx - xs;
+    if (phase == 0) {
+        const long long hw = (long long)g.H * g.W;
+        const float* src = g.p + ((long long)b * g.C + (MIX ? 0 : g.ch[k])) * hw;
+        const float* R = MIX ? mx->m + k * PSF_MAXC : nullptr;
+        const int nq = (lead + ft + 2 * rx + 3) / 4;
+        for (int idx = tid; idx < rows * nq; idx += PSF_THREADS) {
+            const int row = idx / nq, qd = idx % nq;
+            const int gy = y0 - ry + row, gx = xs + 4 * qd;
+            psf_f4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+            if (gy >= 0 && gy < g.H) {
+                const long long at = (long long)gy * g.W + gx;
+                if (VEC) {
+                    if (gx >= 0 && gx < g.W) {                                    // W % 4 == 0: a whole quad
+                        if (MIX) v = psf_mix_quads(src + at, hw, R, g.C);
+                        else v = *reinterpret_cast<const psf_f4*>(src + at);
+                    }
+                } else {
+                    for (int j = 0; j < 4; ++j)
+                        if (gx + j >= 0 && gx + j < g.W) {
+                            if (MIX) {
+                                float u = R[0] * src[at + j];
+                                for (int c = 1; c < g.C; ++c) {
+                                    const float pr = R[c] * src[c * hw + at + j];
+                                    u = u + pr;
+                                }
+                                v[j] = u;
+                            } else {
+                                v[j] = src[at + j];
+                            }
+                        }
+                }
+            }
+            *reinterpret_cast<psf_f4*>(s.patch + row * PSF_PITCH + 4 * qd) = v;
+        }
+        if (tid < ft) s.nh[tid] = psf_norm(tt.x, rx, x0 + tid, g.W);
+        else if (tid >= 64 && tid < 64 + ft) s.nv[tid - 64] = psf_norm(tt.y, ry, y0 + tid - 64, g.H);
+    } else if (phase == 1) {
+        for (int idx = tid; idx < rows * ft; idx += PSF_THREADS) {
+            const int row = idx / ft, x = idx % ft;
+            s.hbuf[row * PSF_MAXT + x] = psf_conv(tt.x, rx, s.patch + row * PSF_PITCH + lead + x, 1);
+        }
+    } else {
+        for (int idx = tid; idx < ft * ft; idx += PSF_THREADS) {
+            const int y = idx / ft, x = idx % ft;
+            float bv = 0.0f;
+            if (y0 + y < g.H && x0 + x < g.W) {
+                const float acc = psf_conv(tt.y, ry, s.hbuf + y * PSF_MAXT + x, PSF_MAXT);
+                const float n = s.nv[y] * s.nh[x];
+                bv = acc / n;
+            }
+            s.patch[y * PSF_MAXT + x] = bv;
+        }
+    }
+}
+
+// The update of a tile: w over (ft + 2 ry) x (ft + 2 rx) pixels from (y0 - ry, x0 - rx), row pitch PSF_ROWS; the coarse pixels under it
+// reach ceil(ry / f) rows and ceil(rx / f) columns beyond the tile's own.  tt holds the REVERSED taps.  phase 0: q (MIX: s_c = sum_k
+// G[c][k] q_k, mx->m = G) and nh / nv;  1: w;  2: horizontal with hx~;  3: vertical with hy~;  4: psf_update_phase's (the copied planes too).
+template <bool VEC, bool VECQ, bool MIX>
+PSF_FN void psf_update_xy_phase(int phase, const PsfArgs& g, const PsfTapsXy& tt, const PsfMix* mx, PsfUpdLds& s, long long item, int tid) {
+    if (phase == 4) {
+        psf_update_phase<VEC, VECQ>(4, g, tt.x, s, item, tid);
+        return;
+    }
+    const PsfTile tl = psf_tile_of(g, item);
+    const int c = (int)(tl.plane % g.C), b = (int)(tl.plane / g.C);
+    const int k = g.kof[c];
+    if (k < 0) return;
+    const int ry = tt.ry, rx = tt.rx, f = g.f, ft = tl.ft, y0 = tl.y0, x0 = tl.x0;
+    const int rows = ft + 2 * ry, cols = ft + 2 * rx;
+    const int Hc = g.H / f, Wc = g.W / f;
+    const int ylo = y0 - ry < 0 ? 0 : y0 - ry, xlo = x0 - rx < 0 ? 0 : x0 - rx;
+    const int yhi = y0 + ft + ry > g.H ? g.H : y0 + ft + ry, xhi = x0 + ft + rx > g.W ? g.W : x0 + ft + rx;   // in-plane part of the w region (never empty)
+    const int cy0 = ylo / f, cx0 = xlo / f, cy1 = (yhi - 1) / f, cx1 = (xhi - 1) / f;
+    const int cxs = cx0 & ~3;
+    if (phase == 0) {
+        const long long chw = (long long)Hc * Wc;
+        const float* src = g.q + ((long long)b * g.K + (MIX ? 0 : k)) * chw;
+        const float* G = MIX ? mx->m + c * PSF_MAXK : nullptr;
+        const int nq = (cx1 - cxs) / 4 + 1, qrows = cy1 - cy0 + 1;
+        for (int idx = tid; idx < qrows * nq; idx += PSF_THREADS) {
+            const int row = idx / nq, qd = idx % nq;
+            const int gy = cy0 + row, gx = cxs + 4 * qd;
+            const long long at = (long long)gy * Wc + gx;
+            psf_f4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+            if (VECQ) {                                             // gx <= cx1 < Wc, Wc % 4 == 0: a whole quad
+                if (MIX) v = psf_mix_quads(src + at, chw, G, g.K);
+                else v = *reinterpret_cast<const psf_f4*>(src + at);
+            } else {
+                for (int j = 0; j < 4; ++j)
+                    if (gx + j < Wc) {
+                        if (MIX) {
+                            float u = G[0] * src[at + j];
+                            for (int kk = 1; kk < g.K; ++kk) {
+                                const float pr = G[kk] * src[kk * chw + at + j];
+                                u = u + pr;
+                            }
+                            v[j] = u;
+                        } else {
+                            v[j] = src[at + j];
+                        }
+                    }
+            }
+            *reinterpret_cast<psf_f4*>(s.qs + row * PSF_PITCH + 4 * qd) = v;
+        }
+        if (tid < cols) s.nh[tid] = psf_norm_rev(tt.x, rx, x0 - rx + tid, g.W);
+        else if (tid >= 64 && tid < 64 + rows) s.nv[tid - 64] = psf_norm_rev(tt.y, ry, y0 - ry + tid - 64, g.H);
+    } else if (phase == 1) {
+        for (int idx = tid; idx < rows * cols; idx += PSF_THREADS) {
+            const int wy = idx / cols, wx = idx % cols;
+            const int gy = y0 - ry + wy, gx = x0 - rx + wx;
+            float wv = 0.0f;
+            if (gy >= 0 && gy < g.H && gx >= 0 && gx < g.W) {
+                const float qv = s.qs[(gy / f - cy0) * PSF_PITCH + (gx / f - cxs)];
+                const float ts = qv * g.step;
+                const float n = s.nv[wy] * s.nh[wx];
+                wv = ts / n;
+            }
+            s.w[wy * PSF_ROWS + wx] = wv;
+        }
+    } else if (phase == 2) {
+        for (int idx = tid; idx < rows * ft; idx += PSF_THREADS) {
+            const int row = idx / ft, x = idx % ft;
+            s.hbuf[row * PSF_MAXT + x] = psf_conv_loop(tt.x, rx, s.w + row * PSF_ROWS + x, 1);
+        }
+    } else {
+        for (int idx = tid; idx < ft * ft; idx += PSF_THREADS) {          // (w is dead: the blur goes where it was, pitch PSF_MAXT)
+            const int y = idx / ft, x = idx % ft;
+            s.w[y * PSF_MAXT + x] = psf_conv_loop(tt.y, ry, s.hbuf + y * PSF_MAXT + x, PSF_MAXT);
+        }
+    }
+}

@@ -13,6 +13,9 @@ eod_ddim_step_spec / eod_dpmpp_step_spec.  `observation=` also takes a list of 1
 evaluation forms its prediction (eod_pred_x0), projects it by one link after the other (eod_spec_project / eod_obs_project, each with its
 own weight) and finishes the step from the result (eod_ddim_step_p0 / eod_dpmpp_step_p0).  A list of one takes the fused kernel.
 
+SeparablePsf gives a PsfObservation one tap vector per axis, asymmetric ones allowed: an anisotropic or shifted PSF
+(eod_psf_residual_xy, eod_psf_update_xy; A^T is the correlation with the reversed taps).
+
 PsfObservation is the observation through a sensor's point spread function: A = D_f N^-1 B0, a renormalised
 zero-padded separable blur followed by the f x f block mean, with values and mask on the COARSE grid.  A+ has no local form, so the link
 takes `iters` Landweber steps p <- p - weight * tau * A^T(mask * (A p - values)) per evaluation (eod_psf_residual, eod_psf_update;
@@ -339,8 +342,9 @@ class BoundSpectral:
         return out
 
 
-def _taps(what, psf):
-    """the 1-D taps h[0 .. 2r] as the fp32 array the kernels use: finite, non-negative, bitwise symmetric, centre tap positive"""
+def _taps(what, psf, symmetric=True):
+    """the 1-D taps h[0 .. 2r] as the fp32 array the kernels use: finite, non-negative, bitwise symmetric (unless symmetric=False: one
+    axis of a SeparablePsf), centre tap positive"""
     try:
         h = np.asarray(psf.detach().cpu().numpy() if torch.is_tensor(psf) else psf)
     except Exception:
@@ -354,11 +358,39 @@ def _taps(what, psf):
         h = np.ascontiguousarray(h, dtype=np.float32)
     if not np.isfinite(h).all() or np.signbit(h).any():
         raise _lib.EodError(f"{what}: the taps of `psf` must be finite and non-negative (as float32)")
-    if h.view(np.uint32).tolist() != h[::-1].view(np.uint32).tolist():
+    if symmetric and not _bit_symmetric(h):
         raise _lib.EodError(f"{what}: the taps of `psf` must be symmetric bit for bit (as float32): A^T is computed with the same stencil")
     if not h[h.size // 2] > 0.0:
         raise _lib.EodError(f"{what}: the centre tap of `psf` must be positive")
     return h
+
+
+def _bit_symmetric(h):
+    return h.view(np.uint32).tolist() == h[::-1].view(np.uint32).tolist()
+
+
+class SeparablePsf:
+    """A separable PSF with one tap vector per axis: `x` along a row, `y` along a column (None: the same taps on
+    both axes).  Each is array-like [2r + 1], r = 0 .. 12 (the two radii independent), finite, non-negative, centre tap positive, and NOT
+    necessarily symmetric: h[t] weights the scene pixel at offset t - r, so mass at t > r means "this sample sees the scene to its right /
+    below" (a band registered a fraction of a pixel off the grid; gaussian_psf(shift=...)).  taps_x / taps_y: float32 arrays.  Taken
+    wherever a `psf` is: PsfObservation(values, SeparablePsf(...), factor, ...) and psf_observe(x, SeparablePsf(...), factor, ...), which
+    then run the eod_psf_*_xy kernels.  A bare array keeps the symmetric rules and kernels."""
+
+    def __init__(self, x, y=None):
+        what = "SeparablePsf"
+        if isinstance(x, SeparablePsf) or isinstance(y, SeparablePsf):
+            raise _lib.EodError(f"{what}: `x` and `y` are 1-D tap vectors, got a SeparablePsf")
+        self.taps_x = _taps(f"{what}: x", x, symmetric=False)
+        self.taps_y = self.taps_x if y is None else _taps(f"{what}: y", y, symmetric=False)
+
+    @property
+    def radii(self):
+        """(ry, rx)"""
+        return self.taps_y.size // 2, self.taps_x.size // 2
+
+    def __repr__(self):
+        return f"SeparablePsf(x={self.taps_x.tolist()}, y={self.taps_y.tolist()})"
 
 
 def _channels(what, channels):
@@ -396,24 +428,32 @@ def psf_cmax(taps, L):
 
 
 def psf_tau(taps, factor, H, W):
-    """the Landweber step size f^2 / (cmax(H) cmax(W)) <= 1 / ||A||^2 (||A||^2 <= ||A||_1 ||A||_inf = cmax(H) cmax(W) / f^2), float64"""
-    return float(factor * factor) / (psf_cmax(taps, H) * psf_cmax(taps, W))
+    """the Landweber step size f^2 / (cmax(H) cmax(W)) <= 1 / ||A||^2 (||A||^2 <= ||A||_1 ||A||_inf = cmax(H) cmax(W) / f^2), float64.
+    taps: one vector for both axes, or a SeparablePsf: f^2 / (cmax(taps_y, H) cmax(taps_x, W))"""
+    ty, tx = (taps.taps_y, taps.taps_x) if isinstance(taps, SeparablePsf) else (taps, taps)
+    return float(factor * factor) / (psf_cmax(ty, H) * psf_cmax(tx, W))
 
 
-def psf_gram(taps, factor, L):
+def psf_gram(taps, factor, L, symmetric=True):
     """(bands, b): the 1-D Gram matrix G_L = A1(L) A1(L)^T of the operator A1 = D_f N^-1 B0 on a line of length L (renormalised zero padding,
     block mean) as its band: bands float32 [L / f, 2b + 1], bands[i][j] = G_L[i][i - b + j], zero where the column lies outside the line;
     b = ceil(2r / f).  float64 of the fp32 taps, band by band (no dense matrix: L may be a scene's width); the upper band is computed and
-    mirrored, so G_L is symmetric bit for bit.  A A^T = G(H) (x) G(W)."""
+    mirrored, so G_L is symmetric bit for bit.  A A^T = G(H) (x) G(W).  symmetric=False: one axis of a SeparablePsf, the taps need not be
+    symmetric (G_L still is: it is a Gram matrix); n is then summed tap by tap in the orientation of the contract."""
     what = "psf_gram"
-    h = _taps(what, taps).astype(np.float64)
+    h = _taps(what, taps, symmetric=bool(symmetric)).astype(np.float64)
     f = _factor(what, factor)
     if isinstance(L, bool) or not isinstance(L, numbers.Integral) or L < 1 or L % f:
         raise _lib.EodError(f"{what}: L is a positive multiple of factor = {f}, got {L!r}")
     L = int(L)
     r, Lc = h.size // 2, L // f
     b = -((-2 * r) // f)
-    n = np.convolve(np.ones(L), h)[r:r + L]                  # N = diag(B0 1)
+    if symmetric:
+        n = np.convolve(np.ones(L), h)[r:r + L]              # N = diag(B0 1) (np.convolve flips the taps: symmetric ones only)
+    else:
+        n, idx = np.zeros(L), np.arange(L)
+        for t in range(h.size):                              # n[y] = sum_t h[t] [0 <= y - r + t < L]
+            n[(idx - r + t >= 0) & (idx - r + t < L)] += h[t]
     w = f + 2 * r                                            # row i of A1 lives on x = i f - r .. i f + f - 1 + r
     rows = np.zeros((Lc, w))
     for a in range(f):                                       # the block's pixel y = i f + a sees x = y - r + t through h[t] / n[y]
@@ -429,6 +469,18 @@ def psf_gram(taps, factor, L):
         bands[np.arange(Lc - k), b + k] = g
         bands[np.arange(k, Lc), b - k] = g
     return bands.astype(np.float32), b
+
+
+def psf_gram_pair(psf, factor, H, W):
+    """(gy, gx, b): the Gram tables of a SeparablePsf's two axes, psf_gram(taps_y, factor, H) and psf_gram(taps_x, factor, W), as eod_psf_cg
+    takes them: ONE half-width b = max(ceil(2 ry / f), ceil(2 rx / f)), the narrower table padded with zero columns on both sides (those
+    entries of G are zero: the rows do not overlap).  An axis with bitwise symmetric taps takes psf_gram's symmetric form, so with equal
+    symmetric taps nothing is padded and the tables have the bits of the bare-taps link."""
+    gy, by = psf_gram(psf.taps_y, factor, H, symmetric=_bit_symmetric(psf.taps_y))
+    gx, bx = psf_gram(psf.taps_x, factor, W, symmetric=_bit_symmetric(psf.taps_x))
+    b = max(by, bx)
+    pad = lambda g, bb: np.ascontiguousarray(np.pad(g, ((0, 0), (b - bb, b - bb))))
+    return pad(gy, by), pad(gx, bx), b
 
 
 def _dampings(what, damping):
@@ -458,19 +510,35 @@ def gaussian_sigma(factor, mtf_nyquist=0.3):
     return f * math.sqrt(-2.0 * math.log(float(mtf_nyquist))) / math.pi
 
 
-def gaussian_psf(factor, mtf_nyquist=0.3, radius=None):
+def gaussian_psf(factor, mtf_nyquist=0.3, radius=None, shift=0.0):
     """The taps of a Gaussian PSF for a sensor `factor` times coarser whose MTF at its Nyquist frequency is mtf_nyquist: sigma =
     f sqrt(-2 ln mtf) / pi, taps on -r .. r with r = min(ceil(3 sigma), 12) (or `radius`), normalised in float64, rounded to fp32,
-    symmetric bit for bit.  float32 [2r + 1]."""
+    symmetric bit for bit.  float32 [2r + 1].  shift (|shift| <= 0.5 factor, in fine pixels): the Gaussian is centred at `shift`, tap t
+    weighing the scene pixel at offset t - r (shift > 0: the sample sees the scene to its right / below); r = min(ceil(3 sigma + |shift|),
+    12), normalised in float64, rounded to fp32 and NOT symmetrised: one axis of a SeparablePsf; refused when mtf_nyquist is so close to 1 that every tap underflows to 0.  shift = 0.0: the bits above."""
     what = "gaussian_psf"
     sigma = gaussian_sigma(factor, mtf_nyquist)
+    if isinstance(shift, bool) or not isinstance(shift, (numbers.Real, np.floating)) or not math.isfinite(float(shift)):
+        raise _lib.EodError(f"{what}: `shift` is a finite float (fine pixels), got {shift!r}")
+    shift = float(shift)
+    if abs(shift) > 0.5 * factor:
+        raise _lib.EodError(f"{what}: `shift` is at most half a coarse pixel, |shift| <= {0.5 * factor}, got {shift!r}")
+    if shift != 0.0 and not sigma > 0.0:
+        raise _lib.EodError(f"{what}: mtf_nyquist = 1 is a point: it has no taps at a sub-pixel `shift`")
     if radius is None:
-        r = min(int(math.ceil(3.0 * sigma)), MAX_RADIUS)
+        r = min(int(math.ceil(3.0 * sigma + abs(shift))), MAX_RADIUS)
     else:
         if isinstance(radius, bool) or not isinstance(radius, numbers.Integral) or not 0 <= radius <= MAX_RADIUS:
             raise _lib.EodError(f"{what}: `radius` is an integer in 0 .. {MAX_RADIUS}, got {radius!r}")
         r = int(radius)
     k = np.arange(-r, r + 1, dtype=np.float64)
+    if shift != 0.0:
+        with np.errstate(under="ignore"):
+            g = np.exp(-((k - shift) * (k - shift)) / (2.0 * sigma * sigma))
+        total = float(g.sum())
+        if not (total > 0.0 and math.isfinite(total)):                  # sigma so small that every tap underflows: nothing to normalise
+            raise _lib.EodError(f"{what}: mtf_nyquist = {mtf_nyquist!r} is too close to a point: every tap at shift = {shift!r} underflows to 0")
+        return (g / total).astype(np.float32)
     g = np.exp(-(k * k) / (2.0 * sigma * sigma)) if sigma > 0.0 else (k == 0).astype(np.float64)
     h = (g / g.sum()).astype(np.float32)
     h[r + 1:] = h[:r][::-1]
@@ -481,7 +549,8 @@ class PsfObservation:
     """K channels seen through a sensor's PSF on a grid `factor` times coarser: A = D_f N^-1 B0 per observed channel (B0 the zero-padded
     separable convolution with the 1-D taps `psf`, horizontally then vertically; N = diag(B0 1); D_f the factor x factor block mean).
     values [B or 1, K, H / f, W / f] fp32 on the COARSE grid: what the sensor delivered; psf: array-like [2r + 1], r = 0 .. 12, finite,
-    non-negative, symmetric bit for bit as float32, centre tap positive; factor 1 .. 8; channels None (all C, C = K) or K strictly
+    non-negative, symmetric bit for bit as float32, centre tap positive, or a SeparablePsf (one tap vector per axis, asymmetric ones
+    allowed: an anisotropic or shifted PSF; the eod_psf_*_xy kernels); factor 1 .. 8; channels None (all C, C = K) or K strictly
     increasing channel numbers; mask None or [B or 1, K or 1, H / f, W / f] fp32; weight as for Observation.  solver "landweber" (the
     default): iters 1 .. 8 Landweber steps per evaluation, which approach the constraint set.  solver "cg": iters 1 .. 64 conjugate-gradient
     iterations of the exact projection per evaluation, p - weight * A^T (M A A^T M + damping I)^-1 mask (A p - values); the mask must then
@@ -498,7 +567,8 @@ class PsfObservation:
 
     def __init__(self, values, psf, factor, channels=None, mask=None, weight=1.0, iters=1, solver="landweber", damping=0.0, response=None):
         what = "PsfObservation"
-        self.taps = _taps(what, psf)
+        self.psf = psf if isinstance(psf, SeparablePsf) else None       # one tap vector per axis: `taps` is then None
+        self.taps = None if self.psf is not None else _taps(what, psf)
         self.factor = _factor(what, factor)
         self.channels = None if channels is None else _channels(what, channels)
         self.response = self.pinv = None
@@ -582,8 +652,15 @@ class BoundPsf:
     def __init__(self, obs, shape, channels, n_evaluations, device):
         B, C, H, W = shape
         self.shape, self.factor, self.iters, self.channels = shape, obs.factor, obs.iters, channels
-        self.r = obs.taps.size // 2
-        self.tau = psf_tau(obs.taps, obs.factor, H, W)
+        self.xy = obs.psf is not None                  # a SeparablePsf: the _xy entry points
+        if self.xy:
+            self.ry, self.rx = obs.psf.radii
+            self.r = max(self.ry, self.rx)
+            self.c_taps_y, self.c_taps_x = _c_floats(obs.psf.taps_y), _c_floats(obs.psf.taps_x)
+        else:
+            self.r = obs.taps.size // 2
+            self.c_taps = _c_floats(obs.taps)
+        self.tau = psf_tau(obs.psf if self.xy else obs.taps, obs.factor, H, W)
         self.mixed = obs.response is not None
         if self.mixed:                                 # A = R (x) A_s: ||A|| = sigma_max(R) ||A_s||; the Landweber adjoint mixes by R^T, cg by pinv(R)
             self.K = obs.response.shape[0]
@@ -593,7 +670,6 @@ class BoundPsf:
         else:
             self.K, self.c_channels = len(channels), _c_ints(channels)
         self.step = float(np.float32(self.tau / (obs.factor * obs.factor)))
-        self.c_taps = _c_floats(obs.taps)
         self.values = f32c(obs.values.to(device))
         self.mask = None if obs.mask is None else f32c(obs.mask.to(device))
         self.weights = obs.weights if obs.per_evaluation else obs.weights * n_evaluations
@@ -601,8 +677,11 @@ class BoundPsf:
         if self.solver == "cg":                        # the two Gram tables beside `values`; workspace and coarse buffers at the first project
             self.dampings = obs.dampings if obs.damping_per_evaluation else obs.dampings * n_evaluations
             self.unit_step = float(np.float32(1.0 / (obs.factor * obs.factor)))
-            gy, self.band = psf_gram(obs.taps, obs.factor, H)
-            gx, _ = psf_gram(obs.taps, obs.factor, W)
+            if self.xy:
+                gy, gx, self.band = psf_gram_pair(obs.psf, obs.factor, H, W)
+            else:
+                gy, self.band = psf_gram(obs.taps, obs.factor, H)
+                gx, _ = psf_gram(obs.taps, obs.factor, W)
             self.gy, self.gx = torch.from_numpy(gy).to(device), torch.from_numpy(gx).to(device)
             self._cg = self._coarse = None
 
@@ -612,6 +691,14 @@ class BoundPsf:
             raise _lib.EodError(f"observation bound to a state of shape {self.shape}, the step got {tuple(p.shape)}")
         B, C, H, W = self.shape
         m = self.mask
+        if self.xy:
+            _lib.check(_lib.lib().eod_psf_residual_xy(p.data_ptr(), self.values.data_ptr(), _lib.ptr(m), self.weights[i] if weight is None else weight,
+                                                      self.c_taps_y, self.ry, self.c_taps_x, self.rx, self.factor,
+                                                      None if self.mixed else self.c_channels, self.c_R if self.mixed else None, self.K, B, C, H, W,
+                                                      int(self.values.shape[0] != B), int(m is not None and m.shape[0] != B),
+                                                      int(self.mixed or (m is not None and m.shape[1] != self.K)),
+                                                      q.data_ptr(), current_stream_ptr(p.device)), "eod_psf_residual_xy")
+            return q
         if self.mixed:
             _lib.check(_lib.lib().eod_psf_residual_mix(p.data_ptr(), self.values.data_ptr(), _lib.ptr(m), self.weights[i] if weight is None else weight,
                                                        self.c_taps, self.r, self.factor, self.c_R, self.K, B, C, H, W,
@@ -628,6 +715,12 @@ class BoundPsf:
     def update(self, p, q, out, step=None):
         """out = p - tau A^T q: eod_psf_update (with a response: eod_psf_update_mix, the coarse planes mixed by R^T or, under cg, pinv(R))"""
         B, C, H, W = self.shape
+        if self.xy:
+            _lib.check(_lib.lib().eod_psf_update_xy(p.data_ptr(), q.data_ptr(), self.step if step is None else step, self.c_taps_y, self.ry,
+                                                    self.c_taps_x, self.rx, self.factor, None if self.mixed else self.c_channels,
+                                                    self.c_G if self.mixed else None, self.K, B, C, H, W, out.data_ptr(),
+                                                    current_stream_ptr(p.device)), "eod_psf_update_xy")
+            return out
         if self.mixed:
             _lib.check(_lib.lib().eod_psf_update_mix(p.data_ptr(), q.data_ptr(), self.step if step is None else step, self.c_taps, self.r, self.factor,
                                                      self.c_G, self.K, B, C, H, W, out.data_ptr(), current_stream_ptr(p.device)), "eod_psf_update_mix")
@@ -811,9 +904,10 @@ def psf_observe(x, psf, factor, channels=None, response=None):
     """A x on the GPU (eod_psf_apply): [B, K, H / f, W / f], the channels `channels` (None: all) of x [B, C, H, W] blurred by the
     renormalised zero-padded separable PSF and averaged over factor x factor blocks.  Makes a PsfObservation's `values` out of an image,
     and measures how far a result is from one.  With `response` [K, C] (not together with `channels`): the K band mixes of x seen that
-    way (eod_psf_apply_mix)."""
+    way (eod_psf_apply_mix).  psf: the symmetric 1-D taps, or a SeparablePsf (eod_psf_apply_xy, either form)."""
     what = "psf_observe"
-    h = _taps(what, psf)
+    xy = isinstance(psf, SeparablePsf)               # one tap vector per axis: eod_psf_apply_xy, either form
+    h = None if xy else _taps(what, psf)
     f = _factor(what, factor)
     if not torch.is_tensor(x) or x.dim() != 4 or not 1 <= x.shape[1] <= MAX_CHANNELS:
         raise _lib.EodError(f"{what}: x must be a tensor [B, C <= {MAX_CHANNELS}, H, W]")
@@ -829,6 +923,11 @@ def psf_observe(x, psf, factor, channels=None, response=None):
         require_gpu(x, what)
         x = f32c(x)
         out = torch.empty((B, R.shape[0], H // f, W // f), device=x.device, dtype=torch.float32)
+        if xy:
+            _lib.check(_lib.lib().eod_psf_apply_xy(x.data_ptr(), _c_floats(psf.taps_y), psf.radii[0], _c_floats(psf.taps_x), psf.radii[1], f, None,
+                                                   _c_floats(R), R.shape[0], out.data_ptr(), B, C, H, W, current_stream_ptr(x.device)),
+                       "eod_psf_apply_xy")
+            return out
         _lib.check(_lib.lib().eod_psf_apply_mix(x.data_ptr(), _c_floats(h), h.size // 2, f, _c_floats(R), R.shape[0], out.data_ptr(), B, C, H, W,
                                                 current_stream_ptr(x.device)), "eod_psf_apply_mix")
         return out
@@ -840,6 +939,10 @@ def psf_observe(x, psf, factor, channels=None, response=None):
     require_gpu(x, what)
     x = f32c(x)
     out = torch.empty((B, len(cs), H // f, W // f), device=x.device, dtype=torch.float32)
+    if xy:
+        _lib.check(_lib.lib().eod_psf_apply_xy(x.data_ptr(), _c_floats(psf.taps_y), psf.radii[0], _c_floats(psf.taps_x), psf.radii[1], f, _c_ints(cs),
+                                               None, len(cs), out.data_ptr(), B, C, H, W, current_stream_ptr(x.device)), "eod_psf_apply_xy")
+        return out
     _lib.check(_lib.lib().eod_psf_apply(x.data_ptr(), _c_floats(h), h.size // 2, f, _c_ints(cs), len(cs), out.data_ptr(), B, C, H, W,
                                         current_stream_ptr(x.device)), "eod_psf_apply")
     return out

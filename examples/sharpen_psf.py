@@ -6,6 +6,7 @@ PSF-aware observations.
     python examples/sharpen_psf.py --mtf 0.2 --iters 4 --steps 25
     python examples/sharpen_psf.py --solver cg --iters 16                # the exact projection: the residuals fall to rounding
     python examples/sharpen_psf.py --solver cg --iters 8 --damping 0.05  # the regularised solve for noisy observations
+    python examples/sharpen_psf.py --mtf-along 0.2 --mtf-across 0.35 --shift 0.3 --solver cg --iters 16  # an anisotropic PSF, the coarse bands 0.3 coarse pixels off the grid
 
 A synthetic 13-band truth is "observed" the way the instrument does it: the six 20 m bands (B5, B6, B7, B8A, B11, B12) blurred by a Gaussian
 PSF and sampled on a 2x coarser grid, the three 60 m bands (B1, B9, B10) on a 6x coarser one, each group with the PSF of its own grid
@@ -13,7 +14,9 @@ PSF and sampled on a 2x coarser grid, the three 60 m bands (B1, B9, B10) on a 6x
 `iters` Landweber steps toward each constraint set after every evaluation's prediction, or with --solver cg `iters`
 conjugate-gradient iterations of the exact projection onto it (section 9.9); the 10 m bands are left to the network.  The script prints both residuals, max |A x - y| on the coarse grids, of the last prediction and of the returned scene, next to
 those of the same call without an observation.  The network is UNTRAINED unless --ckpt is given: the script shows the mechanics and the
-constraints, not image quality.
+constraints, not image quality.  --mtf-along / --mtf-across give the PSF one MTF per axis (along-track: y, across-track: x) and --shift
+registers the coarse bands that fraction of a COARSE pixel off the fine grid along both axes (SeparablePsf, gaussian_psf(shift=); section
+9.11); without them the call and its output are the ones above.
 """
 import argparse
 import os
@@ -25,7 +28,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from eo_diffusion_amd.backbones.unet_openai import UNetModel  # noqa: E402
-from eo_diffusion_amd.diffusion.consistency import PsfObservation, gaussian_psf, psf_observe  # noqa: E402
+from eo_diffusion_amd.diffusion.consistency import PsfObservation, SeparablePsf, gaussian_psf, psf_observe  # noqa: E402
 from eo_diffusion_amd.diffusion.dpm_solver import DPMSolverSampler  # noqa: E402
 from eo_diffusion_amd.diffusion.model import EODiffusion  # noqa: E402
 
@@ -52,6 +55,9 @@ def main():
     ap.add_argument("--height", type=int, default=384)
     ap.add_argument("--width", type=int, default=576)
     ap.add_argument("--mtf", type=float, default=0.3, help="the PSF's MTF at each coarse grid's Nyquist frequency")
+    ap.add_argument("--mtf-along", type=float, default=None, help="the MTF along y (along-track) in the place of --mtf: a SeparablePsf")
+    ap.add_argument("--mtf-across", type=float, default=None, help="the MTF along x (across-track) in the place of --mtf: a SeparablePsf")
+    ap.add_argument("--shift", type=float, default=None, help="misregistration of the coarse bands in COARSE pixels along both axes, |shift| <= 0.5: a SeparablePsf")
     ap.add_argument("--iters", type=int, default=2, help="Landweber steps (1 .. 8) or cg iterations (1 .. 64) per evaluation and link")
     ap.add_argument("--solver", default="landweber", choices=["landweber", "cg"])
     ap.add_argument("--damping", type=float, default=0.0, help="--solver cg: the Tikhonov term mu of (A A^T + mu I)")
@@ -78,7 +84,12 @@ def main():
                     p.normal_(0.0, 0.02)
     model = model.to(device).eval()
     truth = synthetic_scene(args.height, args.width, args.seed).to(device) * 2.0 - 1.0
-    seen = {name: (cs, f, gaussian_psf(f, args.mtf)) for name, (cs, f) in GROUPS.items()}
+    if args.mtf_along is None and args.mtf_across is None and args.shift is None:
+        psf_of = lambda f: gaussian_psf(f, args.mtf)
+    else:                                       # one tap vector per axis: anisotropic and / or shifted
+        along, across, shift = args.mtf_along or args.mtf, args.mtf_across or args.mtf, args.shift or 0.0
+        psf_of = lambda f: SeparablePsf(gaussian_psf(f, across, shift=shift * f), gaussian_psf(f, along, shift=shift * f))
+    seen = {name: (cs, f, psf_of(f)) for name, (cs, f) in GROUPS.items()}
     values = {name: psf_observe(truth, h, f, cs) for name, (cs, f, h) in seen.items()}          # what the sensor delivered, on the coarse grids
     links = [PsfObservation(values[name], h, f, cs, iters=args.iters, solver=args.solver, damping=args.damping) for name, (cs, f, h) in seen.items()]
     sampler = DPMSolverSampler(model)
@@ -97,7 +108,8 @@ def main():
           f"{f', damping {args.damping}' if args.damping else ''}: "
           f"{sampler.num_evaluations} evaluations in {dt:.2f} s (the network is {'the checkpoint' if args.ckpt else 'UNTRAINED'})")
     for name, (cs, f, h) in seen.items():
-        print(f"  {name} group: channels {list(cs)} at f = {f}, {h.size} taps")
+        taps = f"{h.taps_y.size} x {h.taps_x.size}" if isinstance(h, SeparablePsf) else str(h.size)
+        print(f"  {name} group: channels {list(cs)} at f = {f}, {taps} taps")
     for title, z in (("last prediction", inter["pred_x0"][-1]), ("returned scene", scene), ("without an observation: last prediction", free_inter["pred_x0"][-1]),
                      ("without an observation: returned scene", free)):
         res = ", ".join(f"{name} {float((psf_observe(z, h, f, cs) - values[name]).abs().max()):.2e}" for name, (cs, f, h) in seen.items())

@@ -35,7 +35,7 @@ const char* eod_last_error(void);
  * buffer of eod_pack_conv_weight_split, the 4-int state of eod_adamw_step_guarded).  eod_version() returns the value the library was built
  * with; a binding compares it with the header it mirrors at load time (eo_diffusion_amd/_lib.py does) instead of finding out by an
  * out-of-bounds device write. */
-#define EOD_ABI_VERSION 114
+#define EOD_ABI_VERSION 115
 int eod_version(void);
 /* Kernel-selection options ("skip_fuse", "head", "halo_bn256", "halo_splitk", "first", "s2_halo": 1 / 0; "gn_fuse_max_cout": n, -1 = default;
  * "halo_tpw": pixel tiles per workgroup of the streaming halo instances, 1 = off = default, 0 = chosen per launch; "head_tpw": the same of
@@ -489,6 +489,34 @@ int eod_psf_apply_mix(const float* x, const float* taps, int r, int f, const flo
                       void* stream);
 int eod_psf_update_mix(const float* p, const float* q, float step, const float* taps, int r, int f, const float* G, int K, int B, int C,
                        int H, int W, float* out, void* stream);
+/* Anisotropic and shifted PSFs (no reference line): A = D_f N^-1 B0 as above with B0 = B_y B_x built from TWO tap
+ * vectors, hx[0 .. 2 rx] along x and hy[0 .. 2 ry] along y; rx and ry independent, each 0 .. 12; each vector fp32, finite, non-negative,
+ * NOT necessarily symmetric, centre tap positive (hx[rx] > 0, hy[ry] > 0: n > 0 on every line, however short).  h[t] weights the scene
+ * pixel at offset t - r: mass at t > r means "this sample sees the scene to its right / below".  Per pixel, every operation rounded once in
+ * fp32 (u outside the plane is +0.0f, and its product is formed and added like any other):
+ *   conv_x(u; h, r)[y][x] = (((h[0] * u[y][x-r]) + h[1] * u[y][x-r+1]) + ...) + h[2r] * u[y][x+r]      taps in ascending order
+ *   conv_y likewise along y;   blur(u) = conv_y(conv_x(u; hx, rx); hy, ry)                             horizontal first, always
+ *   nh[x] = conv_x of a row of 1.0f with hx;  nv[y] = conv_y of a column of 1.0f with hy;  n[y][x] = nv[y] * nh[x]
+ *   b = blur(p_c) / n;   mean = section 9.5's block sum of b / (float)(f * f);   q = lm * (mean - values),  lm = lambda * m
+ *   w[y][x] = (s[y / f][x / f] * step) / n[y][x]                                                        n from the FORWARD taps
+ *   out_c   = p_c - conv_y(conv_x(w; hx~, rx); hy~, ry),   hx~[t] = hx[2 rx - t],  hy~[t] = hy[2 ry - t]
+ * (horizontal first, the reversed taps in ascending order of the reversed array): B0^T is the correlation with the reversed taps.  With
+ * hx == hy bitwise symmetric these are the lines of the two blocks above, and the results have the bits of eod_psf_residual / eod_psf_apply /
+ * eod_psf_update (and of the _mix triple).  The order is a property of the pixel alone (not of B, the alignment, the tile, the launch
+ * geometry, batch or scene).  A non-finite p pixel reaches exactly the outputs within (ry, rx) of it: the shorter vector is never padded.
+ * taps_y / taps_x are the FORWARD taps (HOST arrays, by value to the kernels); eod_psf_update_xy reverses them itself.  Each entry point
+ * serves the plain and the mixed form: EXACTLY ONE of `channels` (K strictly increasing channel numbers, as in the first block) and the
+ * matrix (R [K][C] / G [C][K], as in the second; u_k, s_c and the one coarse mask as there) is non-NULL.
+ * EOD_EINVAL with nothing launched and the outputs untouched: every refusal of the entry points above except tap symmetry; both or neither
+ * of channels and the matrix; with R: mask_c1 == 0, K > 8.  One launch each, nothing allocated, copied or synchronised; the tile, the
+ * access forms and the striding are those of the first block; a tile stages ft + 2 ry rows of ft + 2 rx columns. */
+int eod_psf_residual_xy(const float* p, const float* values, const float* mask, float lambda, const float* taps_y, int ry, const float* taps_x,
+                        int rx, int f, const int32_t* channels, const float* R, int K, int B, int C, int H, int W, int values_b1, int mask_b1,
+                        int mask_c1, float* q, void* stream);
+int eod_psf_apply_xy(const float* x, const float* taps_y, int ry, const float* taps_x, int rx, int f, const int32_t* channels, const float* R,
+                     int K, float* out, int B, int C, int H, int W, void* stream);
+int eod_psf_update_xy(const float* p, const float* q, float step, const float* taps_y, int ry, const float* taps_x, int rx, int f,
+                      const int32_t* channels, const float* G, int K, int B, int C, int H, int W, float* out, void* stream);
 /* The exact PSF data consistency (no reference line): conjugate gradients on the COARSE grid [Hc][Wc] = [H / f][W / f],
  * one independent system per plane (sample b, observed channel k):
  *   S z = c,   S = M G M + mu I,   M = diag(m), m in {0, 1} (mask NULL: 1),   G = A A^T = G_H (x) G_W

@@ -352,7 +352,9 @@ template <typename T>
 __global__ void resample2x_kernel(const T* __restrict__ x, T* __restrict__ y, int N, int H, int W, int C, int mode, int pad_tl) {
     // pad_tl: mode 1 = zero row / column on top / left of the 2x image (3x3 -> 7x7 hack); mode 2 = the backward of that (the sums
     // skip the first row / column of the input); mode 3 = the average pool dropped a last odd row / column: one zero row / column
-    // at the BOTTOM / RIGHT of the output
+    // at the BOTTOM / RIGHT of the output.  One pad_tl pads BOTH axes, so the backward of an average pool over a map odd in one axis
+    // only (7 x 6) is not expressible: nothing inside a UNet pools such a map, and the trainer raises on it ("resample backward shape
+    // mismatch", tests/test_gpu_glue_ops.py)
     // mode 4 = crop: drops the last row (pad_tl & 1) and / or column (pad_tl & 2) -- the backward-data conv of a stride-2 conv on
     // an odd map is computed on the even (H+1) x (W+1) grid
     const bool up = mode == 1 || mode == 3;

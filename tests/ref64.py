@@ -1,5 +1,5 @@
-"""float64 references of the training-path kernels (csrc/train.hip) and of the conv entry point (eod_conv2d_igemm, csrc/igemm.hip),
-in plain torch.
+"""float64 references of the training-path kernels (csrc/train.hip), of the conv entry point (eod_conv2d_igemm, csrc/igemm.hip) and of
+the ops between the convs of the inference forward (resampling, timestep MLP, bound tables: csrc/misc.hip, csrc/norm.hip), in plain torch.
 
 Nothing here imports the library, so the CPU suite can test every reference against torch autograd
 (tests/test_ref64.py) and the GPU suite can gate the kernels on references that have themselves been tested
@@ -379,3 +379,84 @@ def presplit_decode(p, s):
     h = p.contiguous().view(torch.float16).reshape(p.shape[:-1] + (p.shape[-1] // 8, 16)).to(F64)
     v = (h[..., :8] + h[..., 8:]).reshape(p.shape)
     return v / s.to(F64).reshape((-1,) + (1,) * (p.dim() - 1))
+
+
+# ================================================================================================ glue ops of the inference forward
+def resample2x(x, mode, pad_tl=0):
+    """eod_resample2x on an NHWC map, float64.  mode 0: 2x2 average pool (an odd map drops its last row / column); 1: nearest 2x with
+    pad_tl zero rows / columns on top / left; 2: the adjoint of mode 1 (2x2 sums that skip the first pad_tl rows / columns); 3: nearest
+    2x times 0.25 with pad_tl zero rows / columns at the bottom / right (the adjoint of mode 0; pad_tl = 1 for a map odd in BOTH axes);
+    4: crop of the last row (pad_tl & 1) and / or column (pad_tl & 2)"""
+    x = x.to(F64)
+    N, H, W, C = x.shape
+    if mode == 0:
+        return block_sum2x2(x[:, :H // 2 * 2, :W // 2 * 2]) * 0.25
+    if mode == 1:
+        return torch.nn.functional.pad(upsample2x(x), (0, 0, pad_tl, 0, pad_tl, 0))
+    if mode == 2:
+        x = x[:, pad_tl:, pad_tl:]
+        return block_sum2x2(x[:, :x.shape[1] // 2 * 2, :x.shape[2] // 2 * 2])
+    if mode == 3:
+        return torch.nn.functional.pad(upsample2x(x) * 0.25, (0, 0, 0, pad_tl, 0, pad_tl))
+    assert mode == 4, mode
+    return x[:, :H - (pad_tl & 1), :W - ((pad_tl >> 1) & 1)]
+
+
+def time_embed(t, freqs, w1, b1, w2, b2, wcat, bcat, *, label_emb=None, y=None, emb=None):
+    """the three stages of eod_time_embed: h1 = SiLU(sinusoid(t) W1^T + b1), emb = h1 W2^T + b2 (+ label_emb[y]),
+    out = SiLU(emb) Wcat^T + bcat.  w1 = None: `emb` is the input and only stage 3 runs.  wcat = None: no stage 3.
+    Returns (h1, emb, out), float64 (None for a stage that did not run)"""
+    h1 = None
+    if w1 is not None:
+        h1 = silu(temb_pre1(t, freqs, w1, b1))
+        emb = h1 @ w2.to(F64).t() + b2.to(F64)
+        if label_emb is not None:
+            emb = emb + label_emb.to(F64)[y.long()]
+    else:
+        emb = emb.to(F64)
+    out = None if wcat is None else silu(emb) @ wcat.to(F64).t() + bcat.to(F64)
+    return h1, emb, out
+
+
+AB = 32  # entries per image of a bound table (csrc/common.h: EOD_AB)
+
+
+def act_bound_ranges(L):
+    """[(i0, i1)] * 32: block j of eod_act_bound covers the items [L j / 32, L (j + 1) / 32) of an image's L items (16-byte chunks in
+    direct mode, {sum, sumsq} pairs in parts mode); a range may be empty"""
+    return [(L * j // AB, L * (j + 1) // AB) for j in range(AB)]
+
+
+def _inf_if_nonfinite(v):
+    return torch.where(torch.isfinite(v), v, torch.full_like(v, float("inf")))
+
+
+def act_bound_direct(x, epc):
+    """[N][32] float64: entry j = max|x| over the j-th range of 16-byte chunks (epc elements each) of image n, x [N][per_image];
+    0 for an empty range, +inf where the range holds a NaN or an inf"""
+    x = x.to(F64).flatten(1)
+    out = torch.zeros((x.shape[0], AB), dtype=F64, device=x.device)
+    for j, (i0, i1) in enumerate(act_bound_ranges(x.shape[1] // epc)):
+        if i1 > i0:
+            out[:, j] = _inf_if_nonfinite(x[:, i0 * epc:i1 * epc].abs()).max(1).values
+    return out
+
+
+def act_bound_parts(parts):
+    """[N][32] float64: entry j = sqrt of the largest sum of squares among the j-th range of {sum, sumsq} pairs of every source in
+    `parts` (each [N][P][C][2]); a NaN sum of squares counts as +inf"""
+    N = parts[0].shape[0]
+    out = torch.zeros((N, AB), dtype=F64, device=parts[0].device)
+    for p in parts:
+        q = p.to(F64).reshape(N, -1, 2)[:, :, 1]
+        q = torch.where(q == q, q, torch.full_like(q, float("inf")))
+        for j, (i0, i1) in enumerate(act_bound_ranges(q.shape[1])):
+            if i1 > i0:
+                out[:, j] = torch.maximum(out[:, j], q[:, i0:i1].max(1).values)
+    return out.sqrt()
+
+
+def linear_bound(w, b=None):
+    """(max row L1 norm of w [rows][cols], max|b| or 0): |W x + b| <= coef0 * max|x| + coef1 (eod_weight_l1max, without its safety
+    factor)"""
+    return float(w.to(F64).abs().sum(1).max()), 0.0 if b is None else float(b.to(F64).abs().max())

@@ -341,3 +341,108 @@ def test_conv_forward_from_class_kernels_is_the_same_function(H, W):
     _close(ref64.conv_forward(dy, None, None, ksize=3, pad=1, upsample=4, class_w=wc), ref64.conv_forward(dy, None, w, ksize=3, pad=1, upsample=4))
     s2d = ref64.space_to_depth2(dy)
     assert torch.equal(s2d[:, :, :, 5:10], dy[:, 0::2, 1::2])
+
+
+# ================================================================================================ glue ops of the inference forward
+@pytest.mark.parametrize("N,C,H,W", [(1, 3, 2, 2), (2, 5, 5, 7), (3, 4, 6, 4), (1, 2, 7, 6)])
+def test_resample2x_pool_and_nearest_match_torch(N, C, H, W):
+    x = _randn((N, C, H, W), 60)
+    _close(ref64.resample2x(_nhwc(x), 0), _nhwc(F.avg_pool2d(x, 2)))
+    up = F.interpolate(x, scale_factor=2, mode="nearest")
+    _close(ref64.resample2x(_nhwc(x), 1), _nhwc(up))
+    _close(ref64.resample2x(_nhwc(x), 1, 1), _nhwc(F.pad(up, (1, 0, 1, 0))))
+    for pad in (0, 1, 2, 3):
+        _close(ref64.resample2x(_nhwc(x), 4, pad), _nhwc(x[:, :, :H - (pad & 1), :W - (pad >> 1)]))
+
+
+@pytest.mark.parametrize("N,C,H,W", [(1, 3, 1, 1), (2, 5, 3, 3), (3, 4, 6, 4)])
+@pytest.mark.parametrize("pad", [0, 1])
+def test_resample2x_mode2_is_the_autograd_adjoint_of_mode1(N, C, H, W, pad):
+    x = _randn((N, C, H, W), 61).requires_grad_(True)
+    y = F.pad(F.interpolate(x, scale_factor=2, mode="nearest"), (pad, 0, pad, 0))
+    g = _randn(tuple(y.shape), 62)
+    y.backward(g)
+    got = ref64.resample2x(_nhwc(g), 2, pad)
+    _close(got, _nhwc(x.grad))
+    assert got.shape[1:3] == (H, W)
+
+
+@pytest.mark.parametrize("N,C,H,W", [(1, 3, 2, 2), (2, 5, 5, 7), (3, 4, 6, 4), (2, 2, 3, 3)])
+def test_resample2x_mode3_is_the_autograd_adjoint_of_mode0(N, C, H, W):
+    x = _randn((N, C, H, W), 63).requires_grad_(True)
+    y = F.avg_pool2d(x, 2)
+    g = _randn(tuple(y.shape), 64)
+    y.backward(g)
+    _close(ref64.resample2x(_nhwc(g), 3, H % 2), _nhwc(x.grad))   # (H and W are both odd or both even here)
+
+
+@pytest.mark.parametrize("N,Dm,E,J,labels,t_float", [(3, 32, 16, 24, False, False), (5, 33, 8, 0, True, True), (2, 6, 4, 7, True, False)])
+def test_time_embed_matches_plain_torch_linears(N, Dm, E, J, labels, t_float):
+    half = Dm // 2
+    freqs = torch.exp(-math.log(10000.0) * torch.arange(half, dtype=torch.float32) / half)
+    t = torch.tensor([0.0, 999.0, 12.5, 3.25, 500.0][:N]) if t_float else torch.tensor([0, 999, 17, 4, 250][:N])
+    w1, b1, w2, b2 = _randn((E, Dm), 65, 0.3), _randn((E,), 66), _randn((E, E), 67, 0.3), _randn((E,), 68)
+    wcat, bcat = (_randn((J, E), 69, 0.3), _randn((J,), 70)) if J else (None, None)
+    lab = _randn((4, E), 71) if labels else None
+    y = torch.tensor([3, 0, 3, 1, 2][:N]) if labels else None
+    h1, emb, out = ref64.time_embed(t, freqs, w1, b1, w2, b2, wcat, bcat, label_emb=lab, y=y)
+    arg = (t.float()[:, None] * freqs[None]).double()
+    e = torch.cat([arg.cos(), arg.sin()] + ([torch.zeros(N, 1, dtype=D)] if Dm % 2 else []), 1)
+    rh = F.silu(F.linear(e, w1, b1))
+    re = F.linear(rh, w2, b2) + (F.embedding(y, lab) if labels else 0.0)
+    _close(h1, rh)
+    _close(emb, re)
+    if J:
+        _close(out, F.linear(F.silu(re), wcat, bcat))
+        _, emb3, out3 = ref64.time_embed(None, None, None, None, None, None, wcat, bcat, emb=re)   # stage 3 alone
+        assert torch.equal(emb3, re)
+        _close(out3, out)
+    else:
+        assert out is None
+
+
+@pytest.mark.parametrize("per,epc", [(4, 4), (8, 8), (31 * 4, 4), (40 * 8, 8), ((32 * 7 + 5) * 4, 4)])
+def test_act_bound_direct_is_the_brute_force_maximum(per, epc):
+    x = _randn((3, per), 72)
+    x[2, -1] = 50.0
+    got = ref64.act_bound_direct(x, epc)
+    chunks = per // epc
+    covered = 0
+    for n in range(3):
+        for j in range(32):
+            idx = [i for i in range(chunks) if chunks * j // 32 <= i < chunks * (j + 1) // 32]
+            covered += len(idx)
+            want = max((abs(float(x[n, i * epc + e])) for i in idx for e in range(epc)), default=0.0)
+            assert float(got[n, j]) == want, (n, j)
+    assert covered == 3 * chunks            # the ranges partition the chunks
+    assert float(got[2, 31]) == 50.0 and float(got.max(1).values[0]) == float(x[0].abs().max())
+    x[1, per // 2] = float("nan")
+    x[0, 0] = float("-inf")
+    got = ref64.act_bound_direct(x, epc)
+    assert int(torch.isinf(got[1]).sum()) == 1 and int(torch.isinf(got[0]).sum()) == 1 and float(got[0, 0] if chunks >= 32 else got[0].max()) == math.inf
+
+
+def test_act_bound_parts_is_the_brute_force_maximum():
+    p0, p1 = _randn((2, 3, 5, 2), 73).abs(), _randn((2, 1, 7, 2), 74).abs()   # P*C = 15 and 7 pairs: no multiple of 32
+    got = ref64.act_bound_parts([p0, p1])
+    for n in range(2):
+        for j in range(32):
+            vals = [float(p.reshape(2, -1, 2)[n, i, 1]) for p in (p0, p1) for i in range(p.shape[1] * p.shape[2])
+                    if p.shape[1] * p.shape[2] * j // 32 <= i < p.shape[1] * p.shape[2] * (j + 1) // 32]
+            assert float(got[n, j]) == math.sqrt(max(vals, default=0.0))
+    assert float(got.max(1).values[0]) == math.sqrt(max(float(p0[0, :, :, 1].max()), float(p1[0, :, :, 1].max())))
+    p0[1, 2, 4, 1] = float("nan")
+    got = ref64.act_bound_parts([p0])
+    assert float(got[1, 31]) == math.inf and bool(torch.isfinite(got[0]).all())
+
+
+def test_linear_bound_bounds_a_linear_layer():
+    w, b = _randn((6, 9), 75), _randn((6,), 76)
+    c0, c1 = ref64.linear_bound(w, b)
+    assert c0 == pytest.approx(max(math.fsum(abs(float(v)) for v in row) for row in w), rel=1e-14) and c1 == max(abs(float(v)) for v in b)
+    assert ref64.linear_bound(w) == (c0, 0.0)
+    x = _randn((50, 9), 77)
+    y = F.linear(x, w, b)
+    assert bool((y.abs().amax(1) <= c0 * x.abs().amax(1) + c1).all())
+    xs = torch.sign(w[int(w.abs().sum(1).argmax())])[None]   # the bound is attained
+    assert float(F.linear(xs, w).abs().max()) == pytest.approx(c0, rel=1e-14)

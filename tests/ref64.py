@@ -460,3 +460,87 @@ def linear_bound(w, b=None):
     """(max row L1 norm of w [rows][cols], max|b| or 0): |W x + b| <= coef0 * max|x| + coef1 (eod_weight_l1max, without its safety
     factor)"""
     return float(w.to(F64).abs().sum(1).max()), 0.0 if b is None else float(b.to(F64).abs().max())
+
+
+# ================================================================================================ attention (csrc/attn*.hip), softmax rows
+def head_slices(t, heads, d, off, head_stride):
+    """[N][T][*] -> [N][heads][T][d] float64: channels off + h * head_stride + (0 .. d - 1) of every head (legacy order [h][q|k|v][d]:
+    off = 0 / d / 2d, head_stride = 3d; new order [q|k|v][h][d]: off = 0 / C / 2C, head_stride = d)"""
+    return torch.stack([t[..., off + h * head_stride: off + h * head_stride + d] for h in range(heads)], 1).to(F64)
+
+
+def attention_forward(qkv, heads, d, q_off, k_off, v_off, head_stride):
+    """QKVAttention(Legacy) on the natural layout qkv [N][T][3C]: P = softmax_s(q_t . k_s / sqrt(d)), out = P v.
+    -> out [N][T][C], lse [N][heads][T] (natural log), P [N][heads][T][T], all float64"""
+    N, T = qkv.shape[:2]
+    q, k, v = (head_slices(qkv, heads, d, o, head_stride) for o in (q_off, k_off, v_off))
+    S = (q @ k.transpose(-1, -2)) / float(d) ** 0.5
+    m = S.amax(-1, keepdim=True)
+    E = torch.exp(S - m)
+    l = E.sum(-1, keepdim=True)
+    P = E / l
+    lse = (m + torch.log(l)).squeeze(-1)
+    out = (P @ v).permute(0, 2, 1, 3).reshape(N, T, heads * d)
+    return out, lse, P
+
+
+def attention_backward(qkv, dO, heads, d, q_off, k_off, v_off, head_stride):
+    """the gradient of attention_forward's `out` with respect to qkv for the output gradient dO [N][T][C]:
+    dV = P^T dO, dP = dO v^T, D = rowsum(dP * P) (= sum_j dO * out), dS = P * (dP - D), dQ = dS k / sqrt(d), dK = dS^T q / sqrt(d).
+    -> dqkv [N][T][3C] (channels outside the q / k / v slices are zero), D [N][heads][T], float64"""
+    N, T = qkv.shape[:2]
+    q, k, v = (head_slices(qkv, heads, d, o, head_stride) for o in (q_off, k_off, v_off))
+    _, _, P = attention_forward(qkv, heads, d, q_off, k_off, v_off, head_stride)
+    g = head_slices(dO, heads, d, 0, d)
+    dV = P.transpose(-1, -2) @ g
+    dP = g @ v.transpose(-1, -2)
+    D = (dP * P).sum(-1)
+    dS = P * (dP - D[..., None])
+    a = 1.0 / float(d) ** 0.5
+    dQ, dK = a * (dS @ k), a * (dS.transpose(-1, -2) @ q)
+    dqkv = torch.zeros(qkv.shape, dtype=F64, device=qkv.device)
+    for h in range(heads):
+        for off, t in ((q_off, dQ), (k_off, dK), (v_off, dV)):
+            dqkv[..., off + h * head_stride: off + h * head_stride + d] = t[:, h]
+    return dqkv, D
+
+
+def softmax_rows(s, n):
+    """eod_softmax_rows: softmax over the first n columns of every row of s [rows][lds] -> [rows][n] float64"""
+    z = s[:, :n].to(F64)
+    e = torch.exp(z - z.amax(1, keepdim=True))
+    return e / e.sum(1, keepdim=True)
+
+
+def softmax_backward_rows(P, dP, n):
+    """eod_softmax_bwd_rows: dS = P * (dP - sum_k dP P) over the first n columns -> [rows][n] float64"""
+    p, g = P[:, :n].to(F64), dP[:, :n].to(F64)
+    return p * (g - (g * p).sum(1, keepdim=True))
+
+
+def rowdot(a, b, n0, n1, n2, s0, s1, s2, d):
+    """eod_rowdot: out[i0][i1][i2] = sum_{j < d} a[off + j] b[off + j], off = i0 s0 + i1 s1 + i2 s2 (elements of the flat tensors)"""
+    dev = a.device
+    i0, i1, i2 = (torch.arange(n, device=dev) for n in (n0, n1, n2))
+    off = i0[:, None, None] * s0 + i1[None, :, None] * s1 + i2[None, None, :] * s2
+    idx = off[..., None] + torch.arange(d, device=dev)
+    return (a.reshape(-1).to(F64)[idx] * b.reshape(-1).to(F64)[idx]).sum(-1)
+
+
+def attention_pack(qkv, heads, d, dpad, ldt, new_order):
+    """the operands of eod_attention_fwd, gathered from the natural layout qkv [N][T][3C] the way AttentionBlock._row_maps gathers the
+    rows of the projection weight: qk [N * T][2 * heads * dpad] = [q: heads x dpad | k: heads x dpad] with every head zero-padded from d
+    to dpad channels, and vT [N][C][ldt] = v transposed (head-major channels, keys contiguous, zero beyond T).  Same dtype as qkv"""
+    N, T = qkv.shape[:2]
+    C = heads * d
+    base = (lambda which, h: which * C + h * d) if new_order else (lambda which, h: h * 3 * d + which * d)
+    qk = torch.zeros((N * T, 2 * heads * dpad), dtype=qkv.dtype, device=qkv.device)
+    flat = qkv.reshape(N * T, 3 * C)
+    for which in (0, 1):
+        for h in range(heads):
+            c0 = (which * heads + h) * dpad
+            qk[:, c0: c0 + d] = flat[:, base(which, h): base(which, h) + d]
+    vT = torch.zeros((N, C, ldt), dtype=qkv.dtype, device=qkv.device)
+    for h in range(heads):
+        vT[:, h * d: (h + 1) * d, :T] = qkv[:, :, base(2, h): base(2, h) + d].transpose(1, 2)
+    return qk, vT

@@ -446,3 +446,115 @@ def test_linear_bound_bounds_a_linear_layer():
     assert bool((y.abs().amax(1) <= c0 * x.abs().amax(1) + c1).all())
     xs = torch.sign(w[int(w.abs().sum(1).argmax())])[None]   # the bound is attained
     assert float(F.linear(xs, w).abs().max()) == pytest.approx(c0, rel=1e-14)
+
+
+# ================================================================================================ attention, softmax rows
+def _orders(heads, d):
+    C = heads * d
+    return {"legacy": (0, d, 2 * d, 3 * d), "new": (0, C, 2 * C, d)}
+
+
+def _torch_attention(qkv, heads, d, order):
+    """QKVAttentionLegacy / QKVAttention of the modelled UNet, written on [N][3C][T] as there (scale d^-1/4 on q and on k)"""
+    N, T, W = qkv.shape
+    x = qkv.permute(0, 2, 1)
+    if order == "legacy":
+        q, k, v = x.reshape(N * heads, 3 * d, T).split(d, dim=1)
+    else:
+        q, k, v = (t.reshape(N * heads, d, T) for t in x.chunk(3, dim=1))
+    s = 1.0 / math.sqrt(math.sqrt(d))
+    w = torch.einsum("bct,bcs->bts", q * s, k * s)
+    P = torch.softmax(w, -1)
+    a = torch.einsum("bts,bcs->bct", P, v).reshape(N, heads * d, T).permute(0, 2, 1)
+    return a, torch.logsumexp(w, -1).reshape(N, heads, T), P.reshape(N, heads, T, T)
+
+
+@pytest.mark.parametrize("order", ["legacy", "new"])
+@pytest.mark.parametrize("N,T,heads,d", [(1, 1, 1, 8), (2, 7, 3, 4), (3, 33, 2, 12), (1, 65, 1, 24)])
+def test_attention_forward_and_backward_match_autograd(order, N, T, heads, d):
+    qo, ko, vo, hs = _orders(heads, d)[order]
+    qkv = _randn((N, T, 3 * heads * d), 40, 0.9).requires_grad_(True)
+    dO = _randn((N, T, heads * d), 41)
+    a, lse, P = _torch_attention(qkv, heads, d, order)
+    a.backward(dO)
+    out, lse64, P64 = ref64.attention_forward(qkv.detach(), heads, d, qo, ko, vo, hs)
+    _close(out, a.detach())
+    _close(lse64, lse.detach())
+    _close(P64, P.detach())
+    assert float((P64.sum(-1) - 1).abs().max()) < 1e-14
+    dqkv, Dr = ref64.attention_backward(qkv.detach(), dO, heads, d, qo, ko, vo, hs)
+    _close(dqkv, qkv.grad, 1e-11)
+    _close(Dr, ref64.head_slices(dO * a.detach(), heads, d, 0, d).sum(-1), 1e-11)   # D = rowsum(dP * P) = sum_j dO * out
+
+
+def test_attention_forward_of_one_key_returns_v():
+    heads, d = 3, 8
+    for order, (qo, ko, vo, hs) in _orders(heads, d).items():
+        qkv = _randn((2, 1, 3 * heads * d), 42)
+        out, lse, P = ref64.attention_forward(qkv, heads, d, qo, ko, vo, hs)
+        assert torch.equal(out, ref64.head_slices(qkv, heads, d, vo, hs).permute(0, 2, 1, 3).reshape(2, 1, heads * d)), order
+        assert torch.equal(P, torch.ones_like(P))
+
+
+def test_softmax_rows_and_backward_match_autograd():
+    for rows, n, lds in ((5, 1, 4), (3, 65, 72), (2, 1030, 1036)):
+        s = _randn((rows, lds), 43, 4.0)
+        s[0, :n] += 50.0 * (torch.arange(n) % 7 == 0)   # a peaked row
+        sn = s.clone()
+        sn[:, n:] = float("nan")                        # columns behind n are never read
+        z = s[:, :n].clone().requires_grad_(True)
+        P = torch.softmax(z, -1)
+        g = _randn((rows, lds), 44)
+        P.backward(g[:, :n])
+        got = ref64.softmax_rows(sn, n)
+        _close(got, P.detach())
+        Pp = torch.nn.functional.pad(P.detach(), (0, lds - n), value=float("nan"))
+        _close(ref64.softmax_backward_rows(Pp, g, n), z.grad, 1e-11)
+
+
+def test_rowdot_matches_einsum_in_both_channel_orders():
+    N, T, heads, d = 2, 5, 3, 8
+    C = heads * d
+    a, b = _randn((N, T, C), 45), _randn((N, T, C), 46)
+    ref = torch.einsum("nthj,nthj->nht", a.reshape(N, T, heads, d), b.reshape(N, T, heads, d))
+    _close(ref64.rowdot(a, b, N, heads, T, T * C, d, C, d), ref)
+    # a strided operand: the q slices of a legacy-order qkv tensor against themselves
+    qkv = _randn((N, T, 3 * C), 47)
+    q = ref64.head_slices(qkv, heads, d, 0, 3 * d)
+    _close(ref64.rowdot(qkv, qkv, N, heads, T, T * 3 * C, 3 * d, 3 * C, d), (q * q).sum(-1))
+
+
+@pytest.mark.parametrize("new_order", [False, True])
+@pytest.mark.parametrize("T,heads,d,epc", [(7, 2, 12, 8), (5, 3, 4, 8), (9, 1, 20, 4), (8, 2, 8, 8)])
+def test_attention_pack_matches_the_row_maps_of_the_attention_block(new_order, T, heads, d, epc):
+    """the packed operands against the row maps written out as AttentionBlock._row_maps writes them (an index list with -1 = zero row),
+    and the packed attention against the natural-layout one"""
+    N, C = 2, heads * d
+    dpad, ldt = -(-d // epc) * epc, -(-T // epc) * epc
+    base = (lambda which, h: which * C + h * d) if new_order else (lambda which, h: h * 3 * d + which * d)
+    qk_rows = [r for which in (0, 1) for h in range(heads) for r in [base(which, h) + j for j in range(d)] + [-1] * (dpad - d)]
+    v_rows = [base(2, h) + j for h in range(heads) for j in range(d)]
+    qkv = _randn((N, T, 3 * C), 48)
+    qk, vT = ref64.attention_pack(qkv, heads, d, dpad, ldt, new_order)
+    ext = torch.cat([qkv, torch.zeros((N, T, 1), dtype=D)], -1)
+    assert torch.equal(qk, ext[..., qk_rows].reshape(N * T, 2 * heads * dpad))
+    assert torch.equal(vT[..., :T], qkv[..., v_rows].transpose(1, 2)) and not bool(vT[..., T:].any())
+    # attention on the packed operands == attention on the natural layout
+    Cq = heads * dpad
+    q = qk[:, :Cq].reshape(N, T, heads, dpad).permute(0, 2, 1, 3)
+    k = qk[:, Cq:].reshape(N, T, heads, dpad).permute(0, 2, 1, 3)
+    P = torch.softmax(q @ k.transpose(-1, -2) / math.sqrt(d), -1)
+    a = torch.einsum("nhts,nhjs->nthj", P, vT[..., :T].reshape(N, heads, d, T)).reshape(N, T, C)
+    qo, ko, vo, hs = _orders(heads, d)["new" if new_order else "legacy"]
+    _close(a, ref64.attention_forward(qkv, heads, d, qo, ko, vo, hs)[0])
+
+
+def test_presplit_round_trip_on_attention_operands():
+    """decode(encode(x)) is x to 2^-22 (two fp16 mantissas) plus half an fp16 subnormal step of the scaled value, at the scale of the attention kernels' exponent range"""
+    x = _randn((3, 9, 24), 49) * torch.tensor([1e-3, 1.0, 300.0], dtype=D)[:, None, None]
+    tab = torch.zeros((3, 32))
+    tab[:, 5] = x.abs().amax((1, 2)).float() * 1.5
+    s = ref64.presplit_scale(tab, kmin=ref64.AB_KMIN_ATTN)
+    assert bool((s * x.abs().amax((1, 2)) < 2.0 ** 15).all())
+    back = ref64.presplit_decode(ref64.presplit_encode(x, s), s)
+    assert bool(((back - x).abs() <= 2.0 ** -22 * x.abs() + 2.0 ** -25 / s[:, None, None]).all())

@@ -669,6 +669,20 @@ class BoundPsf:
             self.c_G = _c_floats(obs.pinv if obs.solver == "cg" else np.ascontiguousarray(obs.response.T))
         else:
             self.K, self.c_channels = len(channels), _c_ints(channels)
+        # the entry points (include/eodiff.h) and what each takes between the weight (the step) and K: taps, factor, channel list / matrix
+        f = obs.factor
+        if self.xy:                                    # eod_psf_{residual,update}_xy: both tap vectors, the channel list AND the matrix, one NULL
+            cs, R, G = (None, self.c_R, self.c_G) if self.mixed else (self.c_channels, None, None)
+            self.suffix, self.takes_mask_c1 = "_xy", True
+            self.residual_args = (self.c_taps_y, self.ry, self.c_taps_x, self.rx, f, cs, R)
+            self.update_args = (self.c_taps_y, self.ry, self.c_taps_x, self.rx, f, cs, G)
+        elif self.mixed:                               # eod_psf_{residual,update}_mix: the matrix; one mask plane always, no mask_c1 argument
+            self.suffix, self.takes_mask_c1 = "_mix", False
+            self.residual_args = (self.c_taps, self.r, f, self.c_R)
+            self.update_args = (self.c_taps, self.r, f, self.c_G)
+        else:                                          # eod_psf_{residual,update}: the channel list
+            self.suffix, self.takes_mask_c1 = "", True
+            self.residual_args = self.update_args = (self.c_taps, self.r, f, self.c_channels)
         self.step = float(np.float32(self.tau / (obs.factor * obs.factor)))
         self.values = f32c(obs.values.to(device))
         self.mask = None if obs.mask is None else f32c(obs.mask.to(device))
@@ -691,42 +705,19 @@ class BoundPsf:
             raise _lib.EodError(f"observation bound to a state of shape {self.shape}, the step got {tuple(p.shape)}")
         B, C, H, W = self.shape
         m = self.mask
-        if self.xy:
-            _lib.check(_lib.lib().eod_psf_residual_xy(p.data_ptr(), self.values.data_ptr(), _lib.ptr(m), self.weights[i] if weight is None else weight,
-                                                      self.c_taps_y, self.ry, self.c_taps_x, self.rx, self.factor,
-                                                      None if self.mixed else self.c_channels, self.c_R if self.mixed else None, self.K, B, C, H, W,
-                                                      int(self.values.shape[0] != B), int(m is not None and m.shape[0] != B),
-                                                      int(self.mixed or (m is not None and m.shape[1] != self.K)),
-                                                      q.data_ptr(), current_stream_ptr(p.device)), "eod_psf_residual_xy")
-            return q
-        if self.mixed:
-            _lib.check(_lib.lib().eod_psf_residual_mix(p.data_ptr(), self.values.data_ptr(), _lib.ptr(m), self.weights[i] if weight is None else weight,
-                                                       self.c_taps, self.r, self.factor, self.c_R, self.K, B, C, H, W,
-                                                       int(self.values.shape[0] != B), int(m is not None and m.shape[0] != B),
-                                                       q.data_ptr(), current_stream_ptr(p.device)), "eod_psf_residual_mix")
-            return q
-        _lib.check(_lib.lib().eod_psf_residual(p.data_ptr(), self.values.data_ptr(), _lib.ptr(m), self.weights[i] if weight is None else weight,
-                                               self.c_taps, self.r, self.factor,
-                                               self.c_channels, self.K, B, C, H, W, int(self.values.shape[0] != B),
-                                               int(m is not None and m.shape[0] != B), int(m is not None and m.shape[1] != self.K),
-                                               q.data_ptr(), current_stream_ptr(p.device)), "eod_psf_residual")
+        name = "eod_psf_residual" + self.suffix
+        mask_c1 = (int(self.mixed or (m is not None and m.shape[1] != self.K)),) if self.takes_mask_c1 else ()
+        _lib.check(getattr(_lib.lib(), name)(p.data_ptr(), self.values.data_ptr(), _lib.ptr(m), self.weights[i] if weight is None else weight,
+                                             *self.residual_args, self.K, B, C, H, W, int(self.values.shape[0] != B),
+                                             int(m is not None and m.shape[0] != B), *mask_c1, q.data_ptr(), current_stream_ptr(p.device)), name)
         return q
 
     def update(self, p, q, out, step=None):
         """out = p - tau A^T q: eod_psf_update (with a response: eod_psf_update_mix, the coarse planes mixed by R^T or, under cg, pinv(R))"""
         B, C, H, W = self.shape
-        if self.xy:
-            _lib.check(_lib.lib().eod_psf_update_xy(p.data_ptr(), q.data_ptr(), self.step if step is None else step, self.c_taps_y, self.ry,
-                                                    self.c_taps_x, self.rx, self.factor, None if self.mixed else self.c_channels,
-                                                    self.c_G if self.mixed else None, self.K, B, C, H, W, out.data_ptr(),
-                                                    current_stream_ptr(p.device)), "eod_psf_update_xy")
-            return out
-        if self.mixed:
-            _lib.check(_lib.lib().eod_psf_update_mix(p.data_ptr(), q.data_ptr(), self.step if step is None else step, self.c_taps, self.r, self.factor,
-                                                     self.c_G, self.K, B, C, H, W, out.data_ptr(), current_stream_ptr(p.device)), "eod_psf_update_mix")
-            return out
-        _lib.check(_lib.lib().eod_psf_update(p.data_ptr(), q.data_ptr(), self.step if step is None else step, self.c_taps, self.r, self.factor, self.c_channels, self.K,
-                                             B, C, H, W, out.data_ptr(), current_stream_ptr(p.device)), "eod_psf_update")
+        name = "eod_psf_update" + self.suffix
+        _lib.check(getattr(_lib.lib(), name)(p.data_ptr(), q.data_ptr(), self.step if step is None else step, *self.update_args, self.K, B, C, H, W,
+                                             out.data_ptr(), current_stream_ptr(p.device)), name)
         return out
 
     def project(self, i, p):
@@ -918,31 +909,20 @@ def psf_observe(x, psf, factor, channels=None, response=None):
         R = _response(what, response)
         if R.shape[1] != C:
             raise _lib.EodError(f"{what}: `response` mixes {R.shape[1]} channels, x has {C}")
-        if H % f or W % f:
-            raise _lib.EodError(f"{what}: factor = {f} does not divide {H} x {W}")
-        require_gpu(x, what)
-        x = f32c(x)
-        out = torch.empty((B, R.shape[0], H // f, W // f), device=x.device, dtype=torch.float32)
-        if xy:
-            _lib.check(_lib.lib().eod_psf_apply_xy(x.data_ptr(), _c_floats(psf.taps_y), psf.radii[0], _c_floats(psf.taps_x), psf.radii[1], f, None,
-                                                   _c_floats(R), R.shape[0], out.data_ptr(), B, C, H, W, current_stream_ptr(x.device)),
-                       "eod_psf_apply_xy")
-            return out
-        _lib.check(_lib.lib().eod_psf_apply_mix(x.data_ptr(), _c_floats(h), h.size // 2, f, _c_floats(R), R.shape[0], out.data_ptr(), B, C, H, W,
-                                                current_stream_ptr(x.device)), "eod_psf_apply_mix")
-        return out
-    cs = tuple(range(C)) if channels is None else _channels(what, channels)
-    if cs[-1] >= C:
-        raise _lib.EodError(f"{what}: channel {cs[-1]} of an x with {C} channels")
+        K, c_cs, c_R = R.shape[0], None, _c_floats(R)
+    else:
+        cs = tuple(range(C)) if channels is None else _channels(what, channels)
+        if cs[-1] >= C:
+            raise _lib.EodError(f"{what}: channel {cs[-1]} of an x with {C} channels")
+        K, c_cs, c_R = len(cs), _c_ints(cs), None
     if H % f or W % f:
         raise _lib.EodError(f"{what}: factor = {f} does not divide {H} x {W}")
     require_gpu(x, what)
     x = f32c(x)
-    out = torch.empty((B, len(cs), H // f, W // f), device=x.device, dtype=torch.float32)
+    out = torch.empty((B, K, H // f, W // f), device=x.device, dtype=torch.float32)
     if xy:
-        _lib.check(_lib.lib().eod_psf_apply_xy(x.data_ptr(), _c_floats(psf.taps_y), psf.radii[0], _c_floats(psf.taps_x), psf.radii[1], f, _c_ints(cs),
-                                               None, len(cs), out.data_ptr(), B, C, H, W, current_stream_ptr(x.device)), "eod_psf_apply_xy")
-        return out
-    _lib.check(_lib.lib().eod_psf_apply(x.data_ptr(), _c_floats(h), h.size // 2, f, _c_ints(cs), len(cs), out.data_ptr(), B, C, H, W,
-                                        current_stream_ptr(x.device)), "eod_psf_apply")
+        name, args = "eod_psf_apply_xy", (_c_floats(psf.taps_y), psf.radii[0], _c_floats(psf.taps_x), psf.radii[1], f, c_cs, c_R)
+    else:
+        name, args = ("eod_psf_apply" if c_R is None else "eod_psf_apply_mix"), (_c_floats(h), h.size // 2, f, c_cs if c_R is None else c_R)
+    _lib.check(getattr(_lib.lib(), name)(x.data_ptr(), *args, K, out.data_ptr(), B, C, H, W, current_stream_ptr(x.device)), name)
     return out

@@ -5,8 +5,11 @@
 // of exactly its size, so a read or write outside a plane, and a misaligned 16-byte access, ends the run.  The cases are the shape list of
 // tests/test_gpu_psf_xy.py, each with three tap families (two different symmetric Gaussians; Gaussians shifted by +-0.37 f; the one-sided
 // [0 .. .6 .4]), the plain and the mixed form, every access form the shape allows.  With a directory as its argument it also writes one
-// file per case (inputs and the three outputs) for tests/test_psf_xy_host.py to compare with the torch emulation.  Prints "ok <cases>"
-// and returns 0 when every output is bit-equal.
+// file per case (inputs and the three outputs) for tests/test_psf_xy_host.py to compare with the torch emulation.  A last family is the
+// fact any merge of the bodies rests on: with equal, bitwise symmetric taps (r = 12 on both axes) the one-vector bodies (psf_residual_phase
+// / psf_update_phase and their _mix forms, which the bare and the _mix entry points run) give the bits of the per-axis bodies -- apply,
+// residual and update, plain and mixed, every access form, at the list's two smallest planes (6 x 7, 12 x 28) and at its smallest plane
+// that allows all four access forms (32 x 64 at f = 4).  Prints "ok <cases>" and returns 0 when every output is bit-equal.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -76,6 +79,7 @@ static void ref_blur(const float* hy, int ry, const float* hx, int rx, const flo
 
 struct Case {
     int f, ry, rx, H, W, B, C, K, mixed, mask_form;
+    int one;                           // equal symmetric taps: the one-vector bodies are run as well and must give the same bits
     std::vector<float> hy, hx, M, G;   // forward taps; R [K][C] and G [C][K] of the mixed form
 };
 
@@ -183,6 +187,50 @@ static void run_update(const PsfArgs& g, const PsfTapsXy& tt, const PsfMix* mx) 
     }
     free(s);
 }
+// the one-vector bodies (g.r and t: the radius and the taps of both axes)
+template <bool VEC, bool VECQ, bool MIX>
+static void run_residual_one(const PsfArgs& g, const PsfTaps& t, const PsfMix* mx) {
+    PsfResLds* s = (PsfResLds*)malloc(sizeof(PsfResLds));
+    const long long items = (long long)g.B * g.K * g.tiles_x * g.tiles_y;
+    for (long long item = 0; item < items; ++item) {
+        memset(s, 0xff, sizeof(*s));
+        for (int phase = 0; phase < 4; ++phase)
+            for (int tid = 0; tid < PSF_THREADS; ++tid) {
+                if (MIX) psf_residual_mix_phase<VEC, VECQ>(phase, g, t, *mx, *s, item, tid);
+                else psf_residual_phase<VEC, VECQ>(phase, g, t, *s, item, tid);
+            }
+    }
+    free(s);
+}
+template <bool VEC, bool VECQ, bool MIX>
+static void run_update_one(const PsfArgs& g, const PsfTaps& t, const PsfMix* mx) {
+    PsfUpdLds* s = (PsfUpdLds*)malloc(sizeof(PsfUpdLds));
+    const long long items = (long long)g.B * g.C * g.tiles_x * g.tiles_y;
+    for (long long item = 0; item < items; ++item) {
+        memset(s, 0xff, sizeof(*s));
+        for (int phase = 0; phase < 5; ++phase)
+            for (int tid = 0; tid < PSF_THREADS; ++tid) {
+                if (MIX) psf_update_mix_phase<VEC, VECQ>(phase, g, t, *mx, *s, item, tid);
+                else psf_update_phase<VEC, VECQ>(phase, g, t, *s, item, tid);
+            }
+    }
+    free(s);
+}
+template <bool MIX>
+static void residual_one_form(int form, const PsfArgs& g, const PsfTaps& t, const PsfMix* mx) {
+    if (form == 0) run_residual_one<false, false, MIX>(g, t, mx);
+    else if (form == 1) run_residual_one<true, false, MIX>(g, t, mx);
+    else if (form == 2) run_residual_one<false, true, MIX>(g, t, mx);
+    else run_residual_one<true, true, MIX>(g, t, mx);
+}
+template <bool MIX>
+static void update_one_form(int form, const PsfArgs& g, const PsfTaps& t, const PsfMix* mx) {
+    if (form == 0) run_update_one<false, false, MIX>(g, t, mx);
+    else if (form == 1) run_update_one<true, false, MIX>(g, t, mx);
+    else if (form == 2) run_update_one<false, true, MIX>(g, t, mx);
+    else run_update_one<true, true, MIX>(g, t, mx);
+}
+
 template <bool MIX>
 static void residual_form(int form, const PsfArgs& g, const PsfTapsXy& tt, const PsfMix* mx) {
     if (form == 0) run_residual<false, false, MIX>(g, tt, mx);
@@ -235,7 +283,7 @@ static void put(FILE* fp, const void* p, size_t bytes) { if (fp && fwrite(p, 1, 
 static void one_case(Case cs, int family, const char* dir, int number) {
     const int B = cs.B, C = cs.C, K = cs.K, f = cs.f, H = cs.H, W = cs.W;
     cs.hy = taps_of(family, cs.ry, f, 0.3, 0.37 * f);
-    cs.hx = taps_of(family, cs.rx, f, 0.5, -0.37 * f);
+    cs.hx = cs.one ? cs.hy : taps_of(family, cs.rx, f, 0.5, -0.37 * f);
     PsfArgs g;
     memset(&g, 0, sizeof(g));
     PsfTapsXy fw, rv;
@@ -274,7 +322,7 @@ static void one_case(Case cs, int family, const char* dir, int number) {
     g.mask_b1 = mask_form == 1 || mask_form == 2;
     g.mask_c1 = mask_form == 2 || cs.mixed;
     Buf p(B * C * hw), values((g.values_b1 ? 1 : B) * K * chw), mask((g.mask_b1 ? 1 : B) * (g.mask_c1 ? 1 : K) * chw);
-    Buf q(B * K * chw), qr(B * K * chw), ar(B * K * chw), out(B * C * hw), outr(B * C * hw);
+    Buf q(B * K * chw), qr(B * K * chw), ar(B * K * chw), out(B * C * hw), outr(B * C * hw), q1(B * K * chw), out1(B * C * hw);
     p.fill(); values.fill(); mask.fill();
     g.p = p.p; g.values = values.p; g.mask = mask_form == 3 ? nullptr : mask.p;
     const bool vec = W % 4 == 0, vecq = (W / f) % 4 == 0;
@@ -290,6 +338,12 @@ static void one_case(Case cs, int family, const char* dir, int number) {
             if (cs.mixed) residual_form<true>(form, a, fw, &mr);
             else residual_form<false>(form, a, fw, nullptr);
             same(apply ? "apply" : "residual", q.p, want, q.n, cs, form);
+            if (!cs.one) continue;
+            q1.nan();
+            a.out = q1.p;
+            if (cs.mixed) residual_one_form<true>(form, a, fw.x, &mr);
+            else residual_one_form<false>(form, a, fw.x, nullptr);
+            same(apply ? "apply, one vector against two" : "residual, one vector against two", q1.p, q.p, q.n, cs, form);
         }
     }
     g.q = qr.p;
@@ -301,6 +355,12 @@ static void one_case(Case cs, int family, const char* dir, int number) {
         if (cs.mixed) update_form<true>(form, g, rv, &mg);
         else update_form<false>(form, g, rv, nullptr);
         same("update", out.p, outr.p, out.n, cs, form);
+        if (!cs.one) continue;
+        out1.nan();
+        g.out = out1.p;
+        if (cs.mixed) update_one_form<true>(form, g, fw.x, &mg);       // (a symmetric array is its own reverse)
+        else update_one_form<false>(form, g, fw.x, nullptr);
+        same("update, one vector against two", out1.p, out.p, out.n, cs, form);
     }
     if (!dir) return;
     // int32 [f ry rx H W B C K mixed mask_form], then fp32: hy, hx, lambda, step, p, values, mask (unless mask_form 3), R and G (mixed), and
@@ -343,9 +403,17 @@ int main(int argc, char** argv) {
             for (int mixed = 0; mixed < 2; ++mixed) {
                 Case cs;
                 cs.f = shapes[s][0]; cs.ry = shapes[s][1]; cs.rx = shapes[s][2]; cs.H = shapes[s][3]; cs.W = shapes[s][4];
-                cs.B = 2; cs.C = 3; cs.K = 2; cs.mixed = mixed; cs.mask_form = (s + family) % 4;
+                cs.B = 2; cs.C = 3; cs.K = 2; cs.mixed = mixed; cs.mask_form = (s + family) % 4; cs.one = 0;
                 one_case(cs, family, dir, number++);
             }
+    const int equal[3][3] = {{1, 6, 7}, {2, 12, 28}, {4, 32, 64}};       // f, H, W: the one-vector bodies against the per-axis ones (nothing is dumped)
+    for (int s = 0; s < 3; ++s)
+        for (int mixed = 0; mixed < 2; ++mixed) {
+            Case cs;
+            cs.f = equal[s][0]; cs.ry = cs.rx = PSF_MAXR; cs.H = equal[s][1]; cs.W = equal[s][2];
+            cs.B = 2; cs.C = 3; cs.K = 2; cs.mixed = mixed; cs.mask_form = s; cs.one = 1;
+            one_case(cs, 0, nullptr, 0);
+        }
     if (failures) { printf("FAILED %d of %d\n", failures, cases); return 1; }
     printf("ok %d\n", cases);
     return 0;

@@ -12,6 +12,12 @@ One process, profiler off, the arms alternating:
       return the same bits.  A third chain, anisotropic and shifted (MTF 0.3 along y, 0.5 along x, +-0.37 f), is timed beside them.
 
     python tools/psf_xy_bench.py [--arch A0] [--size 64] [--batch 16] [--steps 25] [--reps 5] [--no-call] [--out FILE]
+
+With --against LIB (another build of libeodiff.so, e.g. tools/build_lib_at.sh <commit> parent -> scratch/altlib/libeodiff_parent.so) it
+does one thing instead: LIB is loaded into this process beside the tree's library and the same entry points of both are timed on the same
+tensors, arms alternating (the bare pair and the _mix pair with K = 4 at r = 6 and r = 12, the _xy pair at (12, 12) and (12, 2)).  Per
+arm: new / LIB median, LIB's own spread (max - min) / median in this run, and whether the two libraries wrote the same bits; an arm passes
+when the ratio exceeds 1 by no more than that spread and the bits are equal.  The default --out is then profiles/psf_against.json.
 """
 import argparse
 import ctypes
@@ -42,6 +48,67 @@ def timed(fn, reps):
     return a.elapsed_time(b) / reps
 
 
+def against(args, dev):
+    """the PSF entry points of this tree's library next to those of args.against, in one process"""
+    from eo_diffusion_amd.diffusion.consistency import SeparablePsf, gaussian_psf, psf_tau
+    L, old = _lib.lib(), ctypes.CDLL(os.path.abspath(args.against))
+    for name, (res, argtypes) in _lib.SYMBOLS.items():
+        if name.startswith("eod_psf_") or name == "eod_last_error":
+            fn = getattr(old, name)
+            fn.restype, fn.argtypes = res, argtypes
+    st = current_stream_ptr(dev)
+    p = lambda t: t.data_ptr()
+    floats = lambda h: (ctypes.c_float * h.size)(*h.ravel().tolist())
+    B, C, f, H, W = 1, 4, 4, 2048, 2048
+    K = C
+    g = torch.Generator(device=dev).manual_seed(1)
+    x = torch.randn((B, C, H, W), device=dev, generator=g)
+    cvals = torch.randn((B, K, H // f, W // f), device=dev, generator=g)
+    qin, q, out = cvals.clone(), torch.empty_like(cvals), torch.empty_like(x)      # both libraries read and write the SAME tensors: no arm is
+                                                                                   # timed on another allocation than the arm it is compared with
+    chans = (ctypes.c_int32 * C)(*range(C))
+    R = floats(torch.randn((K, C), generator=torch.Generator().manual_seed(2)).numpy())
+    G = floats(torch.randn((C, K), generator=torch.Generator().manual_seed(3)).numpy())
+    arms = {}                                                         # name -> the call of one library: (rc, the tensor it wrote)
+    for r in (6, 12):
+        h = gaussian_psf(f, 0.3, radius=r)
+        t, step = floats(h), psf_tau(h, f, H, W) / (f * f)
+        arms[f"psf_residual r={r}"] = lambda lib, t=t, r=r: (lib.eod_psf_residual(p(x), p(cvals), 0, 1.0, t, r, f, chans, C, B, C, H, W, 0, 0, 0, p(q), st), q)
+        arms[f"psf_update r={r}"] = lambda lib, t=t, r=r, step=step: (lib.eod_psf_update(p(x), p(qin), step, t, r, f, chans, C, B, C, H, W, p(out), st), out)
+        arms[f"psf_residual_mix r={r}"] = lambda lib, t=t, r=r: (lib.eod_psf_residual_mix(p(x), p(cvals), 0, 1.0, t, r, f, R, K, B, C, H, W, 0, 0, p(q), st), q)
+        arms[f"psf_update_mix r={r}"] = lambda lib, t=t, r=r, step=step: (lib.eod_psf_update_mix(p(x), p(qin), step, t, r, f, G, K, B, C, H, W, p(out), st), out)
+    for ry, rx in ((12, 12), (12, 2)):
+        hy, hx = gaussian_psf(f, 0.3, radius=ry), gaussian_psf(f, 0.3, radius=rx)
+        ty, tx, step = floats(hy), floats(hx), psf_tau(SeparablePsf(hx, hy), f, H, W) / (f * f)
+        arms[f"psf_residual_xy ({ry}, {rx})"] = lambda lib, ty=ty, tx=tx, ry=ry, rx=rx: (
+            lib.eod_psf_residual_xy(p(x), p(cvals), 0, 1.0, ty, ry, tx, rx, f, chans, None, C, B, C, H, W, 0, 0, 0, p(q), st), q)
+        arms[f"psf_update_xy ({ry}, {rx})"] = lambda lib, ty=ty, tx=tx, ry=ry, rx=rx, step=step: (
+            lib.eod_psf_update_xy(p(x), p(qin), step, ty, ry, tx, rx, f, chans, None, C, B, C, H, W, p(out), st), out)
+    us = lambda v: round(v * 1e3, 2)
+    rows = []
+    for name, arm in arms.items():
+        wrote = []
+        for lib in (L, old):                                          # warm-up of each arm, and the bits
+            rc, dst = arm(lib)
+            assert rc == 0, lib.eod_last_error()
+            wrote.append(dst.clone())
+            dst.fill_(float("nan"))
+            timed(lambda: arm(lib), 5)
+        same = bool(torch.equal(*wrote))
+        ts = {L: [], old: []}
+        for rep in range(args.reps):                                  # the libraries alternate, and so does which of them goes first
+            for lib in ((L, old) if rep % 2 == 0 else (old, L)):
+                ts[lib].append(timed(lambda: arm(lib), args.launches))
+        m_new, m_old = statistics.median(ts[L]), statistics.median(ts[old])
+        spread = (max(ts[old]) - min(ts[old])) / m_old
+        row = {"arm": name, "shape": [B, C, H, W], "f": f, "K": K, "new_us": us(m_new), "against_us": us(m_old), "new_over_against": round(m_new / m_old, 4),
+               "against_spread": round(spread, 4), "new_min_max_us": [us(min(ts[L])), us(max(ts[L]))], "against_min_max_us": [us(min(ts[old])), us(max(ts[old]))],
+               "same_bits": same, "pass": bool(same and m_new / m_old <= 1.0 + spread)}
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    return {"against": os.path.basename(args.against), "launches": args.launches, "reps": args.reps, "arms": rows, "pass": all(r["pass"] for r in rows)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--arch", default="A0")
@@ -53,11 +120,21 @@ def main():
     ap.add_argument("--reps", type=int, default=5, help="alternations")
     ap.add_argument("--launches", type=int, default=50, help="back-to-back launches per timing")
     ap.add_argument("--no-call", action="store_true", help="kernels only")
+    ap.add_argument("--against", default=None, metavar="LIB", help="another build of libeodiff.so: time its PSF entry points next to this tree's, nothing else")
     ap.add_argument("--out", default=None, help="the JSON object is written here, too (default: profiles/psf_xy_bench_<arch>_<size>_T<timesteps>.json)")
     args = ap.parse_args()
-    args.out = args.out or os.path.join(ROOT, "profiles", f"psf_xy_bench_{args.arch}_{args.size}_T{args.timesteps}.json")
+    args.out = args.out or os.path.join(ROOT, "profiles", "psf_against.json" if args.against else f"psf_xy_bench_{args.arch}_{args.size}_T{args.timesteps}.json")
     if not torch.cuda.is_available():
         raise SystemExit("psf_xy_bench.py measures on the GPU; there is nothing to time without one")
+    if args.against:
+        with torch.no_grad():
+            res = against(args, torch.device("cuda", 0))
+        line = json.dumps(res)
+        print(line, flush=True)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            fh.write(line + "\n")
+        return
     from eo_diffusion_amd.diffusion.consistency import PsfObservation, SeparablePsf, gaussian_psf, psf_observe, psf_tau
     from eo_diffusion_amd.diffusion.dpm_solver import DPMSolverSampler
     dev = torch.device("cuda", 0)

@@ -85,7 +85,7 @@ struct IgemmP {
     const char* b2;  // packed [Cout][SC0 + SC1] (the 1x1 weight; split mode: same scale as `b`)
     int SC0, SC1, skc0, skc1;
     int n_base;  // halo kernel: first output column of this launch (a conv of 384 columns runs as a 256-column and a 128-column launch)
-    int tpw;     // halo kernel, STREAM instances: consecutive pixel tiles (of one image and one N-tile) per workgroup; the others: 1
+    int tpw;     // conv_head_kernel: consecutive pixel tiles (of one image) per workgroup; every other kernel: 1, not read
     // split-fp16 products: bound tables (common.h) of the activation operands -> a power-of-two operand scale per image, derived in
     // the kernel.  conv: a_bound [N][32] of the conv input, skip_bound of the fused skip conv's input; gemm (x3): a_bound / b_bound
     // [nb0][32] of the two operands.  NULL = fixed scale 16 (the caller guarantees |x| < 4094).
@@ -710,11 +710,11 @@ __device__ __forceinline__ void halo_epilogue_direct(const IgemmP& p, const Tile
     }
 }
 
-template <typename T, bool CONV, int BM, int BN, int WAVES_M, int WAVES_N, int STAGES, bool SPLIT = false, int MS = 32, bool DIRECT = false>
+template <typename T, bool CONV, int BM, int BN, int WAVES_M, int WAVES_N, bool SPLIT = false, int MS = 32, bool DIRECT = false>
 __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void igemm_kernel(const IgemmP p) {
     static_assert(!DIRECT || (CONV && SPLIT && MS == 16 && sizeof(T) == 4 && BN >= 64), "direct epilogue: fp32-storage split conv instances");
 
-    static_assert(!SPLIT || (sizeof(T) == 4 && STAGES == 2 && MS == 16), "split-fp16 product: fp32 storage, 2-stage ring, 16x16x32 MFMAs");
+    static_assert(!SPLIT || (sizeof(T) == 4 && MS == 16), "split-fp16 product: fp32 storage, 16x16x32 MFMAs");
     static_assert(MS == 32 || SPLIT || sizeof(T) == 2, "the 16x16x32 shape exists for the fp16 products only (see conv3x3_halo_kernel)");
     constexpr int ES = sizeof(T);
     constexpr int EPC = 16 / ES;   // elements per 16-byte chunk
@@ -727,8 +727,9 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void igemm_kernel(const 
     constexpr int LA = GA / NW, LB = GB / NW;            // groups per wave
     constexpr int LPW = LA + LB;                         // DMA instructions per wave per K-step
     constexpr int STAGE_A = BM * BKB, STAGE = (BM + BN) * BKB;
+    constexpr int STAGES = 2;                            // LDS ring depth (three stages measured no faster on any instance, see below)
     constexpr int EP_LD = WN + 4;                        // fp32 epilogue row stride (floats)
-    static_assert(GA % NW == 0 && GB % NW == 0 && (STAGES == 2 || STAGES == 3), "layout");
+    static_assert(GA % NW == 0 && GB % NW == 0, "layout");
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -996,8 +997,8 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void igemm_kernel(const 
     const int b_rd = STAGE_A + (wn * WN + lr) * BKB;
 
     // ---- main loop: STAGES-deep LDS ring, ONE raw barrier per K-step ----
-    //   iteration t:  wait until this wave's DMA for step t has landed (counted vmcnt: the DMA of the next
-    //                 STAGES-2 steps stays in flight)  ->  s_barrier (every wave's part of step t landed, and every
+    //   iteration t:  wait until this wave's DMA for step t has landed (vmcnt(0): with two stages nothing younger is in
+    //                 flight)  ->  s_barrier (every wave's part of step t landed, and every
     //                 wave finished reading step t-1)  ->  issue the DMA of step t+STAGES-1 into the stage that
     //                 step t-1 just vacated  ->  ds_read + MFMA on stage t.
     // __syncthreads() is avoided on purpose: with LDS-DMA in flight it would drain vmcnt to 0 (guide 5.4).
@@ -1007,11 +1008,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void igemm_kernel(const 
         if (ps < KT) issue_loads(ps);
 
     for (int kt = 0; kt < KT; ++kt) {
-        if (STAGES == 3 && kt + 1 < KT) {
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LPW) : "memory");
-        } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if constexpr (SPLIT) {
             // this wave's A pieces of step kt have landed: rewrite each fp32 chunk pair in place as [8 x hi | 8 x lo] (x s), see
             // the fp32x3 note at the top; masked lanes were zero-filled by the DMA and stay zero.  Weights arrive pre-split -- and so
@@ -1154,7 +1151,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void igemm_kernel(const 
 //     fragments per half and a step with dy > 0 reads ONE new row per half: 36 A reads per chunk instead of 72 (108 ds_read_b128 per
 //     chunk with the weights, 12 per 48 MFMAs).  On the 8-wave instance the new rows of steps 1..8 are read one step early, where the
 //     registers they replace die (the chunk's patch buffer is read-only for the chunk): behind a step's barrier it reads only the
-//     weight fragments.  The first step of a chunk reads its rows behind its barrier.  (STREAM instances: the tap order only.)
+//     weight fragments.  The first step of a chunk reads its rows behind its barrier.
 //   * everything else (MFMA tiling, buffer-descriptor OOB zero fill, concat sources, epilogue) is shared with igemm.
 // Requirements (checked by the launcher, otherwise the generic kernel runs): ksize 3, stride 1, pad 1, Wo % 16 == 0 (or Wo == 8, half tiles),
 // Ho % 8 == 0 (with or without the virtual nearest-2x upsampling of the input).
@@ -1184,26 +1181,19 @@ __device__ __forceinline__ void prefetch_bcol(const IgemmP& p, int ncols, int co
     }
 }
 
-template <typename T, int BN, int WAVES_M, int WAVES_N, bool UPS, int BSTAGES, bool GN, bool SPLIT = false, int MS = 32, bool SKIP = false, bool STREAM = false,
-          bool KSPLIT = false>
+template <typename T, int BN, int WAVES_M, int WAVES_N, bool UPS, bool GN, bool SPLIT = false, int MS = 32, bool SKIP = false, bool KSPLIT = false>
 __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void conv3x3_halo_kernel(const IgemmP p) {
     // KSPLIT: the K slices of a split conv (p.splitk workgroups per tile, gridDim.y) are instances of their own.  As a run-time mode of
     // every instance (round 4's first form) the chunk loop's bounds, the second epilogue of the fp16 kernels and the workspace pointer cost
     // the UNSPLIT launches 2-6 % (fp16, 128 -> 128 at 256 x 256: 0.399 -> 0.419 ms, same box) -- found by bisecting the libraries of the
     // round's commits on one box.
-    static_assert(!KSPLIT || (!STREAM && !UPS && BN == 128), "K slices: the 128-column 4-wave instances");
+    static_assert(!KSPLIT || (!UPS && BN == 128), "K slices: the 128-column 4-wave instances");
     static_assert(!SKIP || (MS == 16 && !UPS && WAVES_M == 2), "fused skip conv: 16x16x32 instances of the 8x16 tile");
     static_assert(!SPLIT || (sizeof(T) == 4 && MS == 16), "the split-fp16 product is a mode of fp32 storage, on 16x16x32 MFMAs");
     static_assert(MS == 32 || SPLIT || sizeof(T) == 2, "the 16x16x32 shape exists for the fp16 products only");
     constexpr bool XF = GN || SPLIT;  // the staged patch pieces are rewritten in place by the wave that DMA'd them
     // fp32-storage split instances (not the 32-column NCHW head): swapped MFMA operands + stores straight from the accumulators
     constexpr bool DIRECT = SPLIT && MS == 16 && BN >= 64;
-    // STREAM: a workgroup runs p.tpw consecutive pixel tiles of one image as ONE stream of chunks: the last chunk of tile k stages
-    // chunk 0 of tile k + 1 (patch pieces, their normalise / split pass, the first weight tile) exactly like any other next chunk, so
-    // only the first tile of a workgroup pays the prologue (DMA round trip + rewrite of the whole patch with the matrix pipe idle:
-    // 5.9 of a 48 us workgroup life on the 36-step layers, tools/debug/halo_stamps.py).  Needs an epilogue that leaves the operand
-    // ring alone (DIRECT); the fused skip phase reuses the ring and stays single-tile.
-    static_assert(!STREAM || (DIRECT && !SKIP && !UPS), "streaming instances: direct epilogue, no fused skip phase");
     constexpr int NW = WAVES_M * WAVES_N;      // 4 waves: 8x16 tile, 8 waves: 16x16 tile
     // WAVES_N = 4 (BN = 256): the 8x16 pixel tile with EIGHT waves, 2 x 4, each still 64 x 64 -- one workgroup covers the two N-tiles of a
     // 256-column conv, so the patch is fetched from HBM and normalised / split ONCE for both (one 8-wave workgroup per CU instead of two
@@ -1218,8 +1208,8 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
     constexpr int ES = sizeof(T), EPC = 16 / ES, BKB = 128, BK = BKB / ES;
     constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N, TM = WM / MS, TN = WN / MS;
     constexpr int GB = BN / 8, LB = GB / NW;
-    constexpr int ABUF = PG * 1024, BSTAGE = BN * BKB;
-    static_assert(GB % NW == 0 && LAH <= 6 && BSTAGES == 2, "layout");
+    constexpr int ABUF = PG * 1024, BSTAGE = BN * BKB, BSTAGES = 2;  // (two weight stages: a K-step's stage is step & 1)
+    static_assert(GB % NW == 0 && LAH <= 6, "layout");
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const sA = smem;              // [2][ABUF]
@@ -1232,13 +1222,8 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
     int tile_m, tile_n;
     map_tile(p, tile_m, tile_n);
-    int ntile = 1;  // STREAM: tiles tile_m .. tile_m + ntile - 1 (the launcher keeps a run inside one image)
-    if constexpr (STREAM) {
-        tile_m *= p.tpw;
-        ntile = min(p.tpw, p.tiles_m - tile_m);
-    }
     const int n0 = p.n_base + tile_n * BN;
-    TileGeom g = make_geom<true, BM>(p, tile_m);  // patch mode: ty0, tx0, n_first (of the tile whose K loop runs)
+    const TileGeom g = make_geom<true, BM>(p, tile_m);  // patch mode: ty0, tx0, n_first
     // epilogue operands fetched NOW (their latency passes under the prologue's DMA; older than every DMA, so the counted vmcnt waits of
     // the loop are unaffected): per-column bias terms and the weights' scale
     float pre_bcol[DIRECT ? 1 : TN];
@@ -1286,9 +1271,10 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
         const int px = prow - (prow / PW) * PW;
         pck |= (unsigned)(sslot ^ ((px >> 1) & 7)) << (3 * i);
     }
-    // pixel index / validity of this lane's patch rows for the tile at (ty0, tx0) (STREAM: called again for the next tile of the run)
+    // pixel index / validity of this lane's patch rows for the tile at (ty0, tx0).  (A lambda called once, and a one-trip loop around
+    // the K loop and the epilogue further down: with either written out plainly hipcc emits other instructions for all 42 instances of
+    // this kernel, which nobody has measured -- DESIGN_HISTORY.md 10.21.)
     auto set_tile_pieces = [&](const TileGeom& tg) {
-        pvalid = 0;
 #pragma unroll
         for (int i = 0; i < LAH; ++i) {
             const int prow = (wave + NW * i) * 8 + srow;
@@ -1471,18 +1457,15 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
     int acur[2][3] = {{0, 0, 0}, {0, 0, 0}};
     // The (i, dy) part depends on r = i + dy alone: the fragment of (i, dy + 1) IS the fragment of (i + 1, dy).  The 16x16x32 paths
     // therefore run the taps of a chunk dx-MAJOR (step t = tap (dy, dx) = (t % 3, t / 3), weight slot 3 dy + dx) and keep a ROTATING
-    // WINDOW of TM fragments per half across the three steps of one dx: window row r lives in aw[v][r % TM]; a step with dy > 0 reads
+    // window of TM fragments per half across the three steps of one dx: window row r lives in aw[v][r % TM]; a step with dy > 0 reads
     // the ONE new row TM - 1 + dy into the registers of row dy - 1, which died with the step before.  6 rows per dx and half instead of
     // 12: 36 A reads per chunk instead of 72.  The tap loop is fully unrolled, so every index below is a compile-time constant.
     auto aoff = [](int r) { return (UPS ? ((r + 1) >> 1) : r) * PW * BKB; };
     i32x4 aw[2][TM];
-    // (STREAM instances sit at the 256-register limit with spills: they take the tap order -- their outputs are the bits of the
-    //  single-tile instances -- but re-read all TM rows every step, as before, and read nothing early)
-    constexpr bool WINDOW = !STREAM;
     auto a_load = [&](int v, int dx, int dy) {  // window rows a step (dy, dx) adds: all TM at dy = 0, else row TM - 1 + dy
 #pragma unroll
         for (int r = 0; r < TM + 2; ++r)
-            if (dy == 0 || !WINDOW ? (r >= dy && r < TM + dy) : r == TM - 1 + dy) aw[v][r % TM] = *reinterpret_cast<const i32x4*>(sA + acur[v][dx] + aoff(r));
+            if (dy == 0 ? r < TM : r == TM - 1 + dy) aw[v][r % TM] = *reinterpret_cast<const i32x4*>(sA + acur[v][dx] + aoff(r));
     };
     // The current chunk's patch buffer is read-only for the whole chunk (DMA and the in-place rewrite target the OTHER buffer), so only
     // the weight tile needs a step's barrier.  The 8-wave instance (256 columns: eight waves leave one barrier together and issue their
@@ -1490,7 +1473,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
     // (a_early); the first step of a chunk reads all of its rows behind its barrier: the other waves' rewritten pieces of that chunk
     // are visible only there.  Measured: 256-column layers -1.7 ... -2.6 %, the 4-wave instances and conv_up4_halo_kernel within their
     // repeat spread for 14-34 more registers, so those read behind the barrier (DESIGN_HISTORY.md 10.20).
-    constexpr bool EARLY = WINDOW && MS == 16 && WAVES_N == 4;
+    constexpr bool EARLY = MS == 16 && WAVES_N == 4;
     auto tap_slot = [](int t) { return MS == 16 ? 3 * (t % 3) + t / 3 : t; };
     if constexpr (MS == 16) {
         constexpr int LROW = WM / 16;  // tile rows per wave (even)
@@ -1515,7 +1498,6 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
         kc_end = (int)blockIdx.y == p.splitk - 1 ? KC : kc_begin + p.splitk_per;
     }
     const int NSTEP = (kc_end - kc_begin) * 9;
-    const int TSTEP = NSTEP * ntile;  // K-steps of the whole run of tiles
     // ---- prologue: whole patch of the first chunk + weights of the first step ----
     {
         const Chunk c0 = chunk_of(kc_begin);
@@ -1540,35 +1522,28 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
     //   pp1 : patch pieces (and wave 0's scale / shift table) issued one step ago, behind that step's weights
     EOD_STAMP_AT(1);
     int pp1 = 0;
-    int step = 0;   // K-step of the run (weight stage = step & 1)
+    int step = 0;   // K-step (weight stage = step & 1)
     int qpar = 0;   // patch buffer (and scale / shift table) of the current chunk
-    for (int k = 0; k < ntile; ++k) {
+    for (int once = 0; once < 1; ++once) {  // (one trip: see set_tile_pieces)
     for (int cc = kc_begin; cc < kc_end; ++cc) {
         const Chunk cur = chunk_of(cc);
-        // the chunk behind this one in the stream: the tile's next one, or chunk 0 of the run's next tile (a stream is never split in K)
-        const bool next_tile = STREAM && cc + 1 == kc_end && k + 1 < ntile;
-        const bool has_next = cc + 1 < kc_end || next_tile;
-        const Chunk nxt = chunk_of(cc + 1 < kc_end ? cc + 1 : (next_tile ? 0 : cc));
-        if constexpr (STREAM) {
-            if (next_tile) set_tile_pieces(make_geom<true, BM>(p, tile_m + k + 1));  // this chunk's taps stage the NEXT tile's patch
-        }
+        const int cn = cc + 1 < kc_end ? cc + 1 : cc;  // the chunk that this one's taps stage (the last chunk: none)
+        const bool has_next = cn != cc;
+        const Chunk nxt = chunk_of(cn);
         const char* abuf = sA + qpar * ABUF;
         char* abuf_next = sA + (qpar ^ 1) * ABUF;
         weight_offsets(cur, bve);
 #pragma unroll
         for (int t = 0; t < 9; ++t, ++step) {
-            // (STREAM: the first step of a later tile was waited for and fenced in front of the previous tile's epilogue, see below)
             EOD_TSTAMP_AT(4 * t + 0);
-            if (!(STREAM && t == 0 && cc == kc_begin && k > 0)) {
-                if (pp1 == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                else if (pp1 == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-                if constexpr (XF) __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): in-place normalisation / split writes are done
-                __builtin_amdgcn_s_barrier();
-            }
+            if (pp1 == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            else if (pp1 == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+            if constexpr (XF) __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): in-place normalisation / split writes are done
+            __builtin_amdgcn_s_barrier();
             EOD_TSTAMP_AT(4 * t + 1);
             // DMA for the next step: weights first, then (taps 0..LAH-1) one piece of the next chunk's patch
-            if (step + 1 < TSTEP) {
+            if (step + 1 < NSTEP) {
                 if (t < 8) issue_weights_at(tap_slot(t + 1), cur, bve, sB + ((step + 1) & 1) * BSTAGE);
                 else issue_weights(0, nxt, sB + ((step + 1) & 1) * BSTAGE);
             }
@@ -1688,7 +1663,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
         }
         EOD_TSTAMP_AT(36);
 #ifdef EOD_TSTAMP
-        if (GN && wave == 1 && cc == 1 && k == 0 && blockIdx.x < 2048) {
+        if (GN && wave == 1 && cc == 1 && blockIdx.x < 2048) {
             __builtin_amdgcn_s_waitcnt(0xc07f);
             if (lane < 37) g_eod_tstamp[blockIdx.x][lane] = reinterpret_cast<const unsigned long long*>(sA + ABUF + PR * 128)[lane];
         }
@@ -1817,19 +1792,8 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
         }
       }
     }
-    if constexpr (STREAM) {
-        // The direct epilogue leaves LDS alone.  Before it, the first barrier of the NEXT tile: this wave's DMA for that tile's first step
-        // has landed (the weights issued at the last tap; nothing younger is in flight) and every wave is done with the last tap's reads
-        // -- so the epilogue's loads and stores are never waited for by a counted vmcnt of the loop before they are a K-step old.
-        if (k + 1 < ntile) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            __builtin_amdgcn_s_barrier();
-        }
-    } else {
-        __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
-        __builtin_amdgcn_s_barrier();        // every wave is done with the operand buffers: reuse them for the epilogue
-    }
+    __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
+    __builtin_amdgcn_s_barrier();        // every wave is done with the operand buffers: reuse them for the epilogue
     EOD_STAMP_AT(2);
     IgemmP pe = p;
     if constexpr (KSPLIT) pe.y = p.y + (long long)blockIdx.y * p.M * p.Cout * 4;  // raw fp32 partial tile of this K slice (the launcher cleared bias / residual / statistics)
@@ -1841,17 +1805,6 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
         igemm_epilogue<T, true, BM, BN, WAVES_M, WAVES_N, KSPLIT, MS>(pe, g, acc, smem, wave, lane, n0, nullptr, 0, pre_bcol);  // (K slices: fp32 partial tiles)
     } else {
         igemm_epilogue<T, true, BM, BN, WAVES_M, WAVES_N, sizeof(T) == 4, MS>(pe, g, acc, smem, wave, lane, n0, nullptr, 0, pre_bcol);
-    }
-    if constexpr (STREAM) {
-        if (k + 1 < ntile) {
-            g = make_geom<true, BM>(p, tile_m + k + 1);
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-#pragma unroll
-                    for (int r = 0; r < AccLayout<MS>::R; ++r) acc[i][j][r] = 0.0f;
-        }
     }
     }
     EOD_STAMP_AT(3);
@@ -2996,21 +2949,19 @@ __global__ __launch_bounds__(256) void splitk_reduce_stats_kernel(const float* _
 //   head              EOD_HEAD=0               the output head on the 32-column halo instance instead of conv_head_kernel
 //   halo_bn256        EOD_HALO_BN256=0         256- / 512-column convs as two 4-wave workgroups per pixel tile instead of one 8-wave one
 //   gn_fuse_max_cout  EOD_GN_FUSE_MAX_COUT=n   widest conv that takes its input GroupNorm in its patch staging (-1: the defaults)
-//   halo_tpw          EOD_HALO_TPW=n           pixel tiles per workgroup of the streaming halo instances (1: off = the default; 0: chosen
-//                                              per launch).  Measured (round 4): single layers 3-8 % faster at 4-8 tiles per run, the
-//                                              whole 256 x 256 step 0.4 % SLOWER than off (same-box A/B, three interleaved runs)
 //   halo_splitk       EOD_HALO_SPLITK=0        3x3 convs on maps with fewer than two workgroups per CU unsplit in K (64-column tiles instead)
 //   first             EOD_FIRST=0              the fp32x3 first conv (tap-major weights) on the generic kernel instead of conv_first_x3_kernel
 //   head_tpw          EOD_HEAD_TPW=n           pixel tiles per workgroup of conv_head_kernel's chunk stream (0: chosen per launch = the default)
 //   s2_halo           EOD_S2_HALO=0            3x3 / stride-2 convs on the generic kernel instead of conv_s2_halo_kernel
 // (Round 2's EOD_IGEMM_CFG / EOD_MFMA_SHAPE / EOD_HALO_SPLIT_N / EOD_CONV_PARITY arms were measured slower and are gone: the fp16
-// products run on v_mfma_f32_16x16x32_f16, 384-column convs as 256 + 128, zero-insertion convs as four parity-class launches.)
-enum { OPT_SKIP_FUSE, OPT_HEAD, OPT_HALO_BN256, OPT_GN_FUSE_MAX_COUT, OPT_HALO_TPW, OPT_HALO_SPLITK, OPT_FIRST, OPT_HEAD_TPW, OPT_S2_HALO, OPT_COUNT };
-static const char* const g_opt_name[OPT_COUNT] = {"skip_fuse", "head", "halo_bn256", "gn_fuse_max_cout", "halo_tpw", "halo_splitk", "first", "head_tpw",
-                                                  "s2_halo"};
-static const char* const g_opt_env[OPT_COUNT] = {"EOD_SKIP_FUSE", "EOD_HEAD", "EOD_HALO_BN256", "EOD_GN_FUSE_MAX_COUT", "EOD_HALO_TPW", "EOD_HALO_SPLITK",
-                                                 "EOD_FIRST", "EOD_HEAD_TPW", "EOD_S2_HALO"};
-static int g_opt[OPT_COUNT] = {1, 1, 1, -1, 1, 1, 1, 0, 1};
+// products run on v_mfma_f32_16x16x32_f16, 384-column convs as 256 + 128, zero-insertion convs as four parity-class launches.
+// Round 4's halo_tpw / EOD_HALO_TPW, several pixel tiles per workgroup of the 3x3 halo kernel, is gone too: single layers 3-8 % faster, the
+// whole 256 x 256 step 0.4 % slower, so it was off by default with no workload on its side (DESIGN_HISTORY.md 10.1-10.4, 10.21).)
+enum { OPT_SKIP_FUSE, OPT_HEAD, OPT_HALO_BN256, OPT_GN_FUSE_MAX_COUT, OPT_HALO_SPLITK, OPT_FIRST, OPT_HEAD_TPW, OPT_S2_HALO, OPT_COUNT };
+static const char* const g_opt_name[OPT_COUNT] = {"skip_fuse", "head", "halo_bn256", "gn_fuse_max_cout", "halo_splitk", "first", "head_tpw", "s2_halo"};
+static const char* const g_opt_env[OPT_COUNT] = {"EOD_SKIP_FUSE", "EOD_HEAD", "EOD_HALO_BN256", "EOD_GN_FUSE_MAX_COUT", "EOD_HALO_SPLITK", "EOD_FIRST",
+                                                 "EOD_HEAD_TPW", "EOD_S2_HALO"};
+static int g_opt[OPT_COUNT] = {1, 1, 1, -1, 1, 1, 0, 1};
 static bool g_opt_init = false;
 static int opt(int k) {
     if (!g_opt_init) {
@@ -3041,11 +2992,11 @@ extern "C" int eod_get_option(const char* name) {
     return EOD_EINVAL;
 }
 
-template <typename T, bool CONV, int BM, int BN, int WAVES_M, int WAVES_N, int STAGES, bool SPLIT = false, int MS = 32, bool DIRECT = false>
+template <typename T, bool CONV, int BM, int BN, int WAVES_M, int WAVES_N, bool SPLIT = false, int MS = 32, bool DIRECT = false>
 static int launch_cfg(IgemmP& p, int batch, hipStream_t st) {
     constexpr int BK = 128 / (int)sizeof(T);
     constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N, NW = WAVES_M * WAVES_N;
-    const size_t ring = STAGES * (size_t)(BM + BN) * 128;
+    const size_t ring = 2 * (size_t)(BM + BN) * 128;  // igemm_kernel's two-stage ring
     const size_t epi = NW * (size_t)WM * (WN + 4) * sizeof(float);
     size_t lds = ring > epi ? ring : epi;
     if (SPLIT && CONV) {  // per-image operand scales of a tile that straddles images: at most BM + 1 images of {s, 16/s}
@@ -3053,7 +3004,7 @@ static int launch_cfg(IgemmP& p, int batch, hipStream_t st) {
         p.ab_tab_off = (int)lds;
         lds += (BM + 2) * 2 * sizeof(float);
     }
-    auto kern = igemm_kernel<T, CONV, BM, BN, WAVES_M, WAVES_N, STAGES, SPLIT, MS, DIRECT>;
+    auto kern = igemm_kernel<T, CONV, BM, BN, WAVES_M, WAVES_N, SPLIT, MS, DIRECT>;
     static bool attr_done = false;  // >64 KiB dynamic LDS needs the opt-in attribute once per kernel
     if (!attr_done) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -3097,11 +3048,10 @@ static int launch_cfg(IgemmP& p, int batch, hipStream_t st) {
     return EOD_OK;
 }
 
-template <typename T, int BN, int WAVES_M, int WAVES_N, bool UPS, int BSTAGES, bool GN, bool SPLIT = false, int MS = 32, bool SKIP = false, bool STREAM = false,
-          bool KSPLIT = false>
+template <typename T, int BN, int WAVES_M, int WAVES_N, bool UPS, bool GN, bool SPLIT = false, int MS = 32, bool SKIP = false, bool KSPLIT = false>
 static int launch_halo(IgemmP& p, hipStream_t st) {
-    if constexpr (!KSPLIT && !STREAM && !UPS && BN == 128 && WAVES_N == 2) {
-        if (p.splitk > 1) return launch_halo<T, BN, WAVES_M, WAVES_N, UPS, BSTAGES, GN, SPLIT, MS, SKIP, false, true>(p, st);  // the K-slice instance
+    if constexpr (!KSPLIT && !UPS && BN == 128 && WAVES_N == 2) {
+        if (p.splitk > 1) return launch_halo<T, BN, WAVES_M, WAVES_N, UPS, GN, SPLIT, MS, SKIP, true>(p, st);  // the K-slice instance
     }
     if constexpr (!KSPLIT) {
         if (p.splitk > 1) {
@@ -3113,10 +3063,10 @@ static int launch_halo(IgemmP& p, hipStream_t st) {
     constexpr int NW = WAVES_M * WAVES_N, BM = WAVES_N == 4 ? 64 * WAVES_M : 32 * NW, TH = BM / 16;
     constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N;
     constexpr int PR = UPS ? (TH / 2 + 2) * 10 : (TH + 2) * 18, PG = (PR + 7) / 8;
-    const size_t ring = 2 * (size_t)(PG * 1024) + BSTAGES * (size_t)BN * 128 + (GN ? 2048 : 0);
+    const size_t ring = 2 * (size_t)(PG * 1024) + 2 * (size_t)BN * 128 + (GN ? 2048 : 0);  // two patch buffers, two weight stages
     const size_t epi = NW * (size_t)WM * (WN + 4) * sizeof(float);
     const size_t lds = ring > epi ? ring : epi;
-    auto kern = conv3x3_halo_kernel<T, BN, WAVES_M, WAVES_N, UPS, BSTAGES, GN, SPLIT, MS, SKIP, STREAM, KSPLIT>;
+    auto kern = conv3x3_halo_kernel<T, BN, WAVES_M, WAVES_N, UPS, GN, SPLIT, MS, SKIP, KSPLIT>;
     if constexpr (SKIP) {
         p.skc0 = (p.SC0 + BK - 1) / BK;
         p.skc1 = (p.SC1 + BK - 1) / BK;
@@ -3136,12 +3086,8 @@ static int launch_halo(IgemmP& p, hipStream_t st) {
     p.tiles_pi = p.tiles_pw * (p.Ho / TH);
     p.tiles_m = p.tiles_pi * p.N;
     p.tiles_per_image = p.tiles_pi;  // (statistics slots: tile of the image x WAVES_M)
-    // streaming instances (the kernel's STREAM): runs of p.tpw consecutive pixel tiles of one image per workgroup (ConvPlan.tpw)
-    if constexpr (SPLIT && MS == 16 && BN >= 128 && !SKIP && !UPS && !STREAM) {
-        if (p.tpw > 1) return launch_halo<T, BN, WAVES_M, WAVES_N, UPS, BSTAGES, GN, SPLIT, MS, SKIP, true>(p, st);
-    }
-    if constexpr (!STREAM) p.tpw = 1;
-    const long long nblk = (long long)(p.tiles_m / p.tpw) * p.tiles_n;
+    p.tpw = 1;  // (read by conv_head_kernel only)
+    const long long nblk = (long long)p.tiles_m * p.tiles_n;
     if (nblk <= 0 || nblk > 0x7fffffffLL) {
         eod_set_error("conv_halo: bad grid %lld", nblk);
         return EOD_EINVAL;
@@ -3153,21 +3099,21 @@ static int launch_halo(IgemmP& p, hipStream_t st) {
 
 template <typename T, bool CONV> static int launch_T(IgemmP& p, int batch, hipStream_t st) {
     constexpr int MS = sizeof(T) == 2 ? 16 : 32;  // fp16 products on v_mfma_f32_16x16x32_f16, exact fp32 on v_mfma_f32_32x32x2_f32
-    if (p.Ncols <= 32) return launch_cfg<T, CONV, 128, 32, 4, 1, 2, false, MS>(p, batch, st);
-    if (p.Ncols <= 64) return launch_cfg<T, CONV, 128, 64, 4, 1, 2, false, MS>(p, batch, st);
+    if (p.Ncols <= 32) return launch_cfg<T, CONV, 128, 32, 4, 1, false, MS>(p, batch, st);
+    if (p.Ncols <= 64) return launch_cfg<T, CONV, 128, 64, 4, 1, false, MS>(p, batch, st);
     // (exact fp32: a 256x128 tile / 8 waves / 3-stage ring measured 0-5 % SLOWER than two co-resident 128x128 workgroups per CU)
-    return launch_cfg<T, CONV, 128, 128, 2, 2, 2, false, MS>(p, batch, st);
+    return launch_cfg<T, CONV, 128, 128, 2, 2, false, MS>(p, batch, st);
 }
 
 // fp32 conv as the split-fp16 product on the generic kernel (1x1, stride 2, ragged maps); bn and direct come from the ConvPlan
 static int launch_conv_split(IgemmP& p, int bn, bool direct, int batch, hipStream_t st) {
-    if (bn == 32) return launch_cfg<float, true, 128, 32, 4, 1, 2, true, 16>(p, batch, st);
-    if (bn == 64) return launch_cfg<float, true, 128, 64, 4, 1, 2, true, 16>(p, batch, st);
+    if (bn == 32) return launch_cfg<float, true, 128, 32, 4, 1, true, 16>(p, batch, st);
+    if (bn == 64) return launch_cfg<float, true, 128, 64, 4, 1, true, 16>(p, batch, st);
     if (bn == 256)
-        return direct ? launch_cfg<float, true, 128, 256, 2, 4, 2, true, 16, true>(p, batch, st)
-                      : launch_cfg<float, true, 128, 256, 2, 4, 2, true, 16>(p, batch, st);
-    return direct ? launch_cfg<float, true, 128, 128, 2, 2, 2, true, 16, true>(p, batch, st)
-                  : launch_cfg<float, true, 128, 128, 2, 2, 2, true, 16>(p, batch, st);
+        return direct ? launch_cfg<float, true, 128, 256, 2, 4, true, 16, true>(p, batch, st)
+                      : launch_cfg<float, true, 128, 256, 2, 4, true, 16>(p, batch, st);
+    return direct ? launch_cfg<float, true, 128, 128, 2, 2, true, 16, true>(p, batch, st)
+                  : launch_cfg<float, true, 128, 128, 2, 2, true, 16>(p, batch, st);
 }
 
 // row length (elements) of tap-major packed weights: 9*C0 rounded up to whole 128-byte K-steps
@@ -3304,7 +3250,7 @@ struct ConvPlan {
     bool plus128;    // HALO, bn = 256: all but the last 128 columns on the 8-wave form, the rest as a 128-column launch of its own
     bool direct;     // GENERIC split product: swapped-operand instance with the direct epilogue
     int splitk, splitk_per;  // K slices over gridDim.y (1 = none); halo kernel: channel chunks per slice
-    int tpw, tpw_tail;       // HALO streaming instances / HEAD: pixel tiles per workgroup (tpw_tail: the plus128 form's last launch)
+    int tpw;                 // HEAD: pixel tiles per workgroup (1 everywhere else)
     int64_t workspace_bytes;
     int stats_slots;
     bool gn_fusable, skip_ok;
@@ -3312,7 +3258,7 @@ struct ConvPlan {
 static ConvPlan conv_plan(const eod_conv_desc* d) {
     ConvPlan pl = {};
     pl.bn = 128;
-    pl.splitk = pl.tpw = pl.tpw_tail = 1;
+    pl.splitk = pl.tpw = 1;
     if (d->upsample == 4) {  // dX on the (H/2 x W/2) grid: no workspace, no statistics, nothing fused
         pl.family = FAM_UP4_BWD;
         pl.Heff = pl.Ho = d->H / 2;
@@ -3388,24 +3334,6 @@ static ConvPlan conv_plan(const eod_conv_desc* d) {
         } else if (on256 && d->Cout > 256 && d->Cout % 256 == 128 && d->N * tiles_pi * ((d->Cout - 128) / 256) >= 256 && split && gn) {
             pl.bn = 256;  // 384, 640, ... columns of the split product with a fused GroupNorm: 256 + 128
             pl.plus128 = true;
-        }
-        // streaming instances (split product, 128 / 256 columns, no skip): runs of tpw consecutive pixel tiles of one image per workgroup
-        // (halo_tpw option; 0: chosen per launch).  Which workgroup computes a tile never changes its result (same K order, same MFMAs, its
-        // own statistics slot), so the choice may depend on the batch.
-        auto tpw_of = [&](int cols, int bn) {
-            const long long slots = bn == 256 ? 256 : 512;  // co-resident workgroups of the chip (8 / 4 waves each)
-            const long long wgs = d->N * tiles_pi * ((cols + bn - 1) / bn);
-            int want = opt(OPT_HALO_TPW);
-            if (want <= 0) {  // at least two rounds of workgroups stay (measured on 256 x 256 and 128 x 128 maps: 4 ... 8 tiles per run tie)
-                want = 1;
-                while (want < 8 && wgs / (2 * want) >= 2 * slots) want *= 2;
-            }
-            while (want > 1 && tiles_pi % want) --want;
-            return want;
-        };
-        if (split && !skip && !d->upsample && pl.bn >= 128 && pl.splitk <= 1) {
-            pl.tpw = tpw_of(pl.plus128 ? d->Cout - 128 : d->Cout, pl.bn);
-            if (pl.plus128) pl.tpw_tail = tpw_of(128, 128);
         }
     } else {
         pl.family = pl.splitk <= 1 && !split && conv_parity_ok(d, Ho, Wo) ? FAM_GENERIC_PARITY : FAM_GENERIC;
@@ -3502,27 +3430,26 @@ static int conv_require_workspace(const eod_conv_desc* d, const ConvPlan& pl) {
 template <typename T, bool SPLIT, int MS, bool GN, bool SKIP>
 static int launch_halo_bn(IgemmP& p, const eod_conv_desc* d, const ConvPlan& pl, hipStream_t st) {
     if constexpr (!SKIP) {
-        if (pl.bn == 32) return launch_halo<T, 32, 4, 1, false, 2, GN, SPLIT, MS>(p, st);
+        if (pl.bn == 32) return launch_halo<T, 32, 4, 1, false, GN, SPLIT, MS>(p, st);
     }
     if constexpr (!SKIP && !GN) {
-        if (d->upsample) return launch_halo<T, 128, 2, 2, true, 2, false, SPLIT, MS>(p, st);
+        if (d->upsample) return launch_halo<T, 128, 2, 2, true, false, SPLIT, MS>(p, st);
     }
     if constexpr (MS == 16) {
-        if (pl.bn == 64) return launch_halo<T, 64, 2, 2, false, 2, GN, SPLIT, MS, SKIP>(p, st);
+        if (pl.bn == 64) return launch_halo<T, 64, 2, 2, false, GN, SPLIT, MS, SKIP>(p, st);
     }
     if constexpr (MS == 16 && (GN || (SPLIT && SKIP))) {
         if (pl.bn == 256 && pl.plus128) {  // 256-column tiles on the 8-wave form, the last 128 columns on the 4-wave one
             IgemmP q = p;
             q.Ncols = d->Cout - 128;
-            const int rc = launch_halo<T, 256, 2, 4, false, 2, GN, SPLIT, MS, SKIP>(q, st);
+            const int rc = launch_halo<T, 256, 2, 4, false, GN, SPLIT, MS, SKIP>(q, st);
             if (rc != EOD_OK) return rc;
             p.n_base = d->Cout - 128;
-            p.tpw = pl.tpw_tail;
-            return launch_halo<T, 128, 2, 2, false, 2, GN, SPLIT, MS, SKIP>(p, st);
+            return launch_halo<T, 128, 2, 2, false, GN, SPLIT, MS, SKIP>(p, st);
         }
-        if (pl.bn == 256) return launch_halo<T, 256, 2, 4, false, 2, GN, SPLIT, MS, SKIP>(p, st);
+        if (pl.bn == 256) return launch_halo<T, 256, 2, 4, false, GN, SPLIT, MS, SKIP>(p, st);
     }
-    if (pl.bn == 128) return launch_halo<T, 128, 2, 2, false, 2, GN, SPLIT, MS, SKIP>(p, st);
+    if (pl.bn == 128) return launch_halo<T, 128, 2, 2, false, GN, SPLIT, MS, SKIP>(p, st);
     eod_set_error("conv_halo: no %d-column instance for this storage type", pl.bn);
     return EOD_EINVAL;
 }
@@ -3654,7 +3581,6 @@ extern "C" int eod_conv2d_igemm(const eod_conv_desc* d, void* stream) {
             p.gn_ss = d->gn_scale_shift;
             p.gn_silu = d->gn_silu;
         }
-        p.tpw = pl.tpw;
         IgemmP q = splitk ? splitk_partial(p, d, pl) : p;
         // fp32 storage as three fp16 MFMAs per product (weights pre-split and pre-scaled, activations split in LDS); fp16; exact fp32
         // (v_mfma_f32_32x32x2_f32 on the same byte-oriented LDS image)
@@ -3730,9 +3656,9 @@ extern "C" int eod_gemm_nt(const eod_gemm_desc* d, void* stream) {
         EOD_REQUIRE(d->dtype == EOD_F32 && d->K % 8 == 0, "gemm: x3 needs fp32 operands and K %% 8 == 0");
         p.a_bound = d->a_bound;
         p.b_bound = d->b_bound;
-        if (p.Ncols <= 32) return launch_cfg<float, false, 128, 32, 4, 1, 2, true, 16>(p, batch, st);
-        if (p.Ncols <= 64) return launch_cfg<float, false, 128, 64, 4, 1, 2, true, 16>(p, batch, st);
-        return launch_cfg<float, false, 128, 128, 2, 2, 2, true, 16>(p, batch, st);
+        if (p.Ncols <= 32) return launch_cfg<float, false, 128, 32, 4, 1, true, 16>(p, batch, st);
+        if (p.Ncols <= 64) return launch_cfg<float, false, 128, 64, 4, 1, true, 16>(p, batch, st);
+        return launch_cfg<float, false, 128, 128, 2, 2, true, 16>(p, batch, st);
     }
     return d->dtype == EOD_F16 ? launch_T<half_t, false>(p, batch, st) : launch_T<float, false>(p, batch, st);
 }

@@ -252,7 +252,7 @@ def metrics(got, ref, bound, f16_out):
 
 
 # ================================================================================================ replay
-OPTION_DEFAULT = {"head": 1, "first": 1, "s2_halo": 1, "halo_bn256": 1, "halo_splitk": 1, "halo_tpw": 1, "head_tpw": 0}
+OPTION_DEFAULT = {"head": 1, "first": 1, "s2_halo": 1, "halo_bn256": 1, "halo_splitk": 1, "head_tpw": 0}
 
 
 @contextlib.contextmanager
@@ -285,8 +285,6 @@ def option_arms(g):
         else:
             if g["Cout"] >= 256 and g["Cout"] % 128 == 0:
                 arms += [("halo_bn256", 0)]
-            if g["w_split"] and "skip_x" not in g["nn"] and not g["upsample"] and g["Cout"] >= 128:
-                arms += [("halo_tpw", 4), ("halo_tpw", 8), ("halo_tpw", 0)]
     return arms
 
 

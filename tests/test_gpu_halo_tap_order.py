@@ -106,14 +106,13 @@ def operands(tag, N, Cin, H, W, Cout):
     return x, w, b
 
 
-def plan_arm(prec, N, H, W, cin, cout, *, gn, skip=False, tpw=1, splitk=True):
+def plan_arm(prec, N, H, W, cin, cout, *, gn, skip=False, splitk=True):
     """which conv3x3_halo_kernel instance the launcher takes for a 128- or 256-column conv (csrc/igemm.hip: conv_splitk, conv_plan),
     stated here so that a case can say which arm it is about:
     - K slices (128-column KSPLIT instance): fewer than 256 workgroups at the nominal batch of 16 and at least four channel chunks;
     - else 64-column tiles on maps with fewer than 256 such workgroups;
     - else the 8-wave 256-column instance where Cout % 256 == 0, N * tiles * Cout / 256 >= 256 and the conv has a fused GroupNorm
-      (or, split product, a fused skip conv); else the 4-wave 128-column instance;
-    - STREAM runs of `halo_tpw` tiles: split product without a skip conv on the 128- / 256-column instances, unsplit in K."""
+      (or, split product, a fused skip conv); else the 4-wave 128-column instance."""
     tiles_pi, ct = (H // 8) * ((W + 15) // 16), -(-cout // 128)
     kc = -(-cin // (32 if prec == "fp32x3" else 64))
     ksplit = bool(splitk) and 16 * tiles_pi * ct < 256 and kc >= 4
@@ -125,20 +124,17 @@ def plan_arm(prec, N, H, W, cin, cout, *, gn, skip=False, tpw=1, splitk=True):
         bn = 256
     else:
         bn = 128
-    t = tpw if (prec == "fp32x3" and not skip and bn >= 128 and not ksplit) else 1
-    while t > 1 and tiles_pi % t:
-        t -= 1
-    return dict(bn=bn, tpw=t, ksplit=ksplit)
+    return dict(bn=bn, ksplit=ksplit)
 
 
-def check(prec, x, w, b, *, expect=None, tpw=1, splitk=True, **kw):
+def check(prec, x, w, b, *, expect=None, splitk=True, **kw):
     """run, compare with the float64 reference at the gate; expect: the arm (plan_arm) this case is about.  The K-slice arm is also
     observed: it is the one that needs a workspace."""
     N, cin, H, W = x.shape
-    arm = plan_arm(prec, N, H, W, cin, w.shape[0], gn=kw.get("gn") is not None, skip=kw.get("skip") is not None, tpw=tpw, splitk=splitk)
+    arm = plan_arm(prec, N, H, W, cin, w.shape[0], gn=kw.get("gn") is not None, skip=kw.get("skip") is not None, splitk=splitk)
     if expect is not None and not kw.get("up4"):
         assert {k: arm[k] for k in expect} == expect, (arm, expect)
-    with Options(halo_tpw=tpw, halo_splitk=int(splitk)):
+    with Options(halo_splitk=int(splitk)):
         got, _, used = run_conv(prec, x, w, b, **kw)
     if not kw.get("up4"):
         assert used == arm["ksplit"], ("K slices", used, arm)
@@ -224,7 +220,7 @@ def test_no_early_read_crosses_a_chunk_on_the_8_wave_instance(prec, cin):
     32 channels: no chunk boundary, the early reads alone) and three / two chunks with both patch buffers (96)."""
     x, w, b = operands(("st8", cin), 16, cin, 64, 32, 256)
     arm = plan_arm(prec, 16, 64, 32, cin, 256, gn=True)
-    assert arm == dict(bn=256, tpw=1, ksplit=False), arm
+    assert arm == dict(bn=256, ksplit=False), arm
     every_element(prec, x, w, b, _gamma_beta(cin, True), f64_table=False)
 
 
@@ -239,28 +235,24 @@ def test_fused_skip_phase_behind_the_window(prec, gn):
 
 
 @pytest.mark.parametrize("prec", ["fp32x3", "fp16"])
-def test_halo_tpw_2_on_a_16x32_map_and_an_8_wide_map(prec):
-    """halo_tpw = 2 on a 16 x 32 map: a map this small runs 64-column tiles, which have no STREAM form -- the option must change
-    nothing (the streaming instances are the next test's); an 8-wide map: the right half of every tile masked"""
+def test_a_16x32_map_and_an_8_wide_map(prec):
+    """a 16 x 32 map: two pixel tiles side by side per image, on 64-column tiles, with and without the fused GroupNorm; an 8-wide map:
+    the right half of every tile masked"""
     x, w, b = operands("tpw2", 2, 96, 16, 32, 128)
-    check(prec, x, w, b, gn=_gamma_beta(96, False), tpw=2, expect=dict(bn=64, tpw=1))
-    check(prec, x, w, b, tpw=2, expect=dict(bn=64, tpw=1))
+    check(prec, x, w, b, gn=_gamma_beta(96, False), expect=dict(bn=64))
+    check(prec, x, w, b, expect=dict(bn=64))
     x, w, b = operands("wide8", 2, 96, 16, 8, 128)
     check(prec, x, w, b, gn=_gamma_beta(96, False), expect=dict(bn=64))
 
 
 @pytest.mark.parametrize("case", [(2, 96, 128, False, 128), (2, 96, 128, True, 128), (2, 32, 128, True, 128), (16, 96, 256, True, 256)],
                          ids=lambda c: "-".join(str(v) for v in c))
-def test_stream_tile_change(case):
-    """STREAM instances (split product, 128 / 256 columns; halo_tpw = 2 on a 64 x 32 map = eight runs of two tiles per image): the
-    second tile's first step reads behind the barrier in front of the first tile's epilogue.  They take the tap order but not the row
-    window, and must give the bits of the single-tile instances."""
+def test_split_product_on_the_128_and_256_column_instances_at_64x32(case):
+    """split product without a skip conv on a 64 x 32 map (sixteen pixel tiles per image): the 4-wave 128-column instance with and without
+    the fused GroupNorm, one chunk and three, and the 8-wave 256-column instance at batch 16"""
     N, cin, cout, gn, bn = case
     x, w, b = operands(("stream",) + case, N, cin, 64, 32, cout)
-    g = _gamma_beta(cin, False) if gn else None
-    two = check("fp32x3", x, w, b, gn=g, tpw=2, expect=dict(bn=bn, tpw=2, ksplit=False))
-    one = check("fp32x3", x, w, b, gn=g, tpw=1, expect=dict(bn=bn, tpw=1, ksplit=False))
-    assert torch.equal(two, one), "a run of two tiles differs from single tiles"
+    check("fp32x3", x, w, b, gn=_gamma_beta(cin, False) if gn else None, expect=dict(bn=bn, ksplit=False))
 
 
 @pytest.mark.parametrize("prec", ["fp32x3", "fp16"])

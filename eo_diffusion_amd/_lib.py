@@ -131,6 +131,7 @@ SYMBOLS = {
     "eod_pack_conv_weight_split_pair": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "eod_conv_workspace_size": (i64, [C.POINTER(ConvDesc)]),
     "eod_conv_kernel_name": (C.c_char_p, [C.POINTER(ConvDesc)]),
+    "eod_conv_halo_columns": (i32, [C.POINTER(ConvDesc)]),
     "eod_gn_apply": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp]),
     "eod_attention_fwd": (i32, [C.POINTER(AttnDesc), vp]),
     "eod_softmax_rows": (i32, [vp, i64, vp, i64, i32, i64, i32, vp]),
@@ -223,7 +224,10 @@ def lib():
     # (Loading /opt/rocm's runtime first ends in "no ROCm-capable device is detected" at the first launch.)
     import torch  # noqa: F401
     L = C.CDLL(LIB_PATH)
+    abi_any = os.environ.get("EOD_ABI_ANY", "0") == "1"
     for name, (res, args) in SYMBOLS.items():
+        if abi_any and not hasattr(L, name):  # (A/B tooling: an older build knows no entry point added since)
+            continue
         fn = getattr(L, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype, fn.argtypes = res, args
     if L.eod_version() != ABI_VERSION and os.environ.get("EOD_ABI_ANY", "0") != "1":  # (EOD_ABI_ANY=1: A/B tooling against an older build)

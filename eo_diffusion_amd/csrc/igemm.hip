@@ -286,13 +286,16 @@ extern "C" int eod_debug_read_stamps(unsigned long long* host, int n) {
 // Diagnostic build only (-DEOD_TSTAMP, tools/debug/halo_timeline.py): wave 1 of a workgroup stamps the shader clock at four points of every
 // K-step of its second chunk (into the 512 filler bytes behind the last patch row of that chunk's buffer), copied to a buffer of its own
 // when the chunk ends.
+#ifndef EOD_TSTAMP_WAVE
+#define EOD_TSTAMP_WAVE 1  // (the 8-wave instance: waves 0-3 stage the patch, 4-7 the weights -- -DEOD_TSTAMP_WAVE=5 for the other role)
+#endif
 __device__ unsigned long long g_eod_tstamp[2048][40];
 extern "C" int eod_debug_read_tstamps(unsigned long long* host, int n) {
     return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_eod_tstamp), (size_t)n * 40 * sizeof(unsigned long long), 0, hipMemcpyDeviceToHost);
 }
 #define EOD_TSTAMP_AT(idx)                                                                                      \
     do {                                                                                                        \
-        if (GN && wave == 1 && cc == 1 && k == 0) {                                                             \
+        if (GN && wave == EOD_TSTAMP_WAVE && cc == 1) {                                                         \
             const unsigned long long ts_ = __builtin_amdgcn_s_memtime();                                        \
             if (lane == 0) reinterpret_cast<unsigned long long*>(sA + ABUF + PR * 128)[idx] = ts_;              \
         }                                                                                                       \
@@ -1146,6 +1149,9 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void igemm_kernel(const 
 //   * DMA schedule per K-step (chunk cc, tap t), per wave: [4 weight-tile pieces for step+1][1 patch piece of chunk cc+1
 //     (taps 0..5)].  vmcnt retires in order, so the wait for step s's weights is vmcnt(1) when a patch piece was
 //     issued after them and vmcnt(0) otherwise: every patch piece gets two full K-steps to land.
+//     The 8-wave instance divides this by wave row instead (ROLES below): waves 4-7 issue the whole weight tile, eight pieces each, in
+//     front of their MFMAs; waves 0-3 issue the patch pieces (taps 0..5) and rewrite them (taps 2..7) BEHIND their MFMAs -- the two
+//     waves of a SIMD, w and w + 4, no longer want the matrix pipe and leave it at the same time.
 //   * 16x16x32 paths: the taps of a chunk run dx-MAJOR (K-step t = tap (dy, dx) = (t % 3, t / 3), weight slot 3 dy + dx).  The A fragment
 //     of row block i for tap row dy is patch row i + dy of the wave's window, so the three steps of one dx keep a rotating window of TM
 //     fragments per half and a step with dy > 0 reads ONE new row per half: 36 A reads per chunk instead of 72 (108 ds_read_b128 per
@@ -1204,12 +1210,22 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
     constexpr int BM = WAVES_N == 4 ? 64 * WAVES_M : 32 * NW, TH = BM / 16, TW = 16;
     constexpr int PH = UPS ? TH / 2 + 2 : TH + 2, PW = UPS ? TW / 2 + 2 : TW + 2, PR = PH * PW;  // 180 (60) patch rows
     constexpr int PG = (PR + 7) / 8;                                             // 23 (8) DMA groups of 8 rows
-    constexpr int LAH = (PG + NW - 1) / NW;                                      // patch pieces per wave
+    // ROLES (the 8-wave instance): the two waves of a SIMD are wave w and wave w + 4 of ONE workgroup; behind every barrier they ran the
+    // same body, wanted the matrix pipe together and left it idle together.  The K loop's non-matrix work is therefore divided by wave
+    // row: waves 4-7 issue the whole next weight tile behind the barrier, in FRONT of their MFMAs, and nothing else; waves 0-3 go
+    // straight to their MFMAs and stage + rewrite the next chunk's patch BEHIND them (all PG groups, up to six per wave, the 4-wave
+    // instances' schedule).  Every wave keeps its MFMAs, their operands and their order (DESIGN_HISTORY.md 10.22).  The other instances'
+    // statements stay VERBATIM in the else arms of `if constexpr (ROLES)`: shared through lambdas, all 42 instances compiled differently.
+    constexpr bool ROLES = WAVES_N == 4 && MS == 16;
+    constexpr int RW = ROLES ? 4 : NW;                                           // waves that share a chunk's patch pieces / a weight tile's pieces
+    constexpr int LAH = (PG + RW - 1) / RW;                                      // patch pieces per wave
     constexpr int ES = sizeof(T), EPC = 16 / ES, BKB = 128, BK = BKB / ES;
     constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N, TM = WM / MS, TN = WN / MS;
-    constexpr int GB = BN / 8, LB = GB / NW;
+    constexpr int GB = BN / 8, LB = GB / NW, LBR = GB / RW;                     // weight pieces per wave: skip phase / 3x3 loop
+    constexpr int LBV = ROLES ? 1 : LB;                                          // per-lane offsets kept for them
     constexpr int ABUF = PG * 1024, BSTAGE = BN * BKB, BSTAGES = 2;  // (two weight stages: a K-step's stage is step & 1)
     static_assert(GB % NW == 0 && LAH <= 6, "layout");
+    static_assert(!ROLES || (XF && GB % RW == 0 && LAH % 2 == 0 && LBR % 2 == 0), "role split: in-place rewrite; the prologue halves the pieces");
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const sA = smem;              // [2][ABUF]
@@ -1220,6 +1236,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
+    const int wr = ROLES ? wn : wave;  // this wave's place among the RW waves that share the pieces (ROLES: both wave rows hold all of them)
     int tile_m, tile_n;
     map_tile(p, tile_m, tile_n);
     const int n0 = p.n_base + tile_n * BN;
@@ -1251,7 +1268,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
         }
     }
 
-    // ---- patch pieces of this wave: group gi = wave + 4*i, patch row = gi*8 + (lane>>3), slot = lane&7 ----
+    // ---- patch pieces of this wave: group gi = wr + RW*i, patch row = gi*8 + (lane>>3), slot = lane&7 ----
     const int srow = lane >> 3, sslot = lane & 7;
     // PATCH SWIZZLE: the 16-byte chunk c of patch row (py, px) lives in slot c ^ key(px), key(px) = (px >> 1) & 7 -- a function of the
     // patch COLUMN only.  A fragment read covers 16 consecutive columns of one patch row, so the conflict-free property is the one of
@@ -1267,7 +1284,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
     unsigned pvalid = 0;  // bit i: this lane's row of piece i lies inside the image (zero padding must stay zero)
 #pragma unroll
     for (int i = 0; i < LAH; ++i) {
-        const int prow = (wave + NW * i) * 8 + srow;
+        const int prow = (wr + RW * i) * 8 + srow;
         const int px = prow - (prow / PW) * PW;
         pck |= (unsigned)(sslot ^ ((px >> 1) & 7)) << (3 * i);
     }
@@ -1277,21 +1294,24 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
     auto set_tile_pieces = [&](const TileGeom& tg) {
 #pragma unroll
         for (int i = 0; i < LAH; ++i) {
-            const int prow = (wave + NW * i) * 8 + srow;
+            const int prow = (wr + RW * i) * 8 + srow;
             const int py = prow / PW, px = prow - py * PW;
             const int hi = (UPS ? tg.ty0 / 2 : tg.ty0) - 1 + py, wi = (UPS ? tg.tx0 / 2 : tg.tx0) - 1 + px;
-            const bool ok = (wave + NW * i) < PG && prow < PR && (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
+            const bool ok = (wr + RW * i) < PG && prow < PR && (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
             if (ok) pvalid |= 1u << i;
             ppix[i] = (unsigned)(hi * p.W + wi);
         }
     };
     set_tile_pieces(g);
     auto pchunk_of = [&](int i) { return (int)((pck >> (3 * i)) & 7u); };
-    unsigned b_v[LB];
+    // (ROLES: the LBR weight pieces of a lane are rows 32 apart -- ONE offset, the piece's distance goes through the DMA's scalar offset
+    //  and brem = the rows of the weight tile from this lane's row of piece 0 on says which pieces exist: see issue_weight_tile)
+    unsigned b_v[LBV];
+    const int brem = ROLES ? p.Ncols - n0 - (wr * 8 + srow) : 0;
 #pragma unroll
-    for (int i = 0; i < LB; ++i) {
-        const int row = (wave + NW * i) * 8 + srow;
-        b_v[i] = (n0 + row < p.Ncols) ? (unsigned)(row * p.Cin * ES) + bchunk0 * 16 : EOD_OOB;
+    for (int i = 0; i < LBV; ++i) {
+        const int row = (wr + RW * i) * 8 + srow;
+        b_v[i] = (ROLES || n0 + row < p.Ncols) ? (unsigned)(row * p.Cin * ES) + bchunk0 * 16 : EOD_OOB;
     }
     const __amdgpu_buffer_rsrc_t rsA0 = make_rsrc(p.a0 + (long long)g.n_first * p.H * p.W * p.C0 * ES);
     const __amdgpu_buffer_rsrc_t rsA1 = make_rsrc(p.a1 ? p.a1 + (long long)g.n_first * p.H * p.W * p.C1 * ES : p.a0);
@@ -1324,9 +1344,9 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
         unsigned v = ((pvalid >> i) & 1u) ? ppix[i] * (unsigned)(c.cw * ES) + pc * 16 : EOD_OOB;
         if (__builtin_expect(c.ktail, 0)) v = (c.kin + pc * EPC < c.cw) ? v : EOD_OOB;
         if (c.src)
-            blds16(rsA1, v, (unsigned)(c.kin * ES), abuf + (wave + NW * i) * 1024);
+            blds16(rsA1, v, (unsigned)(c.kin * ES), abuf + (wr + RW * i) * 1024);
         else
-            blds16(rsA0, v, (unsigned)(c.kin * ES), abuf + (wave + NW * i) * 1024);
+            blds16(rsA0, v, (unsigned)(c.kin * ES), abuf + (wr + RW * i) * 1024);
     };
     // GN: wave 0 stages the chunk's 64 x {scale, shift} (512 B) next to the patch; every wave then normalises the patch
     // pieces IT has DMA'd (its own vmcnt tells it when they have landed): x -> silu(x*scale + shift), in place in LDS,
@@ -1345,7 +1365,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
     };
     auto xf_load = [&](int i, char* abuf, const char* ssbuf, XfPre& pre) {
         const int pc = pchunk_of(i);
-        pre.raw = *reinterpret_cast<const i32x4*>(abuf + (wave + NW * i) * 1024 + lane * 16);
+        pre.raw = *reinterpret_cast<const i32x4*>(abuf + (wr + RW * i) * 1024 + lane * 16);
         if constexpr (GN) {
             const float* sp = reinterpret_cast<const float*>(ssbuf) + pc * EPC * 2;
 #pragma unroll
@@ -1355,7 +1375,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
     auto xf_finish = [&](int i, const Chunk& c, char* abuf, const XfPre& pre) {
         const int pc = pchunk_of(i);
         const bool ok = ((pvalid >> i) & 1u) && (!c.ktail || (c.kin + pc * EPC < c.cw));
-        char* ptr = abuf + (wave + NW * i) * 1024 + lane * 16;
+        char* ptr = abuf + (wr + RW * i) * 1024 + lane * 16;
         const i32x4 raw = pre.raw;
         i32x4 outv = raw;
         if constexpr (GN) {
@@ -1409,21 +1429,28 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
     };
     // (the K-tail mask of a lane's weight offsets is a property of the CHUNK: bve holds the current chunk's, rebuilt once per chunk, so
     //  that the eight taps that stay inside it issue their weight DMA without a select per piece)
-    unsigned bve[LB];
-    auto weight_offsets = [&](const Chunk& c, unsigned (&out)[LB]) {
+    unsigned bve[LBV];
+    auto weight_offsets = [&](const Chunk& c, unsigned (&out)[LBV]) {
         const bool kok = !c.ktail || (c.kin + (SPLIT ? (bchunk0 >> 1) * 8 : bchunk0 * EPC) < c.cw);
 #pragma unroll
-        for (int i = 0; i < LB; ++i) out[i] = kok ? b_v[i] : EOD_OOB;
+        for (int i = 0; i < LBV; ++i) out[i] = kok ? b_v[i] : EOD_OOB;
     };
-    auto issue_weights_at = [&](int tap, const Chunk& c, const unsigned (&off)[LB], char* bst) {
+    auto issue_weights_at = [&](int tap, const Chunk& c, const unsigned (&off)[LBV], char* bst) {
         const unsigned soff = (unsigned)(tap * tapstride) + c.bk;
 #pragma unroll
-        for (int i = 0; i < LB; ++i) blds16(rsB, off[i], soff, bst + (wave + NW * i) * 1024);
+        for (int i = 0; i < LBV; ++i) blds16(rsB, off[i], soff, bst + (wr + RW * i) * 1024);
     };
     auto issue_weights = [&](int tap, const Chunk& c, char* bst) {
-        unsigned off[LB];
+        unsigned off[LBV];
         weight_offsets(c, off);
         issue_weights_at(tap, c, off, bst);
+    };
+    // ROLES: pieces i0 .. i1 - 1 of a weight tile from the one offset of the chunk (off = weight_offsets' value: the K-tail mask)
+    auto issue_weight_tile = [&](int tap, const Chunk& c, unsigned off, char* bst, int i0, int i1) {
+        const unsigned soff = (unsigned)(tap * tapstride) + c.bk;
+#pragma unroll
+        for (int i = 0; i < LBR; ++i)
+            if (i >= i0 && i < i1) blds16(rsB, brem > RW * 8 * i ? off : EOD_OOB, soff + (unsigned)(RW * 8 * i * p.Cin * ES), bst + (wr + RW * i) * 1024);
     };
 
     typename AccLayout<MS>::vec acc[TM][TN];
@@ -1501,9 +1528,27 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
     // ---- prologue: whole patch of the first chunk + weights of the first step ----
     {
         const Chunk c0 = chunk_of(kc_begin);
+        if constexpr (ROLES) {
+            // nothing overlaps here yet, so all eight waves share chunk 0's pieces and the first weight tile: of the pieces that waves wr
+            // and wr + 4 both hold, wave row wm stages (and rewrites) half wm
+#pragma unroll
+            for (int i = 0; i < LAH; ++i)
+                if ((i >= LAH / 2) == (wm != 0) && (wr + RW * i) < PG) issue_patch_piece(i, c0, sA);
+            if constexpr (GN) {
+                if (wave == 0) issue_ss(c0, sS);
+            }
+            weight_offsets(c0, bve);
+            issue_weight_tile(0, c0, bve[0], sB, wm * (LBR / 2), (wm + 1) * (LBR / 2));
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if constexpr (GN) __builtin_amdgcn_s_barrier();  // wave 0's scale/shift table is visible
+#pragma unroll
+            for (int i = 0; i < LAH; ++i)
+                if ((i >= LAH / 2) == (wm != 0) && (wr + RW * i) < PG) transform_piece(i, c0, sA, sS);
+            __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): my LDS writes are done before the loop's first barrier
+        } else {
 #pragma unroll
         for (int i = 0; i < LAH; ++i)
-            if ((wave + NW * i) < PG) issue_patch_piece(i, c0, sA);
+            if ((wr + RW * i) < PG) issue_patch_piece(i, c0, sA);
         if constexpr (GN) {
             if (wave == 0) issue_ss(c0, sS);
         }
@@ -1514,8 +1559,9 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
             if constexpr (GN) __builtin_amdgcn_s_barrier();  // wave 0's scale/shift table is visible
 #pragma unroll
             for (int i = 0; i < LAH; ++i)
-                if ((wave + NW * i) < PG) transform_piece(i, c0, sA, sS);
+                if ((wr + RW * i) < PG) transform_piece(i, c0, sA, sS);
             __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): my LDS writes are done before the loop's first barrier
+        }
         }
     }
     // DMA issued AFTER the weights of the step we are about to wait for may stay in flight (vmcnt retires in order):
@@ -1536,19 +1582,40 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
 #pragma unroll
         for (int t = 0; t < 9; ++t, ++step) {
             EOD_TSTAMP_AT(4 * t + 0);
-            if (pp1 == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else if (pp1 == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+            if constexpr (ROLES) {
+                // each role waits on what it owns: waves 4-7 on the weight tile they issued a step ago (all they ever issue); waves 0-3
+                // hold patch pieces only, which they wait for where they rewrite them (behind the MFMAs) -- but wave 0's scale / shift
+                // table, issued behind tap 0's MFMAs in FRONT of piece 0, has to be visible to the rewrites behind tap 2's: at most pieces
+                // 0 and 1 stay in flight across that barrier (waves 1-3 have issued no more than those two)
+                if (wm == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                else if (GN && t == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+            } else {
+                if (pp1 == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                else if (pp1 == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
+                else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+            }
             if constexpr (XF) __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): in-place normalisation / split writes are done
             __builtin_amdgcn_s_barrier();
             EOD_TSTAMP_AT(4 * t + 1);
+            if constexpr (ROLES) {
+                // waves 4-7: the whole weight tile of the next step, LBR pieces each; their patch pieces are waves 0-3's (behind the MFMAs)
+                if (wm == 1 && step + 1 < NSTEP) {
+                    if (t < 8) {
+                        issue_weight_tile(tap_slot(t + 1), cur, bve[0], sB + ((step + 1) & 1) * BSTAGE, 0, LBR);
+                    } else {
+                        unsigned off[LBV];
+                        weight_offsets(nxt, off);
+                        issue_weight_tile(0, nxt, off[0], sB + ((step + 1) & 1) * BSTAGE, 0, LBR);
+                    }
+                }
+            } else {
             // DMA for the next step: weights first, then (taps 0..LAH-1) one piece of the next chunk's patch
             if (step + 1 < NSTEP) {
                 if (t < 8) issue_weights_at(tap_slot(t + 1), cur, bve, sB + ((step + 1) & 1) * BSTAGE);
                 else issue_weights(0, nxt, sB + ((step + 1) & 1) * BSTAGE);
             }
             pp1 = 0;
-            if (t < LAH && has_next && (wave + NW * t) < PG) {
+            if (t < LAH && has_next && (wr + RW * t) < PG) {
                 issue_patch_piece(t, nxt, abuf_next);
                 pp1 = 1;
             }
@@ -1557,6 +1624,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
                     issue_ss(nxt, sS + (qpar ^ 1) * 1024);
                     ++pp1;
                 }
+            }
             }
             EOD_TSTAMP_AT(4 * t + 2);
             // ---- MFMAs of tap t: A fragments = patch rows shifted by (dy, dx) ----
@@ -1652,18 +1720,39 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
             }
             }
             EOD_TSTAMP_AT(4 * t + 3);
-            if constexpr (XF) {
+            if constexpr (ROLES) {
+                // waves 0-3, behind their MFMAs: piece t of the next chunk goes out (taps 0..5), piece t - 2 is rewritten in place (taps
+                // 2..7).  vmcnt retires in order and these waves issue nothing else, so the pieces of this step and of the one before
+                // (pp1) may stay in flight: a piece gets two K-steps to land, as on the 4-wave instances.
+                if (wm == 0 && has_next) {
+                    int now = 0;
+                    if constexpr (GN) {
+                        if (t == 0 && wave == 0) issue_ss(nxt, sS + (qpar ^ 1) * 1024);  // older than every piece: see the wait of tap 2
+                    }
+                    if (t < LAH && (wr + RW * t) < PG) {
+                        issue_patch_piece(t, nxt, abuf_next);
+                        now = 1;
+                    }
+                    if (t >= 2 && t - 2 < LAH && (wr + RW * (t - 2)) < PG) {
+                        if (pp1 + now == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                        else if (pp1 + now == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
+                        else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+                        transform_piece(t - 2, nxt, abuf_next, sS + (qpar ^ 1) * 1024);
+                    }
+                    pp1 = now;
+                }
+            } else if constexpr (XF) {
                 // piece (t-2) of the NEXT chunk was issued two steps ago and is covered by this step's vmcnt wait;
                 // the scale/shift table (wave 0, tap 0) became visible with this step's barrier (t >= 2).
                 // (spreading these ~110 VALU ops into the MFMA gaps with sched_group_barrier was measured: 3 % SLOWER)
                 // (round 4: its LDS reads issued in FRONT of the step's MFMAs instead, +12 live registers: single layers -1 %, step +-0)
-                if (t >= 2 && t - 2 < LAH && has_next && (wave + NW * (t - 2)) < PG)
+                if (t >= 2 && t - 2 < LAH && has_next && (wr + RW * (t - 2)) < PG)
                     transform_piece(t - 2, nxt, abuf_next, sS + (qpar ^ 1) * 1024);
             }
         }
         EOD_TSTAMP_AT(36);
 #ifdef EOD_TSTAMP
-        if (GN && wave == 1 && cc == 1 && blockIdx.x < 2048) {
+        if (GN && wave == EOD_TSTAMP_WAVE && cc == 1 && blockIdx.x < 2048) {
             __builtin_amdgcn_s_waitcnt(0xc07f);
             if (lane < 37) g_eod_tstamp[blockIdx.x][lane] = reinterpret_cast<const unsigned long long*>(sA + ABUF + PR * 128)[lane];
         }
@@ -3369,6 +3458,14 @@ extern "C" const char* eod_conv_kernel_name(const eod_conv_desc* d) {
         case FAM_HALO: return pl.bn == 32 ? "conv3x3_halo_kernel<BN=32>" : "conv3x3_halo_kernel";
         default: return "igemm_kernel";
     }
+}
+
+// output columns per workgroup of conv3x3_halo_kernel for this descriptor (32, 64, 128 or 256; 256 = the 8-wave instance, for a 256 + 128
+// conv its leading part); 0 where another family runs it
+extern "C" int eod_conv_halo_columns(const eod_conv_desc* d) {
+    if (!d) return 0;
+    const ConvPlan pl = conv_plan(d);
+    return pl.family == FAM_HALO ? pl.bn : 0;
 }
 
 static int conv_up4_bwd(const eod_conv_desc* d, void* stream) {

@@ -153,6 +153,9 @@ int64_t eod_conv_workspace_size(const eod_conv_desc* d);
 /* the kernel family eod_conv2d_igemm runs this descriptor on under the current options (a static string): "conv3x3_halo_kernel",
  * "conv3x3_halo_kernel<BN=32>", "conv_up4_halo_kernel", "conv_s2_halo_kernel", "conv_first_x3_kernel", "conv_head_kernel" or "igemm_kernel" */
 const char* eod_conv_kernel_name(const eod_conv_desc* d);
+/* output columns per workgroup where that family is "conv3x3_halo_kernel" (32, 64, 128 or 256; 256 = the 8-wave instance, which a
+ * 256 + 128 conv runs on all but its last 128 columns), 0 for every other family */
+int eod_conv_halo_columns(const eod_conv_desc* d);
 
 /* ------------------------------------------------------------------------------------------
  * k3/k7/k8: batched GEMM on MFMA,  C[b][m][n] = alpha * sum_k A[b][m][k] * B[b][n][k] (+bias)(+res)

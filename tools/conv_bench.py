@@ -16,6 +16,8 @@ SHAPES = {  # name: (N, H, W, Cin, Cout, k, stride, upsample)
     "l1_640": (16, 128, 128, 640, 256, 3, 1, False),
     "l2_384": (16, 64, 64, 384, 384, 3, 1, False),
     "l3_512": (16, 32, 32, 512, 512, 3, 1, False),
+    "l2_896": (16, 64, 64, 896, 384, 3, 1, False),     # decoder in_layers convs over the concatenated skip (256 + 128 columns with --gn)
+    "l3_1024": (16, 32, 32, 1024, 512, 3, 1, False),
     "up_256": (16, 128, 128, 256, 256, 3, 1, True),
     "up_384": (16, 64, 64, 384, 384, 3, 1, True),
     "up_512": (16, 32, 32, 512, 512, 3, 1, True),

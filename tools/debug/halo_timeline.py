@@ -2,7 +2,9 @@
 """Per-K-step timeline of one wave of conv3x3_halo_kernel (diagnostic build of igemm.hip with -DEOD_TSTAMP):
      EOD_LIBRARY=.../libeodiff_tstamp.so python tools/debug/halo_timeline.py [--prec fp32x3] [--shapes ...]
    wave 1 stamps the shader clock at: step top | after wait + barrier | after the DMA issue | after the last MFMA issued | (next top = after
-   the in-place rewrite of a patch piece) for the nine taps of its second chunk; medians over workgroups, in shader cycles."""
+   the in-place rewrite of a patch piece) for the nine taps of its second chunk; medians over workgroups, in shader cycles.
+   The stamped wave is a build option (-DEOD_TSTAMP_WAVE=5: a wave of the 8-wave instance's weight-issuing half; waves 0-3 there issue
+   and rewrite the patch pieces behind their MFMAs, so their "rewrite" column is DMA issue + wait + rewrite)."""
 import argparse, ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np

@@ -764,10 +764,14 @@ class BoundPsf:
 class BoundChain:
     """1 .. 4 bound observations (one: a PsfObservation, which has no fused kernel) applied in order to every evaluation's prediction, each link to the previous link's result and with its own
     weight: eod_pred_x0, one projection launch per link, eod_ddim_step_p0 / eod_dpmpp_step_p0.  The bits are those the fused kernel of
-    every link would give on the same prediction.  pred_x0 (for DPM-Solver++: the next evaluation's history) is the last link's result."""
+    every link would give on the same prediction.  pred_x0 (for DPM-Solver++: the next evaluation's history) is the last link's result.
+    threshold: a diffusion/threshold.py BoundThreshold, or None.  It becomes link 0, in front of the observations (it does not count towards
+    MAX_LINKS, and `links` may then be empty), and it REPLACES the static clamp: the prediction is formed with clip = 0 whatever the
+    sampler asks for."""
 
-    def __init__(self, links):
-        self.links = links
+    def __init__(self, links, threshold=None):
+        self.threshold = threshold
+        self.links = list(links) if threshold is None else [threshold] + list(links)
 
     def _project(self, i, p):
         for link in self.links:
@@ -791,7 +795,7 @@ class BoundChain:
 
     def dpmpp_step(self, i, x, e_t, d_prev, a_s, sqrt_1m_as, c_x, c_d, w_cur, w_prev, clip):
         x, e_t = f32c(x), f32c(e_t)
-        pred_x0 = self._project(i, self._pred_x0(x, e_t, a_s, sqrt_1m_as, clip))
+        pred_x0 = self._project(i, self._pred_x0(x, e_t, a_s, sqrt_1m_as, clip and self.threshold is None))
         x_next = torch.empty_like(x)
         _lib.check(_lib.lib().eod_dpmpp_step_p0(x.data_ptr(), pred_x0.data_ptr(), _lib.ptr(d_prev), float(c_x), float(c_d), float(w_cur),
                                                 float(w_prev), x_next.data_ptr(), x.numel(), current_stream_ptr(x.device)), "eod_dpmpp_step_p0")
@@ -841,8 +845,10 @@ def ddpm_step(bound, k, x_t, pred, noise, t, betas, alphas, acp, clip):
     """One ancestral (DDPM) update with an observation: eod_ddpm_pred_x0 -> each link's project(k, p) in order -> eod_ddpm_step_p0.
     bound: a BoundObservation, BoundSpectral, BoundPsf or BoundChain (a single link is a chain of one); k: the evaluation's number in the
     walk (what `weight` sequences are indexed by; not the timestep); t int64 [N] and the schedule tables [T] on the device.  clip False:
-    the same posterior form without the clamp (algebraically the reference's epsilon form, not its bits)."""
+    the same posterior form without the clamp (algebraically the reference's epsilon form, not its bits).  A chain with a threshold
+    (diffusion/threshold.py) forms its prediction without the clamp whatever `clip` says: the threshold, its link 0, replaces it."""
     x, e, z = f32c(x_t), f32c(pred), f32c(noise)
+    clip = clip and getattr(bound, "threshold", None) is None
     n, T, stream = x.shape[0], acp.numel(), current_stream_ptr(x.device)
     p = torch.empty_like(x)
     _lib.check(_lib.lib().eod_ddpm_pred_x0(x.data_ptr(), e.data_ptr(), t.data_ptr(), acp.data_ptr(), p.data_ptr(), n, x.numel() // n, T,

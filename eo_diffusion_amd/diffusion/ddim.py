@@ -18,13 +18,15 @@ observation=None (the default) every call takes the launches it took before.
 observations applied in order to every prediction (eod_pred_x0, one projection per link, eod_ddim_step_p0); DESIGN.md section 9.6.
 A PsfObservation (the bands seen through the sensor's point spread function on a coarser grid: eod_psf_residual / eod_psf_update,
 DESIGN.md section 9.7) is a link like the others; alone it runs as a chain of one.
+`threshold=` (a diffusion/threshold.py DynamicThreshold) on sample / ddim_sampling / sample_scene: every step's prediction is clamped to
+its own quantile and rescaled -- eod_pred_x0, eod_dyn_threshold, the observation's links if any, eod_ddim_step_p0; DESIGN.md section 9.12.
 """
 import numpy as np
 import torch
 
 from .. import _lib
 from ..engine import current_stream_ptr, f32c, require_gpu
-from . import chain, consistency
+from . import chain, consistency, threshold as thresholding
 from .util import make_ddim_sampling_parameters, make_ddim_timesteps, noise_like, resample_plan
 
 
@@ -71,7 +73,7 @@ class DDIMSampler(object):
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
                quantize_x0=False, eta=0.0, mask=None, x0=None, temperature=1.0, noise_dropout=0.0, score_corrector=None,
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.0,
-               unconditional_conditioning=None, resample=None, jump_noises=None, observation=None, **kwargs):
+               unconditional_conditioning=None, resample=None, jump_noises=None, observation=None, threshold=None, **kwargs):
         if conditioning is not None:
             cbs = (conditioning[list(conditioning.keys())[0]] if isinstance(conditioning, dict) else conditioning).shape[0]
             if cbs != batch_size:
@@ -84,20 +86,23 @@ class DDIMSampler(object):
                                   corrector_kwargs=corrector_kwargs, x_T=x_T, log_every_t=log_every_t,
                                   unconditional_guidance_scale=unconditional_guidance_scale,
                                   unconditional_conditioning=unconditional_conditioning, resample=resample,
-                                  jump_noises=jump_noises, observation=observation, **kwargs)
+                                  jump_noises=jump_noises, observation=observation, threshold=threshold, **kwargs)
 
     @torch.no_grad()
     def ddim_sampling(self, cond, shape, x_T=None, ddim_use_original_steps=False, callback=None, timesteps=None,
                       quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100, temperature=1.0,
                       noise_dropout=0.0, score_corrector=None, corrector_kwargs=None, unconditional_guidance_scale=1.0,
                       unconditional_conditioning=None, *, step_noises=None, mix_noises=None, progress=True, resample=None,
-                      jump_noises=None, observation=None):
+                      jump_noises=None, observation=None, threshold=None):
         """resample=(jump_length, jump_n_sample): RePaint resampling over the indices 0 .. total_steps - 1 of the steps this call walks.
         After the listed evaluations the state (at ddim_alphas_prev[a + 1] = ddim_alphas[a]) is moved up to ddim_alphas[b] by
         eod_renoise; step_noises / mix_noises are then indexed by the evaluation's position in the walk, jump_noises by the jump's
         ordinal (otherwise randn_like when the jump happens); callbacks and intermediates see every executed step.
         observation: an Observation or a SpectralObservation (diffusion/consistency.py) for a state of `shape`, or a list of 1 .. 4 of
-        them, applied in order; a per-evaluation `weight` is indexed like step_noises.  It is independent of the RePaint mix (mask / x0), which is applied in front of the UNet as without it."""
+        them, applied in order; a per-evaluation `weight` is indexed like step_noises.  It is independent of the RePaint mix (mask / x0), which is applied in front of the UNet as without it.
+        threshold: a DynamicThreshold (diffusion/threshold.py): every step's prediction is thresholded per batch member (or per band)
+        before the observation's links, if any, and before the update; pred_x0 in the intermediates is the final prediction.  None:
+        today's launches and bits."""
         if ddim_use_original_steps:
             raise NotImplementedError("ddim_use_original_steps touches attributes the reference never defines (ddim.py:188-190)")
         device = self.model.betas.device
@@ -110,7 +115,7 @@ class DDIMSampler(object):
         total_steps = timesteps.shape[0]
         visits, jump_after = resample_plan("DDIMSampler.ddim_sampling", resample, total_steps,
                                            (("step_noises", step_noises), ("mix_noises", mix_noises)), jump_noises)
-        obs = consistency.bind(observation, "DDIMSampler.ddim_sampling", shape, len(visits), device)
+        obs = thresholding.bind(threshold, observation, "DDIMSampler.ddim_sampling", shape, len(visits), device)
         img = torch.randn(shape, device=device) if x_T is None else f32c(x_T.to(device))
         intermediates = {"x_inter": [img], "pred_x0": [img]}
         if mask is not None:
@@ -188,7 +193,7 @@ class DDIMSampler(object):
     def sample_scene(self, S, scene_size, *, overlap=0, tile_batch=16, conditioning=None, mask=None, x0=None, eta=0.0, x_T=None,
                      temperature=1.0, unconditional_guidance_scale=1.0, unconditional_conditioning=None, step_noises=None,
                      mix_noises=None, callback=None, img_callback=None, log_every_t=100, verbose=False, progress=True, resample=None,
-                     jump_noises=None, skip_known=False, n_scenes=1, observation=None):
+                     jump_noises=None, skip_known=False, n_scenes=1, observation=None, threshold=None):
         """DDIM over ONE scene [1, C, H, W] larger than the UNet's image size (see EODiffusion.sampling_scene and
         eo_diffusion_amd/tiling.py): per step the RePaint mix (mask / x0 scene-sized), the UNet on overlapping tiles in chunks of
         tile_batch, the blend of the noise estimates, ONE scene-level eod_ddim_step.  Classifier-free guidance runs per chunk through
@@ -211,7 +216,10 @@ class DDIMSampler(object):
         single-scene call on scene b's inputs and draws, bit for bit.
         observation: an Observation / SpectralObservation (or a list of 1 .. 4, applied in order) with scene-sized values / mask (leading dimension n_scenes or 1); its blocks are anchored at the
         scene's origin and the projection is part of the ONE scene-level step, so it is seamless across tile borders.  Refused together
-        with skip_known: a block may straddle estimated and non-estimated pixels, and skip_known's bit equality could not hold."""
+        with skip_known: a block may straddle estimated and non-estimated pixels, and skip_known's bit equality could not hold.
+        threshold: a DynamicThreshold: the quantile is taken over the WHOLE scene's prediction (per band with per="channel"), never per
+        tile, inside the one scene-level step, so it is seamless; in a stack per member.  It comes before the observation's links.
+        Refused together with skip_known: the prediction at non-estimated pixels would enter the quantile."""
         from ..tiling import keep_known
         what = "DDIMSampler.sample_scene"
         m = self.model
@@ -219,7 +227,7 @@ class DDIMSampler(object):
         walk = lambda: resample_plan(what, resample, make_ddim_timesteps("uniform", S, m.timesteps, verbose=False).shape[0],
                                      (("step_noises", step_noises), ("mix_noises", mix_noises)), jump_noises)
         sc = self._scene_setup(what, scene_size, overlap, tile_batch, n_scenes, walk, mask, x0, skip_known, conditioning,
-                               unconditional_conditioning, unconditional_guidance_scale, x_T, observation)
+                               unconditional_conditioning, unconditional_guidance_scale, x_T, observation, threshold)
         if sc.known is not None:
             return sc.known, {"x_inter": [sc.known], "pred_x0": [sc.known]}
         img, x0, mask, B, device = sc.img, sc.x0, sc.mask, sc.B, sc.device
@@ -246,7 +254,7 @@ class DDIMSampler(object):
 
     # ------------------------------------------------------------------ what the scene samplers (this one and DPMSolverSampler's) share
     def _scene_setup(self, what, scene_size, overlap, tile_batch, n_scenes, walk, mask, x0, skip_known, conditioning,
-                     unconditional_conditioning, unconditional_guidance_scale, x_T, observation=None):
+                     unconditional_conditioning, unconditional_guidance_scale, x_T, observation=None, threshold=None):
         """Everything of a scene call in front of its first step: the plan, every refusal (walk() -> (visits, jump_after) fixes the walk and
         counts the injected draws, before anything is launched), mask / x0 scene-sized, the tiles to evaluate, the conditioning cut into
         them, the start state.  Returns a namespace; `known` is not None when no tile is active (the call returns it, no UNet call)."""
@@ -262,7 +270,10 @@ class DDIMSampler(object):
         if observation is not None and skip_known:
             raise _lib.EodError(f"{what}: skip_known and observation do not go together (a block of the observation may straddle "
                                 "estimated and non-estimated pixels)")
-        obs = consistency.bind(observation, what, (B, C, plan.H, plan.W), len(visits), device)
+        if threshold is not None and skip_known:
+            raise _lib.EodError(f"{what}: skip_known and threshold do not go together (the prediction at non-estimated pixels would enter "
+                                "the quantile)")
+        obs = thresholding.bind(threshold, observation, what, (B, C, plan.H, plan.W), len(visits), device)
         if (mask is None) != (x0 is None):
             raise _lib.EodError(f"{what}: mask and x0 go together (RePaint mix of the known region)")
         full = plan if B == 1 else TileStack(plan, B)  # (plan: the tiles that go through the UNet -- with skip_known the active ones only)

@@ -19,13 +19,16 @@ combination; the history the next evaluation reads is the projected prediction).
 A SpectralObservation (eod_dpmpp_step_spec) or a list of 1 .. 4 observations (eod_pred_x0, one projection per link, eod_dpmpp_step_p0: the
 history is the last link's result) goes the same way; DESIGN.md section 9.6.
 A PsfObservation is a link like the others; alone it runs as a chain of one.
+`threshold=` (a diffusion/threshold.py DynamicThreshold) on sample / sample_scene: every evaluation's prediction is clamped to its own
+quantile and rescaled in place of the static clamp -- eod_pred_x0 (clip = 0), eod_dyn_threshold, the observation's links if any,
+eod_dpmpp_step_p0; the history is the thresholded (and projected) prediction.  DESIGN.md section 9.12.
 """
 import numpy as np
 import torch
 
 from .. import _lib
 from ..engine import current_stream_ptr, f32c, require_gpu
-from . import consistency
+from . import consistency, threshold as thresholding
 from .ddim import DDIMSampler
 from .util import dpm_coefficients, dpm_lambda, make_dpm_timesteps, resample_plan
 
@@ -84,19 +87,23 @@ class DPMSolverSampler(DDIMSampler):
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, *, order=2, discretize="logsnr", t_start=None, clip_denoised=False,
                mask=None, x0=None, x_T=None, unconditional_guidance_scale=1.0, unconditional_conditioning=None, mix_noises=None,
-               resample=None, jump_noises=None, callback=None, img_callback=None, log_every_t=100, progress=True, observation=None):
+               resample=None, jump_noises=None, callback=None, img_callback=None, log_every_t=100, progress=True, observation=None,
+               threshold=None):
         """`S` steps (self.num_evaluations <= S UNet evaluations: duplicate levels of the logsnr grid are removed) from x_T to an image
         batch [batch_size, *shape].  Returns (samples, {"x_inter", "pred_x0"}) like DDIMSampler.sample.  mask / x0: the RePaint mix at
         every evaluation (mix_noises[i]: its q_sample noise, indexed by the evaluation's position in the walk).  resample /
         jump_noises: RePaint resampling over the indices of the levels, as in DDIMSampler.ddim_sampling.  observation: an Observation or a
         SpectralObservation for a state [batch_size, *shape], or a list of 1 .. 4 of them applied in order; a per-evaluation `weight` is
-        indexed like mix_noises."""
+        indexed like mix_noises.  threshold: a DynamicThreshold (diffusion/threshold.py): every evaluation's prediction is formed without
+        the static clamp, thresholded per batch member (or per band), then projected by the observation's links, if any; it REPLACES the
+        clamp, so clip_denoised makes no difference to a call that has one.  pred_x0 in the intermediates and the history is the final
+        prediction.  None: today's launches and bits."""
         what = "DPMSolverSampler.sample"
         visits, jump_after = self._plan(what, S, order, discretize, t_start, resample, mix_noises, jump_noises, mask, x0)
         device = self.model.betas.device
         C, H, W = shape
         b = batch_size
-        obs = consistency.bind(observation, what, (b, C, H, W), len(visits), device)
+        obs = thresholding.bind(threshold, observation, what, (b, C, H, W), len(visits), device)
         if conditioning is not None and conditioning.shape[0] != b:
             print(f"Warning: Got {conditioning.shape[0]} conditionings but batch-size is {b}")
         img = torch.randn((b, C, H, W), device=device) if x_T is None else f32c(x_T.to(device))
@@ -125,20 +132,22 @@ class DPMSolverSampler(DDIMSampler):
     def sample_scene(self, S, scene_size, *, overlap=0, tile_batch=16, conditioning=None, mask=None, x0=None, order=2, discretize="logsnr",
                      t_start=None, clip_denoised=False, x_T=None, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
                      mix_noises=None, callback=None, img_callback=None, log_every_t=100, progress=True, resample=None, jump_noises=None,
-                     skip_known=False, n_scenes=1, observation=None):
+                     skip_known=False, n_scenes=1, observation=None, threshold=None):
         """The solver over a scene (or a stack of n_scenes) larger than the UNet's image size: DDIMSampler.sample_scene's arguments with
         the solver's keywords in place of `eta` / `step_noises`.  One scene-level state, one scene-level history tensor and ONE
         eod_dpmpp_step on [B, C, H, W] per evaluation; tiles, blending, guidance per chunk, conditioning, skip_known (keep_known at the
         end) and n_scenes as there.  With overlap = 0 and injected draws the result equals sample() on the tiles, bit for bit; with
         skip_known it equals the skip_known=False scene at every estimated pixel and is `x0` elsewhere (at a pixel that is not
         estimated the zero estimate keeps state and history finite; at an estimated pixel pred_x0 depends on that pixel's x and e only).
-        observation: as in DDIMSampler.sample_scene (scene-sized, blocks anchored at the scene's origin, refused with skip_known)."""
+        observation: as in DDIMSampler.sample_scene (scene-sized, blocks anchored at the scene's origin, refused with skip_known).
+        threshold: as in DDIMSampler.sample_scene (the quantile of the whole scene's prediction, per member of a stack; it replaces the
+        clamp, so clip_denoised makes no difference; refused with skip_known)."""
         from ..tiling import keep_known
         what = "DPMSolverSampler.sample_scene"
         m = self.model
         walk = lambda: self._plan(what, S, order, discretize, t_start, resample, mix_noises, jump_noises, mask, x0)
         sc = self._scene_setup(what, scene_size, overlap, tile_batch, n_scenes, walk, mask, x0, skip_known, conditioning,
-                               unconditional_conditioning, unconditional_guidance_scale, x_T, observation)
+                               unconditional_conditioning, unconditional_guidance_scale, x_T, observation, threshold)
         if sc.known is not None:
             return sc.known, {"x_inter": [sc.known], "pred_x0": [sc.known]}
         img, x0, mask, B, device = sc.img, sc.x0, sc.mask, sc.B, sc.device

@@ -15,7 +15,9 @@ Differences from the reference that are deliberate (and documented in DESIGN.md)
   * `resample=(jump_length, jump_n_sample)` on both: RePaint resampling, the chain walks diffusion/util.py's make_resample_schedule
     and moves up it with eod_renoise (DESIGN.md section 9);
   * `observation=` on both: every evaluation's data prediction is projected onto what a sensor delivered before the posterior step uses
-    it (diffusion/consistency.py ddpm_step: eod_ddpm_pred_x0 -> the links -> eod_ddpm_step_p0).
+    it (diffusion/consistency.py ddpm_step: eod_ddpm_pred_x0 -> the links -> eod_ddpm_step_p0; DESIGN.md section 9.8);
+  * `threshold=` on both: dynamic thresholding of every evaluation's prediction in place of the static clamp, on the same route with the
+    threshold as link 0 (diffusion/threshold.py).
 """
 import math
 import os
@@ -26,7 +28,7 @@ import torch.nn as nn
 from .. import _lib
 from ..backbones.unet_openai import *  # noqa: F401,F403  (the reference re-exports these, model.py:5)
 from ..engine import current_stream_ptr, f32c, require_gpu
-from . import chain, consistency
+from . import chain, consistency, threshold as thresholding
 from .util import resample_plan
 
 
@@ -223,7 +225,7 @@ class EODiffusion(nn.Module):
     @torch.no_grad()
     def sampling(self, n_samples, clipped_reverse_diffusion=True, device="cpu", cond=None, y=None, idx=0, save=False,
                  *, x_T=None, noises=None, rng="torch", seed=0, sample_offset=0, progress=True, resample=None, jump_noises=None,
-                 observation=None):
+                 observation=None, threshold=None):
         """Reverse chain t = T-1 ... 0.  RNG order of the reference is kept: x_T is drawn on the CPU
         generator (model.py:48), one `randn_like` per step on the device generator (:55) used for BOTH the
         RePaint q_sample of gt (:59) and the reverse step (:69).
@@ -240,14 +242,19 @@ class EODiffusion(nn.Module):
         evaluation's prediction of x_0 is projected by the links in order and the posterior step uses the result (DESIGN.md section
         9.8); at t = 0 that step returns the prediction, so with weight 1 the returned sample meets a block-mean observation to
         rounding.  The mix stays in front of the UNet.  With clipped_reverse_diffusion=False the same posterior form runs without the
-        clamp: the reference's epsilon form algebraically, not bit for bit.  None: today's launches and bits."""
+        clamp: the reference's epsilon form algebraically, not bit for bit.  None: today's launches and bits.
+        threshold: a DynamicThreshold of diffusion/threshold.py.  Every evaluation forms its prediction WITHOUT the static clamp
+        (eod_ddpm_pred_x0, clip = 0), thresholds it per batch member (per band with per="channel"), applies the observation's links, if
+        any, and takes the posterior step from the result.  It REPLACES the clamp: clipped_reverse_diffusion makes no difference to a
+        call that has one.  The step at t = 0 returns the prediction, so without an observation the returned sample lies in [-1, 1].
+        None: today's launches and bits."""
         dev = torch.device(device)
         if dev.type != "cuda":
             raise _lib.EodError("EODiffusion.sampling: device must be a HIP GPU ('cuda[:i]'); there is no CPU path")
         self._tables_on(dev)
         visits, jump_after = resample_plan("EODiffusion.sampling", resample, self.timesteps, (("noises", noises),), jump_noises)
         shape = (n_samples, self.in_channels, self.image_size, self.image_size)
-        bound = consistency.bind(observation, "EODiffusion.sampling", shape, len(visits), dev)
+        bound = thresholding.bind(threshold, observation, "EODiffusion.sampling", shape, len(visits), dev)
         x_t = f32c(x_T.to(dev)) if x_T is not None else self._x_T(shape, dev, rng, seed, sample_offset)
         gt = mask = None
         if cond is not None and self.cond_type == "sum":
@@ -333,7 +340,7 @@ class EODiffusion(nn.Module):
     @torch.no_grad()
     def sampling_scene(self, scene_size, clipped_reverse_diffusion=True, device="cpu", cond=None, y=None, *, overlap=0, tile_batch=16,
                        x_T=None, noises=None, rng="philox", seed=0, progress=True, resample=None, jump_noises=None, skip_known=False,
-                       n_scenes=1, sample_offset=0, observation=None):
+                       n_scenes=1, sample_offset=0, observation=None, threshold=None):
         """Reverse chain over ONE scene [1, C, H, W], H, W >= image_size, with the UNet applied to overlapping image_size tiles
         (eo_diffusion_amd/tiling.py).  Per step: RePaint mix on the scene (cond_type == "sum"; cond [1, C+1, H, W] split as in
         sampling()) -> gather the tiles -> UNet on chunks of tile_batch tiles (same t, y broadcast, concatenated cond cut into the
@@ -365,21 +372,26 @@ class EODiffusion(nn.Module):
         observation: as in sampling(), on the SCENE: tensors are scene-sized (a PsfObservation's on its coarse grid) with leading
         dimension n_scenes or 1, blocks and PSFs are anchored at the scene origin and the links are part of the one scene-level step, so
         a block or a PSF footprint that a tile edge cuts is handled as anywhere else.  Refused together with skip_known=True (the
-        skipped tiles have no estimate to project)."""
+        skipped tiles have no estimate to project).
+        threshold: as in sampling(), on the SCENE: the quantile is taken over the whole scene's prediction (per band with
+        per="channel"), never per tile, inside the one scene-level step, so it is seamless; in a stack per member, so a member's bits
+        do not depend on what else is in the call.  It replaces the clamp (clipped_reverse_diffusion makes no difference) and comes
+        before the observation's links.  Refused together with skip_known=True."""
         from ..tiling import gather_padded, keep_known, tile_slots, tiles_to_evaluate
         what = "EODiffusion.sampling_scene"
         plan, dev = self._scene_args(what, scene_size, overlap, device)
         if rng not in ("philox", "torch"):
             raise _lib.EodError(f"{what}: rng is 'philox' or 'torch', got {rng!r}")
         self._no_skip_with_observation(what, skip_known, observation)
+        thresholding.no_skip(what, skip_known, threshold)
         if self._scene_count(what, n_scenes) > 1:
             return self._sampling_stack(what, plan, dev, n_scenes, clipped_reverse_diffusion, cond, y, tile_batch, x_T, noises, rng, seed,
-                                        sample_offset, progress, resample, jump_noises, skip_known, observation=observation)
+                                        sample_offset, progress, resample, jump_noises, skip_known, observation=observation, threshold=threshold)
         self._tables_on(dev)
         visits, jump_after = resample_plan(what, resample, self.timesteps, (("noises", noises),), jump_noises)
         shape = (1, self.in_channels, plan.H, plan.W)
         tile_slots(plan, tile_batch)  # (refuses a bad tile_batch)
-        bound = consistency.bind(observation, what, shape, len(visits), dev)
+        bound = thresholding.bind(threshold, observation, what, shape, len(visits), dev)
         gt = mask = cond_tiles = None
         if cond is not None and self.cond_type == "sum":
             cond = self._scene_tensor(what, "cond", cond, None, plan, dev)
@@ -408,10 +420,11 @@ class EODiffusion(nn.Module):
                                 "prediction could be projected")
 
     def check_scene_args(self, scene_size, device, *, n_scenes=1, cond=None, y=None, overlap=0, tile_batch=16, x_T=None, rng="philox",
-                         resample=None, noises=None, jump_noises=None, skip_known=False, observation=None):
+                         resample=None, noises=None, jump_noises=None, skip_known=False, observation=None, threshold=None):
         """Everything sampling_scene refuses from its arguments alone (scene size, overlap, tile_batch, rng, n_scenes, the shapes of
-        cond / x_T, the label count, the resampling walk, skip_known without a known region or with an observation, an observation that
-        does not fit the scene, the stack or the walk), with nothing copied or launched.
+        cond / x_T, the label count, the resampling walk, skip_known without a known region or with an observation or a threshold, an
+        observation that does not fit the scene, the stack or the walk, a `threshold` that is no DynamicThreshold), with nothing copied
+        or launched.
         dist.sharded_sampling_scene runs it on the GLOBAL arguments on every rank, so that all ranks refuse together."""
         from ..tiling import TilePlan, tile_slots
         what = "EODiffusion.sampling_scene"
@@ -419,10 +432,11 @@ class EODiffusion(nn.Module):
         if rng not in ("philox", "torch"):
             raise _lib.EodError(f"{what}: rng is 'philox' or 'torch', got {rng!r}")
         self._no_skip_with_observation(what, skip_known, observation)
+        thresholding.no_skip(what, skip_known, threshold)
         B = self._scene_count(what, n_scenes)
         visits, _ = resample_plan(what, resample, self.timesteps, (("noises", noises),), jump_noises)
         tile_slots(plan, tile_batch)
-        consistency.check(observation, what, (B, self.in_channels, plan.H, plan.W), len(visits))
+        thresholding.bind(threshold, observation, what, (B, self.in_channels, plan.H, plan.W), len(visits), None)
         for name, z, channels in (("x_T", x_T, self.in_channels), ("cond", cond, None)):
             if z is not None:
                 self._scene_shape(what, name, z, channels, plan, B)
@@ -436,7 +450,7 @@ class EODiffusion(nn.Module):
             raise _lib.EodError(f"{what}: a stack of {B} scenes takes one class label, or one per scene; got {torch.as_tensor(y).numel()}")
 
     def _sampling_stack(self, what, plan, dev, B, clip, cond, y, tile_batch, x_T, noises, rng, seed, sample0, progress, resample, jump_noises,
-                        skip_known, *, observation=None):
+                        skip_known, *, observation=None, threshold=None):
         """sampling_scene for n_scenes = B > 1: the same chain on the state [B, C, H, W] and a tiling.TileStack"""
         from ..tiling import TileStack, gather_padded, keep_known, tile_slots, tiles_to_evaluate
         self._tables_on(dev)
@@ -445,11 +459,12 @@ class EODiffusion(nn.Module):
         tile_slots(stack, tile_batch)  # (refuses a bad tile_batch)
         y = self._stack_labels_arg(what, y, B)
         self._no_skip_with_observation(what, skip_known, observation)
+        thresholding.no_skip(what, skip_known, threshold)
         as_stack = lambda name, z, channels=self.in_channels, expand=True: self._scene_tensor(what, name, z, channels, plan, dev, B, expand)
         for name, z, channels in (("x_T", x_T, self.in_channels), ("cond", cond, None)):  # (every shape, before anything is launched)
             if z is not None:
                 self._scene_shape(what, name, z, channels, plan, B)
-        bound = consistency.bind(observation, what, (B, self.in_channels, plan.H, plan.W), len(visits), dev)
+        bound = thresholding.bind(threshold, observation, what, (B, self.in_channels, plan.H, plan.W), len(visits), dev)
         gt = mask = cond_tiles = None
         if cond is not None:
             cond = as_stack("cond", cond, None, False)  # [1 or B, ...]: a broadcast known scene is classified and cut once

@@ -49,10 +49,11 @@ def gather_samples(local, n_total, group=None, force_gather=False):
 
 @torch.no_grad()
 def sharded_sampling(model, n_samples, *, seed=0, clipped_reverse_diffusion=True, cond=None, y=None, device=None,
-                     group=None, progress=False, force_gather=False, observation=None):
+                     group=None, progress=False, force_gather=False, observation=None, threshold=None):
     """EODiffusion.sampling over all ranks of `group`: every rank returns the full [n_samples, C, H, W] tensor.
     cond / y are the GLOBAL tensors (each rank slices its own rows), and so is `observation` (an observation of diffusion/consistency.py
-    or a list of them: each rank takes its shard(n_samples, lo, hi), tensors with leading dimension 1 stay).  force_gather: see
+    or a list of them: each rank takes its shard(n_samples, lo, hi), tensors with leading dimension 1 stay).  threshold (a
+    diffusion/threshold.py DynamicThreshold) is passed on unchanged: it is per sample, so nothing needs sharding.  force_gather: see
     gather_samples."""
     from .diffusion import consistency
     world = dist.get_world_size(group) if dist.is_initialized() else 1
@@ -62,6 +63,8 @@ def sharded_sampling(model, n_samples, *, seed=0, clipped_reverse_diffusion=True
     c = cond[lo:hi] if cond is not None else None
     yy = y[lo:hi] if y is not None else None
     obs = {} if observation is None else dict(observation=consistency.shard(observation, n_samples, lo, hi))   # (None: the call of before)
+    if threshold is not None:
+        obs["threshold"] = threshold
     local = model.sampling(hi - lo, clipped_reverse_diffusion=clipped_reverse_diffusion, device=dev, cond=c, y=yy,
                            rng="philox", seed=seed, sample_offset=lo, progress=progress, **obs)
     return gather_samples(local, n_samples, group=group, force_gather=force_gather)
@@ -78,12 +81,12 @@ def _shard_of(z, n_total, lo, hi):
 @torch.no_grad()
 def sharded_sampling_scene(model, scene_size, n_scenes, *, seed=0, clipped_reverse_diffusion=True, cond=None, y=None, overlap=0,
                            tile_batch=16, resample=None, skip_known=False, device=None, group=None, progress=False, force_gather=False,
-                           observation=None):
+                           observation=None, threshold=None):
     """EODiffusion.sampling_scene(n_scenes=...) over all ranks of `group`: scenes shard like samples do.  Rank r runs the scenes
     shard_bounds(n_scenes, world, r) as one stacked call with rng="philox" and sample_offset = lo -- scene b is sample b of `seed` on
     every rank, so the result does not depend on the world size -- and the scenes are concatenated with ONE all-gather: every rank
     returns [n_scenes, C, H, W].  cond / y are the GLOBAL tensors (leading dimension n_scenes, or 1 for one known scene / label shared
-    by all); `observation` is the GLOBAL observation (or list of them), each rank takes its shard(n_scenes, lo, hi).  A rank whose shard is empty launches nothing and still takes part in the collective.  Every rank first checks the
+    by all); `observation` is the GLOBAL observation (or list of them), each rank takes its shard(n_scenes, lo, hi); `threshold` is passed on unchanged (it is per scene).  A rank whose shard is empty launches nothing and still takes part in the collective.  Every rank first checks the
     GLOBAL arguments (EODiffusion.check_scene_args), so a bad argument is refused on all ranks alike, before any of them launches or
     enters the collective -- a rank with an empty shard included."""
     from .diffusion import consistency
@@ -91,8 +94,9 @@ def sharded_sampling_scene(model, scene_size, n_scenes, *, seed=0, clipped_rever
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     dev = device or f"cuda:{torch.cuda.current_device()}"
     obs = {} if observation is None else dict(observation=observation)                                         # (None: the calls of before)
+    thr = {} if threshold is None else dict(threshold=threshold)
     model.check_scene_args(scene_size, dev, n_scenes=n_scenes, cond=cond, y=y, overlap=overlap, tile_batch=tile_batch, resample=resample,
-                           skip_known=skip_known, **obs)
+                           skip_known=skip_known, **obs, **thr)
     lo, hi = shard_bounds(n_scenes, world, rank)
     h, w = (int(v) for v in scene_size)
     if hi > lo:
@@ -100,7 +104,7 @@ def sharded_sampling_scene(model, scene_size, n_scenes, *, seed=0, clipped_rever
         local = model.sampling_scene((h, w), clipped_reverse_diffusion, dev, cond=_shard_of(cond, n_scenes, lo, hi),
                                      y=None if yy is None else _shard_of(yy, n_scenes, lo, hi), overlap=overlap, tile_batch=tile_batch,
                                      rng="philox", seed=seed, progress=progress, resample=resample, skip_known=skip_known,
-                                     n_scenes=hi - lo, sample_offset=lo,
+                                     n_scenes=hi - lo, sample_offset=lo, **thr,
                                      **({} if observation is None else dict(observation=consistency.shard(observation, n_scenes, lo, hi))))
     else:
         local = torch.empty((0, model.in_channels, h, w), dtype=torch.float32, device=dev)

@@ -14,6 +14,7 @@ checkpoint of the reference's format ({"model": state_dict}): the example shows 
     python examples/inpaint_scene.py --timesteps 50 --resample 5 3 --skip-known
     python examples/inpaint_scene.py --timesteps 50 --skip-known --draws 8
     python examples/inpaint_scene.py --timesteps 1000 --solver dpmpp --steps 25 --skip-known
+    python examples/inpaint_scene.py --timesteps 1000 --solver dpmpp --steps 25 --threshold 0.995
 
 `--solver dpmpp` replaces the ancestral chain (one UNet evaluation per timestep) by `DPMSolverSampler.sample_scene`: DPM-Solver++ (2M)
 over `--steps` levels of a log-SNR grid, at most `--steps` evaluations whatever `--timesteps` is.  The same tiling, mask, resampling,
@@ -22,6 +23,10 @@ over `--steps` levels of a log-SNR grid, at most `--steps` evaluations whatever 
 `--draws K` runs K draws of the one scene in ONE call (`n_scenes=K` with the known scene given once: draw b is Philox sample b of
 `--seed`, the tiles of all draws share the UNet's batches) and writes, next to the first draw, `*_mean.npy` and `*_std.npy`: the per-pixel
 mean of the draws and how far they disagree (`tiling.scene_stats`, the sample standard deviation; zero wherever the scene is known).
+
+`--threshold Q` replaces the static clamp of every evaluation's data prediction by dynamic thresholding (`threshold=DynamicThreshold(Q)`,
+DESIGN.md section 9.12): the prediction is clamped to the scene's own Q-quantile of its magnitude and rescaled, one quantile over the whole
+scene, not per tile.  Not together with `--skip-known` (the prediction at non-estimated pixels would enter the quantile).
 
 `--skip-known` runs the UNet only on the tiles whose window holds a masked pixel (`skip_known=True`): the same bits wherever every
 covering tile is active, the known scene itself elsewhere, and a cost that follows the mask and not the scene.
@@ -70,6 +75,8 @@ def main():
     ap.add_argument("--draws", type=int, default=1, help="K draws of the scene in one call; also writes *_mean.npy and *_std.npy")
     ap.add_argument("--solver", default="ddpm", choices=["ddpm", "dpmpp"], help="ddpm: one evaluation per timestep; dpmpp: DPM-Solver++ (2M)")
     ap.add_argument("--steps", type=int, default=25, help="--solver dpmpp: the number of levels (at most that many UNet evaluations)")
+    ap.add_argument("--threshold", type=float, default=None, metavar="Q",
+                    help="dynamic thresholding of every prediction at the scene's Q-quantile (e.g. 0.995) in place of the static clamp")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--ckpt", default=None)
     ap.add_argument("--out", default="inpainted_scene.npy")
@@ -108,21 +115,27 @@ def main():
     elif args.draws > 1:
         tiles = TileStack(plan, args.draws)
     resample = None if args.resample is None else tuple(args.resample)
+    threshold = None
+    if args.threshold is not None:
+        from eo_diffusion_amd.diffusion.threshold import DynamicThreshold
+        threshold = DynamicThreshold(args.threshold)
     t0 = time.perf_counter()
     if args.solver == "dpmpp":
         from eo_diffusion_amd.diffusion.dpm_solver import DPMSolverSampler
         sampler = DPMSolverSampler(model)
         scene, _ = sampler.sample_scene(args.steps, (args.height, args.width), overlap=args.overlap, tile_batch=args.tile_batch,
                                         mask=cond[:, 3:], x0=cond[:, :3].contiguous(), clip_denoised=True, progress=False, resample=resample,
-                                        skip_known=args.skip_known, n_scenes=args.draws)   # (mask: 1 = keep, as the cond's last channel)
+                                        skip_known=args.skip_known, n_scenes=args.draws, threshold=threshold)   # (mask: 1 = keep, as the cond's last channel)
         num_levels = sampler.num_evaluations
     else:
         scene = model.sampling_scene((args.height, args.width), True, device, cond=cond, overlap=args.overlap, tile_batch=args.tile_batch,
                                      seed=args.seed, progress=False, resample=resample,
-                                     skip_known=args.skip_known, n_scenes=args.draws)   # (cond [1, 4, H, W]: the same known scene for every draw)
+                                     skip_known=args.skip_known, n_scenes=args.draws, threshold=threshold)   # (cond [1, 4, H, W]: the same known scene for every draw)
         num_levels = args.timesteps
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if threshold is not None:
+        print(f"dynamic threshold at q = {args.threshold}: scale of the last evaluation {threshold.last_bound.last_scale.tolist()}")
     out = harness.postprocess_samples(scene, data_nonneg=False)    # (x + 1) / 2
     np.save(args.out, out[0].cpu().numpy())
     if args.draws > 1:

@@ -35,7 +35,7 @@ const char* eod_last_error(void);
  * buffer of eod_pack_conv_weight_split, the 4-int state of eod_adamw_step_guarded).  eod_version() returns the value the library was built
  * with; a binding compares it with the header it mirrors at load time (eo_diffusion_amd/_lib.py does) instead of finding out by an
  * out-of-bounds device write. */
-#define EOD_ABI_VERSION 115
+#define EOD_ABI_VERSION 116
 int eod_version(void);
 /* Kernel-selection options ("skip_fuse", "head", "halo_bn256", "halo_splitk", "first", "s2_halo": 1 / 0; "gn_fuse_max_cout": n, -1 = default;
  * "head_tpw": pixel tiles per workgroup of conv_head_kernel, 0 = chosen per launch = default): every option has one measured-best default, the other arm computes the same function
@@ -435,6 +435,33 @@ int eod_ddpm_pred_x0(const float* x_t, const float* pred, const int64_t* t, cons
                      void* stream);
 int eod_ddpm_step_p0(const float* x_t, const float* p0c, const float* noise, const int64_t* t, const float* betas, const float* alphas,
                      const float* acp, float* out, int N, int64_t chw, int T, void* stream);
+/* Dynamic thresholding (Saharia et al. 2022; no reference line): the data prediction is clamped to the sample's own
+ * q-quantile of |p| and rescaled, where the static clamp of the entries above saturates.  p and out [B][n] fp32, s_out [B] fp32 on the
+ * device; sample b is the n elements at p + b * n (64-bit indexing: B * n may exceed 2^31).  Per sample, every operation rounded once in
+ * fp32:
+ *     key(x) = bits(x) & 0x7fffffff              as an unsigned integer (|x|; NaNs rank above +inf)
+ *     a_(0) <= a_(1) <= ... <= a_(n-1)           the sample's keys in ascending order: an EXACT order statistic (radix selection)
+ *     lo = float(a_(k));  hi = float(a_(min(k + 1, n - 1)))
+ *     v  = (frac == 0) ? lo : lo + (frac * (hi - lo))
+ *     s  = fminf(fmaxf(v, 1.0f), cap)            (a NaN v gives s = 1: the static clamp)
+ *     out[i] = fminf(fmaxf(p[i], -s), s) / s     (IEEE division; a NaN element becomes -1 as in eod_ddpm_step)
+ *     s_out[b] = s
+ * The caller computes k and frac from the quantile q: pos = q * (n - 1) in float64, k = floor(pos), frac = fp32(pos - k).
+ * Consequences: where v <= 1, s = 1 and out has the bits of the static clamp fminf(fmaxf(p, -1), 1) (division by 1 is exact), so
+ * eod_pred_x0(clip = 0) -> eod_dyn_threshold -> eod_*_step_p0 then has the bits of the clipped fused step; and the operator is idempotent:
+ * |out| <= 1, so a second application has s = 1 and returns the same bits.
+ * The result is a function of the sample's data, n, k, frac and cap alone: not of B, the pointers' alignment, the launch geometry or what
+ * the workspace held (all counters are integers; the call clears them itself, on the stream).  ws: caller-owned DEVICE workspace of at
+ * least eod_dyn_threshold_workspace_size(B, n) bytes (-1 for B <= 0 or n outside 1 .. 2^31 - 1), any alignment, private layout, reusable
+ * from call to call.  One clear, four reading passes over p and the apply pass; 16-byte accesses where n % 4 == 0 and p / out are 16-byte
+ * aligned, element by element otherwise: same bits.  Nothing is allocated, copied to or from the host, or synchronised: the call can be
+ * captured in a graph.
+ * EOD_EINVAL with nothing launched and the outputs untouched: a null pointer, B <= 0, n <= 0 or n > 2^31 - 1, k outside [0, n - 1], frac
+ * outside [0, 1) (NaN included), cap < 1 or NaN (+inf is allowed), a workspace that is too small, out / s_out / ws overlapping p or each
+ * other. */
+int64_t eod_dyn_threshold_workspace_size(int B, int64_t n);
+int eod_dyn_threshold(const float* p, int64_t k, float frac, float cap, float* out, float* s_out, int B, int64_t n, void* ws,
+                      int64_t ws_bytes, void* stream);
 /* PSF-aware observations (no reference line): the K channels `channels` (strictly increasing) of p [B][C][H][W] are
  * observed through A = D_f N^-1 B0 -- B0 the zero-padded separable convolution with the 1-D taps h[0 .. 2r] (r = 0 .. 12; fp32, finite,
  * non-negative, bitwise symmetric, h[r] > 0), horizontally, then vertically; N = diag(B0 1); D_f the f x f block mean of section 9.5 -- on

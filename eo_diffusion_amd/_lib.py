@@ -175,6 +175,10 @@ SYMBOLS = {
     "eod_ddpm_step_p0": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, i32, vp]),
     "eod_dyn_threshold_workspace_size": (i64, [i32, i64]),
     "eod_dyn_threshold": (i32, [vp, i64, f32, f32, vp, vp, i32, i64, vp, i64, vp]),
+    "eod_band_stats_workspace_size": (i64, [i32, i32, i32, i32]),
+    "eod_band_stats": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, f64, f64, vp, vp, vp, i64, vp]),
+    "eod_ssim_workspace_size": (i64, [i32, i32, i32, i32, i32]),
+    "eod_ssim": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, C.POINTER(f64), i32, f64, f64, f64, f64, vp, vp, vp, i64, vp]),
     "eod_ldm_p_sample": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, i32, i32, vp]),
     "eod_repaint_cond": (i32, [vp, vp, vp, i32, i32, i64, i32, vp]),
     "eod_postprocess": (i32, [vp, vp, i64, i32, vp]),
@@ -208,7 +212,7 @@ class EodError(RuntimeError):
     pass
 
 
-ABI_VERSION = 116  # EOD_ABI_VERSION of the include/eodiff.h this file mirrors
+ABI_VERSION = 117  # EOD_ABI_VERSION of the include/eodiff.h this file mirrors
 SPEC_GRID_BLOCKS = 4096  # EOD_SPEC_GRID_BLOCKS there
 
 

@@ -80,6 +80,7 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--ckpt", default=None)
     ap.add_argument("--out", default="inpainted_scene.npy")
+    ap.add_argument("--metrics", action="store_true", help="score the painted region (metrics.hole_of) of every draw, and of their mean, against the synthetic scene (eo_diffusion_amd.metrics.quality)")
     args = ap.parse_args()
     device = "cuda:0"
     torch.manual_seed(args.seed)
@@ -146,6 +147,14 @@ def main():
         hole = (mask != 0).expand_as(mean)
         print(f"{args.draws} draws: wrote {stem}_mean.npy and {stem}_std.npy; per-pixel std over the draws: mean {float(std[hole].mean()):.4f} "
               f"in the masked region, max {float(std[~hole].max()):.2e} over the kept region")
+    if args.metrics:                                               # on the painted region alone; out and image are in [0, 1]
+        from eo_diffusion_amd import metrics
+        hole_w = metrics.hole_of(cond[:, 3:])
+        q = metrics.quality(out, image, where=hole_w)
+        for b in range(args.draws):
+            print(metrics.describe(q, f"draw {b} against the scene, painted region", b))
+        if args.draws > 1:
+            print(metrics.describe(metrics.quality(mean, image, where=hole_w), "mean of the draws against the scene, painted region"))
     out = out[:1]
     keep = (mask == 0).expand_as(image)
     dev_kept = float((out - image)[keep].abs().max())

@@ -57,6 +57,7 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--ckpt", default=None)
     ap.add_argument("--out", default="pansharpened_scene.npy")
+    ap.add_argument("--metrics", action="store_true", help="score the returned scene against the synthetic truth (eo_diffusion_amd.metrics.quality)")
     args = ap.parse_args()
     device = "cuda:0"
     torch.manual_seed(args.seed)
@@ -88,6 +89,9 @@ def main():
         r_bands = float((block_mean(z, factors) - bands).abs().max())
         print(f"  {name}: max |pan of it - pan| = {r_pan:.2e}, max |block mean of it - bands| = {r_bands:.2e}")
     print(f"  sharpness the bands alone cannot give: max |scene - replicated bands| = {float((scene - bands).abs().max()):.2f}; wrote {args.out}")
+    if args.metrics:                                                   # (both in [-1, 1]: scored as reflectance-like [0, 1])
+        from eo_diffusion_amd import metrics
+        print(metrics.describe(metrics.quality(scene, truth, affine=(0.5, 0.5), ratio=args.factor), "returned scene against the truth"))
 
 
 if __name__ == "__main__":

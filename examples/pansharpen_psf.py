@@ -64,6 +64,7 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--ckpt", default=None)
     ap.add_argument("--out", default="pansharpened_psf_scene.npy")
+    ap.add_argument("--metrics", action="store_true", help="score the returned scene against the synthetic truth (eo_diffusion_amd.metrics.quality)")
     args = ap.parse_args()
     device = "cuda:0"
     torch.manual_seed(args.seed)
@@ -105,6 +106,9 @@ def main():
         r_ms = float((psf_observe(z, h_ms, f) - bands).abs().max())
         print(f"  {title}: max |A x - y|: pan {r_pan:.2e}, bands {r_ms:.2e}")
     print(f"  wrote {args.out}")
+    if args.metrics:                                                   # (both in [-1, 1]: scored as reflectance-like [0, 1])
+        from eo_diffusion_amd import metrics
+        print(metrics.describe(metrics.quality(scene, truth, affine=(0.5, 0.5), ratio=args.factor), "returned scene against the truth"))
 
 
 if __name__ == "__main__":

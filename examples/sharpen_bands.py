@@ -56,6 +56,7 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--ckpt", default=None)
     ap.add_argument("--out", default="sharpened_scene.npy")
+    ap.add_argument("--metrics", action="store_true", help="score the returned scene against the synthetic truth (eo_diffusion_amd.metrics.quality)")
     args = ap.parse_args()
     device = "cuda:0"
     torch.manual_seed(args.seed)
@@ -88,6 +89,10 @@ def main():
     res = (block_mean(scene, args.factors) - values).abs().amax(dim=(0, 2, 3)).tolist()
     print(f"{args.height} x {args.width}, factors {tuple(args.factors)}, weight {args.weight}: {evaluations} evaluations in {dt:.2f} s; "
           f"max |block mean of the result - observation| per band: " + ", ".join(f"{r:.2e}" for r in res) + f"; wrote {args.out}")
+    if args.metrics:                                                   # (both in [-1, 1]: scored as reflectance-like [0, 1])
+        from eo_diffusion_amd import metrics
+        ratio = max(args.factors) if max(args.factors) > 1 else None
+        print(metrics.describe(metrics.quality(scene, truth, affine=(0.5, 0.5), ratio=ratio), "returned scene against the truth"))
 
 
 if __name__ == "__main__":

@@ -69,6 +69,7 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--ckpt", default=None)
     ap.add_argument("--out", default="sharpened_psf_scene.npy")
+    ap.add_argument("--metrics", action="store_true", help="score the returned scene against the synthetic truth (eo_diffusion_amd.metrics.quality)")
     args = ap.parse_args()
     device = "cuda:0"
     torch.manual_seed(args.seed)
@@ -115,6 +116,9 @@ def main():
         res = ", ".join(f"{name} {float((psf_observe(z, h, f, cs) - values[name]).abs().max()):.2e}" for name, (cs, f, h) in seen.items())
         print(f"  {title}: max |A x - y|: {res}")
     print(f"  wrote {args.out}")
+    if args.metrics:                                                   # (both in [-1, 1]: scored as reflectance-like [0, 1])
+        from eo_diffusion_amd import metrics
+        print(metrics.describe(metrics.quality(scene, truth, affine=(0.5, 0.5), ratio=min(f for _, f in GROUPS.values())), "returned scene against the truth"))
 
 
 if __name__ == "__main__":

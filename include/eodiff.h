@@ -35,7 +35,7 @@ const char* eod_last_error(void);
  * buffer of eod_pack_conv_weight_split, the 4-int state of eod_adamw_step_guarded).  eod_version() returns the value the library was built
  * with; a binding compares it with the header it mirrors at load time (eo_diffusion_amd/_lib.py does) instead of finding out by an
  * out-of-bounds device write. */
-#define EOD_ABI_VERSION 116
+#define EOD_ABI_VERSION 117
 int eod_version(void);
 /* Kernel-selection options ("skip_fuse", "head", "halo_bn256", "halo_splitk", "first", "s2_halo": 1 / 0; "gn_fuse_max_cout": n, -1 = default;
  * "head_tpw": pixel tiles per workgroup of conv_head_kernel, 0 = chosen per launch = default): every option has one measured-best default, the other arm computes the same function
@@ -462,6 +462,52 @@ int eod_ddpm_step_p0(const float* x_t, const float* p0c, const float* noise, con
 int64_t eod_dyn_threshold_workspace_size(int B, int64_t n);
 int eod_dyn_threshold(const float* p, int64_t k, float frac, float cap, float* out, float* s_out, int B, int64_t n, void* ws,
                       int64_t ws_bytes, void* stream);
+/* Image-quality metrics (inference.py:136-138 evaluates torchmetrics' PSNR / SSIM on the GPU).  Two operators over
+ * pred [B][C][H][W] and ref [ref_B][C][H][W], ref_B = B or 1 (one truth against a stack), fp32 on the device, any 4-byte alignment, any W,
+ * 64-bit indexing; where: null or [where_B][1][H][W] fp32, where_B = B or 1 -- a pixel is COUNTED iff its value != 0.0f (a NaN counts).
+ * C <= 32.  Both images pass an affine on load, every operation below rounded once in float64 (-ffp-contract=off):
+ *     p = (a * (double)pred[i]) + b;      t = (a * (double)ref[i]) + b
+ *
+ * eod_band_stats: band [B][C][8] and sample [B][3], float64, 8-byte aligned.  Over the counted pixels of (sample, band):
+ *     band = { n, sum p, sum t, sum (p * p), sum (t * t), sum (p * t), sum ((p - t) * (p - t)), max |p - t| }
+ *   and per counted pixel, with the SAME rounded products summed over the bands c = 0 .. C - 1 in ascending order:
+ *     pp = sum_c p_c * p_c;   tt = sum_c t_c * t_c;   dot = sum_c p_c * t_c
+ *     pp == 0 or tt == 0:  the pixel has no angle (sample[2] += 1)
+ *     else  w = (pp * tt) - (dot * dot);  theta = atan2(sqrt(w > 0 ? w : 0), dot);  sample[0] += theta;  sample[1] += 1
+ *   (bit-identical spectra: pp * tt and dot * dot are the same rounded product, theta is exactly 0; atan2 is well conditioned at 0 where
+ *   acos(dot / (|p| |t|)) is not).  The maximum keeps a NaN: m = (d > m || d != d) ? d : m.  A NaN element therefore makes the sums and the
+ *   maximum of its own (sample, band) NaN, and its sample's angle sum; nothing else.
+ *   Order of the additions: a pixel belongs to chunk i / 2048 and there to thread (i % 2048) % 256; a thread adds its pixels in ascending
+ *   order from 0.0; of the 256 thread sums x[0 .. 255] of a chunk, y[l] = ((x[l] + x[l + 32]) + ..) + x[l + 224] for l = 0 .. 31, and the 32 y
+ *   meet by the butterfly y[l] = y[l] + y[l ^ 16], .. y[l] + y[l ^ 1]; the chunks of a sample are added from left to right from 0.0 in groups
+ *   of 64, the group sums again in groups of 64, until one is left (up to 64 chunks: plainly left to right).  A function of (C, H, W) alone:
+ *   not of B, the grid, the alignment or what the workspace held.
+ *
+ * eod_ssim: the window is taps[0 .. 2r] (HOST array of float64, read during the call), r = 0 .. 12, applied horizontally, then vertically,
+ * WITHOUT padding: window position (y, x), y = 0 .. H - 2r - 1, x = 0 .. W - 2r - 1, covers rows y .. y + 2r and columns x .. x + 2r and has
+ * its centre at (y + r, x + r).  (torchmetrics reflect-pads and crops the pad away again: the cropped map is this valid region.)  For each of
+ * q = p, t, p * p, t * t, p * t (the products rounded in float64), taps in ascending order, one rounded multiply and one rounded add per tap:
+ *     h_q[y'][x] = ((taps[0] * q[y'][x]) + taps[1] * q[y'][x + 1]) + ... + taps[2r] * q[y'][x + 2r]
+ *     E_q[y][x]  = ((taps[0] * h_q[y][x]) + taps[1] * h_q[y + 1][x]) + ... + taps[2r] * h_q[y + 2r][x]
+ *     mpp = Ep * Ep;  mtt = Et * Et;  mpt = Ep * Et;   spp = Epp - mpp;  stt = Ett - mtt;  spt = Ept - mpt
+ *     ssim = (((2 * mpt) + c1) * ((2 * spt) + c2)) / (((mpp + mtt) + c1) * ((spp + stt) + c2))
+ *   map: null, or [B][C][H][W] fp32: map[centre] = (float)ssim; the elements outside the valid region are not written.
+ *   sums [B][C][2] float64, 8-byte aligned: { sum of ssim, n } over the positions whose CENTRE is counted by `where`.
+ *   Order of the additions: position (y, x) belongs to tile (y / 32, x / 32) and there to thread ((y % 32) * 32 + x % 32) % 256; threads,
+ *   then tiles (row-major) are added as above.  A function of (H, W, r) alone.
+ *
+ * ws: caller-owned DEVICE workspace of at least *_workspace_size(...) bytes (-1 for arguments the operator refuses), any alignment, private
+ * layout, reusable: every slot is written before it is read.  No floating-point atomics; nothing is allocated, copied or synchronised: the
+ * calls can be captured in a graph.  EOD_EINVAL with nothing launched and the outputs untouched: a null pointer (where and map may be null),
+ * B, H or W <= 0, C outside 1 .. 32, ref_B or where_B neither B nor 1, a or b not finite, a float64 output that is not 8-byte aligned, a
+ * workspace that is too small, outputs overlapping each other or the workspace; eod_ssim also: r outside 0 .. 12, H or W < 2r + 1, a tap,
+ * c1 or c2 not finite, map overlapping an input.  The tile body of eod_ssim is csrc/ssim_body.h. */
+int64_t eod_band_stats_workspace_size(int B, int C, int H, int W);
+int eod_band_stats(const float* pred, const float* ref, const float* where, int B, int ref_B, int where_B, int C, int H, int W, double a,
+                   double b, double* band, double* sample, void* ws, int64_t ws_bytes, void* stream);
+int64_t eod_ssim_workspace_size(int B, int C, int H, int W, int r);
+int eod_ssim(const float* pred, const float* ref, const float* where, int B, int ref_B, int where_B, int C, int H, int W, const double* taps,
+             int r, double a, double b, double c1, double c2, float* map, double* sums, void* ws, int64_t ws_bytes, void* stream);
 /* PSF-aware observations (no reference line): the K channels `channels` (strictly increasing) of p [B][C][H][W] are
  * observed through A = D_f N^-1 B0 -- B0 the zero-padded separable convolution with the 1-D taps h[0 .. 2r] (r = 0 .. 12; fp32, finite,
  * non-negative, bitwise symmetric, h[r] > 0), horizontally, then vertically; N = diag(B0 1); D_f the f x f block mean of section 9.5 -- on

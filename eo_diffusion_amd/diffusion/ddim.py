@@ -26,7 +26,7 @@ import torch
 
 from .. import _lib
 from ..engine import current_stream_ptr, f32c, require_gpu
-from . import chain, consistency, threshold as thresholding
+from . import chain, consistency, scene, threshold as thresholding
 from .util import make_ddim_sampling_parameters, make_ddim_timesteps, noise_like, resample_plan
 
 
@@ -250,71 +250,44 @@ class DDIMSampler(object):
             return self._after_step(i, index, img, pred_x0, intermediates, callback, img_callback, log_every_t, total_steps)
 
         img = self._walk(img, sc.visits, sc.jump_after, step, jump_noises, sc.as_scene, "DDIM Sampler (scene)" if progress else None)
-        return (img if sc.plan is sc.full else keep_known(img, x0, sc.plan)), intermediates
+        return (img if sc.tiles is sc.full else keep_known(img, x0, sc.tiles)), intermediates
 
     # ------------------------------------------------------------------ what the scene samplers (this one and DPMSolverSampler's) share
     def _scene_setup(self, what, scene_size, overlap, tile_batch, n_scenes, walk, mask, x0, skip_known, conditioning,
                      unconditional_conditioning, unconditional_guidance_scale, x_T, observation=None, threshold=None):
-        """Everything of a scene call in front of its first step: the plan, every refusal (walk() -> (visits, jump_after) fixes the walk and
-        counts the injected draws, before anything is launched), mask / x0 scene-sized, the tiles to evaluate, the conditioning cut into
-        them, the start state.  Returns a namespace; `known` is not None when no tile is active (the call returns it, no UNet call)."""
-        from types import SimpleNamespace
-        from ..tiling import TileStack, gather_padded, tile_slots, tiles_to_evaluate
+        """scene.check and scene.setup for mask / x0 samplers: the known region is x0 [B or 1, C, H, W] under a mask that broadcasts
+        against the state as in ddim_sampling().  Returns setup's namespace."""
         m = self.model
-        device = m.betas.device
-        plan, device = m._scene_args(what, scene_size, overlap, device)
-        C = m.in_channels
-        B = m._scene_count(what, n_scenes)
-        visits, jump_after = walk()
-        tile_slots(plan, tile_batch)  # (refuses a bad tile_batch)
-        if observation is not None and skip_known:
-            raise _lib.EodError(f"{what}: skip_known and observation do not go together (a block of the observation may straddle "
-                                "estimated and non-estimated pixels)")
-        if threshold is not None and skip_known:
-            raise _lib.EodError(f"{what}: skip_known and threshold do not go together (the prediction at non-estimated pixels would enter "
-                                "the quantile)")
-        obs = thresholding.bind(threshold, observation, what, (B, C, plan.H, plan.W), len(visits), device)
-        if (mask is None) != (x0 is None):
-            raise _lib.EodError(f"{what}: mask and x0 go together (RePaint mix of the known region)")
-        full = plan if B == 1 else TileStack(plan, B)  # (plan: the tiles that go through the UNet -- with skip_known the active ones only)
-        if B > 1:  # (every shape, before anything is launched)
-            for name, z, channels in (("x_T", x_T, C), ("x0", x0, C), ("conditioning", conditioning, None),
-                                      ("unconditional_conditioning", unconditional_conditioning, None)):
-                if z is not None:
-                    m._scene_shape(what, name, z, channels, plan, B)
-        if mask is not None:
-            x0 = m._scene_tensor(what, "x0", x0, C, plan, device, B, expand=False)
+
+        def against(mk, state):  # (a mask that is the same for every scene stays [1, ...]: it is classified once)
+            return state if mk.dim() == 4 and mk.shape[0] != 1 else (1,) + state[1:]
+
+        def known(sized, state):
+            if (mask is None) != (x0 is None):
+                raise _lib.EodError(f"{what}: mask and x0 go together (RePaint mix of the known region)")
+            if mask is None:
+                return False
+            sized("x0", x0, state[1])
             mk = torch.as_tensor(mask)
-            if mk.dim() < 2 or tuple(mk.shape[-2:]) != (plan.H, plan.W):
-                raise _lib.EodError(f"{what}: `mask` must be scene-sized ({plan.H} x {plan.W}), got {tuple(mk.shape)}")
-            like = x0.expand(B, *x0.shape[1:])  # (a mask that is the same for every scene stays [1, ...]: it is classified once)
-            mask = m._broadcast_mask(mk.to(device), like if mk.dim() == 4 and mk.shape[0] != 1 else like[:1])
-        plan = tiles_to_evaluate(what, full, mask, skip_known, "mask and x0")
-        if mask is not None and B > 1:
-            x0, mask = (z.expand(B, *z.shape[1:]).contiguous() for z in (x0, mask))
-        sc = SimpleNamespace(plan=plan, full=full, B=B, device=device, tile_batch=tile_batch, x0=x0, mask=mask, visits=visits,
-                             jump_after=jump_after, known=None, c_tiles=None, uc_tiles=None, obs=obs)
-        if plan is None:
-            sc.known = x0.clone()
-            return sc
-        sc.chunk, _ = tile_slots(plan, tile_batch)
-        guided = unconditional_conditioning is not None and unconditional_guidance_scale != 1.0
-        if conditioning is not None:
-            sc.c_tiles = gather_padded(m._scene_tensor(what, "conditioning", conditioning, None, plan, device, B), plan, tile_batch)
-        if guided:
-            if sc.c_tiles is None:
-                raise _lib.EodError(f"{what}: classifier-free guidance needs `conditioning` next to `unconditional_conditioning`")
-            sc.uc_tiles = gather_padded(m._scene_tensor(what, "unconditional_conditioning", unconditional_conditioning, sc.c_tiles.shape[1],
-                                                        plan, device, B), plan, tile_batch)
-        sc.img = torch.randn((B, C, plan.H, plan.W), device=device) if x_T is None else m._scene_tensor(what, "x_T", x_T, C, plan, device, B)
-        sc.as_scene = lambda name, z: m._scene_tensor(what, name, z, C, plan, device, B)
-        return sc
+            if mk.dim() < 2 or tuple(mk.shape[-2:]) != state[2:]:
+                raise _lib.EodError(f"{what}: `mask` must be scene-sized ({state[2]} x {state[3]}), got {tuple(mk.shape)}")
+            m._mask_broadcasts(mk.shape, against(mk, state))
+            return True
+
+        def known_on_device(as_scene, state):
+            x0_d, mk = as_scene("x0", x0, state[1], False), torch.as_tensor(mask)
+            return x0_d, m._broadcast_mask(mk.to(x0_d.device), x0_d.expand(state)[:against(mk, state)[0]])
+
+        hs = scene.check(m, what, scene_size, overlap, m.betas.device, n_scenes, walk, tile_batch, skip_known, observation, threshold,
+                         needs="mask and x0", known=(known, known_on_device), x_T=x_T, conditioning=conditioning,
+                         unconditional_conditioning=unconditional_conditioning, guidance_scale=unconditional_guidance_scale)
+        return scene.setup(m, hs, lambda shape, dev: torch.randn(shape, device=dev))
 
     def _scene_eps(self, sc, img, t, unconditional_guidance_scale):
         """the blended noise estimate of the scene state at timestep t: the UNet (plain or guided, _eps) on the tiles in chunks"""
         from ..tiling import tiled_estimate
         ts = torch.full((sc.chunk,), t, device=sc.device, dtype=torch.long)
-        return tiled_estimate(img, sc.plan, sc.tile_batch, lambda x, lo: self._eps(
+        return tiled_estimate(img, sc.tiles, sc.tile_batch, lambda x, lo: self._eps(
             x, ts, None if sc.c_tiles is None else sc.c_tiles[lo:lo + sc.chunk], unconditional_guidance_scale,
             None if sc.uc_tiles is None else sc.uc_tiles[lo:lo + sc.chunk]))
 

@@ -166,7 +166,7 @@ class DPMSolverSampler(DDIMSampler):
             return self._after_step(i, index, img, pred_x0, intermediates, callback, img_callback, log_every_t, total_steps)
 
         img = self._walk(img, sc.visits, sc.jump_after, step, jump_noises, sc.as_scene, "DPM-Solver++ Sampler (scene)" if progress else None)
-        return (img if sc.plan is sc.full else keep_known(img, x0, sc.plan)), intermediates
+        return (img if sc.tiles is sc.full else keep_known(img, x0, sc.tiles)), intermediates
 
     # ------------------------------------------------------------------ DDIM's own entry points do not apply to this sampler
     def ddim_sampling(self, *args, **kwargs):

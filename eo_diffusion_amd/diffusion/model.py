@@ -28,7 +28,7 @@ import torch.nn as nn
 from .. import _lib
 from ..backbones.unet_openai import *  # noqa: F401,F403  (the reference re-exports these, model.py:5)
 from ..engine import current_stream_ptr, f32c, require_gpu
-from . import chain, consistency, threshold as thresholding
+from . import chain, consistency, scene, threshold as thresholding
 from .util import resample_plan
 
 
@@ -118,15 +118,20 @@ class EODiffusion(nn.Module):
         differs between channels, [N,C,H,W]"""
         n, c, h, w = like.shape
         m = torch.as_tensor(mask, device=like.device).float()
-        try:
-            shape = torch.broadcast_shapes(tuple(m.shape), (n, c, h, w))
-        except RuntimeError:
-            shape = None
-        if shape != (n, c, h, w):
-            raise _lib.EodError(f"mask of shape {tuple(m.shape)} does not broadcast against {(n, c, h, w)}")
+        EODiffusion._mask_broadcasts(m.shape, (n, c, h, w))
         while m.dim() < 4:
             m = m[None]
         return m.expand(n, m.shape[1], h, w).contiguous()
+
+    @staticmethod
+    def _mask_broadcasts(mask_shape, state):
+        """_broadcast_mask's refusal, from the shapes alone"""
+        try:
+            shape = torch.broadcast_shapes(tuple(mask_shape), tuple(state))
+        except RuntimeError:
+            shape = None
+        if shape != tuple(state):
+            raise _lib.EodError(f"mask of shape {tuple(mask_shape)} does not broadcast against {tuple(state)}")
 
     def _ddpm_update(self, x_t, pred, noise, t, clip):
         x, e, z = f32c(x_t), f32c(pred), f32c(noise)
@@ -286,7 +291,7 @@ class EODiffusion(nn.Module):
     @staticmethod
     def _scene_count(what, n_scenes):
         import numbers
-        if isinstance(n_scenes, bool) or not isinstance(n_scenes, numbers.Integral) or n_scenes < 1:  # (numpy integers included, as in TileStack)
+        if isinstance(n_scenes, bool) or not isinstance(n_scenes, numbers.Integral) or n_scenes < 1:  # (numpy integers included, as in tiling.py)
             raise _lib.EodError(f"{what}: n_scenes must be an integer >= 1, got {n_scenes!r}")
         return int(n_scenes)
 
@@ -306,36 +311,6 @@ class EODiffusion(nn.Module):
             want = f"[{1 if n_scenes == 1 else f'{n_scenes} (or 1)'}, {'*' if channels is None else channels}, {plan.H}, {plan.W}]"
             raise _lib.EodError(f"{what}: `{name}` must be scene-sized, {want}; got {tuple(t.shape)}")
         return t
-
-    def _scene_labels(self, y, chunk, dev):
-        if y is None:
-            return None
-        y = torch.as_tensor(y, device=dev).reshape(-1)
-        if y.numel() != 1:
-            raise _lib.EodError(f"scene sampling takes ONE class label for the scene (it is broadcast to every tile), got {y.numel()}")
-        return y.to(torch.int64).expand(chunk).contiguous()
-
-    @staticmethod
-    def _stack_labels_arg(what, y, n_scenes):
-        """the labels of a stack as a host-checked 1-D tensor of 1 or n_scenes entries (None: no labels); refuses before any launch"""
-        if y is None:
-            return None
-        y = torch.as_tensor(y).reshape(-1)
-        if y.numel() not in (1, n_scenes):
-            raise _lib.EodError(f"{what}: a stack of {n_scenes} scenes takes one class label, or one per scene; got {y.numel()}")
-        return y
-
-    @staticmethod
-    def _stack_labels(y, stack, tile_batch, dev):
-        """int64 [slots]: the label of the scene each tile slot belongs to (padding slots repeat the last listed tile, and its label)"""
-        from ..tiling import tile_slots
-        if y is None:
-            return None
-        _, slots = tile_slots(stack, tile_batch)
-        scene_of = torch.from_numpy(stack.index // stack.plan.n_tiles).to(torch.int64)
-        scene_of = torch.cat([scene_of, scene_of[-1:].expand(slots - stack.n_tiles)])
-        y = y.to(torch.int64).expand(stack.n_scenes) if y.numel() == 1 else y.to(torch.int64)
-        return y.to(dev)[scene_of.to(dev)].contiguous()
 
     @torch.no_grad()
     def sampling_scene(self, scene_size, clipped_reverse_diffusion=True, device="cpu", cond=None, y=None, *, overlap=0, tile_batch=16,
@@ -377,116 +352,54 @@ class EODiffusion(nn.Module):
         per="channel"), never per tile, inside the one scene-level step, so it is seamless; in a stack per member, so a member's bits
         do not depend on what else is in the call.  It replaces the clamp (clipped_reverse_diffusion makes no difference) and comes
         before the observation's links.  Refused together with skip_known=True."""
-        from ..tiling import gather_padded, keep_known, tile_slots, tiles_to_evaluate
-        what = "EODiffusion.sampling_scene"
-        plan, dev = self._scene_args(what, scene_size, overlap, device)
-        if rng not in ("philox", "torch"):
-            raise _lib.EodError(f"{what}: rng is 'philox' or 'torch', got {rng!r}")
-        self._no_skip_with_observation(what, skip_known, observation)
-        thresholding.no_skip(what, skip_known, threshold)
-        if self._scene_count(what, n_scenes) > 1:
-            return self._sampling_stack(what, plan, dev, n_scenes, clipped_reverse_diffusion, cond, y, tile_batch, x_T, noises, rng, seed,
-                                        sample_offset, progress, resample, jump_noises, skip_known, observation=observation, threshold=threshold)
-        self._tables_on(dev)
-        visits, jump_after = resample_plan(what, resample, self.timesteps, (("noises", noises),), jump_noises)
-        shape = (1, self.in_channels, plan.H, plan.W)
-        tile_slots(plan, tile_batch)  # (refuses a bad tile_batch)
-        bound = thresholding.bind(threshold, observation, what, shape, len(visits), dev)
-        gt = mask = cond_tiles = None
-        if cond is not None and self.cond_type == "sum":
-            cond = self._scene_tensor(what, "cond", cond, None, plan, dev)
-            if cond.shape[1] < 4:
-                raise _lib.EodError(f"{what}: cond_type='sum' needs cond = cat(gt[3], mask[1]), got {cond.shape[1]} channels")
-            gt, mask = cond[:, :3].contiguous(), cond[:, 3][:, None].contiguous()
-            if skip_known and gt.shape[1] != self.in_channels:
-                raise _lib.EodError(f"{what}: skip_known=True returns gt outside the estimated pixels; gt has {gt.shape[1]} channels, "
-                                    f"the state {self.in_channels}")
-        tiles = tiles_to_evaluate(what, plan, mask, skip_known, "cond_type='sum' with cond = cat(gt, mask)")
-        if tiles is None:
-            return gt.clone()
-        if cond is not None and gt is None:
-            cond_tiles = gather_padded(self._scene_tensor(what, "cond", cond, None, plan, dev), plan, tile_batch)
-        as_scene = lambda name, z: self._scene_tensor(what, name, z, self.in_channels, plan, dev)
-        x_t = as_scene("x_T", x_T) if x_T is not None else self._x_T(shape, dev, rng, seed, sample_offset)
-        estimate = self._scene_estimate(tiles, tile_batch, cond_tiles, self._scene_labels(y, tile_slots(tiles, tile_batch)[0], dev))
-        x_t = self._ddpm_chain(x_t, visits, jump_after, estimate, clipped_reverse_diffusion, gt, mask, noises=noises, jump_noises=jump_noises,
-                               as_draw=as_scene, rng=rng, seed=seed, sample0=sample_offset, desc="Sampling scene" if progress else None, bound=bound)
-        return x_t if tiles is plan else keep_known(x_t, gt, tiles)
+        from ..tiling import keep_known
+        hs = self._scene_check(scene_size, device, n_scenes, cond, y, overlap, tile_batch, x_T, rng, resample, noises, jump_noises, skip_known,
+                               observation, threshold)
+        sc = scene.setup(self, hs, lambda shape, dev: self._x_T(shape, dev, rng, seed, sample_offset))
+        if sc.known is not None:
+            return sc.known
+        estimate = self._scene_estimate(sc.tiles, tile_batch, sc.c_tiles, None, sc.y_slots)
+        x_t = self._ddpm_chain(sc.img, sc.visits, sc.jump_after, estimate, clipped_reverse_diffusion, sc.x0, sc.mask, noises=noises,
+                               jump_noises=jump_noises, as_draw=sc.as_scene, rng=rng, seed=seed, sample0=sample_offset,
+                               desc=("Sampling scene" if sc.B == 1 else "Sampling scenes") if progress else None, bound=sc.obs)
+        return x_t if sc.tiles is sc.full else keep_known(x_t, sc.x0, sc.tiles)
 
-    @staticmethod
-    def _no_skip_with_observation(what, skip_known, observation):
-        if skip_known and observation is not None:
-            raise _lib.EodError(f"{what}: skip_known=True cannot be combined with `observation`: a skipped tile has no estimate whose "
-                                "prediction could be projected")
+    def _scene_check(self, scene_size, device, n_scenes, cond, y, overlap, tile_batch, x_T, rng, resample, noises, jump_noises, skip_known,
+                     observation, threshold):
+        """scene.check for sampling_scene: the known region is cut out of `cond` (cond_type == "sum": cat(gt[3], mask[1]), as in sampling());
+        any other `cond` is the UNet's conditioning"""
+        what = "EODiffusion.sampling_scene"
+        summed = cond is not None and self.cond_type == "sum"
+
+        def known(sized, state):
+            if not summed:
+                return False
+            channels = sized("cond", cond, None).shape[1]
+            if channels < 4:
+                raise _lib.EodError(f"{what}: cond_type='sum' needs cond = cat(gt[3], mask[1]), got {channels} channels")
+            if skip_known and self.in_channels != 3:
+                raise _lib.EodError(f"{what}: skip_known=True returns gt outside the estimated pixels; gt has 3 channels, "
+                                    f"the state {self.in_channels}")
+            return True
+
+        def known_on_device(as_scene, state):
+            c = as_scene("cond", cond, None, False)
+            return c[:, :3].contiguous(), c[:, 3][:, None].contiguous()
+
+        return scene.check(self, what, scene_size, overlap, device, n_scenes,
+                           lambda: resample_plan(what, resample, self.timesteps, (("noises", noises),), jump_noises), tile_batch, skip_known,
+                           observation, threshold, needs="cond_type='sum' with cond = cat(gt, mask)", known=(known, known_on_device), rng=rng,
+                           x_T=x_T, conditioning=None if summed else cond, conditioning_name="cond", y=y)
 
     def check_scene_args(self, scene_size, device, *, n_scenes=1, cond=None, y=None, overlap=0, tile_batch=16, x_T=None, rng="philox",
                          resample=None, noises=None, jump_noises=None, skip_known=False, observation=None, threshold=None):
-        """Everything sampling_scene refuses from its arguments alone (scene size, overlap, tile_batch, rng, n_scenes, the shapes of
-        cond / x_T, the label count, the resampling walk, skip_known without a known region or with an observation or a threshold, an
-        observation that does not fit the scene, the stack or the walk, a `threshold` that is no DynamicThreshold), with nothing copied
-        or launched.
+        """Everything sampling_scene refuses (scene size, overlap, tile_batch, rng, n_scenes, the shapes of cond / x_T, the label count,
+        the resampling walk, skip_known without a known region or with an observation or a threshold, an observation that does not fit
+        the scene, the stack or the walk, a `threshold` that is no DynamicThreshold), with nothing copied or launched: the host half of
+        the call itself (scene.check), so the two cannot drift apart.
         dist.sharded_sampling_scene runs it on the GLOBAL arguments on every rank, so that all ranks refuse together."""
-        from ..tiling import TilePlan, tile_slots
-        what = "EODiffusion.sampling_scene"
-        plan, dev = self._scene_args(what, scene_size, overlap, device)
-        if rng not in ("philox", "torch"):
-            raise _lib.EodError(f"{what}: rng is 'philox' or 'torch', got {rng!r}")
-        self._no_skip_with_observation(what, skip_known, observation)
-        thresholding.no_skip(what, skip_known, threshold)
-        B = self._scene_count(what, n_scenes)
-        visits, _ = resample_plan(what, resample, self.timesteps, (("noises", noises),), jump_noises)
-        tile_slots(plan, tile_batch)
-        thresholding.bind(threshold, observation, what, (B, self.in_channels, plan.H, plan.W), len(visits), None)
-        for name, z, channels in (("x_T", x_T, self.in_channels), ("cond", cond, None)):
-            if z is not None:
-                self._scene_shape(what, name, z, channels, plan, B)
-        known = cond is not None and self.cond_type == "sum"
-        if known and torch.as_tensor(cond).shape[1] < 4:
-            raise _lib.EodError(f"{what}: cond_type='sum' needs cond = cat(gt[3], mask[1]), got {torch.as_tensor(cond).shape[1]} channels")
-        if skip_known and not known:
-            raise _lib.EodError(f"{what}: skip_known=True needs a known region (cond_type='sum' with cond = cat(gt, mask)); there is nothing to "
-                                "skip without one")
-        if y is not None and torch.as_tensor(y).numel() not in (1, B):
-            raise _lib.EodError(f"{what}: a stack of {B} scenes takes one class label, or one per scene; got {torch.as_tensor(y).numel()}")
-
-    def _sampling_stack(self, what, plan, dev, B, clip, cond, y, tile_batch, x_T, noises, rng, seed, sample0, progress, resample, jump_noises,
-                        skip_known, *, observation=None, threshold=None):
-        """sampling_scene for n_scenes = B > 1: the same chain on the state [B, C, H, W] and a tiling.TileStack"""
-        from ..tiling import TileStack, gather_padded, keep_known, tile_slots, tiles_to_evaluate
-        self._tables_on(dev)
-        visits, jump_after = resample_plan(what, resample, self.timesteps, (("noises", noises),), jump_noises)
-        stack = TileStack(plan, B)
-        tile_slots(stack, tile_batch)  # (refuses a bad tile_batch)
-        y = self._stack_labels_arg(what, y, B)
-        self._no_skip_with_observation(what, skip_known, observation)
-        thresholding.no_skip(what, skip_known, threshold)
-        as_stack = lambda name, z, channels=self.in_channels, expand=True: self._scene_tensor(what, name, z, channels, plan, dev, B, expand)
-        for name, z, channels in (("x_T", x_T, self.in_channels), ("cond", cond, None)):  # (every shape, before anything is launched)
-            if z is not None:
-                self._scene_shape(what, name, z, channels, plan, B)
-        bound = thresholding.bind(threshold, observation, what, (B, self.in_channels, plan.H, plan.W), len(visits), dev)
-        gt = mask = cond_tiles = None
-        if cond is not None:
-            cond = as_stack("cond", cond, None, False)  # [1 or B, ...]: a broadcast known scene is classified and cut once
-            if self.cond_type == "sum":
-                if cond.shape[1] < 4:
-                    raise _lib.EodError(f"{what}: cond_type='sum' needs cond = cat(gt[3], mask[1]), got {cond.shape[1]} channels")
-                gt, mask = cond[:, :3].contiguous(), cond[:, 3][:, None].contiguous()
-                if skip_known and gt.shape[1] != self.in_channels:
-                    raise _lib.EodError(f"{what}: skip_known=True returns gt outside the estimated pixels; gt has {gt.shape[1]} channels, "
-                                        f"the state {self.in_channels}")
-        tiles = tiles_to_evaluate(what, stack, mask, skip_known, "cond_type='sum' with cond = cat(gt, mask)")
-        if gt is not None:
-            gt, mask = (z.expand(B, *z.shape[1:]).contiguous() for z in (gt, mask))
-        if tiles is None:
-            return gt.clone()
-        if cond is not None and gt is None:
-            cond_tiles = gather_padded(as_stack("cond", cond, None), tiles, tile_batch)
-        x_t = as_stack("x_T", x_T) if x_T is not None else self._x_T((B, self.in_channels, plan.H, plan.W), dev, rng, seed, sample0)
-        estimate = self._scene_estimate(tiles, tile_batch, cond_tiles, None, self._stack_labels(y, tiles, tile_batch, dev))
-        x_t = self._ddpm_chain(x_t, visits, jump_after, estimate, clip, gt, mask, noises=noises, jump_noises=jump_noises,
-                               as_draw=as_stack, rng=rng, seed=seed, sample0=sample0, desc="Sampling scenes" if progress else None, bound=bound)
-        return x_t if tiles is stack else keep_known(x_t, gt, tiles)
+        self._scene_check(scene_size, device, n_scenes, cond, y, overlap, tile_batch, x_T, rng, resample, noises, jump_noises, skip_known,
+                          observation, threshold)
 
     def _scene_estimate(self, plan, tile_batch, cond_tiles, y_chunk, y_slots=None):
         """estimate(x_t, t, i) of a scene: tiles -> UNet in chunks -> blended estimate (tiling.tiled_estimate).  y_chunk: one label repeated

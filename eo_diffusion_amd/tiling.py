@@ -1,16 +1,20 @@
 """Whole-scene sampling: the tile plan and the two kernels between a scene-sized tensor and UNet-sized tiles.
 
     plan  = TilePlan(H, W, tile, overlap)        host-side (numpy), importable without a GPU
-    tiles = gather_tiles(scene, plan)            [1,C,H,W] (or [C,H,W]) -> [n_tiles, C, tile, tile]    eod_scene_gather
-    scene = blend_tiles(tiles, plan)             [n_tiles, C, tile, tile] -> [1, C, H, W]              eod_scene_blend
+    tiles = gather_tiles(scene, plan)            [1,C,H,W] (or [C,H,W]) -> [n_tiles, C, tile, tile]    eod_scene_stack_gather
+    scene = blend_tiles(tiles, plan)             [n_tiles, C, tile, tile] -> [1, C, H, W]              eod_scene_stack_blend
     e     = tiled_estimate(scene, plan, tile_batch, fn)   gather -> fn on chunks of tile_batch tiles -> blend
-    idx   = active_tiles(mask, plan)             the tiles whose window holds a hole pixel of a RePaint mask      eod_scene_tile_active
+    idx   = active_tiles(mask, plan)             the tiles whose window holds a hole pixel of a RePaint mask      eod_scene_stack_tile_active
     sub   = plan.subset(idx)                     a TileSubset: goes wherever a plan goes above, on the listed tiles only
-    out   = keep_known(x, known, sub)            x at estimated pixels, known elsewhere                           eod_scene_keep_known
+    out   = keep_known(x, known, sub)            x at estimated pixels, known elsewhere                           eod_scene_stack_keep_known
     tiles = tiles_to_evaluate(what, plan, mask, skip_known, needs)   what a scene sampler evaluates: plan | sub | None (nothing active)
     stack = TileStack(plan, B)                   B scenes of one plan ([B, C, H, W]): goes wherever a plan goes above; tiles of every scene
     part  = TileStack(plan, B, indices)          ... or the listed tiles only (global numbers b * n_tiles + i), like a TileSubset
     mean, std = scene_stats(scenes)              [B, C, H, W] -> per-pixel mean and sample standard deviation, each [1, C, H, W]   eod_scene_stats
+
+One path: a scene is a stack of one.  Whatever kind of plan an operation is given, it makes ONE library call, the eod_scene_stack_* entry
+point, with B = 1 for a TilePlan / TileSubset and a null index / slot_of for the full form (_launch_form).  The library's single-scene
+entry points (eod_scene_gather ...) are the same launches with B = 1 and remain for C callers; nothing here calls them.
 
 Plan, per axis of length L: origins min(i * (tile - overlap), L - tile) until the axis is covered -- the last tile is shifted
 inwards, never padded.  Weights, per axis, [n][tile]: 1 in a tile's interior, a linear ramp (k + 1) / (o + 1) across the o pixels
@@ -142,7 +146,45 @@ class TilePlan:
         return hit
 
 
-class TileSubset:
+def _tile_list(who, noun, indices, total):
+    """(index int32 [n], slot_of int32 [total]) of a tile list that is 1-D, non-empty, integer, in [0, total), ascending and unique;
+    refused otherwise, in the name of the class `who` that is being made"""
+    raw = np.asarray(list(indices) if not isinstance(indices, np.ndarray) else indices)
+    if raw.ndim != 1 or raw.size < 1:
+        raise _lib.EodError(f"{who}: the tile list must be a non-empty 1-D sequence of {noun}, got shape {tuple(raw.shape)}")
+    if not np.issubdtype(raw.dtype, np.integer):
+        raise _lib.EodError(f"{who}: {noun} are integers, got {raw.dtype}")
+    idx = raw.astype(np.int64)
+    if idx.min() < 0 or idx.max() >= total:
+        raise _lib.EodError(f"{who}: {noun} must be in [0, {total}), got {int(idx.min())} .. {int(idx.max())}")
+    if np.any(np.diff(idx) <= 0):
+        raise _lib.EodError(f"{who}: {noun} must be ascending and unique")
+    slot_of = np.full(total, -1, dtype=np.int32)
+    slot_of[idx] = np.arange(idx.size, dtype=np.int32)
+    return idx.astype(np.int32), slot_of
+
+
+class _TileList:
+    """what a TileSubset and a TileStack are made of: a plan and the list (index, slot_of) of the tiles that go through the network"""
+
+    def _set(self, plan, index, slot_of):
+        self.plan, self.index, self.slot_of = plan, index, slot_of
+        self.n_tiles = int(index.size)
+        self.H, self.W, self.tile, self.overlap = plan.H, plan.W, plan.tile, plan.overlap
+        self._dev = {}
+
+    def device_tables(self, device):
+        """(index, slot_of) as device int32 tensors, uploaded once per device"""
+        import torch
+        dev = torch.device(device)
+        hit = self._dev.get(dev)
+        if hit is None:
+            hit = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (self.index, self.slot_of))
+            self._dev[dev] = hit
+        return hit
+
+
+class TileSubset(_TileList):
     """Some tiles of a TilePlan, in ascending order: what gather_tiles / blend_tiles / tile_slots / gather_padded / tiled_estimate
     work on when only these tiles go through the network.
 
@@ -152,23 +194,7 @@ class TileSubset:
     def __init__(self, plan, indices):
         if not isinstance(plan, TilePlan):
             raise _lib.EodError(f"TileSubset: a subset is taken of a TilePlan, got {type(plan).__name__}")
-        raw = np.asarray(list(indices) if not isinstance(indices, np.ndarray) else indices)
-        if raw.ndim != 1 or raw.size < 1:
-            raise _lib.EodError(f"TileSubset: the tile list must be a non-empty 1-D sequence of tile indices, got shape {tuple(raw.shape)}")
-        if not np.issubdtype(raw.dtype, np.integer):
-            raise _lib.EodError(f"TileSubset: tile indices are integers, got {raw.dtype}")
-        idx = raw.astype(np.int64)
-        if idx.min() < 0 or idx.max() >= plan.n_tiles:
-            raise _lib.EodError(f"TileSubset: tile indices must be in [0, {plan.n_tiles}), got {int(idx.min())} .. {int(idx.max())}")
-        if np.any(np.diff(idx) <= 0):
-            raise _lib.EodError("TileSubset: tile indices must be ascending and unique")
-        self.plan = plan
-        self.index = idx.astype(np.int32)
-        self.n_tiles = int(idx.size)
-        self.slot_of = np.full(plan.n_tiles, -1, dtype=np.int32)
-        self.slot_of[idx] = np.arange(idx.size, dtype=np.int32)
-        self.H, self.W, self.tile, self.overlap = plan.H, plan.W, plan.tile, plan.overlap
-        self._dev = {}
+        self._set(plan, *_tile_list("TileSubset", "tile indices", indices, plan.n_tiles))
 
     def __repr__(self):
         return f"TileSubset({self.n_tiles} of {self.plan.n_tiles} tiles of {self.plan!r})"
@@ -186,18 +212,8 @@ class TileSubset:
             est[y0:y0 + p.tile, x0:x0 + p.tile] = False
         return est
 
-    def device_tables(self, device):
-        """(index, slot_of) as device int32 tensors, uploaded once per device"""
-        import torch
-        dev = torch.device(device)
-        hit = self._dev.get(dev)
-        if hit is None:
-            hit = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (self.index, self.slot_of))
-            self._dev[dev] = hit
-        return hit
 
-
-class TileStack:
+class TileStack(_TileList):
     """n_scenes copies of one TilePlan, tiled together; with `indices` only the listed global tiles g = b * plan.n_tiles + i (ascending,
     unique, in range -- refused otherwise, like a TileSubset).  Goes wherever a plan or a subset goes; scenes are then [B, C, H, W].
 
@@ -213,27 +229,12 @@ class TileStack:
         total = int(n_scenes) * plan.n_tiles
         if total > 0x7fffffff:
             raise _lib.EodError(f"TileStack: {n_scenes} scenes of {plan.n_tiles} tiles cannot be numbered in an int32")
-        self.plan, self.n_scenes, self.listed = plan, int(n_scenes), indices is not None
+        self.n_scenes, self.listed = int(n_scenes), indices is not None
         if indices is None:
-            self.index = np.arange(total, dtype=np.int32)
-            self.slot_of = self.index
+            index = np.arange(total, dtype=np.int32)
+            self._set(plan, index, index)
         else:
-            raw = np.asarray(list(indices) if not isinstance(indices, np.ndarray) else indices)
-            if raw.ndim != 1 or raw.size < 1:
-                raise _lib.EodError(f"TileStack: the tile list must be a non-empty 1-D sequence of global tile numbers, got shape {tuple(raw.shape)}")
-            if not np.issubdtype(raw.dtype, np.integer):
-                raise _lib.EodError(f"TileStack: tile numbers are integers, got {raw.dtype}")
-            idx = raw.astype(np.int64)
-            if idx.min() < 0 or idx.max() >= total:
-                raise _lib.EodError(f"TileStack: global tile numbers must be in [0, {total}), got {int(idx.min())} .. {int(idx.max())}")
-            if np.any(np.diff(idx) <= 0):
-                raise _lib.EodError("TileStack: global tile numbers must be ascending and unique")
-            self.index = idx.astype(np.int32)
-            self.slot_of = np.full(total, -1, dtype=np.int32)
-            self.slot_of[idx] = np.arange(idx.size, dtype=np.int32)
-        self.n_tiles = int(self.index.size)
-        self.H, self.W, self.tile, self.overlap = plan.H, plan.W, plan.tile, plan.overlap
-        self._dev = {}
+            self._set(plan, *_tile_list("TileStack", "global tile numbers", indices, total))
 
     def __repr__(self):
         return f"TileStack({self.n_tiles} of {self.n_scenes} x {self.plan.n_tiles} tiles of {self.plan!r})"
@@ -270,43 +271,38 @@ class TileStack:
         nt = self.plan.n_tiles
         return np.concatenate([self.plan.active_tiles(m[b]).astype(np.int64) + b * nt for b in range(self.n_scenes)]).astype(np.int32)
 
-    def device_tables(self, device):
-        """(index, slot_of) as device int32 tensors, uploaded once per device"""
-        import torch
-        dev = torch.device(device)
-        hit = self._dev.get(dev)
-        if hit is None:
-            hit = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (self.index, self.slot_of))
-            self._dev[dev] = hit
-        return hit
+
+def _launch_form(plan):
+    """(base, B, tile list, single) of any of the three plan kinds, as a launch needs it: the TilePlan, the number of scenes, the object
+    whose device_tables() hold (index, slot_of) or None for the full form, and whether the argument was a single-scene kind (a TilePlan
+    or a TileSubset: B = 1, and a scene may come without its leading dimension)"""
+    if isinstance(plan, TilePlan):
+        return plan, 1, None, True
+    if isinstance(plan, TileSubset):
+        return plan.plan, 1, plan, True
+    if isinstance(plan, TileStack):
+        return plan.plan, plan.n_scenes, (plan if plan.listed else None), False
+    raise _lib.EodError(f"a TilePlan, a TileSubset or a TileStack is needed, got {type(plan).__name__}")
 
 
 def active_tiles(mask, plan):
-    """TilePlan.active_tiles for a mask on the GPU ([H, W] or [..., H, W]): eod_scene_tile_active, then ONE device-to-host copy of
-    plan.n_tiles ints (the only synchronisation).  Ascending int32 tile indices (numpy)."""
+    """TilePlan.active_tiles for a mask on the GPU ([H, W] or [..., H, W]): eod_scene_stack_tile_active, then ONE device-to-host copy of
+    plan.n_tiles ints (the only synchronisation).  Ascending int32 tile indices (numpy).  With a TileStack: a stacked mask
+    [B, ..., H, W] and the global numbers, still one launch and one copy."""
     import torch
     from .engine import current_stream_ptr, f32c, require_gpu
     require_gpu(mask, "active_tiles")
-    if isinstance(plan, TileStack):  # a stacked mask [B, ..., H, W]: global numbers, one launch, one copy
-        stack, plan = plan, plan.plan
-        if mask.dim() < 3 or mask.shape[0] != stack.n_scenes or tuple(mask.shape[-2:]) != (plan.H, plan.W):
-            raise _lib.EodError(f"active_tiles: the mask of a stack must be [{stack.n_scenes}, ..., {plan.H}, {plan.W}], got {tuple(mask.shape)}")
-        m = f32c(mask.reshape(stack.n_scenes, -1, plan.H, plan.W))
-        active = torch.empty(stack.n_scenes * plan.n_tiles, dtype=torch.int32, device=m.device)
-        oy, ox, _, _ = plan.device_tables(m.device)
-        _lib.check(_lib.lib().eod_scene_stack_tile_active(m.data_ptr(), active.data_ptr(), stack.n_scenes, m.shape[1], plan.H, plan.W, plan.tile,
-                                                          oy.data_ptr(), ox.data_ptr(), plan.nty, plan.ntx, current_stream_ptr(m.device)),
-                   "eod_scene_stack_tile_active")
-        return np.flatnonzero(active.cpu().numpy()).astype(np.int32)
-    if not isinstance(plan, TilePlan):
-        raise _lib.EodError(f"active_tiles: `plan` is a TilePlan, got {type(plan).__name__}")
-    if mask.dim() < 2 or tuple(mask.shape[-2:]) != (plan.H, plan.W):
-        raise _lib.EodError(f"active_tiles: the mask must be [..., {plan.H}, {plan.W}], got {tuple(mask.shape)}")
-    m = f32c(mask.reshape(-1, plan.H, plan.W))
-    active = torch.empty(plan.n_tiles, dtype=torch.int32, device=m.device)
+    plan, B, lst, single = _launch_form(plan)
+    if single and lst is not None:
+        raise _lib.EodError(f"active_tiles: `plan` is a TilePlan, got {type(lst).__name__}")
+    if tuple(mask.shape[-2:]) != (plan.H, plan.W) or (mask.dim() < 2 if single else mask.dim() < 3 or mask.shape[0] != B):
+        want = "the mask must be [" if single else f"the mask of a stack must be [{B}, "
+        raise _lib.EodError(f"active_tiles: {want}..., {plan.H}, {plan.W}], got {tuple(mask.shape)}")
+    m = f32c(mask.reshape(B, -1, plan.H, plan.W))
+    active = torch.empty(B * plan.n_tiles, dtype=torch.int32, device=m.device)
     oy, ox, _, _ = plan.device_tables(m.device)
-    _lib.check(_lib.lib().eod_scene_tile_active(m.data_ptr(), active.data_ptr(), m.shape[0], plan.H, plan.W, plan.tile, oy.data_ptr(),
-                                                ox.data_ptr(), plan.nty, plan.ntx, current_stream_ptr(m.device)), "eod_scene_tile_active")
+    _lib.check(_lib.lib().eod_scene_stack_tile_active(m.data_ptr(), active.data_ptr(), B, m.shape[1], plan.H, plan.W, plan.tile, oy.data_ptr(),
+                                                      ox.data_ptr(), plan.nty, plan.ntx, current_stream_ptr(m.device)), "eod_scene_stack_tile_active")
     return np.flatnonzero(active.cpu().numpy()).astype(np.int32)
 
 
@@ -320,44 +316,25 @@ def tiles_to_evaluate(what, plan, mask, skip_known, needs):
         return plan
     if mask is None:
         raise _lib.EodError(f"{what}: skip_known=True needs a known region ({needs}); there is nothing to skip without one")
-    if isinstance(plan, TileStack):
-        B, nt = plan.n_scenes, plan.plan.n_tiles
-        if B > 1 and mask.shape[0] == 1:
-            one = active_tiles(mask, plan.plan).astype(np.int64)
-            active = (np.arange(B, dtype=np.int64)[:, None] * nt + one[None, :]).reshape(-1).astype(np.int32)
-        else:
-            active = active_tiles(mask, plan)
-        if active.size == 0:
-            return None
-        return plan if active.size == plan.n_tiles and not plan.listed else TileStack(plan.plan, B, active)
-    active = active_tiles(mask, plan)
+    base, B, lst, single = _launch_form(plan)
+    if B > 1 and mask.shape[0] == 1:
+        one = active_tiles(mask, base).astype(np.int64)
+        active = (np.arange(B, dtype=np.int64)[:, None] * base.n_tiles + one[None, :]).reshape(-1).astype(np.int32)
+    else:
+        active = active_tiles(mask, plan)
     if active.size == 0:
         return None
-    return plan if active.size == plan.n_tiles else plan.subset(active)
+    if lst is None and active.size == plan.n_tiles:
+        return plan
+    return base.subset(active) if single else TileStack(base, B, active)
 
 
-def _split(plan):
-    """(plan, subset or None) of an argument that is either; for a TileStack (plan, the stack when it is a listed one, else None)"""
-    if isinstance(plan, TileSubset):
-        return plan.plan, plan
-    if isinstance(plan, TilePlan):
-        return plan, None
-    if isinstance(plan, TileStack):
-        return plan.plan, (plan if plan.listed else None)
-    raise _lib.EodError(f"a TilePlan, a TileSubset or a TileStack is needed, got {type(plan).__name__}")
-
-
-def _scenes_of(plan):
-    """None for a TilePlan / TileSubset (one scene, the single-scene entry points), B for a TileStack"""
-    return plan.n_scenes if isinstance(plan, TileStack) else None
-
-
-def _scene4(scene, what, n_scenes=None):
+def _scene4(scene, what, B, single):
     from .engine import f32c, require_gpu
     require_gpu(scene, what)
-    if n_scenes is not None:
-        if scene.dim() != 4 or scene.shape[0] != n_scenes:
-            raise _lib.EodError(f"{what}: a stack of {n_scenes} scene(s) is [{n_scenes}, C, H, W], got {tuple(scene.shape)}")
+    if not single:
+        if scene.dim() != 4 or scene.shape[0] != B:
+            raise _lib.EodError(f"{what}: a stack of {B} scene(s) is [{B}, C, H, W], got {tuple(scene.shape)}")
         return f32c(scene)
     x = scene if scene.dim() == 4 else scene[None]
     if x.dim() != 4 or x.shape[0] != 1:
@@ -368,102 +345,78 @@ def _scene4(scene, what, n_scenes=None):
 def gather_tiles(scene, plan, out=None):
     """scene [1, C, H, W] (or [C, H, W]) fp32 on the GPU -> tiles [n_tiles, C, tile, tile], tile i = the window at plan.origin(i).
     `out`: a contiguous fp32 buffer of at least n_tiles tiles (its first n_tiles are written, and returned).
-    `plan` may be a TileSubset: its n_tiles listed tiles, in the list's order (eod_scene_gather_list)."""
+    `plan` may be a TileSubset: its n_tiles listed tiles, in the list's order; or a TileStack: scene [B, C, H, W], the tiles of every
+    scene or the listed ones.  One call for all of them: eod_scene_stack_gather, B = 1 for a single scene, a null index for the full form."""
     import torch
     from .engine import current_stream_ptr
-    B = _scenes_of(plan)
-    plan, sub = _split(plan)
-    x = _scene4(scene, "gather_tiles", B)
+    plan, B, lst, single = _launch_form(plan)
+    n = B * plan.n_tiles if lst is None else lst.n_tiles
+    x = _scene4(scene, "gather_tiles", B, single)
     _, c, h, w = x.shape
     if (h, w) != (plan.H, plan.W):
         raise _lib.EodError(f"gather_tiles: scene is {h} x {w}, the plan is for {plan.H} x {plan.W}")
     s = plan.tile
-    n = (B or 1) * plan.n_tiles if sub is None else sub.n_tiles
     if out is None:
         out = torch.empty((n, c, s, s), dtype=torch.float32, device=x.device)
     elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 4 and out.shape[0] >= n
               and tuple(out.shape[1:]) == (c, s, s)):
         raise _lib.EodError(f"gather_tiles: `out` must be a contiguous fp32 GPU tensor [>= {n}, {c}, {s}, {s}], got {tuple(out.shape)}")
     oy, ox, _, _ = plan.device_tables(x.device)
-    if B is not None:  # a TileStack: `scene` is [B, C, H, W]
-        index = None if sub is None else sub.device_tables(x.device)[0]
-        _lib.check(_lib.lib().eod_scene_stack_gather(x.data_ptr(), out.data_ptr(), B, c, h, w, s, oy.data_ptr(), ox.data_ptr(), plan.nty, plan.ntx,
-                                                     _lib.ptr(index), n, current_stream_ptr(x.device)), "eod_scene_stack_gather")
-        return out[:n]
-    if sub is not None:
-        index, _ = sub.device_tables(x.device)
-        _lib.check(_lib.lib().eod_scene_gather_list(x.data_ptr(), out.data_ptr(), c, h, w, s, oy.data_ptr(), ox.data_ptr(), plan.nty,
-                                                    plan.ntx, index.data_ptr(), n, current_stream_ptr(x.device)), "eod_scene_gather_list")
-        return out[:n]
-    _lib.check(_lib.lib().eod_scene_gather(x.data_ptr(), out.data_ptr(), c, h, w, s, oy.data_ptr(), ox.data_ptr(), plan.nty, plan.ntx,
-                                           current_stream_ptr(x.device)), "eod_scene_gather")
-    return out[:plan.n_tiles]
+    index = None if lst is None else lst.device_tables(x.device)[0]
+    _lib.check(_lib.lib().eod_scene_stack_gather(x.data_ptr(), out.data_ptr(), B, c, h, w, s, oy.data_ptr(), ox.data_ptr(), plan.nty, plan.ntx,
+                                                 _lib.ptr(index), n, current_stream_ptr(x.device)), "eod_scene_stack_gather")
+    return out[:n]
 
 
 def blend_tiles(tiles, plan, out=None):
     """tiles [>= n_tiles, C, tile, tile] fp32 on the GPU (the first n_tiles are read) -> scene [1, C, H, W]: the weighted sum of the
     module docstring.  Every scene element is written.
     `plan` may be a TileSubset: tiles holds its n_tiles listed tiles in the list's order; the result is the full blend at the
-    subset's estimated pixels and 0.0 at every other pixel (eod_scene_blend_list)."""
+    subset's estimated pixels and 0.0 at every other pixel.  Or a TileStack: the result is [B, C, H, W], each scene blended from its own
+    tiles.  One call for all of them: eod_scene_stack_blend, B = 1 for a single scene, a null slot_of for the full form."""
     import torch
     from .engine import current_stream_ptr, f32c, require_gpu
     require_gpu(tiles, "blend_tiles")
-    B = _scenes_of(plan)
-    plan, sub = _split(plan)
+    plan, B, lst, single = _launch_form(plan)
+    n = B * plan.n_tiles if lst is None else lst.n_tiles
     s = plan.tile
-    n = (B or 1) * plan.n_tiles if sub is None else sub.n_tiles
     if tiles.dim() != 4 or tiles.shape[0] < n or tuple(tiles.shape[2:]) != (s, s):
         raise _lib.EodError(f"blend_tiles: tiles must be [>= {n}, C, {s}, {s}], got {tuple(tiles.shape)}")
     e = f32c(tiles)
     c = e.shape[1]
     if out is None:
-        out = torch.empty((B or 1, c, plan.H, plan.W), dtype=torch.float32, device=e.device)
-    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == (B or 1) * c * plan.H * plan.W):
-        raise _lib.EodError(f"blend_tiles: `out` must be a contiguous fp32 GPU tensor of {'' if B is None else f'{B} x '}{c} x {plan.H} x {plan.W} elements")
+        out = torch.empty((B, c, plan.H, plan.W), dtype=torch.float32, device=e.device)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == B * c * plan.H * plan.W):
+        raise _lib.EodError(f"blend_tiles: `out` must be a contiguous fp32 GPU tensor of {'' if single else f'{B} x '}{c} x {plan.H} x {plan.W} elements")
     oy, ox, wy, wx = plan.device_tables(e.device)
-    if B is not None:  # a TileStack: the result is [B, C, H, W]
-        slot_of = None if sub is None else sub.device_tables(e.device)[1]
-        _lib.check(_lib.lib().eod_scene_stack_blend(e.data_ptr(), out.data_ptr(), wy.data_ptr(), wx.data_ptr(), oy.data_ptr(), ox.data_ptr(),
-                                                    _lib.ptr(slot_of), n, B, c, plan.H, plan.W, s, plan.nty, plan.ntx,
-                                                    current_stream_ptr(e.device)), "eod_scene_stack_blend")
-        return out
-    if sub is not None:
-        _, slot_of = sub.device_tables(e.device)
-        _lib.check(_lib.lib().eod_scene_blend_list(e.data_ptr(), out.data_ptr(), wy.data_ptr(), wx.data_ptr(), oy.data_ptr(), ox.data_ptr(),
-                                                   slot_of.data_ptr(), n, c, plan.H, plan.W, s, plan.nty, plan.ntx,
-                                                   current_stream_ptr(e.device)), "eod_scene_blend_list")
-        return out
-    _lib.check(_lib.lib().eod_scene_blend(e.data_ptr(), out.data_ptr(), wy.data_ptr(), wx.data_ptr(), oy.data_ptr(), ox.data_ptr(), c,
-                                          plan.H, plan.W, s, plan.nty, plan.ntx, current_stream_ptr(e.device)), "eod_scene_blend")
+    slot_of = None if lst is None else lst.device_tables(e.device)[1]
+    _lib.check(_lib.lib().eod_scene_stack_blend(e.data_ptr(), out.data_ptr(), wy.data_ptr(), wx.data_ptr(), oy.data_ptr(), ox.data_ptr(),
+                                                _lib.ptr(slot_of), n, B, c, plan.H, plan.W, s, plan.nty, plan.ntx,
+                                                current_stream_ptr(e.device)), "eod_scene_stack_blend")
     return out
 
 
 def keep_known(x, known, subset, out=None):
     """x, known [1, C, H, W] (or [C, H, W]) fp32 on the GPU -> [1, C, H, W]: x at the subset's estimated pixels, `known` at every
-    other pixel (the end of a skip_known call: what was never estimated is the known image itself)."""
+    other pixel (the end of a skip_known call: what was never estimated is the known image itself).  With a listed TileStack both are
+    [B, C, H, W] and every scene keeps its own.  One call: eod_scene_stack_keep_known, B = 1 for a TileSubset."""
     import torch
     from .engine import current_stream_ptr
-    B = _scenes_of(subset)
-    if not (isinstance(subset, TileSubset) or (B is not None and subset.listed)):
+    plan, B, lst, single = _launch_form(subset)
+    if lst is None:
         raise _lib.EodError(f"keep_known: a TileSubset (or a TileStack with a tile list) is needed, got {type(subset).__name__}")
-    plan = subset.plan
-    a, b = _scene4(x, "keep_known", B), _scene4(known, "keep_known", B)
+    a, b = _scene4(x, "keep_known", B, single), _scene4(known, "keep_known", B, single)
     if a.shape != b.shape or tuple(a.shape[2:]) != (plan.H, plan.W) or a.device != b.device:
-        raise _lib.EodError(f"keep_known: x {tuple(a.shape)} and known {tuple(b.shape)} must both be [{B or 1}, C, {plan.H}, {plan.W}] on one GPU")
+        raise _lib.EodError(f"keep_known: x {tuple(a.shape)} and known {tuple(b.shape)} must both be [{B}, C, {plan.H}, {plan.W}] on one GPU")
     if out is None:
         out = torch.empty_like(a)
     elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == a.numel()):
         raise _lib.EodError(f"keep_known: `out` must be a contiguous fp32 GPU tensor of {a.numel()} elements")
     oy, ox, _, _ = plan.device_tables(a.device)
-    _, slot_of = subset.device_tables(a.device)
-    if B is not None:
-        _lib.check(_lib.lib().eod_scene_stack_keep_known(a.data_ptr(), b.data_ptr(), slot_of.data_ptr(), subset.n_tiles, oy.data_ptr(),
-                                                         ox.data_ptr(), B, a.shape[1], plan.H, plan.W, plan.tile, plan.nty, plan.ntx,
-                                                         out.data_ptr(), current_stream_ptr(a.device)), "eod_scene_stack_keep_known")
-        return out
-    _lib.check(_lib.lib().eod_scene_keep_known(a.data_ptr(), b.data_ptr(), slot_of.data_ptr(), subset.n_tiles, oy.data_ptr(), ox.data_ptr(),
-                                               a.shape[1], plan.H, plan.W, plan.tile, plan.nty, plan.ntx, out.data_ptr(),
-                                               current_stream_ptr(a.device)), "eod_scene_keep_known")
+    _, slot_of = lst.device_tables(a.device)
+    _lib.check(_lib.lib().eod_scene_stack_keep_known(a.data_ptr(), b.data_ptr(), slot_of.data_ptr(), lst.n_tiles, oy.data_ptr(), ox.data_ptr(),
+                                                     B, a.shape[1], plan.H, plan.W, plan.tile, plan.nty, plan.ntx, out.data_ptr(),
+                                                     current_stream_ptr(a.device)), "eod_scene_stack_keep_known")
     return out
 
 
@@ -481,7 +434,8 @@ def tile_slots(plan, tile_batch):
 def gather_padded(scene, plan, tile_batch):
     """gather_tiles into a buffer of tile_slots(...) tiles; the padding slots repeat the last (listed) tile"""
     import torch
-    x = _scene4(scene, "gather_padded", _scenes_of(plan))
+    _, B, _, single = _launch_form(plan)
+    x = _scene4(scene, "gather_padded", B, single)
     chunk, slots = tile_slots(plan, tile_batch)
     buf = torch.empty((slots, x.shape[1], plan.tile, plan.tile), dtype=torch.float32, device=x.device)
     gather_tiles(x, plan, out=buf)

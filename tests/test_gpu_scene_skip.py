@@ -607,3 +607,45 @@ def test_tables_are_not_trusted_with_an_address():
     src = torch.ones(1, 3, 32, 48, device=DEV)
     assert L.eod_scene_gather_list(p(src), p(t), 3, 32, 48, 16, p(oy), p(ox), plan.nty, plan.ntx, p(bad), 2, 0) == 0
     assert bool((t[0] == 1).all()) and bool(torch.isnan(t[1]).all())
+
+
+@pytest.mark.parametrize("H,W,tile,overlap", [(40, 57, 16, 4), (32, 48, 16, 0)])
+def test_the_single_scene_c_entry_points_have_the_bits_of_the_python_layer(H, W, tile, overlap):
+    """The Python layer calls only the eod_scene_stack_* entry points; the six single-scene ones remain for C callers
+    (INTEGRATION.md).  Each of them, called directly, against the Python layer on the same inputs, bit for bit.  (40, 57): 3 x 5 tiles,
+    an odd width and both last tiles shifted inwards, so the scalar path; (32, 48), overlap 0: 2 x 3 tiles on the 16-byte path.  The
+    subset is tiles 1, 4, 7 as far as the plan has them (six tiles: 1, 4)."""
+    from eo_diffusion_amd.engine import current_stream_ptr
+    plan, C = TilePlan(H, W, tile, overlap), 3
+    assert (plan.nty, plan.ntx) == ((3, 5) if W == 57 else (2, 3))
+    sub = plan.subset([i for i in (1, 4, 7) if i < plan.n_tiles])
+    nt, n = plan.n_tiles, sub.n_tiles
+    L, st, p = _lib.lib(), current_stream_ptr(torch.device(DEV)), lambda x: x.data_ptr()
+    oy, ox, wy, wx = plan.device_tables(DEV)
+    index, slot_of = sub.device_tables(DEV)
+    scene = synth_input("cw_scene", (1, C, H, W), 3).to(DEV)
+    known = synth_input("cw_known", (1, C, H, W), 4).to(DEV)
+    tiles = synth_input("cw_tiles", (nt, C, tile, tile), 5).to(DEV)
+    mask = torch.ones(1, H, W, device=DEV)
+    mask[0, 20:23, 18:21] = 0.0                                       # one hole, in some tiles and not in others
+    want = active_tiles(mask, plan)
+    assert 0 < want.size < nt
+
+    got = _nan(nt, C, tile, tile)
+    assert L.eod_scene_gather(p(scene), p(got), C, H, W, tile, p(oy), p(ox), plan.nty, plan.ntx, st) == 0
+    assert torch.equal(got, gather_tiles(scene, plan))
+    got = _nan(n, C, tile, tile)
+    assert L.eod_scene_gather_list(p(scene), p(got), C, H, W, tile, p(oy), p(ox), plan.nty, plan.ntx, p(index), n, st) == 0
+    assert torch.equal(got, gather_tiles(scene, sub))
+    got = _nan(1, C, H, W)
+    assert L.eod_scene_blend(p(tiles), p(got), p(wy), p(wx), p(oy), p(ox), C, H, W, tile, plan.nty, plan.ntx, st) == 0
+    assert torch.equal(got, blend_tiles(tiles, plan))
+    got = _nan(1, C, H, W)
+    assert L.eod_scene_blend_list(p(tiles), p(got), p(wy), p(wx), p(oy), p(ox), p(slot_of), n, C, H, W, tile, plan.nty, plan.ntx, st) == 0
+    assert torch.equal(got, blend_tiles(tiles[:n], sub))
+    act = torch.full((nt,), -7, dtype=torch.int32, device=DEV)
+    assert L.eod_scene_tile_active(p(mask), p(act), 1, H, W, tile, p(oy), p(ox), plan.nty, plan.ntx, st) == 0
+    assert np.array_equal(np.flatnonzero(act.cpu().numpy()), want) and set(act.tolist()) == {0, 1}
+    got = _nan(1, C, H, W)
+    assert L.eod_scene_keep_known(p(scene), p(known), p(slot_of), n, p(oy), p(ox), C, H, W, tile, plan.nty, plan.ntx, p(got), st) == 0
+    assert torch.equal(got, keep_known(scene, known, sub))

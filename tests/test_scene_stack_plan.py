@@ -198,3 +198,60 @@ def test_scene_arguments_are_checked_on_the_host_for_every_rank():
     for kw in (dict(cond=ok[:2]), dict(cond=ok, y=torch.tensor([1, 2])), dict(cond=ok, tile_batch=0), dict(skip_known=True)):
         with pytest.raises(EodError):
             sharded_sampling_scene(m, size, 3, device="cuda:0", **kw)
+
+
+def test_sampling_scene_itself_refuses_before_it_touches_a_device():
+    """Every bad-argument case that this file, test_ancestral_host.py and test_threshold_host.py put to check_scene_args, put to
+    sampling_scene itself, as one scene and as a stack of three where the case leaves that open.  The model's buffers are on the host and
+    there may be no GPU at all: the first thing the device half of the call does is refuse the buffers' device ("call .to(device)
+    first"), so a refusal with any OTHER text was made from the arguments alone, before anything was copied or launched."""
+    import torch
+    from eo_diffusion_amd.diffusion.consistency import Observation, PsfObservation, SpectralObservation, gaussian_psf
+    from eo_diffusion_amd.diffusion.model import EODiffusion
+    from eo_diffusion_amd.diffusion.threshold import DynamicThreshold
+
+    class Never(torch.nn.Module):
+        def forward(self, x, t, cond=None, y=None):
+            raise AssertionError("the network was reached")
+
+    def refused(m, size, device="cuda:0", **kw):
+        with pytest.raises(EodError) as e:
+            m.sampling_scene(size, device=device, progress=False, **kw)
+        assert "call .to(device) first" not in str(e.value), (kw, str(e.value))
+
+    T, H, W = 20, 32, 48
+    m4, m20 = (EODiffusion(Never(), timesteps=t, image_size=16, in_channels=3, cond_type="sum", device="cpu") for t in (4, T))
+    v = lambda *shape: torch.zeros(*shape)
+    ok = Observation(v(1, 3, H, W), (1, 2, 4))
+    psf = lambda *shape, **kw: PsfObservation(v(*shape), gaussian_psf(4), 4, **kw)
+    spec = lambda *shape, **kw: SpectralObservation(v(*shape), [[.2, .5, .3]], **kw)
+    for B in (1, 3):
+        cond = torch.ones(B, 4, H, W)
+        with pytest.raises(EodError, match="call .to\\(device\\) first"):                                   # good arguments get as far as the device half
+            m4.sampling_scene((H, W), device="cuda:0", progress=False, n_scenes=B, cond=cond, y=torch.arange(B), overlap=4, skip_known=True,
+                              resample=(2, 2))
+        # tests/test_scene_stack_plan.py
+        for kw in (dict(cond=torch.ones(2, 4, H, W)), dict(cond=cond, y=torch.tensor([1, 2])), dict(cond=cond, tile_batch=0), dict(cond=cond, overlap=9),
+                   dict(skip_known=True), dict(cond=cond[:, :3]), dict(cond=cond, resample=(2,)), dict(cond=cond, x_T=torch.zeros(2, 3, H, W)),
+                   dict(cond=cond, rng="numpy")):
+            refused(m4, (H, W), n_scenes=B, **kw)
+        refused(m4, (H, W), device="cpu", n_scenes=B, cond=cond)
+        refused(m4, (8, W), n_scenes=B, cond=cond)
+        # tests/test_ancestral_host.py (the cases that name n_scenes themselves follow below)
+        for kw in (dict(observation=ok, skip_known=True), dict(observation=[ok], skip_known=True),
+                   dict(observation=Observation(v(1, 4, H, W), (1, 2, 4, 1))), dict(observation=SpectralObservation(v(1, 1, H, W), [[.5, .5]])),
+                   dict(observation=psf(1, 4, H // 4, W // 4)), dict(observation=psf(1, 2, H // 4, W // 4, channels=[1, 3])),
+                   dict(observation=Observation(v(2, 3, H, W), (1, 2, 4))), dict(observation=Observation(v(1, 3, H, W), (1, 2, 4), mask=v(2, 1, H, W))),
+                   dict(observation=psf(2, 3, H // 4, W // 4)), dict(observation=Observation(v(1, 3, 16, 16), (1, 2, 4))), dict(observation=psf(1, 3, H, W)),
+                   dict(observation=Observation(v(1, 3, H, W), (1, 2, 4), weight=[0.5] * (T + 1))),
+                   dict(observation=Observation(v(1, 3, H, W), (1, 2, 4), weight=[0.5] * T), resample=(4, 3)),
+                   dict(observation=[ok, spec(1, 1, H, W, weight=[0.5] * 51)], resample=(4, 3)),
+                   dict(observation=[ok] * 5), dict(observation=[ok, None]), dict(observation="obs"), dict(observation=[])):
+            refused(m20, (H, W), "cuda", n_scenes=B, cond=v(1, 4, H, W), **kw)
+        # tests/test_threshold_host.py
+        for kw in (dict(skip_known=True, threshold=DynamicThreshold(0.9)), dict(threshold=0.9)):
+            refused(m4, (24, 24), n_scenes=B, cond=torch.zeros(1, 4, 24, 24), overlap=8, **kw)
+    for n in (0, True, 1.5):
+        refused(m4, (H, W), n_scenes=n)
+    for o in (Observation(v(3, 3, H, W), (1, 2, 4)), spec(3, 1, H, W)):
+        refused(m20, (H, W), "cuda", n_scenes=2, cond=v(1, 4, H, W), observation=o)

@@ -179,6 +179,9 @@ SYMBOLS = {
     "eod_band_stats": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, f64, f64, vp, vp, vp, i64, vp]),
     "eod_ssim_workspace_size": (i64, [i32, i32, i32, i32, i32]),
     "eod_ssim": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, C.POINTER(f64), i32, f64, f64, f64, f64, vp, vp, vp, i64, vp]),
+    "eod_scene_quantiles": (i32, [vp, vp, i32, i64, C.POINTER(i32), C.POINTER(f32), i32, vp]),
+    "eod_ensemble_stats_workspace_size": (i64, [i32, i32, i32, i32]),
+    "eod_ensemble_stats": (i32, [vp, vp, vp, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(f32), i32, vp, vp, vp, vp, i64, vp]),
     "eod_ldm_p_sample": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, i32, i32, vp]),
     "eod_repaint_cond": (i32, [vp, vp, vp, i32, i32, i64, i32, vp]),
     "eod_postprocess": (i32, [vp, vp, i64, i32, vp]),
@@ -212,7 +215,7 @@ class EodError(RuntimeError):
     pass
 
 
-ABI_VERSION = 117  # EOD_ABI_VERSION of the include/eodiff.h this file mirrors
+ABI_VERSION = 118  # EOD_ABI_VERSION of the include/eodiff.h this file mirrors
 SPEC_GRID_BLOCKS = 4096  # EOD_SPEC_GRID_BLOCKS there
 
 

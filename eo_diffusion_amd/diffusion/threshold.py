@@ -16,7 +16,7 @@ import numbers
 import torch
 
 from .. import _lib
-from ..engine import current_stream_ptr, f32c, require_gpu
+from ..engine import current_stream_ptr, f32c, quantile_rank, require_gpu
 from . import consistency
 
 MAX_N = 2 ** 31 - 1     # elements of one sample (eod_dyn_threshold)
@@ -48,13 +48,7 @@ class DynamicThreshold:
     def rank(self, n):
         """(k, frac) of eod_dyn_threshold for samples of n elements: pos = q * (n - 1) in float64, k = floor(pos), frac = fp32(pos - k)
         (returned as the Python float that holds the fp32 value); frac < 1 after the rounding, too"""
-        n = int(n)
-        pos = self.quantile * (n - 1)
-        k = min(int(math.floor(pos)), n - 1)
-        frac = float(torch.tensor(pos - k, dtype=torch.float64).to(torch.float32)) if pos > k else 0.0
-        if frac >= 1.0:   # (pos - k rounds up to 1 in fp32 only where k + 1 is the better description)
-            k, frac = k + 1, 0.0
-        return k, frac
+        return quantile_rank(self.quantile, n)
 
     def samples(self, shape):
         """(number of samples, elements of one) of a state [B, C, H, W]"""

@@ -41,6 +41,19 @@ def f32c(t):
     return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
 
 
+def quantile_rank(q, n):
+    """(k, frac) of the q-quantile of n sorted values x_(0) <= .. <= x_(n-1), the rule of eod_dyn_threshold and eod_scene_quantiles:
+    pos = q * (n - 1) in float64, k = floor(pos), frac = fp32(pos - k), returned as the Python float that holds the fp32 value; where
+    pos - k rounds up to 1 in fp32, k + 1 is the better description: (k + 1, 0).  The quantile is x_(k) + frac * (x_(k+1) - x_(k))."""
+    n = int(n)
+    pos = float(q) * (n - 1)
+    k = min(int(math.floor(pos)), n - 1)
+    frac = float(torch.tensor(pos - k, dtype=torch.float64).to(torch.float32)) if pos > k else 0.0
+    if frac >= 1.0:
+        k, frac = k + 1, 0.0
+    return k, frac
+
+
 class Act:
     """Channels-last activation handle: tensor of shape [N, H, W, C] in the storage dtype."""
     __slots__ = ("t", "N", "H", "W", "C", "stats", "bound", "presplit", "csum")

@@ -231,3 +231,117 @@ def psnr(pred, ref, data_range=1.0, *, where=None, affine=(1.0, 0.0)):
         return float("nan")
     mse = sdd / n
     return float("inf") if mse == 0.0 else float(10.0 * np.log10(data_range * data_range / mse))
+
+
+# ---------------------------------------------------------------------------------------------------------------- the ensemble as a whole
+MAX_MEMBERS = 64    # members of a stack (csrc/ensemble_body.h: ENS_MAXB)
+MAX_LEVELS = 4      # central intervals of one eod_ensemble_stats call
+ENS_NV = 5          # float64 sums per band of eod_ensemble_stats
+
+
+class Ensemble:
+    """What ensemble() returns: numpy arrays (float64), per band [C] unless noted; see the table in DESIGN.md section 9.14.  rank_hist is
+    [C, B + 1] (counts), coverage [C, L] (fractions), levels [L]."""
+    FIELDS = ("n", "crps", "crps_fair", "mae_members", "rmse_mean", "bias_mean", "spread", "spread_skill", "rank_hist", "reliability_index",
+              "ties", "coverage", "levels")
+
+    def __init__(self, **kw):
+        for f in self.FIELDS:
+            setattr(self, f, kw[f])
+
+    def __repr__(self):
+        return "Ensemble(" + ", ".join(f"{f}={getattr(self, f)!r}" for f in self.FIELDS) + ")"
+
+
+def _levels(what, levels, members):
+    """the central intervals as ranks: level p -> the quantiles (1 - p) / 2 and (1 + p) / 2 by tiling.quantile_ranks"""
+    from .tiling import quantile_ranks
+    try:
+        lv = list(levels)
+    except TypeError:
+        raise EodError(f"{what}: levels is a sequence of numbers in [0, 1], got {levels!r}") from None
+    if len(lv) > MAX_LEVELS:
+        raise EodError(f"{what}: at most {MAX_LEVELS} levels per call, got {len(lv)}")
+    for p in lv:
+        if isinstance(p, bool) or not isinstance(p, numbers.Real) or not 0.0 <= float(p) <= 1.0:
+            raise EodError(f"{what}: every level is a number in [0, 1], got {p!r}")
+    lv = [float(p) for p in lv]
+    lo = quantile_ranks(what, [(1.0 - p) / 2.0 for p in lv], members)
+    hi = quantile_ranks(what, [(1.0 + p) / 2.0 for p in lv], members)
+    return lv, lo, hi
+
+
+def _derive_ensemble(sums, counts, B, levels):
+    """the float64 host arithmetic of ensemble(): sums [C, 5], counts [C, 2 + (B + 1) + L] (numpy)"""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        cnt = counts.astype(np.float64)
+        n = cnt[:, 0]
+        hist = cnt[:, 2:2 + B + 1]
+        a, g, se, s2, e = (sums[:, i] / n for i in range(ENS_NV))
+        rmse, spread = np.sqrt(se), np.sqrt(s2)
+        fair = a - g * (B / (B - 1.0)) if B > 1 else np.full_like(a, np.nan)
+        return Ensemble(n=n.copy(), crps=a - g, crps_fair=fair, mae_members=a, rmse_mean=rmse, bias_mean=e, spread=spread,
+                        spread_skill=math.sqrt((B + 1.0) / B) * spread / rmse, rank_hist=hist.copy(),
+                        reliability_index=np.abs(hist / n[:, None] - 1.0 / (B + 1)).sum(1), ties=cnt[:, 1].copy(),
+                        coverage=cnt[:, 2 + B + 1:] / n[:, None], levels=np.asarray(levels, dtype=np.float64))
+
+
+def ensemble(draws, ref, *, where=None, levels=(0.5, 0.9), return_map=False):
+    """The verification of an ensemble against a truth: draws [B, C, H, W] (B <= 64 draws of one scene), ref [1, C, H, W], where None or
+    [1, 1, H, W] (a pixel counts iff its value is not 0: hole_of(mask) for an inpainting) -> an Ensemble of numpy arrays per band, after one
+    call of eod_ensemble_stats and ONE device-to-host copy; with return_map=True: (Ensemble, CRPS map [1, C, H, W] fp32 on the device, NaN
+    where the pixel is not counted).  quality() scores members one at a time; whether their SPREAD is calibrated needs the sorted members
+    of every pixel:
+
+        crps               mean over the pixels of  E|X - y| - 1/2 E|X - X'|  over the B members (both expectations with divisor B resp. B^2)
+        crps_fair          the same with E|X - X'| over the B (B - 1) pairs of different members (Ferro 2014); NaN at B = 1
+        mae_members        mean of E|X - y|: the first term alone, so crps <= mae_members
+        rmse_mean, bias_mean   of the ensemble mean
+        spread             sqrt(mean of the per-pixel sample variance, divisor B - 1)
+        spread_skill       sqrt((B + 1) / B) * spread / rmse_mean: 1 for a calibrated ensemble
+        rank_hist          [C, B + 1]: how many pixels have exactly r members below the truth (Talagrand); flat when calibrated
+        reliability_index  sum over r of |rank_hist_r / n - 1 / (B + 1)|
+        ties               pixels at which some member equals the truth
+        coverage           [C, L]: the fraction of pixels with q_((1-p)/2) <= y <= q_((1+p)/2), the quantiles of scene_quantiles, per level p
+
+    Ties: the rank counts STRICT inequalities (members below the truth, in the total order -0.0 < +0.0 < .. < NaN) and ties are reported,
+    not randomised.  The known pixels of an inpainting are all ties -- every draw equals the truth there -- and pile up in rank 0: exclude
+    them with where=hole_of(mask).  There is no `affine`: every float measure is positively homogeneous (crps(a x + b, a y + b) = a crps(x, y)
+    for a > 0; bias likewise) and the counts do not change, so rescale the result.  A region without a counted pixel gives NaN, not an
+    error."""
+    what = "ensemble"
+    B, C, H, W = _shapes(what, draws, ref, where)
+    if B > MAX_MEMBERS:
+        raise EodError(f"{what}: at most {MAX_MEMBERS} members are sorted per pixel, draws has {B}")
+    if int(ref.shape[0]) != 1 or (where is not None and int(where.shape[0]) != 1):
+        raise EodError(f"{what}: one truth [1, {C}, {H}, {W}] and one where [1, 1, {H}, {W}] for the whole ensemble, got {tuple(ref.shape)}"
+                       + ("" if where is None else f" and {tuple(where.shape)}"))
+    lv, lo, hi = _levels(what, levels, B)
+    p, t, w = _gpu(what, draws, ref, where)
+    L, nl = _lib.lib(), len(lv)
+    nc = 2 + B + 1 + nl
+    ws = torch.empty(int(L.eod_ensemble_stats_workspace_size(B, C, H, W)), dtype=torch.uint8, device=p.device)
+    out = torch.empty(C * (ENS_NV + nc), dtype=torch.float64, device=p.device)      # the sums, then the counts (int64 in the same buffer)
+    sums, counts = out[:C * ENS_NV], out[C * ENS_NV:].view(torch.int64)
+    cmap = torch.empty((1, C, H, W), dtype=torch.float32, device=p.device) if return_map else None
+    lk = (ctypes.c_int32 * max(2 * nl, 1))(*[k for pair in zip(lo, hi) for k, _ in pair])
+    lf = (ctypes.c_float * max(2 * nl, 1))(*[f for pair in zip(lo, hi) for _, f in pair])
+    _lib.check(L.eod_ensemble_stats(p.data_ptr(), t.data_ptr(), _lib.ptr(w), B, C, H, W, lk, lf, nl, sums.data_ptr(), counts.data_ptr(),
+                                    _lib.ptr(cmap), ws.data_ptr(), ws.numel(), current_stream_ptr(p.device)), "eod_ensemble_stats")
+    host = out.cpu().numpy()      # the one device-to-host copy (and the synchronisation)
+    e = _derive_ensemble(host[:C * ENS_NV].reshape(C, ENS_NV), host[C * ENS_NV:].view(np.int64).reshape(C, nc), B, lv)
+    return (e, cmap) if return_map else e
+
+
+def describe_ensemble(e, title="ensemble"):
+    """an Ensemble as a few lines of text (what examples/inpaint_scene.py prints under --metrics with --draws K)"""
+    row = lambda a, fmt: ", ".join(format(float(v), fmt) for v in a)
+    B = e.rank_hist.shape[1] - 1
+    lines = [f"{title}: {B} members, {int(e.n[0]) if len(e.n) else 0} pixels per band",
+             f"  per band: CRPS {row(e.crps, '.4f')} (fair {row(e.crps_fair, '.4f')}; members' MAE {row(e.mae_members, '.4f')})",
+             f"            RMSE of the mean {row(e.rmse_mean, '.4f')}, bias {row(e.bias_mean, '+.4f')}",
+             f"            spread {row(e.spread, '.4f')}, spread / skill {row(e.spread_skill, '.3f')}",
+             f"            rank histogram off flat by {row(e.reliability_index, '.3f')}, ties {row(e.ties, '.0f')}"]
+    for i, p in enumerate(e.levels):
+        lines.append(f"            {100 * p:.0f} % interval covers {row(100 * e.coverage[:, i], '.1f')} %")
+    return "\n".join(lines)

@@ -11,6 +11,7 @@
     stack = TileStack(plan, B)                   B scenes of one plan ([B, C, H, W]): goes wherever a plan goes above; tiles of every scene
     part  = TileStack(plan, B, indices)          ... or the listed tiles only (global numbers b * n_tiles + i), like a TileSubset
     mean, std = scene_stats(scenes)              [B, C, H, W] -> per-pixel mean and sample standard deviation, each [1, C, H, W]   eod_scene_stats
+    qs = scene_quantiles(scenes, (0.05, 0.5, 0.95))   [B, C, H, W] -> per-pixel quantiles over the B members, [Q, C, H, W]        eod_scene_quantiles
 
 One path: a scene is a stack of one.  Whatever kind of plan an operation is given, it makes ONE library call, the eod_scene_stack_* entry
 point, with B = 1 for a TilePlan / TileSubset and a null index / slot_of for the full form (_launch_form).  The library's single-scene
@@ -481,3 +482,64 @@ def scene_stats(stack, out=None):
     _lib.check(_lib.lib().eod_scene_stats(x.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), b, c * h * w, current_stream_ptr(x.device)),
                "eod_scene_stats")
     return out[0:1], out[1:2]
+
+
+MAX_MEMBERS = 64    # members of a stack eod_scene_quantiles / eod_ensemble_stats sort (csrc/ensemble_body.h: ENS_MAXB)
+MAX_QUANTILES = 8   # quantiles of one eod_scene_quantiles call
+
+
+def quantile_ranks(what, q, members):
+    """The ranks (k, frac) of the quantiles `q` (a number or a sequence of numbers in [0, 1]) over `members` sorted values, by
+    engine.quantile_rank; every refusal of `q` as an EodError"""
+    import numbers
+    from .engine import quantile_rank
+    qs = [q] if isinstance(q, numbers.Real) else q
+    try:
+        qs = list(qs)
+    except TypeError:
+        raise _lib.EodError(f"{what}: q is a number or a sequence of numbers in [0, 1], got {q!r}") from None
+    for v in qs:
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or not 0.0 <= float(v) <= 1.0:   # (NaN fails the comparison)
+            raise _lib.EodError(f"{what}: every quantile is a number in [0, 1], got {v!r}")
+    return [quantile_rank(float(v), members) for v in qs]
+
+
+def scene_quantiles(stack, q=(0.05, 0.5, 0.95), out=None):
+    """stack [B, C, H, W] fp32 on the GPU (B <= 64 draws of one scene) -> [Q, C, H, W]: per pixel, the quantiles `q` over the B members
+    (eod_scene_quantiles: the members are sorted in registers while the stack streams through once; no temporaries).  The quantile is the
+    linear one of numpy / torch.quantile: pos = q * (B - 1) in float64, k = floor(pos), frac = fp32(pos - k) (engine.quantile_rank, the
+    rule of DynamicThreshold.rank), the value x_(k) itself at frac = 0 and x_(k) + frac * (x_(k+1) - x_(k)) otherwise, every operation
+    rounded separately in fp32.  The order is total: -inf < .. < -0.0 < +0.0 < .. < +inf < NaN, so a NaN member sorts last and an order
+    statistic that is a NaN gives a NaN.  Painted pixels of an inpainting are clipped and, at a cloud edge, bimodal: the median and a
+    5 % / 95 % band describe them where mean +- std does not.  `out`: a contiguous fp32 GPU buffer [Q, C, H, W] that must not overlap
+    the stack."""
+    import ctypes
+    import torch
+    from .engine import current_stream_ptr, f32c, require_gpu
+    what = "scene_quantiles"
+    if not torch.is_tensor(stack) or stack.dim() != 4 or stack.numel() == 0:
+        raise _lib.EodError(f"{what}: a stack is a non-empty tensor [B, C, H, W], got {tuple(getattr(stack, 'shape', ()))}")
+    b, c, h, w = (int(v) for v in stack.shape)
+    if b > MAX_MEMBERS:
+        raise _lib.EodError(f"{what}: at most {MAX_MEMBERS} members are sorted per pixel, the stack has {b}")
+    ranks = quantile_ranks(what, q, b)
+    if not 1 <= len(ranks) <= MAX_QUANTILES:
+        raise _lib.EodError(f"{what}: 1 .. {MAX_QUANTILES} quantiles per call, got {len(ranks)}")
+    nq = len(ranks)
+    if out is not None and not (torch.is_tensor(out) and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (nq, c, h, w)
+                                and out.device == stack.device):
+        raise _lib.EodError(f"{what}: `out` must be a contiguous fp32 tensor [{nq}, {c}, {h}, {w}] on the stack's device, got "
+                            f"{tuple(getattr(out, 'shape', ()))}")
+    require_gpu(stack, what)
+    x = f32c(stack)
+    if out is None:
+        out = torch.empty((nq, c, h, w), dtype=torch.float32, device=x.device)
+    else:
+        lo, hi = out.data_ptr(), out.data_ptr() + out.numel() * 4
+        if lo < x.data_ptr() + x.numel() * 4 and x.data_ptr() < hi:
+            raise _lib.EodError(f"{what}: `out` overlaps the stack")
+    ks = (ctypes.c_int32 * nq)(*[k for k, _ in ranks])
+    fr = (ctypes.c_float * nq)(*[f for _, f in ranks])
+    _lib.check(_lib.lib().eod_scene_quantiles(x.data_ptr(), out.data_ptr(), b, c * h * w, ks, fr, nq, current_stream_ptr(x.device)),
+               "eod_scene_quantiles")
+    return out

@@ -13,6 +13,7 @@ checkpoint of the reference's format ({"model": state_dict}): the example shows 
     python examples/inpaint_scene.py --timesteps 50 --resample 5 3
     python examples/inpaint_scene.py --timesteps 50 --resample 5 3 --skip-known
     python examples/inpaint_scene.py --timesteps 50 --skip-known --draws 8
+    python examples/inpaint_scene.py --timesteps 50 --skip-known --draws 8 --quantiles 0.05 0.5 0.95 --metrics
     python examples/inpaint_scene.py --timesteps 1000 --solver dpmpp --steps 25 --skip-known
     python examples/inpaint_scene.py --timesteps 1000 --solver dpmpp --steps 25 --threshold 0.995
 
@@ -23,6 +24,11 @@ over `--steps` levels of a log-SNR grid, at most `--steps` evaluations whatever 
 `--draws K` runs K draws of the one scene in ONE call (`n_scenes=K` with the known scene given once: draw b is Philox sample b of
 `--seed`, the tiles of all draws share the UNet's batches) and writes, next to the first draw, `*_mean.npy` and `*_std.npy`: the per-pixel
 mean of the draws and how far they disagree (`tiling.scene_stats`, the sample standard deviation; zero wherever the scene is known).
+
+`--quantiles Q [Q ...]` (with `--draws K`, K >= 2) also writes the per-pixel quantiles of the draws, `*_q05.npy`, `*_q50.npy`, `*_q95.npy`
+(`tiling.scene_quantiles`): painted pixels are clipped and, at a cloud edge, bimodal, so the median and a band say what mean and std cannot.
+With `--metrics` the K draws are also scored as an ensemble on the painted region (`metrics.ensemble`: CRPS, rank histogram, coverage of the
+central intervals, spread against skill).
 
 `--threshold Q` replaces the static clamp of every evaluation's data prediction by dynamic thresholding (`threshold=DynamicThreshold(Q)`,
 DESIGN.md section 9.12): the prediction is clamped to the scene's own Q-quantile of its magnitude and rescaled, one quantile over the whole
@@ -73,6 +79,8 @@ def main():
                     help="RePaint resampling: jump length and number of descents per jump (default: one descent, no jumps)")
     ap.add_argument("--skip-known", action="store_true", help="run the UNet only on the tiles whose window holds a masked pixel")
     ap.add_argument("--draws", type=int, default=1, help="K draws of the scene in one call; also writes *_mean.npy and *_std.npy")
+    ap.add_argument("--quantiles", type=float, nargs="+", default=None, metavar="Q",
+                    help="with --draws K >= 2: also write the per-pixel quantiles of the draws (*_q05.npy for 0.05 and so on)")
     ap.add_argument("--solver", default="ddpm", choices=["ddpm", "dpmpp"], help="ddpm: one evaluation per timestep; dpmpp: DPM-Solver++ (2M)")
     ap.add_argument("--steps", type=int, default=25, help="--solver dpmpp: the number of levels (at most that many UNet evaluations)")
     ap.add_argument("--threshold", type=float, default=None, metavar="Q",
@@ -82,6 +90,8 @@ def main():
     ap.add_argument("--out", default="inpainted_scene.npy")
     ap.add_argument("--metrics", action="store_true", help="score the painted region (metrics.hole_of) of every draw, and of their mean, against the synthetic scene (eo_diffusion_amd.metrics.quality)")
     args = ap.parse_args()
+    if args.quantiles is not None and args.draws < 2:
+        ap.error("--quantiles needs --draws K with K >= 2")
     device = "cuda:0"
     torch.manual_seed(args.seed)
     unet = UNetModel(args.image_size, in_channels=3, model_channels=64, out_channels=3, channel_mult=[1, 2, 3], attention_resolutions=[],
@@ -147,6 +157,13 @@ def main():
         hole = (mask != 0).expand_as(mean)
         print(f"{args.draws} draws: wrote {stem}_mean.npy and {stem}_std.npy; per-pixel std over the draws: mean {float(std[hole].mean()):.4f} "
               f"in the masked region, max {float(std[~hole].max()):.2e} over the kept region")
+        if args.quantiles is not None:
+            from eo_diffusion_amd.tiling import scene_quantiles
+            qs = scene_quantiles(out, args.quantiles)                # [Q, 3, H, W]
+            names = [f"{stem}_q{f'{100 * q:.4f}'.rstrip('0').rstrip('.').replace('.', 'p').zfill(2)}.npy" for q in args.quantiles]
+            for name, plane in zip(names, qs):
+                np.save(name, plane.cpu().numpy())
+            print(f"wrote {', '.join(names)}: per-pixel quantiles over the {args.draws} draws")
     if args.metrics:                                               # on the painted region alone; out and image are in [0, 1]
         from eo_diffusion_amd import metrics
         hole_w = metrics.hole_of(cond[:, 3:])
@@ -155,6 +172,7 @@ def main():
             print(metrics.describe(q, f"draw {b} against the scene, painted region", b))
         if args.draws > 1:
             print(metrics.describe(metrics.quality(mean, image, where=hole_w), "mean of the draws against the scene, painted region"))
+            print(metrics.describe_ensemble(metrics.ensemble(out, image, where=hole_w), "the draws as an ensemble against the scene, painted region"))
     out = out[:1]
     keep = (mask == 0).expand_as(image)
     dev_kept = float((out - image)[keep].abs().max())

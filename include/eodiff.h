@@ -35,7 +35,7 @@ const char* eod_last_error(void);
  * buffer of eod_pack_conv_weight_split, the 4-int state of eod_adamw_step_guarded).  eod_version() returns the value the library was built
  * with; a binding compares it with the header it mirrors at load time (eo_diffusion_amd/_lib.py does) instead of finding out by an
  * out-of-bounds device write. */
-#define EOD_ABI_VERSION 117
+#define EOD_ABI_VERSION 118
 int eod_version(void);
 /* Kernel-selection options ("skip_fuse", "head", "halo_bn256", "halo_splitk", "first", "s2_halo": 1 / 0; "gn_fuse_max_cout": n, -1 = default;
  * "head_tpw": pixel tiles per workgroup of conv_head_kernel, 0 = chosen per launch = default): every option has one measured-best default, the other arm computes the same function
@@ -508,6 +508,38 @@ int eod_band_stats(const float* pred, const float* ref, const float* where, int 
 int64_t eod_ssim_workspace_size(int B, int C, int H, int W, int r);
 int eod_ssim(const float* pred, const float* ref, const float* where, int B, int ref_B, int where_B, int C, int H, int W, const double* taps,
              int r, double a, double b, double c1, double c2, float* map, double* sums, void* ws, int64_t ws_bytes, void* stream);
+/* Ensemble statistics (no reference line): order statistics over the B members of a stack, 1 <= B <= 64.  One lane
+ * owns one pixel at a time: the pixel's B members become order-preserving 32-bit keys (the sign bit of a non-negative float flipped, every
+ * bit of a negative one; every NaN the top key), so the order is total, -inf < .. < -0.0 < +0.0 < .. < +inf < NaN, and are sorted in
+ * registers by a fixed compare-exchange network padded to 1, 2, 4 .. 64 keys; the stack is read once.  x_(0) <= .. <= x_(B-1) below are the
+ * sorted members; a NaN that is an order statistic comes back as the quiet NaN 0x7fc00000, every other member with its own bits.
+ * A rank (k, frac), 0 <= k < B, 0 <= frac < 1, frac > 0 only with k + 1 < B, names the quantile
+ *   frac == 0: x_(k) (no arithmetic);  else d = hi - lo, m = frac * d, v = lo + m with lo = x_(k), hi = x_(k+1), each rounded in fp32
+ * (the form of eod_dyn_threshold).
+ * eod_scene_quantiles: x [B][n] -> out [Q][n], out[j][i] = the quantile (k[j], frac[j]) of pixel i; 1 <= Q <= 8, k and frac host arrays
+ * read during the call.  out must not overlap x.  One launch, no workspace, no host synchronisation.  16-byte accesses where n % 4 == 0,
+ * both pointers are 16-byte aligned and B <= 16; element by element otherwise: the same bits.
+ * eod_ensemble_stats: x [B][C][H][W] against one truth [C][H][W], 1 <= C <= 32; where: NULL or [H][W], a pixel counts iff its value is not
+ * 0; L = 0 .. 4 central intervals, level_k [L][2] and level_frac [L][2] (host arrays) the ranks of the lower and the upper quantile.  Per
+ * counted pixel of band c, in float64 on the converted members, y the truth:
+ *   a = sum |x_(i) - y| and g = sum (2 i - B + 1) x_(i) (= sum over i < j of x_(j) - x_(i)) and s = sum x_(i), ascending i, left to right;
+ *   m = s / B;  s2 = (sum (x_(i) - m)^2, ascending i) / (B - 1), 0 at B = 1;  crps = a / B - g / (B B);
+ *   rank = members whose key is below the truth's key (0 .. B);  tie: a member's key equals the truth's;
+ *   covered_l: q_lo <= y <= q_hi in fp32, the two quantiles formed as eod_scene_quantiles forms them.
+ *   sums [C][5] (float64)               sum over the counted pixels of a / B, g / (B B), (m - y)^2, s2, m - y
+ *   counts [C][2 + (B + 1) + L] (int64)  counted pixels, ties, the rank histogram, covered pixels per level
+ *   crps_map [C][H][W] (fp32) or NULL   (float)crps at a counted pixel, NaN elsewhere
+ * The float64 sums follow eod_band_stats: no floating-point atomics, every thread adds its pixels in ascending order, a workgroup its
+ * threads in a fixed order, the workgroups' slots are added left to right; which pixels a thread and a workgroup own depends on H * W
+ * alone, so a band of a C-band call has the bits of its single-band call.  The counts use integer atomics.  The call clears what it
+ * accumulates into: the contents of the workspace and of the outputs before the call do not matter.  No host synchronisation
+ * (graph-capturable).  A NaN in a band's members or truth propagates into that band's sums and into no other band; the counts stay defined
+ * through the keys.  eod_ensemble_stats_workspace_size: bytes of ws (any alignment), -1 for arguments the call refuses. */
+int eod_scene_quantiles(const float* x, float* out, int B, int64_t n, const int32_t* k, const float* frac, int Q, void* stream);
+int64_t eod_ensemble_stats_workspace_size(int B, int C, int H, int W);
+int eod_ensemble_stats(const float* x, const float* truth, const float* where, int B, int C, int H, int W, const int32_t* level_k,
+                       const float* level_frac, int L, double* sums, int64_t* counts, float* crps_map, void* ws, int64_t ws_bytes,
+                       void* stream);
 /* PSF-aware observations (no reference line): the K channels `channels` (strictly increasing) of p [B][C][H][W] are
  * observed through A = D_f N^-1 B0 -- B0 the zero-padded separable convolution with the 1-D taps h[0 .. 2r] (r = 0 .. 12; fp32, finite,
  * non-negative, bitwise symmetric, h[r] > 0), horizontally, then vertically; N = diag(B0 1); D_f the f x f block mean of section 9.5 -- on

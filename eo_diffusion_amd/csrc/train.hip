@@ -1707,6 +1707,11 @@ __device__ __forceinline__ void tr_philox4(unsigned c0, unsigned c1, unsigned c2
     o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
 }
 
+// scale = 1 / keep > 0, so x * scale has the sign of x.  It is put back explicitly: for fp16 the compiler forms the product and its rounding
+// as ONE v_fma_mixlo_f16 whose addend is +0, and (-0) * scale + (+0) = +0 -- a kept -0 came out as +0 (p = 0 was not the identity)
+__device__ __forceinline__ float sign_of(float v, float s) { return __builtin_copysignf(v, s); }
+__device__ __forceinline__ half_t sign_of(half_t v, half_t s) { return __builtin_copysignf16(v, s); }
+
 template <typename T>
 __global__ void dropout_kernel(const T* __restrict__ x, T* __restrict__ y, long long n, unsigned keep_thr, float scale, unsigned long long seed,
                                unsigned layer, unsigned step) {
@@ -1717,7 +1722,10 @@ __global__ void dropout_kernel(const T* __restrict__ x, T* __restrict__ y, long 
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const long long e = qd * 4 + j;
-            if (e < n) y[e] = (T)(r[j] < keep_thr ? (float)x[e] * scale : 0.0f);
+            if (e < n) {
+                const T xe = x[e];
+                y[e] = r[j] < keep_thr ? sign_of((T)((float)xe * scale), xe) : (T)0.0f;
+            }
         }
     }
 }

@@ -14,6 +14,13 @@
 
 typedef float ddpm_f4 __attribute__((ext_vector_type(4)));
 
+// The static clamp of a data prediction, torch.clamp(v, -1, 1): fminf / fmaxf drop a NaN operand (a NaN would become -1 and the step
+// a plausible image), so the NaN is put back.  The ONE statement of the clamp for every sampler kernel; bits of a non-NaN v: fminf(fmaxf()).
+DDPM_P0_FN float clamp_pm1(float v) {
+    const float c = fminf(fmaxf(v, -1.0f), 1.0f);
+    return v != v ? v : c;
+}
+
 struct DdpmP0Args {
     const float* x;        // [N][chw] x_t
     const float* e;        // pred: [N][chw] the noise estimate
@@ -77,7 +84,7 @@ DDPM_P0_FN void ddpm_pred_x0_thread(const DdpmP0Args& g, int n, long long first,
             const float u = c_x0 * xv[j];
             const float v = c_pred * ev[j];
             float p0 = u - v;
-            if (g.clip) p0 = fminf(fmaxf(p0, -1.0f), 1.0f);
+            if (g.clip) p0 = clamp_pm1(p0);
             o[j] = ddpm_p0_poison(bad, p0);
         }
         ddpm_p0_store<VEC>(g.out + base + i0, o, nv);

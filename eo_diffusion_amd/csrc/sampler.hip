@@ -12,6 +12,9 @@
 //   ddim_step     diffusion/ddim.py:192-206
 //   renoise       (no reference line: the forward move of RePaint resampling)
 #include "common.h"
+// (clamp_pm1, and the bodies of the split DDPM step further down)
+#define DDPM_P0_FN __device__ __host__ __forceinline__
+#include "ddpm_p0_body.h"
 
 // Caller-supplied timesteps index the schedule tables: an index outside [0, T) would read behind them (the reference's gather
 // raises there).  Such a sample is computed with index 0 and its whole output is poisoned with NaN -- loud, but memory-safe.
@@ -77,7 +80,7 @@ __global__ void ddpm_step_kernel(const float* __restrict__ x_t, const float* __r
         c_x0 = sqrtf(1.0f / acp_t);           // torch.sqrt(1. / alpha_t_cumprod)
         c_pred = sqrtf(1.0f / acp_t - 1.0f);  // torch.sqrt(1. / alpha_t_cumprod - 1.)
         if (all_pos) {
-            const float acp_prev = acp[tn - 1];
+            const float acp_prev = acp[tn > 0 ? tn - 1 : 0];  // (tn == 0 here: a sample out of range, whose output is NaN)
             m_x0 = beta_t * sqrtf(acp_prev) / (1.0f - acp_t);
             m_xt = (1.0f - acp_prev) * sqrtf(alpha_t) / (1.0f - acp_t);
             std = sqrtf(beta_t * (1.0f - acp_prev) / (1.0f - acp_t));
@@ -88,7 +91,7 @@ __global__ void ddpm_step_kernel(const float* __restrict__ x_t, const float* __r
         k_mean = 1.0f / sqrtf(alpha_t);          // (1./torch.sqrt(alpha_t))
         k_pred = (1.0f - alpha_t) / s1m[tn];     // ((1.0-alpha_t)/sqrt_one_minus_alpha_cumprod_t)
         if (all_pos) {
-            const float acp_prev = acp[tn - 1];
+            const float acp_prev = acp[tn > 0 ? tn - 1 : 0];  // (tn == 0 here: a sample out of range, whose output is NaN)
             std = sqrtf(beta_t * (1.0f - acp_prev) / (1.0f - acp_t));
         }
     }
@@ -100,7 +103,7 @@ __global__ void ddpm_step_kernel(const float* __restrict__ x_t, const float* __r
             const float u = c_x0 * x;
             const float v = c_pred * e;
             float x0 = u - v;
-            x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+            x0 = clamp_pm1(x0);              // x0.clamp(-1, 1): a NaN stays NaN
             if (all_pos) {
                 const float p = m_x0 * x0;
                 const float q = m_xt * x;
@@ -174,7 +177,7 @@ __global__ void ldm_p_sample_kernel(const float* __restrict__ x, const float* __
         const float u = a * xv;
         const float v = b * eps[base + i];
         float x0 = u - v;
-        if (CLIP) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+        if (CLIP) x0 = clamp_pm1(x0);
         const float p = k1 * x0;
         const float q = k2 * xv;
         const float mean = p + q;
@@ -355,7 +358,7 @@ extern "C" int eod_renoise(const float* x, const float* noise, float acp_from, f
 // ---------------------------------------------------------------------------------------------
 // DPM-Solver++ (2M), one step of the data-prediction multistep solver (no reference line):
 //   se = s1m_as * e;  p0 = (x - se) / sqrtf(a_s)          -- ddim_step_kernel's very operations: the same pred_x0 bits
-//   [CLIP] p0 = fminf(fmaxf(p0, -1), 1)                   -- ddpm_step_kernel<true>'s clamp (a NaN becomes -1)
+//   [CLIP] p0 = clamp_pm1(p0)                            -- ddpm_step_kernel<true>'s clamp, torch.clamp(p0, -1, 1) (a NaN stays NaN)
 //   D = SECOND ? (w_cur * p0) + (w_prev * d_prev) : p0
 //   x_next = (c_x * x) + (c_d * D);  pred_x0 = p0
 // every operation rounded once (-ffp-contract=off).  The level is shared by all samples: scalars by value, computed on the host in
@@ -366,7 +369,7 @@ __device__ __forceinline__ void dpmpp_one(float xv, float e, float d, float sq_a
                                           float w_prev, float& xn, float& p0) {
     const float se = s1m_as * e;
     p0 = (xv - se) / sq_as;
-    if (CLIP) p0 = fminf(fmaxf(p0, -1.0f), 1.0f);
+    if (CLIP) p0 = clamp_pm1(p0);
     float D = p0;
     if (SECOND) {
         const float u = w_cur * p0;
@@ -503,7 +506,7 @@ __device__ __forceinline__ float obs_p0(float xv, float e, const ObsK& k) {
     if (!OBS_STEP(KIND)) return xv;
     const float se = k.s1m * e;
     float p0 = (xv - se) / k.sq_a;
-    if (KIND == OBS_DPMPP && k.clip) p0 = fminf(fmaxf(p0, -1.0f), 1.0f);
+    if (KIND == OBS_DPMPP && k.clip) p0 = clamp_pm1(p0);
     return p0;
 }
 
@@ -1119,9 +1122,6 @@ extern "C" int eod_dpmpp_step_p0(const float* x, const float* p0c, const float* 
 // bodies are ddpm_p0_body.h (a host program compiles them, too).  grid (blocks, N) as ddpm_step_kernel; quads of a sample, 16-byte
 // accesses where chw % 4 == 0 and every pointer is aligned, element by element otherwise.
 // ---------------------------------------------------------------------------------------------
-#define DDPM_P0_FN __device__ __host__ __forceinline__
-#include "ddpm_p0_body.h"
-
 template <bool STEP, bool VEC>
 __global__ void __launch_bounds__(256) ddpm_p0_kernel(DdpmP0Args g) {
     const long long first = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
@@ -1192,6 +1192,9 @@ extern "C" int eod_ldm_p_sample(const float* x, const float* eps, const float* n
 //   postprocess    inference.py:128       samples.clip(0, 1)  |  (samples + 1) / 2
 //   masked_preview inference.py:134       image * (mask + 0.7).clip(0, 1)
 // ---------------------------------------------------------------------------------------------
+// torch.clip(v, 0, 1) = min(max(v, 0), 1) with torch's comparisons: a NaN stays NaN and -0 stays -0 (fmaxf(-0, 0) returns +0 here)
+__device__ __forceinline__ float clip_01(float v) { return v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v); }
+
 __global__ void repaint_cond_kernel(const float* __restrict__ image, const float* __restrict__ mask, float* __restrict__ cond, int C,
                                     long long hw, int invert) {
     const int n = blockIdx.y;
@@ -1213,8 +1216,7 @@ __global__ void postprocess_kernel(const float* __restrict__ x, float* __restric
         const float v = x[i];
         float o;
         if (mode == 0) {
-            o = fminf(fmaxf(v, 0.0f), 1.0f);
-            if (v != v) o = v;  // torch.clip propagates NaN
+            o = clip_01(v);
         } else {
             const float a = v + 1.0f;
             o = a / 2.0f;
@@ -1229,7 +1231,7 @@ __global__ void masked_preview_kernel(const float* __restrict__ image, const flo
     const long long per = (long long)C * hw;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < per; i += (long long)gridDim.x * blockDim.x) {
         const float a = mask[(long long)n * hw + (i % hw)] + lift;
-        const float g = fminf(fmaxf(a, 0.0f), 1.0f);
+        const float g = clip_01(a);
         out[(long long)n * per + i] = image[(long long)n * per + i] * g;
     }
 }

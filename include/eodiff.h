@@ -301,7 +301,9 @@ int eod_timestep_embedding(const float* t, const float* freqs, float* out, int N
  * k11-k15: fused sampler updates.  fp32, built with -ffp-contract=off so that every rounding of
  * the reference's torch op sequence is reproduced bit-for-bit.  x/pred/noise/out are [N][CHW] fp32.
  * tables are the EODiffusion buffers (model.py:23-32) of length T, t is int64 [N].  A timestep outside [0, T) never reads
- * behind the tables: that sample's output is filled with NaN (the reference's gather raises there).
+ * behind (or in front of) the tables: that sample is computed with index 0 and its output is filled with NaN (the reference's gather
+ * raises there); the batch-wide branch of eod_ddpm_step follows the minimum of the timesteps as given.  The clamp of the clipped steps is
+ * torch.clamp(x0, -1, 1): fminf(fmaxf(x0, -1), 1) with a NaN put back, so a NaN estimate or state gives a NaN output, never an image.
  * ------------------------------------------------------------------------------------------ */
 /* model.py:94-98 (== ddpm.py:279-282) */
 int eod_q_sample(const float* x0, const float* noise, const int64_t* t, const float* sqrt_acp,
@@ -322,7 +324,7 @@ int eod_ddim_step(const float* x, const float* e_t, const float* noise, float a_
  * line).  Per element, every operation rounded once in fp32, in this order:
  *   se = sqrt_1m_as * e_t
  *   p0 = (x - se) / sqrtf(a_s)                     -- eod_ddim_step's operations: pred_x0 has its bits for the same (x, e_t, a, sqrt_1m_a)
- *   clip != 0:  p0 = fminf(fmaxf(p0, -1), 1)       -- eod_ddpm_step's clamp (a NaN becomes -1)
+ *   clip != 0:  p0 = clamp(p0, -1, 1)              -- eod_ddpm_step's clamp: fminf(fmaxf(p0, -1), 1), a NaN stays NaN (torch.clamp)
  *   D = d_prev ? (w_cur * p0) + (w_prev * d_prev) : p0
  *   x_next = (c_x * x) + (c_d * D)
  *   pred_x0 = p0                                   -- the next step's d_prev
@@ -419,7 +421,7 @@ int eod_dpmpp_step_p0(const float* x, const float* p0c, const float* d_prev, flo
  *   eod_ddpm_pred_x0:
  *     c_x0 = sqrtf(1.0f / acp_t);  c_pred = sqrtf(1.0f / acp_t - 1.0f)
  *     u = c_x0 * x;  v = c_pred * e;  p0 = u - v
- *     clip != 0:  p0 = fminf(fmaxf(p0, -1), 1)                               -- eod_ddpm_step's clamp (a NaN becomes -1)
+ *     clip != 0:  p0 = clamp(p0, -1, 1)                                      -- eod_ddpm_step's clamp: fminf(fmaxf(p0, -1), 1), a NaN stays NaN
  *   eod_ddpm_step_p0:
  *     all_pos = (min over the batch of t) > 0                                -- the reference's batch-wide branch, as eod_ddpm_step
  *     all_pos:  m_x0 = beta_t * sqrtf(acp_prev) / (1 - acp_t);  m_xt = (1 - acp_prev) * sqrtf(alpha_t) / (1 - acp_t)
@@ -444,10 +446,10 @@ int eod_ddpm_step_p0(const float* x_t, const float* p0c, const float* noise, con
  *     lo = float(a_(k));  hi = float(a_(min(k + 1, n - 1)))
  *     v  = (frac == 0) ? lo : lo + (frac * (hi - lo))
  *     s  = fminf(fmaxf(v, 1.0f), cap)            (a NaN v gives s = 1: the static clamp)
- *     out[i] = fminf(fmaxf(p[i], -s), s) / s     (IEEE division; a NaN element becomes -1 as in eod_ddpm_step)
+ *     out[i] = fminf(fmaxf(p[i], -s), s) / s     (IEEE division; a NaN element becomes -1 HERE -- the static clamp of the step kernels keeps it)
  *     s_out[b] = s
  * The caller computes k and frac from the quantile q: pos = q * (n - 1) in float64, k = floor(pos), frac = fp32(pos - k).
- * Consequences: where v <= 1, s = 1 and out has the bits of the static clamp fminf(fmaxf(p, -1), 1) (division by 1 is exact), so
+ * Consequences: where v <= 1, s = 1 and out has the bits of the static clamp of a p without NaN (division by 1 is exact), so
  * eod_pred_x0(clip = 0) -> eod_dyn_threshold -> eod_*_step_p0 then has the bits of the clipped fused step; and the operator is idempotent:
  * |out| <= 1, so a second application has s = 1 and returns the same bits.
  * The result is a function of the sample's data, n, k, frac and cap alone: not of B, the pointers' alignment, the launch geometry or what
@@ -745,7 +747,8 @@ int eod_scene_stats(const float* x, float* mean, float* std_out, int B, int64_t 
 /* harness-side elementwise ops of inference.py, fp32, bit-exact vs the torch expressions:
  *   eod_repaint_cond   :100-109  cond [N][C+1][hw] = cat(image [N][C][hw], invert ? 1 - mask : mask), mask [N][1][hw]
  *   eod_postprocess    :128      mode 0: y = clip(x, 0, 1) (data in [0,1]);  mode 1: y = (x + 1) / 2 (data in [-1,1])
- *   eod_masked_preview :134      out = image * clip(mask + lift, 0, 1)   (lift = 0.7 in the reference) */
+ *   eod_masked_preview :134      out = image * clip(mask + lift, 0, 1)   (lift = 0.7 in the reference)
+ * clip is torch.clip: a NaN stays NaN (a NaN in the mask reaches every channel of its pixel) and -0 stays -0. */
 int eod_repaint_cond(const float* image, const float* mask, float* cond, int N, int C, int64_t hw, int invert, void* stream);
 int eod_postprocess(const float* x, float* y, int64_t numel, int mode, void* stream);
 int eod_masked_preview(const float* image, const float* mask, float* out, int N, int C, int64_t hw, float lift, void* stream);

@@ -42,7 +42,7 @@ static void ref_pred(const DdpmP0Args& g, float* out) {
             const float u = c_x0 * g.x[n * g.chw + i];
             const float v = c_pred * g.e[n * g.chw + i];
             float p0 = u - v;
-            if (g.clip) p0 = fminf(fmaxf(p0, -1.0f), 1.0f);
+            if (g.clip) p0 = p0 != p0 ? p0 : fminf(fmaxf(p0, -1.0f), 1.0f);   // torch.clamp: a NaN stays NaN
             out[n * g.chw + i] = bad ? NAN : p0;
         }
     }

@@ -50,7 +50,7 @@ def pred_x0(tb, x, e, t, clip=True):
     v = c_pred * e
     p0 = u - v
     if clip:
-        p0 = torch.fmin(torch.fmax(p0, torch.tensor(-1.0)), torch.tensor(1.0))      # (a NaN becomes -1, as fminf(fmaxf()) does)
+        p0 = torch.clamp(p0, -1.0, 1.0)                                              # (a NaN stays NaN, as clamp_pm1 keeps it)
     return _poison(p0, bad)
 
 

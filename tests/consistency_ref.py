@@ -90,7 +90,7 @@ def dpm_step(x, e, d_prev, a_s, sqrt_1m_as, c_x, c_d, w_cur, w_prev, clip, value
     d = x - se
     p0 = d / float(np.sqrt(np.float32(a_s)))
     if clip:
-        p0 = torch.fmin(torch.fmax(p0, torch.tensor(-1.0)), torch.tensor(1.0))
+        p0 = torch.clamp(p0, -1.0, 1.0)                                              # (clamp_pm1: a NaN stays NaN)
     p0c = project(p0, values, factors, mask, lam)
     if d_prev is not None:
         u = p0c * _f(w_cur)

@@ -90,7 +90,7 @@ def step(x, e, d_prev, a_s, sqrt_1m_as, c_x, c_d, w_cur, w_prev, clip):
     d = x - se
     p0 = d / float(np.sqrt(np.float32(a_s)))
     if clip:
-        p0 = torch.fmin(torch.fmax(p0, torch.tensor(-1.0)), torch.tensor(1.0))   # fminf(fmaxf(p0, -1), 1): a NaN becomes -1
+        p0 = torch.clamp(p0, -1.0, 1.0)                                          # clamp_pm1 of csrc/ddpm_p0_body.h: a NaN stays NaN
     if d_prev is not None:
         u = p0 * f(w_cur)
         v = d_prev * f(w_prev)

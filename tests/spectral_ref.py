@@ -104,7 +104,7 @@ def pred_x0(x, e, a, sqrt_1m_a, clip=False):
     d = x - se
     p0 = d / float(np.sqrt(np.float32(a)))
     if clip:
-        p0 = torch.fmin(torch.fmax(p0, torch.tensor(-1.0)), torch.tensor(1.0))
+        p0 = torch.clamp(p0, -1.0, 1.0)                                              # (clamp_pm1: a NaN stays NaN)
     return p0
 
 

@@ -103,18 +103,21 @@ def test_one_unaligned_pointer_takes_the_scalar_form_with_the_same_bits(unaligne
 
 
 def test_a_nan_is_clamped_as_eod_ddpm_step_clamps_it():
-    """fminf(fmaxf(p0, -1), 1): a NaN prediction becomes -1 (the state stays NaN: loud)"""
+    """the clamp is torch.clamp(p0, -1, 1), as eod_ddpm_step's (clamp_pm1 of csrc/ddpm_p0_body.h): a NaN prediction stays NaN, in
+    pred_x0 AND in the next state, and nowhere else -- whether the NaN comes from the state or from the estimate alone"""
     n = 256
-    x, e = synth_input("kx", (n,), 3).to(DEV), synth_input("ke", (n,), 4).to(DEV)
-    x[5] = float("nan")
-    a, s1m, c = _scalars(0.37, 0.61, False)
-    rc, got_x, got_p = dpmpp(x, e, None, a, s1m, c, True)
-    want_x, want_p = DR.step(x.cpu(), e.cpu(), None, a, s1m, *c, True)
-    assert rc == 0 and float(got_p[5]) == -1.0 and bool(torch.isnan(got_x[5])) and bits_equal(got_p.cpu(), want_p)
     keep = torch.arange(n) != 5
-    assert bits_equal(got_x.cpu()[keep], want_x[keep])
-    rc, got_x, got_p = dpmpp(x, e, None, a, s1m, c, False)
-    assert rc == 0 and bool(torch.isnan(got_p[5])) and int(torch.isnan(got_p).sum()) == 1
+    a, s1m, c = _scalars(0.37, 0.61, False)
+    for where in ("x", "e"):
+        x, e = synth_input("kx", (n,), 3).to(DEV), synth_input("ke", (n,), 4).to(DEV)
+        (x if where == "x" else e)[5] = float("nan")
+        for clip in (True, False):
+            rc, got_x, got_p = dpmpp(x, e, None, a, s1m, c, clip)
+            want_x, want_p = DR.step(x.cpu(), e.cpu(), None, a, s1m, *c, clip)
+            assert rc == 0 and bool(torch.isnan(got_p[5])) and bool(torch.isnan(got_x[5])), (where, clip)
+            assert int(torch.isnan(got_p).sum()) == 1 and int(torch.isnan(got_x).sum()) == 1, (where, clip)
+            assert bool(torch.isnan(want_p[5])) and bool(torch.isnan(want_x[5]))
+            assert bits_equal(got_p.cpu()[keep], want_p[keep]) and bits_equal(got_x.cpu()[keep], want_x[keep]), (where, clip)
 
 
 @pytest.mark.parametrize("numel", [3 * 16 * 16, 77])

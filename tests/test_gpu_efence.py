@@ -30,7 +30,7 @@ def test_unet_fuzz_cases_under_the_electric_fence():
 
 def test_kernel_tests_under_the_electric_fence():
     _run(["tests/test_gpu_kernels.py", "tests/test_gpu_train_kernels.py", "tests/test_gpu_conv_programs.py", "tests/test_gpu_glue_ops.py", "tests/test_gpu_attention.py",
-          "tests/test_gpu_train_tail.py",
+          "tests/test_gpu_train_tail.py", "tests/test_gpu_sampler_edges.py",
           "-k",
           "conv_vs_torch or fused_1x1_skip or parity_class_form_vs_torch or attention_forward_natural_layout or first_conv or head_conv or gemm_nt"
           " or test_edge_"])   # (test_gpu_train_kernels.py: the small hand-picked training-kernel cases; the harvested full-size ones stay out)

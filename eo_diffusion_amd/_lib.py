@@ -114,6 +114,11 @@ SYMBOLS = {
     "eod_adamw_step": (i32, [vp, vp, vp, vp, i64, f64, f64, f64, f64, f64, i32, vp]),
     "eod_adamw_step_guarded": (i32, [vp, vp, vp, vp, i64, f64, f64, f64, f64, f64, i32, vp, vp, i32, vp]),
     "eod_ema_update": (i32, [vp, vp, i64, f64, vp]),
+    "eod_diffusion_loss_workspace_size": (i64, [i32, i32, i32, i32]),
+    "eod_diffusion_loss": (i32, [vp, vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, i64, vp]),
+    "eod_grad_sumsq_workspace_size": (i64, [i32]),
+    "eod_grad_sumsq": (i32, [vp, i64, vp, vp, i64, i32, vp]),
+    "eod_adamw_step_clipped": (i32, [vp, vp, vp, vp, i64, f64, f64, f64, f64, f64, i32, f64, vp, i32, vp, vp]),
     "eod_pack_rows": (i32, [vp, i64, vp, vp, i64, i32, i32, i32, vp]),
     "eod_nchw_to_nhwc": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp]),
     "eod_nhwc_to_nchw": (i32, [vp, i32, vp, i32, i32, i32, i32, vp]),
@@ -215,7 +220,7 @@ class EodError(RuntimeError):
     pass
 
 
-ABI_VERSION = 118  # EOD_ABI_VERSION of the include/eodiff.h this file mirrors
+ABI_VERSION = 119  # EOD_ABI_VERSION of the include/eodiff.h this file mirrors
 SPEC_GRID_BLOCKS = 4096  # EOD_SPEC_GRID_BLOCKS there
 
 

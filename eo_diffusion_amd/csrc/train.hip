@@ -15,6 +15,7 @@
 //     same partial sums.
 // Everything here is HBM-bound elementwise / reduction work: 16-byte accesses, fixed-order sums, no atomics.
 #include "common.h"
+#include "met_sum.h"
 
 template <typename T> __device__ __forceinline__ T cvt_to(float v) { return (T)v; }
 __device__ __forceinline__ float wave_sum_t(float v) {
@@ -1082,6 +1083,276 @@ extern "C" int eod_adamw_step_guarded(float* p, const float* g, float* m, float*
     hipLaunchKernelGGL(adamw_guarded_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p, g, m, v, (long long)n, (float)(1.0 - lr * weight_decay),
                        (float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (const int*)state);
     EOD_CHECK_LAUNCH("adamw_step_guarded");
+    return EOD_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The training objective of the reference's vendored trainers (denoising_diffusion_pytorch.py:662-706: loss_type l1 / l2, reduced per
+// sample, times a per-timestep weight, mean over the batch), with a pixel mask (cloud, shadow, nodata) and a Huber kind.  With
+// d = pred - target, m the mask broadcast over the sample (1 without one) and S_n = sum_e m_e:
+//   L_n = sum_e m_e * l(d_e) / S_n (0 where S_n = 0),  loss = (1/N) sum_n w_n L_n,
+//   dpred_e = (s_n * m_e) * l'(d_e),  s_n = (float)(w_n / (N * S_n)) formed in double (0 where S_n = 0)
+// An element with m_e == 0 is SKIPPED: it adds nothing and its dpred is +0.0 whatever pred / target hold there.
+// Sums: float64 in the discipline of met_sum.h -- one workgroup per BST_CHUNK elements of one sample, thread t adds its elements
+// t, t + 256, .. in ascending order, met_reduce, one slot per (sample, chunk), met_fold per sample: a sample's bits depend on that sample
+// alone.  The terms are float64 from the start (d = (double)pred - (double)target); the gradient is float32 in the order written above,
+// from the float32 difference.
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(BST_THREADS) dloss_count_kernel(const float* __restrict__ mask, long long Em, double* __restrict__ part) {
+    __shared__ double red[BST_THREADS];
+    const int t = threadIdx.x;
+    const long long e0 = (long long)blockIdx.x * BST_CHUNK;
+    const float* mp = mask + (long long)blockIdx.y * Em;
+    float mv[BST_PER];
+#pragma unroll
+    for (int j = 0; j < BST_PER; ++j) {
+        const long long e = e0 + t + BST_THREADS * j;
+        mv[j] = e < Em ? mp[e] : 0.0f;
+    }
+    double s = 0.0;
+#pragma unroll
+    for (int j = 0; j < BST_PER; ++j) s += (double)mv[j];
+    const double v = met_reduce<1, -1>(red, &s, t);
+    if (t == 0) part[(long long)blockIdx.y * gridDim.x + blockIdx.x] = v;
+}
+
+// l(d) in float64 and l'(d) in float32; KIND 0 = l2, 1 = l1, 2 = huber
+template <int KIND> __device__ __forceinline__ double dloss_term(double d, double delta) {
+    if (KIND == 0) return d * d;
+    const double a = fabs(d);
+    if (KIND == 1) return a;
+    return a <= delta ? (0.5 * d) * d : delta * (a - 0.5 * delta);
+}
+__device__ __forceinline__ float dloss_sign(float d) { return d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : (d == 0.0f ? 0.0f : d)); }  // sign(+-0) = +0, NaN stays
+template <int KIND> __device__ __forceinline__ float dloss_slope(float d, float delta) {
+    if (KIND == 0) return 2.0f * d;
+    if (KIND == 1) return dloss_sign(d);
+    return fabsf(d) <= delta ? d : delta * dloss_sign(d);
+}
+
+// grid (chunks of a sample, N).  S: the mask sums of dloss_count_kernel after their fold ([N], or [1] with mask_nstride == 0), times
+// s_mul (C for a one-channel mask: it counts once per channel); without a mask S_n = E
+template <int KIND, bool MASK>
+__global__ void __launch_bounds__(BST_THREADS) dloss_kernel(const float* __restrict__ pred, const float* __restrict__ target, const float* __restrict__ mask,
+                                                            const float* __restrict__ weight, const double* __restrict__ S, double s_mul, long long E,
+                                                            long long Em, long long mask_nstride, int N, float delta, float* __restrict__ dpred,
+                                                            double* __restrict__ part) {
+    __shared__ double red[BST_THREADS];
+    const int t = threadIdx.x, n = blockIdx.y;
+    const long long e0 = (long long)blockIdx.x * BST_CHUNK + t;
+    const float* pp = pred + (long long)n * E;
+    const float* tp = target + (long long)n * E;
+    const float* mp = MASK ? mask + (long long)n * mask_nstride : nullptr;
+    float pv[BST_PER], tv[BST_PER], mv[BST_PER];
+    long long r = MASK ? e0 % Em : 0;
+#pragma unroll
+    for (int j = 0; j < BST_PER; ++j) {
+        const long long e = e0 + BST_THREADS * j;
+        const bool in = e < E;
+        pv[j] = in ? pp[e] : 0.0f;
+        tv[j] = in ? tp[e] : 0.0f;
+        mv[j] = !in ? 0.0f : (MASK ? mp[r] : 1.0f);
+        if (MASK) {
+            r += BST_THREADS;
+            if (r >= Em) r %= Em;
+        }
+    }
+    float sn = 0.0f;
+    if (dpred) {
+        const double Sn = MASK ? S[mask_nstride ? n : 0] * s_mul : (double)E;
+        const double w = weight ? (double)weight[n] : 1.0;
+        sn = Sn > 0.0 ? (float)(w / ((double)N * Sn)) : 0.0f;
+    }
+    const double dl = (double)delta;
+    double s = 0.0;
+#pragma unroll
+    for (int j = 0; j < BST_PER; ++j) {
+        const long long e = e0 + BST_THREADS * j;
+        if (e >= E) break;
+        float gout = 0.0f;
+        if (mv[j] != 0.0f) {  // (m == 0: skipped, not multiplied -- pred / target may hold NaN or inf there)
+            const double term = dloss_term<KIND>((double)pv[j] - (double)tv[j], dl);
+            s += MASK ? (double)mv[j] * term : term;
+            const float slope = dloss_slope<KIND>(pv[j] - tv[j], delta);
+            gout = (MASK ? sn * mv[j] : sn) * slope;
+        }
+        if (dpred) dpred[(long long)n * E + e] = gout;
+    }
+    const double v = met_reduce<1, -1>(red, &s, t);
+    if (t == 0) part[(long long)n * gridDim.x + blockIdx.x] = v;
+}
+
+// per_sample[n] = L_n, loss = (1/N) sum_n w_n L_n with the samples added in ascending order (N is a batch size)
+__global__ void dloss_final_kernel(const double* __restrict__ sums, const double* __restrict__ S, double s_mul, int s_per_sample, double E,
+                                   const float* __restrict__ weight, int N, float* __restrict__ loss, float* __restrict__ per_sample) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double acc = 0.0;
+    for (int n = 0; n < N; ++n) {
+        const double Sn = S ? S[s_per_sample ? n : 0] * s_mul : E;
+        const double Ln = Sn > 0.0 ? sums[n] / Sn : 0.0;
+        per_sample[n] = (float)Ln;
+        acc += (weight ? (double)weight[n] : 1.0) * Ln;
+    }
+    loss[0] = (float)(acc / (double)N);
+}
+
+static inline long long dloss_chunks(long long E) { return (E + BST_CHUNK - 1) / BST_CHUNK; }
+
+extern "C" int64_t eod_diffusion_loss_workspace_size(int N, int C, int H, int W) {
+    if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return -1;
+    const long long chunks = dloss_chunks((long long)C * H * W);
+    return (2LL * N + (long long)N * chunks + met_fold_extra(N, chunks, 1)) * 8;
+}
+
+extern "C" int eod_diffusion_loss(const float* pred, const float* target, const float* mask, int mask_n, int mask_c, const float* weight, int N,
+                                  int C, int H, int W, int kind, float delta, float* loss, float* per_sample, float* dpred, void* ws,
+                                  int64_t ws_bytes, void* stream) {
+    const char* what = "diffusion_loss";
+    EOD_REQUIRE(pred && target && loss && per_sample && ws && N > 0 && N <= 65535 && C > 0 && H > 0 && W > 0, "%s: bad args", what);
+    EOD_REQUIRE(kind >= 0 && kind <= 2, "%s: kind %d is none of 0 = l2, 1 = l1, 2 = huber", what, kind);
+    EOD_REQUIRE(kind != 2 || delta > 0.0f, "%s: huber needs delta > 0, got %g", what, (double)delta);
+    EOD_REQUIRE(!mask || ((mask_n == 1 || mask_n == N) && (mask_c == 1 || mask_c == C)), "%s: the mask is [N or 1][1 or C][H][W], got [%d][%d]", what,
+                mask_n, mask_c);
+    const long long HW = (long long)H * W, E = (long long)C * HW;
+    EOD_REQUIRE(E < 0x7fffffffLL * BST_CHUNK, "%s: sample too large", what);
+    EOD_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 7u) == 0 && ws_bytes >= eod_diffusion_loss_workspace_size(N, C, H, W),
+                "%s: the workspace must be 8-byte aligned and hold eod_diffusion_loss_workspace_size = %lld bytes, got %lld", what,
+                (long long)eod_diffusion_loss_workspace_size(N, C, H, W), (long long)ws_bytes);
+    hipStream_t st = (hipStream_t)stream;
+    double* S = (double*)ws;
+    double* sums = S + N;
+    double* part = sums + N;
+    const long long chunks = dloss_chunks(E);
+    const long long Em = mask ? (long long)mask_c * HW : 0, mask_nstride = mask && mask_n == N && N > 1 ? Em : 0;
+    const double s_mul = mask && mask_c == 1 ? (double)C : 1.0;
+    if (mask) {  // S_n is needed before the gradient: one pass over the mask alone
+        const int outer = mask_nstride ? N : 1;
+        const long long mchunks = dloss_chunks(Em);
+        hipLaunchKernelGGL(dloss_count_kernel, dim3((unsigned)mchunks, (unsigned)outer), dim3(BST_THREADS), 0, st, mask, Em, part);
+        EOD_CHECK_LAUNCH(what);
+        const int rc = met_fold(what, part, outer, mchunks, 1, 0, S, nullptr, nullptr, st);
+        if (rc != EOD_OK) return rc;
+    }
+    const dim3 grid((unsigned)chunks, (unsigned)N), block(BST_THREADS);
+#define DLOSS_LAUNCH(K, M) \
+    hipLaunchKernelGGL((dloss_kernel<K, M>), grid, block, 0, st, pred, target, mask, weight, (const double*)S, s_mul, E, Em, mask_nstride, N, delta, dpred, part)
+    if (mask) {
+        if (kind == 0) DLOSS_LAUNCH(0, true); else if (kind == 1) DLOSS_LAUNCH(1, true); else DLOSS_LAUNCH(2, true);
+    } else {
+        if (kind == 0) DLOSS_LAUNCH(0, false); else if (kind == 1) DLOSS_LAUNCH(1, false); else DLOSS_LAUNCH(2, false);
+    }
+#undef DLOSS_LAUNCH
+    EOD_CHECK_LAUNCH(what);
+    const int rc = met_fold(what, part, N, chunks, 1, 0, sums, nullptr, nullptr, st);
+    if (rc != EOD_OK) return rc;
+    hipLaunchKernelGGL(dloss_final_kernel, dim3(1), dim3(64), 0, st, (const double*)sums, mask ? (const double*)S : nullptr, s_mul, mask_nstride ? 1 : 0,
+                       (double)E, weight, N, loss, per_sample);
+    EOD_CHECK_LAUNCH(what);
+    return EOD_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Gradient clipping to a global norm (denoising_diffusion_pytorch.py:877: clip_grad_norm_(.., 1.0)) inside the guarded step.  The scan
+// that looks for inf / NaN forms the float64 sum of g^2 instead of a flag (eod_grad_sumsq, one double per parameter group): a gradient
+// that is not finite makes the sum inf or NaN (FLT_MAX^2 is far inside the double range, so nothing finite does), and the step's fold
+// adds the groups' doubles in group order, skips on a sum that is not finite, and otherwise forms
+//   total_norm = sqrt(sum),  coef = (float) min(1, max_norm / (total_norm + 1e-6))          (torch's clip_grad_norm_)
+// The update is adamw_guarded_kernel's with gi = g[i] * coef; g itself is never written.
+// state (10 ints, 8-byte aligned, zeroed once by the caller): {skipped now, skipped so far, clipped now, clipped so far,
+// bits(sqrt(1 - beta2^a)), bits(-lr / (1 - beta1^a)), bits(coef), 0, total_norm as a double in [8..9]}.
+// ---------------------------------------------------------------------------------------------
+// workgroup b walks the chunks b, b + gridDim.x, ..; thread t adds the squares of its elements in ascending order
+__global__ void __launch_bounds__(BST_THREADS) grad_sumsq_kernel(const float* __restrict__ g, long long n, double* __restrict__ part) {
+    __shared__ double red[BST_THREADS];
+    const int t = threadIdx.x;
+    double s = 0.0;
+    for (long long e0 = (long long)blockIdx.x * BST_CHUNK; e0 < n; e0 += (long long)gridDim.x * BST_CHUNK) {
+        float gv[BST_PER];
+#pragma unroll
+        for (int j = 0; j < BST_PER; ++j) {
+            const long long e = e0 + t + BST_THREADS * j;
+            gv[j] = e < n ? g[e] : 0.0f;
+        }
+#pragma unroll
+        for (int j = 0; j < BST_PER; ++j) s += (double)gv[j] * (double)gv[j];
+    }
+    const double v = met_reduce<1, -1>(red, &s, t);
+    if (t == 0) part[blockIdx.x] = v;
+}
+
+extern "C" int64_t eod_grad_sumsq_workspace_size(int slots) {
+    if (slots < 1) return -1;
+    return ((long long)slots + met_fold_extra(1, slots, 1)) * 8;
+}
+
+extern "C" int eod_grad_sumsq(const float* g, int64_t n, double* sumsq, void* ws, int64_t ws_bytes, int slots, void* stream) {
+    const char* what = "grad_sumsq";
+    EOD_REQUIRE(g && sumsq && ws && n > 0 && slots >= 1, "%s: bad args", what);
+    EOD_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 7u) == 0 && (reinterpret_cast<uintptr_t>(sumsq) & 7u) == 0 &&
+                    ws_bytes >= eod_grad_sumsq_workspace_size(slots),
+                "%s: sumsq and the workspace must be 8-byte aligned, the workspace eod_grad_sumsq_workspace_size(%d) = %lld bytes, got %lld", what,
+                slots, (long long)eod_grad_sumsq_workspace_size(slots), (long long)ws_bytes);
+    long long blocks = (n + BST_CHUNK - 1) / BST_CHUNK;
+    if (blocks > slots) blocks = slots;
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)blocks), dim3(BST_THREADS), 0, (hipStream_t)stream, g, (long long)n, (double*)ws);
+    EOD_CHECK_LAUNCH(what);
+    return met_fold(what, (double*)ws, 1, blocks, 1, 0, sumsq, nullptr, nullptr, (hipStream_t)stream);
+}
+
+__global__ void clip_fold_kernel(const double* __restrict__ sumsq, int n_groups, int* __restrict__ state, int calls, double lr, double beta1,
+                                 double beta2, double max_norm) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double sum = 0.0;
+    for (int k = 0; k < n_groups; ++k) sum += sumsq[k];
+    const int bad = !(sum <= 1.7976931348623157e308);  // inf or NaN
+    const double norm = sqrt(sum);
+    const double c = max_norm / (norm + 1e-6);
+    const float coef = bad ? 1.0f : (float)(c < 1.0 ? c : 1.0);
+    const int clipped = !bad && coef < 1.0f;
+    state[0] = bad;
+    state[1] += bad;
+    state[2] = clipped;
+    state[3] += clipped;
+    const int applied = calls - state[1] > 1 ? calls - state[1] : 1;
+    state[4] = __float_as_int((float)sqrt(1.0 - pow(beta2, (double)applied)));
+    state[5] = __float_as_int((float)(-(lr / (1.0 - pow(beta1, (double)applied)))));
+    state[6] = __float_as_int(coef);
+    state[7] = 0;
+    *reinterpret_cast<double*>(state + 8) = norm;
+}
+__global__ void adamw_clipped_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long long n,
+                                     float decay_mul, float beta1, float one_m_beta1, float beta2, float one_m_beta2, float eps,
+                                     const int* __restrict__ state) {
+    if (state[0]) return;  // the norm is not finite: skipped (uniform over the grid)
+    const float bc2_sqrt = __int_as_float(state[4]), neg_step_size = __int_as_float(state[5]), coef = __int_as_float(state[6]);
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const float gi = g[i] * coef;
+        float pi = p[i] * decay_mul;
+        const float mi = m[i] * beta1 + gi * one_m_beta1;
+        const float vi = v[i] * beta2 + (one_m_beta2 * gi) * gi;
+        const float denom = sqrtf(vi) / bc2_sqrt + eps;
+        pi = pi + neg_step_size * (mi / denom);
+        p[i] = pi;
+        m[i] = mi;
+        v[i] = vi;
+    }
+}
+
+extern "C" int eod_adamw_step_clipped(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2, double eps,
+                                      double weight_decay, int step, double max_norm, const double* sumsq, int n_groups, int* state,
+                                      void* stream) {
+    EOD_REQUIRE(p && g && m && v && n > 0 && step >= 1 && sumsq && n_groups >= 1 && state, "adamw_step_clipped: bad args");
+    EOD_REQUIRE(max_norm > 0.0, "adamw_step_clipped: max_norm must be positive, got %g", max_norm);
+    EOD_REQUIRE((reinterpret_cast<uintptr_t>(state) & 7u) == 0 && (reinterpret_cast<uintptr_t>(sumsq) & 7u) == 0,
+                "adamw_step_clipped: state and sumsq must be 8-byte aligned");
+    long long blocks = (n + 255) / 256;
+    if (blocks > 256 * 32) blocks = 256 * 32;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(clip_fold_kernel, dim3(1), dim3(64), 0, st, sumsq, n_groups, state, step, lr, beta1, beta2, max_norm);
+    hipLaunchKernelGGL(adamw_clipped_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p, g, m, v, (long long)n, (float)(1.0 - lr * weight_decay),
+                       (float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (const int*)state);
+    EOD_CHECK_LAUNCH("adamw_step_clipped");
     return EOD_OK;
 }
 

@@ -77,10 +77,26 @@ class EODiffusion(nn.Module):
         return t.to(device=dev, dtype=torch.int64).contiguous()
 
     # ------------------------------------------------------------------ training forward (model.py:38-44)
-    def forward(self, x, noise, cond=None, y=None):
-        t = torch.randint(0, self.timesteps, (x.shape[0],)).to(x.device)
+    def forward(self, x, noise, cond=None, y=None, *, t=None):
+        """t: int64 [N], the timesteps to use (a caller that weights the loss by timestep draws them itself and looks its weights up with
+        loss_weights(...)[t]); None draws them here as the reference does, with the same call and the same RNG consumption."""
+        if t is None:
+            t = torch.randint(0, self.timesteps, (x.shape[0],)).to(x.device)
+        else:
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or tuple(t.shape) != (x.shape[0],):
+                got = f"{tuple(t.shape)} {t.dtype}" if isinstance(t, torch.Tensor) else type(t).__name__
+                raise _lib.EodError(f"EODiffusion.forward: t must be an int64 tensor of shape ({x.shape[0]},), got {got}")
+            t = self._t64(t, x.device)
         x_t = self._forward_diffusion(x, t, noise)
         return self.model(x_t, t, cond=cond, y=y)
+
+    def loss_weights(self, kind, gamma=0.0, k=1.0):
+        """A [T] fp32 table of per-timestep loss weights on the schedule's device, built in float64 from the `alphas_cumprod` BUFFER
+        (a = alphas_cumprod[t]); use as `weight = table[t]` with optim.diffusion_loss / DiffusionLoss:
+          "min_snr"  min(1, gamma * (1 - a) / a): min(SNR, gamma) / SNR for noise prediction, in a form without inf / inf; 1 where a = 0
+          "p2"       (k + a / (1 - a)) ** -gamma: the reference's p2_loss_weight (denoising_diffusion_pytorch.py:504)
+          "uniform"  ones"""
+        return loss_weight_table(self.alphas_cumprod, kind, gamma, k)
 
     # ------------------------------------------------------------------ q(x_t | x_0)  (model.py:94-98)
     def _forward_diffusion(self, x_0, t, noise):
@@ -429,6 +445,26 @@ class EODiffusion(nn.Module):
             t = torch.full((img.shape[0],), i, dtype=torch.int64, device=img.device)
             out.append(self._forward_diffusion(img, t, noise))
         return out
+
+
+def loss_weight_table(alphas_cumprod, kind, gamma=0.0, k=1.0):
+    """EODiffusion.loss_weights on any schedule: float64 arithmetic on the fp32 table, rounded to fp32 once"""
+    if kind not in ("min_snr", "p2", "uniform"):
+        raise _lib.EodError(f"loss_weights: kind must be 'min_snr', 'p2' or 'uniform', got {kind!r}")
+    a = alphas_cumprod.detach().double()
+    if kind == "uniform":
+        w = torch.ones_like(a)
+    elif kind == "min_snr":
+        if not float(gamma) > 0.0:
+            raise _lib.EodError(f"loss_weights: min_snr needs gamma > 0, got {gamma!r}")
+        safe = torch.where(a > 0, a, torch.ones_like(a))
+        w = torch.where(a > 0, torch.clamp(float(gamma) * (1.0 - a) / safe, max=1.0), torch.ones_like(a))
+    else:
+        if not float(k) > 0.0:
+            raise _lib.EodError(f"loss_weights: p2 needs k > 0, got {k!r}")
+        snr = torch.where(a < 1, a / torch.where(a < 1, 1.0 - a, torch.ones_like(a)), torch.full_like(a, float("inf")))
+        w = (float(k) + snr) ** (-float(gamma))
+    return w.float()
 
 
 def _save_grid(x, path, nrow):

@@ -1,6 +1,8 @@
 """Fused optimizer side of the training step on the HIP path (train.py:70-75,119-124): `AdamW` and
 `ExponentialMovingAverage` with the constructor signatures the reference uses, running as ONE kernel launch over flat fp32
 buffers (csrc/train.hip: eod_adamw_step, eod_ema_update) instead of torch's per-tensor loops, and `mse_loss`.
+Opt-in, the objective beyond plain MSE: `diffusion_loss` / `DiffusionLoss` (masked, per-sample-weighted l1 / l2 / huber with its
+gradient, eod_diffusion_loss) and `AdamW(max_grad_norm=...)` (gradient clipping to a global norm inside the guarded step).
 
     from eo_diffusion_amd.optim import AdamW, ExponentialMovingAverage        # instead of torch.optim / utils.py
     optimizer = AdamW(model.parameters(), lr=args.lr)
@@ -45,14 +47,120 @@ def mse_loss(pred, target, want_grad=True):
     return loss, dp
 
 
+LOSS_KINDS = {"l2": 0, "l1": 1, "huber": 2}
+SUMSQ_SLOTS = 4096  # workgroups of the clipped step's scan (eod_grad_sumsq): one float64 slot each, folded 64 at a time in two launches
+
+
+def _loss_args(pred, target, mask, weight, kind, delta):
+    """the refusals of diffusion_loss, host-side and before any launch; returns the kind's id"""
+    what = "diffusion_loss"
+    if kind not in LOSS_KINDS:
+        raise _lib.EodError(f"{what}: kind must be one of {sorted(LOSS_KINDS)}, got {kind!r}")
+    if isinstance(delta, bool) or not isinstance(delta, (int, float)) or not delta > 0:
+        raise _lib.EodError(f"{what}: delta must be a number > 0, got {delta!r}")
+    for name, t in (("pred", pred), ("target", target), ("mask", mask), ("weight", weight)):
+        if t is None and name in ("mask", "weight"):
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise _lib.EodError(f"{what}: `{name}` must be a tensor, got {type(t).__name__}")
+        if not t.is_cuda:
+            raise _lib.EodError(f"{what}: `{name}` must be on the HIP GPU, it is on {t.device}")
+        if t.device != pred.device:
+            raise _lib.EodError(f"{what}: `{name}` is on {t.device}, pred on {pred.device}")
+        if t.dtype != torch.float32:
+            raise _lib.EodError(f"{what}: `{name}` must be float32, got {t.dtype}")
+    if pred.dim() != 4 or pred.numel() == 0:
+        raise _lib.EodError(f"{what}: pred must be [N, C, H, W], got {tuple(pred.shape)}")
+    if target.shape != pred.shape:
+        raise _lib.EodError(f"{what}: target {tuple(target.shape)} does not match pred {tuple(pred.shape)}")
+    n, c, h, w = pred.shape
+    if mask is not None and (mask.dim() != 4 or mask.shape[0] not in (1, n) or mask.shape[1] not in (1, c) or tuple(mask.shape[2:]) != (h, w)):
+        raise _lib.EodError(f"{what}: mask must be [{n} or 1, {c} or 1, {h}, {w}], got {tuple(mask.shape)}")
+    if weight is not None and tuple(weight.shape) != (n,):
+        raise _lib.EodError(f"{what}: weight must be [{n}], got {tuple(weight.shape)}")
+    return LOSS_KINDS[kind]
+
+
+def diffusion_loss(pred, target, *, mask=None, weight=None, kind="l2", delta=1.0, want_grad=True, return_per_sample=False):
+    """The objective of the reference's vendored trainers (denoising_diffusion_pytorch.py:662-706: loss_type, mean per sample, times a
+    per-timestep weight, mean over the batch) with a pixel mask, in one C call (eod_diffusion_loss, csrc/train.hip):
+        S_n = sum m,  L_n = sum m * l(pred - target) / S_n (0 where S_n = 0),  loss = mean_n weight_n * L_n
+    kind: "l2" (d^2) | "l1" (|d|) | "huber" (torch's huber_loss with `delta`).  mask: fp32 [N or 1, 1 or C, H, W], finite and >= 0, 0 = no
+    loss here (cloud, shadow, nodata); such an element is skipped, so pred / target may hold NaN there; a one-channel mask counts once
+    per channel.  weight: fp32 [N], e.g. EODiffusion.loss_weights("min_snr", 5.0)[t].  All tensors fp32 on the GPU (no conversions here).
+    Returns (loss [1], dLoss/dpred or None) like mse_loss; with return_per_sample=True also the L_n [N] (the loss by timestep bucket).
+    No mask, no weight, "l2": nn.MSELoss(reduction="mean") up to rounding."""
+    k = _loss_args(pred, target, mask, weight, kind, delta)
+    L = _lib.lib()
+    p, t = pred.detach().contiguous(), target.detach().contiguous()
+    m = None if mask is None else mask.detach().contiguous()
+    w = None if weight is None else weight.detach().contiguous()
+    n, c, h, wd = p.shape
+    loss = torch.empty((1,), dtype=torch.float32, device=p.device)
+    per = torch.empty((n,), dtype=torch.float32, device=p.device)
+    dp = torch.empty_like(p) if want_grad else None
+    nbytes = L.eod_diffusion_loss_workspace_size(n, c, h, wd)
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=p.device)
+    check(L.eod_diffusion_loss(ptr(p), ptr(t), ptr(m), 0 if m is None else m.shape[0], 0 if m is None else m.shape[1], ptr(w), n, c, h, wd, k,
+                               float(delta), ptr(loss), ptr(per), ptr(dp), ptr(ws), nbytes, current_stream_ptr(p.device)), "eod_diffusion_loss")
+    return (loss, dp, per) if return_per_sample else (loss, dp)
+
+
+class _DiffusionLossFn(torch.autograd.Function):
+    """the HIP-computed dpred kept for backward, times the incoming gradient"""
+
+    @staticmethod
+    def forward(ctx, pred, target, mask, weight, kind, delta, owner):
+        loss, dp, per = diffusion_loss(pred, target, mask=mask, weight=weight, kind=kind, delta=delta, want_grad=True, return_per_sample=True)
+        owner.per_sample = per
+        ctx.save_for_backward(dp)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, gout):
+        dp, = ctx.saved_tensors
+        return dp * gout, None, None, None, None, None, None
+
+
+class DiffusionLoss(torch.nn.Module):
+    """diffusion_loss as a loss module: `loss = loss_fn(pred, noise, mask=.., weight=..); loss.backward()` -- the reference's loop shape
+    (train.py:117-118) with nn.MSELoss replaced.  The scalar is connected to `pred` only (target, mask and weight get no gradient).
+    `per_sample` holds the latest L_n [N]."""
+
+    def __init__(self, kind="l2", delta=1.0):
+        super().__init__()
+        if kind not in LOSS_KINDS:
+            raise _lib.EodError(f"DiffusionLoss: kind must be one of {sorted(LOSS_KINDS)}, got {kind!r}")
+        if isinstance(delta, bool) or not isinstance(delta, (int, float)) or not delta > 0:
+            raise _lib.EodError(f"DiffusionLoss: delta must be a number > 0, got {delta!r}")
+        self.kind, self.delta = kind, float(delta)
+        self.per_sample = None
+
+    def forward(self, pred, target, mask=None, weight=None):
+        return _DiffusionLossFn.apply(pred, target, mask, weight, self.kind, self.delta, self)
+
+
 class AdamW(torch.optim.Optimizer):
     """torch.optim.AdamW semantics (decoupled weight decay, no amsgrad), one fused launch per parameter group."""
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, *, skip_nonfinite=True):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, *, skip_nonfinite=True, max_grad_norm=None):
         """skip_nonfinite (default on): a step whose gradients contain inf / NaN (fp16 training overflowing its static loss scale)
-        is skipped on the device -- parameters and moments stay untouched; `skipped_steps()` reads the count (one host sync)."""
+        is skipped on the device -- parameters and moments stay untouched; `skipped_steps()` reads the count (one host sync).
+        max_grad_norm (a positive float; needs skip_nonfinite): every step clips the gradients to this GLOBAL norm over all parameter
+        groups by torch.nn.utils.clip_grad_norm_'s rule (the reference's trainer: denoising_diffusion_pytorch.py:877), on the device and
+        inside the step -- the scan that looks for inf / NaN forms the squared norm (eod_grad_sumsq), the update reads g * coef
+        (eod_adamw_step_clipped).  Unlike torch's in-place clip, `p.grad` keeps the RAW gradient.  `last_grad_norm()` and
+        `clipped_steps()` read the state (one host sync each).  None (default): today's calls."""
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.skip_nonfinite = bool(skip_nonfinite)
+        if max_grad_norm is not None:
+            if isinstance(max_grad_norm, bool) or not isinstance(max_grad_norm, (int, float)) or not max_grad_norm > 0:
+                raise _lib.EodError(f"AdamW: max_grad_norm must be a positive number or None, got {max_grad_norm!r}")
+            if not self.skip_nonfinite:
+                raise _lib.EodError("AdamW: max_grad_norm needs skip_nonfinite=True (the norm comes out of the guarded step's scan)")
+            max_grad_norm = float(max_grad_norm)
+        self.max_grad_norm = max_grad_norm
+        self._sumsq = None
         self._flat = []
         for group in self.param_groups:
             ps = [p for p in group["params"] if p.requires_grad]
@@ -68,6 +176,9 @@ class AdamW(torch.optim.Optimizer):
             st = dict(params=ps, p=flat_p, g=torch.zeros_like(flat_p), m=torch.zeros_like(flat_p), v=torch.zeros_like(flat_p), step=0,
                       gviews=[None] * len(ps), guard=torch.zeros((4,), dtype=torch.int32, device=dev),
                       scratch=torch.zeros((8192,), dtype=torch.int32, device=dev))
+            if self.max_grad_norm is not None:  # the clipped step's state (10 ints, include/eodiff.h) and the scan's float64 slots
+                st["clip"] = torch.zeros((10,), dtype=torch.int32, device=dev)
+                st["slots"] = torch.zeros((_lib.lib().eod_grad_sumsq_workspace_size(SUMSQ_SLOTS) // 8,), dtype=torch.float64, device=dev)
             off = 0
             for k, p in enumerate(ps):
                 st["gviews"][k] = st["g"][off:off + p.numel()].view(p.shape)
@@ -78,45 +189,11 @@ class AdamW(torch.optim.Optimizer):
     def step(self, closure=None):
         loss = closure() if closure is not None else None
         L = _lib.lib()
-        for group, st in zip(self.param_groups, self._flat):
-            if st is None:
-                continue
-            untouched = []  # torch.optim.AdamW skips parameters without a gradient (no decay, no state update): keep their values
-            # Fast path: the gradients already lie in ONE flat buffer with this optimizer's own layout (UNetTrainer.flat_grad: same
-            # parameter order, same 16-byte-aligned offsets) -> the kernel reads it in place, no per-tensor copies.
-            gptr, base, off = ptr(st["g"]), None, 0
-            in_place = True
-            for p in st["params"]:
-                if p.grad is not None:
-                    b = p.grad.data_ptr() - 4 * off
-                    if base is None:
-                        base = b
-                    in_place = in_place and b == base and p.grad.dtype == torch.float32 and p.grad.is_contiguous()
-                off += (p.numel() + 3) // 4 * 4
-            if in_place and base is not None and base % 16 == 0:
-                owner = next(p.grad for p in st["params"] if p.grad is not None)
-                in_place = owner.untyped_storage().data_ptr() <= base and \
-                    base + 4 * st["p"].numel() <= owner.untyped_storage().data_ptr() + owner.untyped_storage().nbytes()
-            else:
-                in_place = False
-            def keep(p, o):  # value AND moments of a parameter without a gradient: torch.optim.AdamW leaves all three alone
-                sl = slice(o, o + p.numel())
-                untouched.append((p, p.detach().clone(), sl, st["m"][sl].clone(), st["v"][sl].clone()))
-            off = 0
-            if in_place:
-                gptr = base
-                for p in st["params"]:
-                    if p.grad is None:  # (its slice of the flat buffer is never written by the backward: zeros)
-                        keep(p, off)
-                    off += (p.numel() + 3) // 4 * 4
-            else:
-                for p, gv in zip(st["params"], st["gviews"]):
-                    if p.grad is None:
-                        gv.zero_()
-                        keep(p, off)
-                    elif p.grad.data_ptr() != gv.data_ptr():
-                        gv.copy_(p.grad)
-                    off += (p.numel() + 3) // 4 * 4
+        live = [(group, st) for group, st in zip(self.param_groups, self._flat) if st is not None]
+        if self.max_grad_norm is not None:
+            return self._step_clipped(L, live, loss)
+        for group, st in live:
+            gptr, untouched = self._gradients(st)
             st["step"] += 1
             b1, b2 = group["betas"]
             if self.skip_nonfinite:
@@ -128,17 +205,105 @@ class AdamW(torch.optim.Optimizer):
                 check(L.eod_adamw_step(ptr(st["p"]), gptr, ptr(st["m"]), ptr(st["v"]), st["p"].numel(), float(group["lr"]), float(b1),
                                        float(b2), float(group["eps"]), float(group["weight_decay"]), st["step"], current_stream_ptr(st["p"].device)),
                       "eod_adamw_step")
-            for p, val, sl, m0, v0 in untouched:  # undo the weight decay and the moment decay a zero gradient went through
-                p.detach().copy_(val)
-                st["m"][sl].copy_(m0)
-                st["v"][sl].copy_(v0)
-            for p in st["params"]:  # written through the flat buffer: advance torch's version counters (the packed-weight
-                torch.autograd.graph.increment_version(p)  # caches of the kernels key on them); no kernel is launched
+            self._after(st, untouched)
         return loss
+
+    def _step_clipped(self, L, live, loss):
+        """the norm is global: every group's scan first (one double each), then every group's step folds all of them in group order"""
+        if not live:
+            return loss
+        dev = live[0][1]["p"].device
+        if any(st["p"].device != dev for _, st in live):
+            raise _lib.EodError("AdamW: max_grad_norm needs every parameter group on one device")
+        if self._sumsq is None:
+            self._sumsq = torch.zeros((len(live),), dtype=torch.float64, device=dev)
+        stream = current_stream_ptr(dev)
+        prepared = [self._gradients(st) for _, st in live]
+        for k, ((_, st), (gptr, _)) in enumerate(zip(live, prepared)):
+            check(L.eod_grad_sumsq(gptr, st["p"].numel(), ptr(self._sumsq) + 8 * k, ptr(st["slots"]), st["slots"].numel() * 8, SUMSQ_SLOTS, stream),
+                  "eod_grad_sumsq")
+        for (group, st), (gptr, untouched) in zip(live, prepared):
+            st["step"] += 1
+            b1, b2 = group["betas"]
+            check(L.eod_adamw_step_clipped(ptr(st["p"]), gptr, ptr(st["m"]), ptr(st["v"]), st["p"].numel(), float(group["lr"]), float(b1),
+                                           float(b2), float(group["eps"]), float(group["weight_decay"]), st["step"], self.max_grad_norm,
+                                           ptr(self._sumsq), len(live), ptr(st["clip"]), stream), "eod_adamw_step_clipped")
+            self._after(st, untouched)
+        return loss
+
+    def _gradients(self, st):
+        """(pointer to the group's flat gradient, [(parameter without a gradient, its value, slice, m, v)])"""
+        untouched = []  # torch.optim.AdamW skips parameters without a gradient (no decay, no state update): keep their values
+        # Fast path: the gradients already lie in ONE flat buffer with this optimizer's own layout (UNetTrainer.flat_grad: same
+        # parameter order, same 16-byte-aligned offsets) -> the kernel reads it in place, no per-tensor copies.
+        gptr, base, off = ptr(st["g"]), None, 0
+        in_place = True
+        for p in st["params"]:
+            if p.grad is not None:
+                b = p.grad.data_ptr() - 4 * off
+                if base is None:
+                    base = b
+                in_place = in_place and b == base and p.grad.dtype == torch.float32 and p.grad.is_contiguous()
+            off += (p.numel() + 3) // 4 * 4
+        if in_place and base is not None and base % 16 == 0:
+            owner = next(p.grad for p in st["params"] if p.grad is not None)
+            in_place = owner.untyped_storage().data_ptr() <= base and \
+                base + 4 * st["p"].numel() <= owner.untyped_storage().data_ptr() + owner.untyped_storage().nbytes()
+        else:
+            in_place = False
+        def keep(p, o):  # value AND moments of a parameter without a gradient: torch.optim.AdamW leaves all three alone
+            sl = slice(o, o + p.numel())
+            untouched.append((p, p.detach().clone(), sl, st["m"][sl].clone(), st["v"][sl].clone()))
+        off = 0
+        if in_place:
+            gptr = base
+            for p in st["params"]:
+                if p.grad is None:  # (its slice of the flat buffer is never written by the backward: zeros)
+                    keep(p, off)
+                off += (p.numel() + 3) // 4 * 4
+        else:
+            for p, gv in zip(st["params"], st["gviews"]):
+                if p.grad is None:
+                    gv.zero_()
+                    keep(p, off)
+                elif p.grad.data_ptr() != gv.data_ptr():
+                    gv.copy_(p.grad)
+                off += (p.numel() + 3) // 4 * 4
+        return gptr, untouched
+
+    @staticmethod
+    def _after(st, untouched):
+        for p, val, sl, m0, v0 in untouched:  # undo the weight decay and the moment decay a zero gradient went through
+            p.detach().copy_(val)
+            st["m"][sl].copy_(m0)
+            st["v"][sl].copy_(v0)
+        for p in st["params"]:  # written through the flat buffer: advance torch's version counters (the packed-weight
+            torch.autograd.graph.increment_version(p)  # caches of the kernels key on them); no kernel is launched
+
+    def _clip_state(self):
+        """the clipped step's state of the first live group (the norm, and with it every counter, is the same in all of them)"""
+        st = next((st for st in self._flat if st is not None and "clip" in st), None)
+        if st is None:
+            raise _lib.EodError("AdamW: built without max_grad_norm: there is no clipping state")
+        return st["clip"]
 
     def skipped_steps(self):
         """number of steps skipped because of non-finite gradients (host synchronisation)"""
+        if self.max_grad_norm is not None:  # (one global decision per step)
+            return int(self._clip_state()[1])
         return sum(int(st["guard"][1]) for st in self._flat if st is not None)
+
+    def clipped_steps(self):
+        """number of applied steps whose gradient was scaled down (host synchronisation)"""
+        return int(self._clip_state()[3])
+
+    def last_grad_norm(self):
+        """the global gradient norm the latest step saw, before clipping; inf / NaN on a skipped step (host synchronisation)"""
+        return float(self._clip_state()[8:10].view(torch.float64)[0])
+
+    def last_clip_coef(self):
+        """the factor the latest step's gradients were multiplied by (host synchronisation)"""
+        return float(self._clip_state()[6:7].view(torch.float32)[0])
 
 
 class ExponentialMovingAverage(torch.nn.Module):

@@ -7,6 +7,13 @@ the EMA copy -- only the dataset is replaced by random tensors (no network acces
 AveragedModel-based EMA for the one-launch versions in eo_diffusion_amd.optim (the only optional change to the script).
 
     python examples/train_synthetic.py --steps 20 --image-size 64 --batch-size 16 [--fp16] [--fused] [--ckpt out.pt]
+
+The training objective beyond the reference script's plain MSE (all opt-in; without these flags the loop is the one above): `--loss
+l1|l2|huber [--delta D]`, `--weighting min_snr|p2|uniform --gamma G` (a per-timestep weight: the script then draws t itself and hands it
+to the model), `--cloud-mask` (a synthetic blob per chip where no loss is taken) run eo_diffusion_amd.optim.DiffusionLoss in place of
+nn.MSELoss; `--clip 1.0` clips the gradients to a global norm inside the fused optimizer's step (needs --fused).
+
+    python examples/train_synthetic.py --fused --loss huber --weighting min_snr --gamma 5 --cloud-mask --clip 1.0
 """
 import argparse
 import math
@@ -33,9 +40,18 @@ def main():
     ap.add_argument("--fp16", action="store_true", help="fp16 storage / MFMA with fp32 accumulation (default: exact-fp32 mode)")
     ap.add_argument("--fused", action="store_true", help="eo_diffusion_amd.optim.AdamW / ExponentialMovingAverage (one launch each)")
     ap.add_argument("--ckpt", default=None)
+    ap.add_argument("--loss", default=None, choices=["l1", "l2", "huber"], help="optim.DiffusionLoss of this kind instead of nn.MSELoss")
+    ap.add_argument("--delta", type=float, default=1.0, help="the huber threshold")
+    ap.add_argument("--weighting", default=None, choices=["min_snr", "p2", "uniform"], help="per-timestep loss weight (EODiffusion.loss_weights)")
+    ap.add_argument("--gamma", type=float, default=5.0)
+    ap.add_argument("--clip", type=float, default=None, help="clip the gradients to this global norm (optim.AdamW(max_grad_norm=...), needs --fused)")
+    ap.add_argument("--cloud-mask", action="store_true", help="a synthetic blob mask per chip: no loss under the blob")
     ap.add_argument("--n-samples", type=int, default=4)
     args = ap.parse_args()
     device = "cuda:0"
+    objective = args.loss is not None or args.weighting is not None or args.cloud_mask
+    if args.clip is not None and not args.fused:
+        ap.error("--clip runs inside eo_diffusion_amd.optim.AdamW: add --fused")
     torch.manual_seed(0)
     # train.py:50-61
     unet = UNetModel(args.image_size, in_channels=3, model_channels=128, out_channels=3, channel_mult=[1, 2, 3, 4],
@@ -44,7 +60,7 @@ def main():
     print(f"Diffusion with {sum(p.numel() for p in model.parameters() if p.requires_grad) / 1e6:.2f} M params")
     if args.fused:
         from eo_diffusion_amd.optim import AdamW, ExponentialMovingAverage
-        optimizer = AdamW(model.parameters(), lr=args.lr)
+        optimizer = AdamW(model.parameters(), lr=args.lr, max_grad_norm=args.clip)
         model_ema = ExponentialMovingAverage(model, device=device, decay=args.model_ema_decay)
     else:
         from torch.optim import AdamW
@@ -59,14 +75,29 @@ def main():
         {"position": 0, "lr": args.lr / 100}, {"transition": "cos"}, {"position": posmax, "lr": args.lr},
         {"transition": lambda last_lr, sf, ef, pos, *_: args.lr * math.exp(-3 * (pos - posmax) / max(1, max_steps - posmax))}])
     loss_fn = nn.MSELoss(reduction="mean")
+    if objective:
+        from eo_diffusion_amd.optim import DiffusionLoss
+        loss_fn = DiffusionLoss(args.loss or "l2", args.delta)
+        table = model.loss_weights(args.weighting, args.gamma) if args.weighting else None
+        yy, xx = torch.meshgrid(torch.arange(args.image_size, device=device), torch.arange(args.image_size, device=device), indexing="ij")
     g = torch.Generator(device=device).manual_seed(1)
     model.train()
     t0 = time.perf_counter()
     for step in range(args.steps):
         image = torch.rand((args.batch_size, 3, args.image_size, args.image_size), device=device, generator=g)  # data in [0, 1]
         noise = torch.randn_like(image)
-        pred = model(image, noise)           # train.py:116
-        loss = loss_fn(pred, noise)          # :117
+        if objective:
+            t = torch.randint(0, args.timesteps, (args.batch_size,))   # the draw EODiffusion.forward makes, made here so that the weights can follow it
+            mask = None
+            if args.cloud_mask:  # one disc per chip, a fifth to two fifths of the chip wide: 0 inside (no loss), 1 outside
+                c = torch.rand((args.batch_size, 3, 1, 1), device=device, generator=g)
+                cy, cx, rad = c[:, 0:1] * args.image_size, c[:, 1:2] * args.image_size, (0.1 + 0.1 * c[:, 2:3]) * args.image_size
+                mask = ((yy - cy) ** 2 + (xx - cx) ** 2 >= rad ** 2).float()
+            pred = model(image, noise, t=t)
+            loss = loss_fn(pred, noise, mask=mask, weight=None if table is None else table[t.to(device)])
+        else:
+            pred = model(image, noise)       # train.py:116
+            loss = loss_fn(pred, noise)      # :117
         loss.backward()                      # :118
         optimizer.step()                     # :119
         optimizer.zero_grad()                # :120
@@ -74,7 +105,8 @@ def main():
         model_ema.update_parameters(model)   # :123
         if step % 5 == 0 or step == args.steps - 1:
             torch.cuda.synchronize()
-            print(f"Step[{step + 1}/{args.steps}], loss:{loss.detach().item():.5f}, {(time.perf_counter() - t0) / (step + 1) * 1e3:.1f} ms/step")
+            extra = f", |grad| {optimizer.last_grad_norm():.4g} (clipped {optimizer.clipped_steps()} steps)" if args.clip is not None else ""
+            print(f"Step[{step + 1}/{args.steps}], loss:{loss.detach().item():.5f}, {(time.perf_counter() - t0) / (step + 1) * 1e3:.1f} ms/step{extra}")
     if args.ckpt:
         torch.save({"model": model.state_dict(), "model_ema": model_ema.state_dict()}, args.ckpt)  # train.py:137-138
         print("saved", args.ckpt)

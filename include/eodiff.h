@@ -35,7 +35,7 @@ const char* eod_last_error(void);
  * buffer of eod_pack_conv_weight_split, the 4-int state of eod_adamw_step_guarded).  eod_version() returns the value the library was built
  * with; a binding compares it with the header it mirrors at load time (eo_diffusion_amd/_lib.py does) instead of finding out by an
  * out-of-bounds device write. */
-#define EOD_ABI_VERSION 118
+#define EOD_ABI_VERSION 119
 int eod_version(void);
 /* Kernel-selection options ("skip_fuse", "head", "halo_bn256", "halo_splitk", "first", "s2_halo": 1 / 0; "gn_fuse_max_cout": n, -1 = default;
  * "head_tpw": pixel tiles per workgroup of conv_head_kernel, 0 = chosen per launch = default): every option has one measured-best default, the other arm computes the same function
@@ -934,6 +934,34 @@ int eod_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, doub
  * reaches the optimizer, as with torch.cuda.amp.GradScaler.  No host synchronisation. */
 int eod_adamw_step_guarded(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2, double eps,
                            double weight_decay, int step, int* state, int* scratch, int scratch_len, void* stream);
+/* The training objective of the reference's vendored trainers (denoising_diffusion_pytorch.py:662-706: loss_type, per-sample reduction,
+ * per-timestep weight, batch mean) with a pixel mask.  pred, target: [N][C][H][W] fp32; mask (optional): [mask_n][mask_c][H][W] fp32 with
+ * mask_n = N or 1, mask_c = C or 1, values finite and >= 0 (a one-channel mask counts once per channel); weight (optional): [N] fp32.
+ * kind 0 = l2 (l = d^2), 1 = l1 (|d|, l' = sign(d), sign(+-0) = 0), 2 = huber (torch's huber_loss, delta > 0), d = pred - target:
+ *   S_n = sum_e m_e,  L_n = sum_e m_e l(d_e) / S_n (0 where S_n = 0),  loss[0] = (1/N) sum_n w_n L_n,  per_sample[n] = L_n,
+ *   dpred (optional) = (s_n * m_e) * l'(d_e) in fp32, s_n = (float)(w_n / (N * S_n)) formed in double (0 where S_n = 0).
+ * An element whose m_e is exactly 0 is skipped: it adds 0 and its dpred is +0.0 even where pred / target are NaN or inf.  Sums are float64
+ * in the discipline of csrc/met_sum.h (no floating-point atomics; a sample's L_n and dpred bits depend on that sample alone).  With a mask:
+ * one pass over the mask, then one fused loss + gradient pass; without: the fused pass alone.  No host synchronisation; capturable.
+ * ws: eod_diffusion_loss_workspace_size(N, C, H, W) bytes (-1: bad arguments), 8-byte aligned. */
+int64_t eod_diffusion_loss_workspace_size(int N, int C, int H, int W);
+int eod_diffusion_loss(const float* pred, const float* target, const float* mask, int mask_n, int mask_c, const float* weight, int N, int C,
+                       int H, int W, int kind, float delta, float* loss, float* per_sample, float* dpred, void* ws, int64_t ws_bytes,
+                       void* stream);
+/* sumsq[0] = the float64 sum of g[i]^2 (inf or NaN iff a g[i] is): the guarded step's scan, forming the squared norm.  Up to
+ * min(slots, 8192) workgroups, one float64 slot each, added in the order of csrc/met_sum.h; ws: eod_grad_sumsq_workspace_size(slots) bytes,
+ * 8-byte aligned like sumsq. */
+int64_t eod_grad_sumsq_workspace_size(int slots);
+int eod_grad_sumsq(const float* g, int64_t n, double* sumsq, void* ws, int64_t ws_bytes, int slots, void* stream);
+/* eod_adamw_step_guarded with gradient clipping to a GLOBAL norm (denoising_diffusion_pytorch.py:877, torch's clip_grad_norm_ rule):
+ * sumsq[0 .. n_groups) are the eod_grad_sumsq results of ALL parameter groups (every group's call passes the same array); they are added in
+ * group order, total_norm = sqrt(sum), coef = (float) min(1, max_norm / (total_norm + 1e-6)), and the update is the guarded step's with
+ * g[i] * coef in place of g[i].  g is NOT written (torch's clip scales p.grad in place).  A sum that is not finite skips the step as the
+ * guarded step does (`step` = the number of calls, bias corrections from the applied steps).  state (device, 10 ints, 8-byte aligned,
+ * zeroed once): {skipped now, skipped so far, clipped now, clipped so far, bits(sqrt(1 - beta2^a)), bits(-lr / (1 - beta1^a)),
+ * bits(coef) (1.0 on a skipped step), 0, total_norm as a double}.  max_norm > 0, inf allowed.  No host synchronisation. */
+int eod_adamw_step_clipped(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2, double eps,
+                           double weight_decay, int step, double max_norm, const double* sumsq, int n_groups, int* state, void* stream);
 /* EMA of script_utils/utils.py:56-67: avg = decay*avg + (1-decay)*p */
 int eod_ema_update(float* avg, const float* p, int64_t n, double decay, void* stream);
 

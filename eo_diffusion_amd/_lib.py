@@ -213,6 +213,13 @@ SYMBOLS = {
     "eod_resample2x": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
 }
 
+# every symbol include/eodiff_param.h declares (the prediction-target kernels; eodiff.h includes that header)
+PARAM_SYMBOLS = {
+    "eod_param_pred": (i32, [vp, vp, i32, f32, f32, i32, vp, vp, i64, vp]),
+    "eod_ddpm_param_pred": (i32, [vp, vp, vp, vp, vp, i32, i32, vp, i32, i64, i32, vp]),
+    "eod_q_sample_v": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i64, i32, vp]),
+}
+
 _lib = None
 
 
@@ -220,7 +227,7 @@ class EodError(RuntimeError):
     pass
 
 
-ABI_VERSION = 119  # EOD_ABI_VERSION of the include/eodiff.h this file mirrors
+ABI_VERSION = 120  # EOD_ABI_VERSION of the include/eodiff.h this file mirrors
 SPEC_GRID_BLOCKS = 4096  # EOD_SPEC_GRID_BLOCKS there
 
 
@@ -239,7 +246,7 @@ def lib():
     import torch  # noqa: F401
     L = C.CDLL(LIB_PATH)
     abi_any = os.environ.get("EOD_ABI_ANY", "0") == "1"
-    for name, (res, args) in SYMBOLS.items():
+    for name, (res, args) in {**SYMBOLS, **PARAM_SYMBOLS}.items():
         if abi_any and not hasattr(L, name):  # (A/B tooling: an older build knows no entry point added since)
             continue
         fn = getattr(L, name)  # AttributeError if the .so does not export a declared symbol

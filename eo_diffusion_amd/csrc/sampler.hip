@@ -15,6 +15,9 @@
 // (clamp_pm1, and the bodies of the split DDPM step further down)
 #define DDPM_P0_FN __device__ __host__ __forceinline__
 #include "ddpm_p0_body.h"
+// (the bodies of the x0 / v prediction kernels at the end of the chain section)
+#define PARAM_FN __device__ __host__ __forceinline__
+#include "param_body.h"
 
 // Caller-supplied timesteps index the schedule tables: an index outside [0, T) would read behind them (the reference's gather
 // raises there).  Such a sample is computed with index 0 and its whole output is poisoned with NaN -- loud, but memory-safe.
@@ -1162,6 +1165,69 @@ extern "C" int eod_ddpm_step_p0(const float* x_t, const float* p0c, const float*
     EOD_REQUIRE(p0c && noise && betas && alphas, "ddpm_step_p0: bad args");
     DdpmP0Args g = {x_t, nullptr, p0c, noise, (const long long*)t, betas, alphas, acp, out, N, (long long)chw, T, 0};
     return ddpm_p0_launch<true>("ddpm_step_p0", g, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Prediction targets other than the noise (DESIGN.md sections 8.2 and 9.16): the model output read as x0 or as v.  The data prediction is
+// formed directly from (x, o), never through a noise estimate, and the chain route goes on from it (the links, then the _p0 steps).  The
+// bodies are param_body.h (a host program compiles them, too).  Streaming kernels in ddpm_p0_kernel's shape: grid (blocks, N), quads of a
+// sample, 16-byte accesses where chw % 4 == 0 and every pointer is aligned, element by element otherwise; the scalar-level form is N = 1.
+// ---------------------------------------------------------------------------------------------
+template <bool PAIR, bool VEC>
+__global__ void __launch_bounds__(256) param_kernel(ParamArgs g) {
+    const long long first = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
+    if (PAIR) q_sample_v_thread<VEC>(g, blockIdx.y, first, stride);
+    else param_pred_thread<VEC>(g, blockIdx.y, first, stride);
+}
+
+template <bool PAIR>
+static int param_launch(const char* what, const ParamArgs& g, void* stream) {
+    EOD_REQUIRE(g.x && g.o && g.out0 && g.N > 0 && g.chw > 0, "%s: bad args", what);
+    EOD_REQUIRE(!g.t || (g.sa_tab && g.s1_tab && g.T > 0), "%s: bad args", what);
+    const long long n = (long long)g.N * g.chw;
+    float* const outs[2] = {g.out0, g.out1};
+    const float* const ins[2] = {g.x, g.o};
+    const float* const tables[2] = {g.sa_tab, g.s1_tab};
+    bool vec = g.chw % 4 == 0 && eod_aligned16(g.x) && eod_aligned16(g.o);
+    EOD_REQUIRE(!g.out1 || !eod_overlap2(g.out0, n, g.out1, n), "%s: the two outputs overlap", what);
+    for (float* o : outs) {
+        if (!o) continue;
+        for (const float* p : ins) EOD_REQUIRE(!eod_overlap2(o, n, p, n), "%s: an output overlaps an input", what);
+        if (g.t) {
+            for (const float* p : tables) EOD_REQUIRE(!eod_overlap2(o, n, p, g.T), "%s: an output overlaps a schedule table", what);
+            EOD_REQUIRE(!eod_overlap2(o, n, reinterpret_cast<const float*>(g.t), 2LL * g.N), "%s: an output overlaps t", what);
+        }
+        vec = vec && eod_aligned16(o);
+    }
+    const dim3 grid(blocks_for((g.chw + 3) / 4, 2048), g.N), block(256);
+    if (vec) hipLaunchKernelGGL((param_kernel<PAIR, true>), grid, block, 0, (hipStream_t)stream, g);
+    else hipLaunchKernelGGL((param_kernel<PAIR, false>), grid, block, 0, (hipStream_t)stream, g);
+    EOD_CHECK_LAUNCH(what);
+    return EOD_OK;
+}
+
+extern "C" int eod_param_pred(const float* x, const float* o, int kind, float a, float sqrt_1m_a, int clip, float* p0, float* e_t, int64_t numel,
+                              void* stream) {
+    EOD_REQUIRE(kind == PARAM_X0 || kind == PARAM_V, "param_pred: kind is 1 (x0) or 2 (v), got %d (the noise form is eod_pred_x0)", kind);
+    EOD_REQUIRE(a >= 0.0f && a <= 1.0f, "param_pred: needs 0 <= a <= 1, got %g", (double)a);
+    EOD_REQUIRE(kind != PARAM_X0 || !e_t || sqrt_1m_a > 0.0f, "param_pred: the noise estimate of an x0 output needs sqrt_1m_a > 0, got %g", (double)sqrt_1m_a);
+    ParamArgs g = {x, o, nullptr, nullptr, nullptr, a, sqrt_1m_a, p0, e_t, 1, (long long)numel, 0, kind, clip};
+    return param_launch<false>("param_pred", g, stream);
+}
+
+extern "C" int eod_ddpm_param_pred(const float* x_t, const float* o, const int64_t* t, const float* sqrt_acp, const float* sqrt_1m_acp, int kind,
+                                   int clip, float* p0, int N, int64_t chw, int T, void* stream) {
+    EOD_REQUIRE(kind == PARAM_X0 || kind == PARAM_V, "ddpm_param_pred: kind is 1 (x0) or 2 (v), got %d (the noise form is eod_ddpm_pred_x0)", kind);
+    EOD_REQUIRE(t && sqrt_acp && sqrt_1m_acp && T > 0, "ddpm_param_pred: bad args");
+    ParamArgs g = {x_t, o, (const long long*)t, sqrt_acp, sqrt_1m_acp, 0.0f, 0.0f, p0, nullptr, N, (long long)chw, T, kind, clip};
+    return param_launch<false>("ddpm_param_pred", g, stream);
+}
+
+extern "C" int eod_q_sample_v(const float* x0, const float* noise, const int64_t* t, const float* sqrt_acp, const float* sqrt_1m_acp, float* x_t,
+                              float* v, int N, int64_t chw, int T, void* stream) {
+    EOD_REQUIRE(t && sqrt_acp && sqrt_1m_acp && v && T > 0, "q_sample_v: bad args");
+    ParamArgs g = {x0, noise, (const long long*)t, sqrt_acp, sqrt_1m_acp, 0.0f, 0.0f, x_t, v, N, (long long)chw, T, PARAM_V, 0};
+    return param_launch<true>("q_sample_v", g, stream);
 }
 
 extern "C" int eod_cfg_combine(const float* e_uncond, const float* e_cond, float scale, float* out, int64_t numel, void* stream) {

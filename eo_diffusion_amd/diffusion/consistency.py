@@ -49,6 +49,14 @@ MAX_LINKS = 4           # observations in one chain
 MAX_RADIUS = 12         # of a PSF's taps (PSF_MAXR of csrc/psf_body.h)
 MAX_ITERS = 8           # Landweber steps of a PsfObservation per evaluation
 MAX_CG_ITERS = 64       # conjugate-gradient iterations of a PsfObservation(solver="cg") per evaluation (CG_MAX_ITERS of csrc/psf_cg_body.h)
+PARAMETERIZATIONS = ("eps", "x0", "v")   # what a model's output is; the index is the `kind` of eod_param_pred / eod_ddpm_param_pred
+
+
+def parameterization_kind(what, parameterization):
+    """0 / 1 / 2 for "eps" / "x0" / "v"; anything else is refused"""
+    if not isinstance(parameterization, str) or parameterization not in PARAMETERIZATIONS:
+        raise _lib.EodError(f"{what}: parameterization is one of {PARAMETERIZATIONS}, got {parameterization!r}")
+    return PARAMETERIZATIONS.index(parameterization)
 SOLVERS = ("landweber", "cg")
 MIN_RCOND = 1e-3        # sigma_min / sigma_max of a response matrix below which it is refused (DESIGN.md section 9.6: the fp32 residual
                         # of the projection grows with the conditioning, 0.55 eps at cond 45 and 11.6 eps at cond 268)
@@ -767,27 +775,37 @@ class BoundChain:
     every link would give on the same prediction.  pred_x0 (for DPM-Solver++: the next evaluation's history) is the last link's result.
     threshold: a diffusion/threshold.py BoundThreshold, or None.  It becomes link 0, in front of the observations (it does not count towards
     MAX_LINKS, and `links` may then be empty), and it REPLACES the static clamp: the prediction is formed with clip = 0 whatever the
-    sampler asks for."""
+    sampler asks for.
+    parameterization: what the `e_t` handed to the steps is -- "eps": the noise estimate; "x0" / "v": the model's raw output, from which
+    eod_param_pred (ancestral: eod_ddpm_param_pred) forms the prediction directly, and for DDIM the noise estimate its update needs.
+    Every call of such a model runs a chain, with no links when it has neither an observation nor a threshold."""
 
-    def __init__(self, links, threshold=None):
+    def __init__(self, links, threshold=None, parameterization="eps"):
         self.threshold = threshold
         self.links = list(links) if threshold is None else [threshold] + list(links)
+        self.kind = parameterization_kind("BoundChain", parameterization)
 
     def _project(self, i, p):
         for link in self.links:
             p = link.project(i, p)
         return p
 
-    @staticmethod
-    def _pred_x0(x, e_t, a, sqrt_1m_a, clip):
+    def _pred_x0(self, x, e_t, a, sqrt_1m_a, clip, with_eps=False):
+        """(the prediction, the noise estimate): e_t itself under "eps"; under "x0" / "v" eod_param_pred's, or None unless with_eps"""
         p0 = torch.empty_like(x)
-        _lib.check(_lib.lib().eod_pred_x0(x.data_ptr(), e_t.data_ptr(), float(a), float(sqrt_1m_a), int(bool(clip)), p0.data_ptr(), x.numel(),
-                                          current_stream_ptr(x.device)), "eod_pred_x0")
-        return p0
+        if self.kind == 0:
+            _lib.check(_lib.lib().eod_pred_x0(x.data_ptr(), e_t.data_ptr(), float(a), float(sqrt_1m_a), int(bool(clip)), p0.data_ptr(), x.numel(),
+                                              current_stream_ptr(x.device)), "eod_pred_x0")
+            return p0, e_t
+        eps = torch.empty_like(x) if with_eps else None
+        _lib.check(_lib.lib().eod_param_pred(x.data_ptr(), e_t.data_ptr(), self.kind, float(a), float(sqrt_1m_a), int(bool(clip)), p0.data_ptr(),
+                                             _lib.ptr(eps), x.numel(), current_stream_ptr(x.device)), "eod_param_pred")
+        return p0, eps
 
     def ddim_step(self, i, x, e_t, noise, a_t, a_prev, sigma_t, sqrt_1m_at, temperature):
         x, e_t = f32c(x), f32c(e_t)
-        pred_x0 = self._project(i, self._pred_x0(x, e_t, a_t, sqrt_1m_at, False))
+        pred_x0, e_t = self._pred_x0(x, e_t, a_t, sqrt_1m_at, False, with_eps=True)
+        pred_x0 = self._project(i, pred_x0)
         x_prev = torch.empty_like(x)
         _lib.check(_lib.lib().eod_ddim_step_p0(e_t.data_ptr(), pred_x0.data_ptr(), _lib.ptr(noise), float(a_prev), float(sigma_t),
                                                float(temperature), x_prev.data_ptr(), x.numel(), current_stream_ptr(x.device)), "eod_ddim_step_p0")
@@ -795,7 +813,7 @@ class BoundChain:
 
     def dpmpp_step(self, i, x, e_t, d_prev, a_s, sqrt_1m_as, c_x, c_d, w_cur, w_prev, clip):
         x, e_t = f32c(x), f32c(e_t)
-        pred_x0 = self._project(i, self._pred_x0(x, e_t, a_s, sqrt_1m_as, clip and self.threshold is None))
+        pred_x0 = self._project(i, self._pred_x0(x, e_t, a_s, sqrt_1m_as, clip and self.threshold is None)[0])
         x_next = torch.empty_like(x)
         _lib.check(_lib.lib().eod_dpmpp_step_p0(x.data_ptr(), pred_x0.data_ptr(), _lib.ptr(d_prev), float(c_x), float(c_d), float(w_cur),
                                                 float(w_prev), x_next.data_ptr(), x.numel(), current_stream_ptr(x.device)), "eod_dpmpp_step_p0")
@@ -841,8 +859,25 @@ def shard(observation, n_total, lo, hi):
     return observation.shard(n_total, lo, hi) if hasattr(observation, "shard") else observation
 
 
-def ddpm_step(bound, k, x_t, pred, noise, t, betas, alphas, acp, clip):
+def ddpm_pred_x0(parameterization, x, o, t, acp, sqrt_acp, sqrt_1m_acp, clip):
+    """the data prediction of the model output o [N, ...] at per-sample timesteps t (int64 [N] on the device): eod_ddpm_pred_x0 for "eps"
+    (from the acp table), eod_ddpm_param_pred for "x0" / "v" (from the two square-root tables of eod_q_sample); contiguous fp32 tensors"""
+    kind = parameterization_kind("ddpm_pred_x0", parameterization)
+    n, T, stream = x.shape[0], acp.numel(), current_stream_ptr(x.device)
+    p = torch.empty_like(x)
+    if kind == 0:
+        _lib.check(_lib.lib().eod_ddpm_pred_x0(x.data_ptr(), o.data_ptr(), t.data_ptr(), acp.data_ptr(), p.data_ptr(), n, x.numel() // n, T,
+                                               int(bool(clip)), stream), "eod_ddpm_pred_x0")
+    else:
+        _lib.check(_lib.lib().eod_ddpm_param_pred(x.data_ptr(), o.data_ptr(), t.data_ptr(), sqrt_acp.data_ptr(), sqrt_1m_acp.data_ptr(), kind,
+                                                  int(bool(clip)), p.data_ptr(), n, x.numel() // n, T, stream), "eod_ddpm_param_pred")
+    return p
+
+
+def ddpm_step(bound, k, x_t, pred, noise, t, betas, alphas, acp, clip, sqrt_acp=None, sqrt_1m_acp=None):
     """One ancestral (DDPM) update with an observation: eod_ddpm_pred_x0 -> each link's project(k, p) in order -> eod_ddpm_step_p0.
+    A BoundChain of an "x0" / "v" model forms the prediction with eod_ddpm_param_pred from `pred`, the model's raw output, and the tables
+    sqrt_acp / sqrt_1m_acp [T] (the model's buffers); its `links` may be empty.
     bound: a BoundObservation, BoundSpectral, BoundPsf or BoundChain (a single link is a chain of one); k: the evaluation's number in the
     walk (what `weight` sequences are indexed by; not the timestep); t int64 [N] and the schedule tables [T] on the device.  clip False:
     the same posterior form without the clamp (algebraically the reference's epsilon form, not its bits).  A chain with a threshold
@@ -850,9 +885,7 @@ def ddpm_step(bound, k, x_t, pred, noise, t, betas, alphas, acp, clip):
     x, e, z = f32c(x_t), f32c(pred), f32c(noise)
     clip = clip and getattr(bound, "threshold", None) is None
     n, T, stream = x.shape[0], acp.numel(), current_stream_ptr(x.device)
-    p = torch.empty_like(x)
-    _lib.check(_lib.lib().eod_ddpm_pred_x0(x.data_ptr(), e.data_ptr(), t.data_ptr(), acp.data_ptr(), p.data_ptr(), n, x.numel() // n, T,
-                                           int(bool(clip)), stream), "eod_ddpm_pred_x0")
+    p = ddpm_pred_x0(PARAMETERIZATIONS[getattr(bound, "kind", 0)], x, e, t, acp, sqrt_acp, sqrt_1m_acp, clip)
     for link in (bound.links if isinstance(bound, BoundChain) else (bound,)):
         p = link.project(k, p)
     out = torch.empty_like(x)

@@ -20,6 +20,9 @@ A PsfObservation (the bands seen through the sensor's point spread function on a
 DESIGN.md section 9.7) is a link like the others; alone it runs as a chain of one.
 `threshold=` (a diffusion/threshold.py DynamicThreshold) on sample / ddim_sampling / sample_scene: every step's prediction is clamped to
 its own quantile and rescaled -- eod_pred_x0, eod_dyn_threshold, the observation's links if any, eod_ddim_step_p0; DESIGN.md section 9.12.
+A model with `parameterization="x0" | "v"` (its UNet predicts the image or v, not the noise) runs every call on that route, with no links when
+it has neither observation nor threshold: eod_param_pred forms the prediction AND the noise estimate the update needs directly from the raw
+(for guidance: combined) output, then eod_ddim_step_p0; DESIGN.md section 9.16.
 """
 import numpy as np
 import torch
@@ -36,6 +39,10 @@ class DDIMSampler(object):
         self.model = model
         self.ddpm_num_timesteps = model.timesteps
         self.schedule = schedule
+
+    def _parameterization(self):
+        """what the model's output is (a model object without the attribute predicts the noise)"""
+        return getattr(self.model, "parameterization", "eps")
 
     def register_buffer(self, name, attr):
         if type(attr) == torch.Tensor:
@@ -115,7 +122,7 @@ class DDIMSampler(object):
         total_steps = timesteps.shape[0]
         visits, jump_after = resample_plan("DDIMSampler.ddim_sampling", resample, total_steps,
                                            (("step_noises", step_noises), ("mix_noises", mix_noises)), jump_noises)
-        obs = thresholding.bind(threshold, observation, "DDIMSampler.ddim_sampling", shape, len(visits), device)
+        obs = thresholding.bind(threshold, observation, "DDIMSampler.ddim_sampling", shape, len(visits), device, self._parameterization())
         img = torch.randn(shape, device=device) if x_T is None else f32c(x_T.to(device))
         intermediates = {"x_inter": [img], "pred_x0": [img]}
         if mask is not None:
@@ -164,7 +171,8 @@ class DDIMSampler(object):
         return img
 
     def _eps(self, x, t, c, unconditional_guidance_scale=1.0, unconditional_conditioning=None):
-        """the noise estimate of a batch (for a scene: of a chunk of tiles), plain or with classifier-free guidance"""
+        """the model output of a batch (for a scene: of a chunk of tiles), plain or with classifier-free guidance: the noise estimate, or
+        under parameterization "x0" / "v" the raw output (the guidance combine is linear, so it equals combining the noise estimates)"""
         if unconditional_conditioning is None or unconditional_guidance_scale == 1.0:
             return self.model.model(x, t, cond=c)
         # classifier-free guidance (ddim.py:177-181): one UNet call on the doubled batch, then a fused combine
@@ -177,8 +185,11 @@ class DDIMSampler(object):
 
     def _ddim_update(self, x, e_t, noise, index, temperature, obs=None):
         """(x_prev, pred_x0) of step `index` in one pass; noise None: sigma_t is 0 and nothing is read.  obs = (BoundObservation, number
-        of the evaluation): the step with the data prediction made consistent with the observation (eod_ddim_step_obs)"""
+        of the evaluation): the step with the data prediction made consistent with the observation (eod_ddim_step_obs).  e_t: the
+        model's output; one that is no noise estimate ("x0" / "v") goes through a chain, with no links when obs is None"""
         x = f32c(x)
+        if obs is None and self._parameterization() != "eps":
+            obs = (consistency.BoundChain([], parameterization=self._parameterization()), 0)
         if obs is not None:
             return obs[0].ddim_step(obs[1], x, e_t, noise, self.ddim_alphas[index], self.ddim_alphas_prev[index], self.ddim_sigmas[index],
                                     self.ddim_sqrt_one_minus_alphas[index], temperature)

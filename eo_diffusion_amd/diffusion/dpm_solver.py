@@ -22,6 +22,9 @@ A PsfObservation is a link like the others; alone it run
 `threshold=` (a diffusion/threshold.py DynamicThreshold) on sample / sample_scene: every evaluation's prediction is clamped to its own
 quantile and rescaled in place of the static clamp -- eod_pred_x0 (clip = 0), eod_dyn_threshold, the observation's links if any,
 eod_dpmpp_step_p0; the history is the thresholded (and projected) prediction.  DESIGN.md section 9.12.
+A model with `parameterization="x0" | "v"` runs every call on that route, with no links when it has neither observation nor threshold:
+eod_param_pred (no noise estimate: the solver needs none) forms the prediction directly from the raw output, then eod_dpmpp_step_p0;
+DESIGN.md section 9.16.
 """
 import numpy as np
 import torch
@@ -74,6 +77,8 @@ class DPMSolverSampler(DDIMSampler):
         c_x, c_d, w_cur, w_prev = self.dpm_first[index] if second is None else second
         x, e_t = f32c(x), f32c(e_t)
         d_prev = None if second is None else hist[1]
+        if obs is None and self._parameterization() != "eps":   # an "x0" / "v" output: a chain with no links
+            obs = (consistency.BoundChain([], parameterization=self._parameterization()), 0)
         if obs is not None:
             return obs[0].dpmpp_step(obs[1], x, e_t, d_prev, self.ddim_alphas[index], self.dpm_sqrt_one_minus_alphas[index], c_x, c_d, w_cur,
                                      w_prev, clip)
@@ -103,7 +108,7 @@ class DPMSolverSampler(DDIMSampler):
         device = self.model.betas.device
         C, H, W = shape
         b = batch_size
-        obs = thresholding.bind(threshold, observation, what, (b, C, H, W), len(visits), device)
+        obs = thresholding.bind(threshold, observation, what, (b, C, H, W), len(visits), device, self._parameterization())
         if conditioning is not None and conditioning.shape[0] != b:
             print(f"Warning: Got {conditioning.shape[0]} conditionings but batch-size is {b}")
         img = torch.randn((b, C, H, W), device=device) if x_T is None else f32c(x_T.to(device))

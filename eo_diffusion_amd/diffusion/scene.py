@@ -87,5 +87,5 @@ def setup(m, hs, start):
         scene_of = torch.cat([scene_of, scene_of[-1:].expand(slots - tiles.n_tiles)])
         sc.y_slots = torch.as_tensor(hs.y).reshape(-1).to(torch.int64).expand(B).to(dev)[scene_of.to(dev)].contiguous()
     sc.img = as_scene("x_T", hs.x_T) if hs.x_T is not None else start(hs.state, dev)
-    sc.obs = thresholding.bind(hs.threshold, hs.observation, what, hs.state, len(hs.visits), dev)
+    sc.obs = thresholding.bind(hs.threshold, hs.observation, what, hs.state, len(hs.visits), dev, getattr(m, "parameterization", "eps"))
     return sc

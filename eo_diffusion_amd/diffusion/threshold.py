@@ -113,19 +113,23 @@ def no_skip(what, skip_known, threshold):
                             "prediction at non-estimated pixels would enter the quantile")
 
 
-def bind(threshold, observation, what, shape, n_evaluations, device):
+def bind(threshold, observation, what, shape, n_evaluations, device, parameterization="eps"):
     """consistency.bind(observation, ...) with the threshold in front: None when both are None, the bound observation as before when
     threshold is None, else a BoundChain whose link 0 is the BoundThreshold (the chain then forms its prediction without the static
-    clamp).  Every refusal of either comes before anything is allocated or launched; device None: the refusals alone."""
+    clamp).  Every refusal of either comes before anything is allocated or launched; device None: the refusals alone.
+    parameterization: the model's.  "x0" / "v": ALWAYS a BoundChain that carries it -- a single observation as a chain of one (its fused
+    step kernel starts from a noise estimate), neither observation nor threshold as a chain with no links."""
     check(threshold, what, shape)
-    if threshold is None:
+    consistency.parameterization_kind(what, parameterization)
+    if threshold is None and parameterization == "eps":
         return consistency.bind(observation, what, shape, n_evaluations, device)
     consistency.bind(observation, what, shape, n_evaluations, None)
     if device is None:
         return None
     obs = consistency.bind(observation, what, shape, n_evaluations, device)
     links = [] if obs is None else (obs.links if isinstance(obs, consistency.BoundChain) else [obs])
-    return consistency.BoundChain(links, threshold=threshold.bind(what, shape, device))
+    return consistency.BoundChain(links, threshold=None if threshold is None else threshold.bind(what, shape, device),
+                                  parameterization=parameterization)
 
 
 def dynamic_threshold(x, quantile=0.995, max_value=None, per="sample"):

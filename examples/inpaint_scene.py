@@ -16,6 +16,10 @@ checkpoint of the reference's format ({"model": state_dict}): the example shows 
     python examples/inpaint_scene.py --timesteps 50 --skip-known --draws 8 --quantiles 0.05 0.5 0.95 --metrics
     python examples/inpaint_scene.py --timesteps 1000 --solver dpmpp --steps 25 --skip-known
     python examples/inpaint_scene.py --timesteps 1000 --solver dpmpp --steps 25 --threshold 0.995
+    python examples/inpaint_scene.py --timesteps 1000 --solver dpmpp --steps 25 --parameterization v
+
+`--parameterization v|x0` reads the UNet's output as v or as the image instead of the noise (a checkpoint trained that way:
+examples/train_synthetic.py --parameterization); every option above stays as it is.
 
 `--solver dpmpp` replaces the ancestral chain (one UNet evaluation per timestep) by `DPMSolverSampler.sample_scene`: DPM-Solver++ (2M)
 over `--steps` levels of a log-SNR grid, at most `--steps` evaluations whatever `--timesteps` is.  The same tiling, mask, resampling,
@@ -85,6 +89,8 @@ def main():
     ap.add_argument("--steps", type=int, default=25, help="--solver dpmpp: the number of levels (at most that many UNet evaluations)")
     ap.add_argument("--threshold", type=float, default=None, metavar="Q",
                     help="dynamic thresholding of every prediction at the scene's Q-quantile (e.g. 0.995) in place of the static clamp")
+    ap.add_argument("--parameterization", default="eps", choices=["eps", "x0", "v"],
+                    help="what the checkpoint's UNet predicts: the noise, the image, or v (EODiffusion(parameterization=...))")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--ckpt", default=None)
     ap.add_argument("--out", default="inpainted_scene.npy")
@@ -96,7 +102,8 @@ def main():
     torch.manual_seed(args.seed)
     unet = UNetModel(args.image_size, in_channels=3, model_channels=64, out_channels=3, channel_mult=[1, 2, 3], attention_resolutions=[],
                      num_res_blocks=1, num_heads=1).set_precision(args.precision)
-    model = EODiffusion(unet, timesteps=args.timesteps, image_size=args.image_size, in_channels=3, cond_type="sum", device=device)
+    model = EODiffusion(unet, timesteps=args.timesteps, image_size=args.image_size, in_channels=3, cond_type="sum", device=device,
+                        parameterization=args.parameterization)
     if args.ckpt:
         model.load_state_dict(torch.load(args.ckpt, map_location="cpu")["model"])
     else:

@@ -35,7 +35,7 @@ const char* eod_last_error(void);
  * buffer of eod_pack_conv_weight_split, the 4-int state of eod_adamw_step_guarded).  eod_version() returns the value the library was built
  * with; a binding compares it with the header it mirrors at load time (eo_diffusion_amd/_lib.py does) instead of finding out by an
  * out-of-bounds device write. */
-#define EOD_ABI_VERSION 119
+#define EOD_ABI_VERSION 120
 int eod_version(void);
 /* Kernel-selection options ("skip_fuse", "head", "halo_bn256", "halo_splitk", "first", "s2_halo": 1 / 0; "gn_fuse_max_cout": n, -1 = default;
  * "head_tpw": pixel tiles per workgroup of conv_head_kernel, 0 = chosen per launch = default): every option has one measured-best default, the other arm computes the same function
@@ -437,6 +437,9 @@ int eod_ddpm_pred_x0(const float* x_t, const float* pred, const int64_t* t, cons
                      void* stream);
 int eod_ddpm_step_p0(const float* x_t, const float* p0c, const float* noise, const int64_t* t, const float* betas, const float* alphas,
                      const float* acp, float* out, int N, int64_t chw, int T, void* stream);
+/* Prediction targets other than the noise (a model output read as x0 or as v; DESIGN.md sections 8.2 and 9.16): the three entry points
+ * are declared, with their operations, in eodiff_param.h, which this header includes.  They are part of this ABI revision. */
+#include "eodiff_param.h"
 /* Dynamic thresholding (Saharia et al. 2022; no reference line): the data prediction is clamped to the sample's own
  * q-quantile of |p| and rescaled, where the static clamp of the entries above saturates.  p and out [B][n] fp32, s_out [B] fp32 on the
  * device; sample b is the n elements at p + b * n (64-bit indexing: B * n may exceed 2^31).  Per sample, every operation rounded once in

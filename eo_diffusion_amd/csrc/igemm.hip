@@ -1206,7 +1206,8 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
     // 4-wave ones: the same waves per SIMD): +3.5 ... 10 % on the 256- and 512-column convs.  (The mirror image for 128-column convs -- a
     // 16 x 16 pixel tile, 4 x 2 waves, halo 1.27x instead of 1.41x and one weight tile per 256 pixels -- measured -1 ... +2 % (round 4, fp16
     // storage, where the weight DMA is the larger share of a K-step: -1 ... +3 %), and the
-    // same 2 x 4 form of conv_up4_halo_kernel +0.4 %: neither is used; a three-stage weight ring on this instance: -2 %.)
+    // same 2 x 4 form of conv_up4_halo_kernel +0.4 %: neither was used; a three-stage weight ring on this instance: -2 %.  With the wave
+    // roles below the 2 x 4 form of conv_up4_halo_kernel pays: DESIGN_HISTORY.md 10.23.)
     constexpr int BM = WAVES_N == 4 ? 64 * WAVES_M : 32 * NW, TH = BM / 16, TW = 16;
     constexpr int PH = UPS ? TH / 2 + 2 : TH + 2, PW = UPS ? TW / 2 + 2 : TW + 2, PR = PH * PW;  // 180 (60) patch rows
     constexpr int PG = (PR + 7) / 8;                                             // 23 (8) DMA groups of 8 rows
@@ -1907,10 +1908,11 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
 // taps (rows: p = 0 -> [w0 | w1+w2], p = 1 -> [w0+w1 | w2]).  The host packs those sums as ONE weight tensor with 4*Cout output columns,
 // column block `cls` = 2p+q holding its 2x2 kernel in the 3x3 tap slots (dy' in {p, p+1}, dx' in {q, q+1}; the other five slots are never
 // read), in the usual [tap][4*Cout][Cin] format (split fp16 pairs for fp32 storage).  A workgroup = one 8x16 tile of STORED positions x
-// one class x 128 output channels: the ordinary (8+2) x (16+2) halo patch of the stored tensor, FOUR taps per 32/64-channel chunk instead
+// one class x 128 output channels: the class's (8+1) x (16+1) window of the stored tensor, origin (ty0 - 1 + p, tx0 - 1 + q) -- the 153 of
+// the 180 rows of the (8+2) x (16+2) halo patch that its 2x2 taps read -- FOUR taps per 32/64-channel chunk instead
 // of nine, and the epilogue scatters to the (2i+p, 2j+q) positions of the (2H x 2W) output (decode_row, parity mode).
-// Schedule per chunk (4 K-steps): step s issues the weight tile of step s+1 and (s < 2) patch pieces 3s .. 3s+2 of the NEXT chunk; a
-// piece is split in place (fp32 storage) two steps after it was issued, behind that step's MFMAs.  16x16x32 MFMAs only.
+// Schedule per chunk (4 K-steps): step s issues the weight tile of step s+1 and (s < 2) patch pieces 3s .. of the NEXT chunk (3 + 2 of
+// the 5 per wave); a piece is split in place (fp32 storage) two steps after it was issued, behind that step's MFMAs.  16x16x32 MFMAs only.
 // =============================================================================================
 // BWD = true: the BACKWARD-DATA of that conv with the same machinery (training).  dX[m][n] = sum over the four classes of a 2x2-tap conv
 // of G_pq[i][j] = dY[2i+p][2j+q] (the class's stride-2 view of the output gradient) with the transposed class kernels: class (p, q)
@@ -1924,12 +1926,14 @@ __global__ __launch_bounds__(256, 2) void conv_up4_halo_kernel(const IgemmP p) {
     static_assert(!SPLIT || sizeof(T) == 4, "the split-fp16 product is a mode of fp32 storage");
     static_assert(SPLIT || sizeof(T) == 2, "fp16 storage or split fp32");
     constexpr int NW = 4, WAVES_M = 2, WAVES_N = 2, BN = 128, BM = 128, MS = 16;
-    constexpr int PH = 10, PW = 18, PR = PH * PW, PG = (PR + 7) / 8, LAH = (PG + NW - 1) / NW;  // 180 rows, 23 groups, 6 pieces per wave
+    // forward: the 9 x 17 window of the class (153 rows, 20 groups, 5 pieces per wave); backward: the whole 10 x 18 patch (180, 23, 6)
+    constexpr int PH = BWD ? 10 : 9, PW = BWD ? 18 : 17, PR = PH * PW, PG = (PR + 7) / 8, LAH = (PG + NW - 1) / NW;
     constexpr int ES = sizeof(T), EPC = 16 / ES, BKB = 128, BK = BKB / ES;
     constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N, TM = WM / MS, TN = WN / MS;
     constexpr int LB = (BN / 8) / NW;
     constexpr int ABUF = PG * 1024, BSTAGE = BN * BKB;
-    static_assert(LAH == 6, "schedule: three patch pieces per K-step in steps 0 and 1");
+    static_assert(LAH == (BWD ? 6 : 5), "schedule: up to three patch pieces per K-step in steps 0 and 1");
+    static_assert((WAVES_M - 1) * (WM / 16) + TM + (BWD ? 1 : 0) < PH && 15 + 1 + (BWD ? 1 : 0) < PW, "the fragment reads stay inside the staged patch");
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const sA = smem;             // [2][ABUF]
@@ -1942,7 +1946,7 @@ __global__ __launch_bounds__(256, 2) void conv_up4_halo_kernel(const IgemmP p) {
     int tile_m, tile_nn;
     map_tile(p, tile_m, tile_nn);                 // tile_nn enumerates (class, 128-column tile): the four classes of a tile run together
     const int tpc = BWD ? p.tiles_n : p.tiles_n >> 2;  // column tiles per class
-    const int cls = BWD ? 0 : tile_nn / tpc, n0 = (tile_nn - cls * tpc) * BN;
+    const int cls = BWD ? 0 : tile_nn / tpc, n0 = (BWD ? 0 : p.n_base) + (tile_nn - cls * tpc) * BN;  // (n_base: the last 128 of 256 + 128 columns)
     const int par_y = cls >> 1, par_x = cls & 1;        // (forward: the workgroup's class; backward: classes rotate inside the K loop)
     const TileGeom g = make_geom<true, BM>(p, tile_m);  // patch mode on the STORED map: ty0, tx0, n_first
     float pre_bcol[DIRECT ? 1 : TN];  // epilogue operands fetched at entry (see conv3x3_halo_kernel)
@@ -1969,7 +1973,8 @@ __global__ __launch_bounds__(256, 2) void conv_up4_halo_kernel(const IgemmP p) {
     for (int i = 0; i < LAH; ++i) {
         const int prow = (wave + NW * i) * 8 + srow;
         const int py = prow / PW, px = prow - py * PW;
-        const int hi = g.ty0 - 1 + py, wi = g.tx0 - 1 + px;
+        // forward: the window starts at the class's first tap, (par_y, par_x) inside the 10 x 18 halo patch
+        const int hi = g.ty0 - 1 + py + (BWD ? 0 : par_y), wi = g.tx0 - 1 + px + (BWD ? 0 : par_x);
         const bool ok = (wave + NW * i) < PG && prow < PR && (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
         if (ok) pvalid |= 1u << i;
         ppix[i] = BWD ? (unsigned)(4 * hi * p.W + 2 * wi)   // pixel (2 hi, 2 wi) of the (2H x 2W) gradient; the class adds (p*2W + q)
@@ -2059,7 +2064,7 @@ __global__ __launch_bounds__(256, 2) void conv_up4_halo_kernel(const IgemmP p) {
             acur[1][b] = rowb + ((c1 ^ key) << 4);
         }
     };
-    set_acur(BWD ? 1 : par_y, BWD ? 1 : par_x, 0);  // (backward: class 0 = (0, 0) -> offsets (1, 1))
+    set_acur(BWD ? 1 : 0, BWD ? 1 : 0, 0);  // (forward: the staged window IS the class's; backward: class 0 = (0, 0) -> offsets (1, 1))
     const int bsw = (lr >> 1) & 7;
     const int b_rd = (wn * WN + lr) * BKB;
     const int boff0 = b_rd + ((c0 ^ bsw) << 4), boff1 = b_rd + ((c1 ^ bsw) << 4);
@@ -2101,10 +2106,10 @@ __global__ __launch_bounds__(256, 2) void conv_up4_halo_kernel(const IgemmP p) {
             const bool w_next = step + 1 < NSTEP;
             if (w_next) issue_weights((s + 1) & 3, s == 3 ? nxt : cur, sB + ((step + 1) & 1) * BSTAGE);
             int np = 0;
-            if (s < 2 && has_next) {  // three patch pieces of the next chunk in each of steps 0 and 1: every piece gets two full steps to land
+            if (s < 2 && has_next) {  // patch pieces 3s .. of the next chunk in steps 0 and 1 (forward: 3 + 2): every piece gets two full steps to land
 #pragma unroll
                 for (int k = 0; k < 3; ++k)
-                    if ((wave + NW * (3 * s + k)) < PG) {
+                    if (3 * s + k < LAH && (wave + NW * (3 * s + k)) < PG) {
                         issue_patch_piece(3 * s + k, nxt, abuf_next);
                         ++np;
                     }
@@ -2158,7 +2163,7 @@ __global__ __launch_bounds__(256, 2) void conv_up4_halo_kernel(const IgemmP p) {
                 if (s >= 2 && has_next) {
 #pragma unroll
                     for (int k = 0; k < 3; ++k)
-                        if ((wave + NW * (3 * (s - 2) + k)) < PG) split_piece(3 * (s - 2) + k, abuf_next);
+                        if (3 * (s - 2) + k < LAH && (wave + NW * (3 * (s - 2) + k)) < PG) split_piece(3 * (s - 2) + k, abuf_next);
                 }
             }
             np_prev = np;
@@ -2195,7 +2200,7 @@ __global__ __launch_bounds__(256, 2) void conv_up4_halo_kernel(const IgemmP p) {
 
 template <typename T, bool SPLIT, bool BWD = false> static int launch_up4(IgemmP& p, hipStream_t st) {
     constexpr int BK = 128 / (int)sizeof(T);
-    const size_t ring = 2 * (size_t)(23 * 1024) + 2 * (size_t)128 * 128;
+    const size_t ring = 2 * (size_t)((BWD ? 23 : 20) * 1024) + 2 * (size_t)128 * 128;  // patch groups: see the kernel's PG
     const size_t epi = 4 * (size_t)64 * (64 + 4) * sizeof(float);
     const size_t lds = ring > epi ? ring : epi;
     auto kern = conv_up4_halo_kernel<T, SPLIT, BWD>;
@@ -2207,7 +2212,7 @@ template <typename T, bool SPLIT, bool BWD = false> static int launch_up4(IgemmP
     p.kc0 = (p.C0 + BK - 1) / BK;
     p.kc1 = 0;
     p.KT = p.kc0 * 4;
-    p.tiles_n = (BWD ? 1 : 4) * ((p.Cout + 127) / 128);  // forward: (class, column tile)
+    p.tiles_n = BWD ? (p.Cout + 127) / 128 : 4 * ((p.Cout - p.n_base + 127) / 128);  // forward: (class, column tile from n_base on)
     p.tw_log2 = 4;                            // 8 x 16 tiles of the STORED map
     p.th = 8;
     p.tiles_pw = (p.W + 15) / 16;
@@ -2220,6 +2225,256 @@ template <typename T, bool SPLIT, bool BWD = false> static int launch_up4(IgemmP
     }
     hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(256), lds, st, p);
     EOD_CHECK_LAUNCH("conv_up4_halo");
+    return EOD_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// conv_up4_halo_kernel<T, SPLIT, BWD, WAVES_N = 4>: the 8-wave, 256-column forward instance of the split product (fp32 storage).
+// 2 x 4 waves, each still 64 x 64: one workgroup = one 8 x 16 tile of stored positions x one class x TWO adjacent 128-column tiles of
+// that class, so the class window is staged and split ONCE for both (the 4-wave form does it once per 128 columns: 4 * Cout / 128
+// times per pixel tile).  2 x 20 KiB patch + 2 x 32 KiB weights, one workgroup per CU.  K loop with the wave roles of
+// conv3x3_halo_kernel's 8-wave instance (DESIGN_HISTORY.md 10.22): behind a step's barrier waves 4-7 issue the whole next weight tile
+// (eight pieces each, ONE per-lane offset, a piece's 32-row distance in the DMA's scalar offset) in front of their MFMAs and nothing
+// else; waves 0-3 go straight to their MFMAs and behind them issue the next chunk's patch pieces (3 + 2 of the five per wave, steps 0
+// and 1) and split the pieces issued two steps before (steps 2 and 3), waiting on their own vmcnt there.  One barrier per step for
+// every wave, none inside a role branch; the prologue is shared by all eight waves.  A wave's MFMAs, their operands and the K order
+// are those of the 4-wave form: the same output bits and statistics, in the same (tile, class, wave row) slots.
+// (A function template of its own, overloaded on the fourth parameter: the 4-wave instances above keep their statements and code.)
+// ---------------------------------------------------------------------------------------------
+template <typename T, bool SPLIT, bool BWD, int WAVES_N>
+__global__ __launch_bounds__(512, 1) void conv_up4_halo_kernel(const IgemmP p) {
+    static_assert(SPLIT && !BWD && sizeof(T) == 4 && WAVES_N == 4, "the 8-wave form: forward, split product of fp32 storage");
+    constexpr int NW = 8, WAVES_M = 2, RW = 4, BN = 256, BM = 128, MS = 16;
+    constexpr int PH = 9, PW = 17, PR = PH * PW, PG = (PR + 7) / 8, LAH = (PG + RW - 1) / RW;  // 153 rows, 20 groups, 5 pieces per wave of a row
+    constexpr int ES = sizeof(T), EPC = 16 / ES, BKB = 128, BK = BKB / ES;
+    constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N, TM = WM / MS, TN = WN / MS;
+    constexpr int LBR = (BN / 8) / RW;  // weight pieces per wave of the row that issues them (8)
+    constexpr int ABUF = PG * 1024, BSTAGE = BN * BKB;
+    constexpr bool EARLY = true;  // A rows of steps 1 .. 3 read one step early: -1.0 ... -2.5 % per layer by itself, six registers fewer (DESIGN_HISTORY.md 10.23)
+    static_assert(LAH == 5 && PG == RW * LAH && LBR % 2 == 0, "schedule: 3 + 2 patch pieces, every wave holds all five; the prologue halves the weight pieces");
+    static_assert((WAVES_M - 1) * (WM / 16) + TM < PH && 15 + 1 < PW, "the fragment reads stay inside the staged window");
+
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* const sA = smem;             // [2][ABUF]
+    char* const sB = smem + 2 * ABUF;  // [2][BSTAGE]
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave / WAVES_N, wn = wave % WAVES_N;
+    const int wr = wn;  // this wave's place among the four that share the pieces (both wave rows hold all of them: the prologue)
+    int tile_m, tile_nn;
+    map_tile(p, tile_m, tile_nn);      // tile_nn enumerates (class, 256-column tile)
+    const int tpc = p.tiles_n >> 2;    // column tiles per class
+    const int cls = tile_nn / tpc, n0 = (tile_nn - cls * tpc) * BN;
+    const int par_y = cls >> 1, par_x = cls & 1;
+    const TileGeom g = make_geom<true, BM>(p, tile_m);  // patch mode on the STORED map: ty0, tx0, n_first
+    f32x4 pre_bq[TN];                  // epilogue operands fetched at entry (see conv3x3_halo_kernel)
+    int pre_we[TN];
+    prefetch_bcol4<TN>(p, p.Ncols, n0 + wn * WN, lane, g.n_first, pre_bq);
+    prefetch_wexp4<TN>(p, p.Ncols, n0 + wn * WN, cls * p.Cout, lane, pre_we);  // (class kernels: weight row = class * Cout + column)
+    const float wsc1 = p.w_scale[1];
+    AbScale asc = {EOD_SPLIT_ASCALE, 1.0f};
+    if (p.a_bound) asc = ab_scale_of(ab_wave_bound(p.a_bound, g.n_first));
+
+    const int srow = lane >> 3, sslot = lane & 7;
+    unsigned ppix[LAH];
+    const int bchunk0 = sslot ^ ((4 * wave + (srow >> 1)) & 7);
+    unsigned pck = 0, pvalid = 0;
+#pragma unroll
+    for (int i = 0; i < LAH; ++i) {
+        const int prow = (wr + RW * i) * 8 + srow;
+        const int py = prow / PW, px = prow - py * PW;
+        const int hi = g.ty0 - 1 + py + par_y, wi = g.tx0 - 1 + px + par_x;  // the window starts at the class's first tap
+        const bool ok = prow < PR && (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
+        if (ok) pvalid |= 1u << i;
+        ppix[i] = (unsigned)(hi * p.W + wi);
+        pck |= (unsigned)(sslot ^ ((px >> 1) & 7)) << (3 * i);
+    }
+    auto pchunk_of = [&](int i) { return (int)((pck >> (3 * i)) & 7u); };
+    // the LBR weight pieces of a lane are rows 32 apart: ONE offset; brem = the rows of the weight tile from this lane's row of piece 0 on
+    const int brem = p.Ncols - n0 - (wr * 8 + srow);
+    const unsigned b_v = (unsigned)((wr * 8 + srow) * p.Cin * ES) + bchunk0 * 16;
+    const __amdgpu_buffer_rsrc_t rsA = make_rsrc(p.a0 + (long long)g.n_first * p.H * p.W * p.C0 * ES);
+    const __amdgpu_buffer_rsrc_t rsB = make_rsrc(p.b + ((long long)cls * p.Cout + n0) * p.Cin * ES);  // [slot][4*Cout rows][Cin]
+    const int tapstride = 4 * p.Cout * p.Cin * ES;
+
+    struct Chunk {
+        int kin;  // first channel of the chunk
+        bool ktail;
+    };
+    auto chunk_of = [&](int cc) {
+        Chunk c;
+        c.kin = cc * BK;
+        c.ktail = c.kin + BK > p.C0;
+        return c;
+    };
+    auto issue_patch_piece = [&](int i, const Chunk& c, char* abuf) {
+        const int pc = pchunk_of(i);
+        unsigned v = ((pvalid >> i) & 1u) ? ppix[i] * (unsigned)(p.C0 * ES) + pc * 16 : EOD_OOB;
+        if (c.ktail) v = (c.kin + pc * EPC < p.C0) ? v : EOD_OOB;
+        blds16(rsA, v, (unsigned)(c.kin * ES), abuf + (wr + RW * i) * 1024);
+    };
+    auto split_piece = [&](int i, char* abuf) {  // fp32 chunk -> its half of the pair's [8 x hi | 8 x lo] image (zeros stay zeros)
+        char* ptr = abuf + (wr + RW * i) * 1024 + lane * 16;
+        const f32x4 f = *reinterpret_cast<const f32x4*>(ptr);
+        *reinterpret_cast<i32x4*>(ptr) = split_pair_exchange_scaled(f, asc.s, (pchunk_of(i) & 1) != 0);
+    };
+    // pieces i0 .. i1 - 1 of the weight tile of K-step s (row a = s & 1 runs inner, column b = s >> 1): tap slot (par_y + a, par_x + b)
+    auto issue_weight_tile = [&](int s, const Chunk& c, char* bst, int i0, int i1) {
+        const int tap = (par_y + (s & 1)) * 3 + par_x + (s >> 1);
+        const unsigned soff = (unsigned)(tap * tapstride) + (unsigned)(c.kin * ES);
+        unsigned v = b_v;
+        if (c.ktail) v = (c.kin + (bchunk0 >> 1) * 8 < p.C0) ? v : EOD_OOB;
+#pragma unroll
+        for (int i = 0; i < LBR; ++i)
+            if (i >= i0 && i < i1) blds16(rsB, brem > RW * 8 * i ? v : EOD_OOB, soff + (unsigned)(RW * 8 * i * p.Cin * ES), bst + (wr + RW * i) * 1024);
+    };
+
+    f32x4 acc[TM][TN];
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+
+    // fragment addresses (see the 4-wave form): acur[v][b] for the two column taps b of the class, rows via compile-time offsets
+    const int lr = lane & 15, lh = lane >> 4;
+    const int c0 = 2 * ((0x2130 >> (4 * lh)) & 3), c1 = c0 + 1;
+    int acur[2][2];
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        const int pxc = lr + b;
+        const int key = (pxc >> 1) & 7;
+        const int rowb = (wm * (WM / 16) * PW + pxc) * BKB;
+        acur[0][b] = rowb + ((c0 ^ key) << 4);
+        acur[1][b] = rowb + ((c1 ^ key) << 4);
+    }
+    const int bsw = (lr >> 1) & 7;
+    const int b_rd = (wn * WN + lr) * BKB;
+    const int boff0 = b_rd + ((c0 ^ bsw) << 4), boff1 = b_rd + ((c1 ^ bsw) << 4);
+    i32x4 aw[2][TM];  // rotating row window of the A fragments (see the 4-wave form)
+    auto a_load = [&](int v, int b, int a) {
+#pragma unroll
+        for (int r = 0; r < TM + 1; ++r)
+            if (a == 0 ? r < TM : r == TM) aw[v][r % TM] = *reinterpret_cast<const i32x4*>(sA + acur[v][b] + r * PW * BKB);
+    };
+    const int KC = p.kc0, NSTEP = KC * 4;
+    {  // prologue, all eight waves: wave row 0 stages and splits pieces 0 .. 2 of chunk 0, wave row 1 pieces 3, 4; half a weight tile each
+        const Chunk ch0 = chunk_of(0);
+#pragma unroll
+        for (int i = 0; i < LAH; ++i)
+            if ((i >= 3) == (wm != 0)) issue_patch_piece(i, ch0, sA);
+        issue_weight_tile(0, ch0, sB, wm * (LBR / 2), (wm + 1) * (LBR / 2));
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+        for (int i = 0; i < LAH; ++i)
+            if ((i >= 3) == (wm != 0)) split_piece(i, sA);
+    }
+    int step = 0;
+    for (int cc = 0; cc < KC; ++cc) {
+        const Chunk cur = chunk_of(cc);
+        const bool has_next = cc + 1 < KC;
+        const Chunk nxt = chunk_of(has_next ? cc + 1 : cc);
+        char* abuf_next = sA + ((cc + 1) & 1) * ABUF;
+#pragma unroll
+        for (int s = 0; s < 4; ++s, ++step) {
+            // each role waits on what it owns: waves 4-7 on the weight tile they issued a step ago (all they ever issue in the loop);
+            // waves 0-3 hold patch pieces only, which they wait for where they split them
+            if (wm == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): my in-place splits are written, my reads of the other stage are done
+            __builtin_amdgcn_s_barrier();
+            if (wm == 1 && step + 1 < NSTEP) issue_weight_tile((s + 1) & 3, s == 3 ? nxt : cur, sB + ((step + 1) & 1) * BSTAGE, 0, LBR);
+            // ---- MFMAs of tap (a, b) ----
+            const int a = s & 1, b = s >> 1;
+            const char* bst = sB + (step & 1) * BSTAGE;
+            // EARLY: steps 1 .. 3 of a chunk get their new A rows one step early, each half where the registers it replaces die (the
+            // current chunk's patch buffer is read-only for the whole chunk); step 0 reads behind its barrier, where the chunk's splits are visible
+            const bool a_here = !EARLY || s == 0, a_early = EARLY && s < 3;
+            const int na = (s + 1) & 1, nb = (s + 1) >> 1;
+            i32x4 bh[TN], bl[TN];  // (A: the window aw[0] = hi, aw[1] = lo; row block i = window row i + a)
+            if (a_here) a_load(1, b, a);
+#pragma unroll
+            for (int j = 0; j < TN; ++j) bh[j] = *reinterpret_cast<const i32x4*>(bst + boff0 + j * MS * BKB);
+            if (a_here) a_load(0, b, a);
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, bh[j]), __builtin_bit_cast(half8, aw[1][(i + a) % TM]), acc[i][j], 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < TN; ++j) bl[j] = *reinterpret_cast<const i32x4*>(bst + boff1 + j * MS * BKB);
+            if (a_early) a_load(1, nb, na);  // the lo rows of this step are dead
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, bl[j]), __builtin_bit_cast(half8, aw[0][(i + a) % TM]), acc[i][j], 0, 0, 0);
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, bh[j]), __builtin_bit_cast(half8, aw[0][(i + a) % TM]), acc[i][j], 0, 0, 0);
+            if (a_early) a_load(0, nb, na);  // and now the hi rows
+            // waves 0-3, behind their MFMAs: pieces 0 .. 2 (step 0) and 3, 4 (step 1) of the next chunk go out; steps 2 and 3 split the
+            // pieces issued two steps before.  vmcnt retires in order and these waves issue nothing else: at step 2 the two pieces of
+            // step 1 may stay in flight, at step 3 nothing is left.
+            if (wm == 0 && has_next) {
+                if (s < 2) {
+#pragma unroll
+                    for (int k = 0; k < 3; ++k)
+                        if (3 * s + k < LAH) issue_patch_piece(3 * s + k, nxt, abuf_next);
+                } else {
+                    if (s == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+                    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+                    for (int k = 0; k < 3; ++k)
+                        if (3 * (s - 2) + k < LAH) split_piece(3 * (s - 2) + k, abuf_next);
+                }
+            }
+        }
+        const int flip = (cc & 1) ? -ABUF : ABUF;  // the next chunk reads the other patch buffer
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            acur[0][b] += flip;
+            acur[1][b] += flip;
+        }
+    }
+    // epilogue on the (2H x 2W) output, straight from the accumulators (no LDS): rows of the tile are positions (i, j) of the stored map
+    IgemmP pe = p;
+    TileGeom ge = g;
+    pe.par = 1; pe.par_y = par_y; pe.par_x = par_x;
+    pe.Wd = p.W;  // decode_row masks the tile columns behind an 8-wide STORED map (before the parity scaling)
+    pe.tiles_per_image = p.tiles_pi * 4;  // statistics slots: (tile of the stored map, class)
+    ge.tile_m = g.n_first * pe.tiles_per_image + (tile_m - g.n_first * p.tiles_pi) * 4 + cls;
+    pe.alpha = p.alpha * wsc1 * asc.inv;
+    pe.w_row0 = cls * p.Cout;
+    halo_epilogue_direct<BM, BN, WAVES_M, WAVES_N>(pe, ge, acc, wave, lane, n0, pre_bq, pe.alpha, pre_we);
+}
+
+// the 8-wave form over columns [0, p.Ncols) (a multiple of 256; 256 + 128 columns: the caller sends the last 128 through launch_up4 with n_base)
+static int launch_up4_w8(IgemmP& p, hipStream_t st) {
+    const size_t lds = 2 * (size_t)(20 * 1024) + 2 * (size_t)256 * 128;
+    auto kern = conv_up4_halo_kernel<float, true, false, 4>;
+    static bool attr_done = false;
+    if (!attr_done) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        attr_done = true;
+    }
+    p.kc0 = (p.C0 + 31) / 32;
+    p.kc1 = 0;
+    p.KT = p.kc0 * 4;
+    p.tiles_n = 4 * ((p.Ncols + 255) / 256);  // (class, column tile)
+    p.tw_log2 = 4;                            // 8 x 16 tiles of the STORED map
+    p.th = 8;
+    p.tiles_pw = (p.W + 15) / 16;
+    p.tiles_pi = p.tiles_pw * (p.H / 8);
+    p.tiles_m = p.tiles_pi * p.N;
+    const long long nblk = (long long)p.tiles_m * p.tiles_n;
+    if (p.Ncols <= 0 || p.Ncols % 256 || nblk <= 0 || nblk > 0x7fffffffLL) {
+        eod_set_error("conv_up4 (8 waves): bad grid %lld, %d columns", nblk, p.Ncols);
+        return EOD_EINVAL;
+    }
+    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(512), lds, st, p);
+    EOD_CHECK_LAUNCH("conv_up4_halo (8 waves)");
     return EOD_OK;
 }
 
@@ -3335,8 +3590,8 @@ struct ConvPlan {
     int Heff, Weff, Ho, Wo;
     bool halo;       // halo-patch geometry (conv_uses_halo)
     int family;      // FAM_*
-    int bn;          // HALO / GENERIC: columns per workgroup (32, 64, 128, 256)
-    bool plus128;    // HALO, bn = 256: all but the last 128 columns on the 8-wave form, the rest as a 128-column launch of its own
+    int bn;          // HALO / GENERIC / UP4: columns per workgroup (32, 64, 128, 256)
+    bool plus128;    // HALO / UP4, bn = 256: all but the last 128 columns on the 8-wave form, the rest as a 128-column launch of its own
     bool direct;     // GENERIC split product: swapped-operand instance with the direct epilogue
     int splitk, splitk_per;  // K slices over gridDim.y (1 = none); halo kernel: channel chunks per slice
     int tpw;                 // HEAD: pixel tiles per workgroup (1 everywhere else)
@@ -3381,6 +3636,20 @@ static ConvPlan conv_plan(const eod_conv_desc* d) {
     const long long tiles_pi = (long long)(Ho / 8) * ((Wo + 15) / 16);  // 8 x 16 pixel tiles per image
     if (d->upsample == 3) {
         pl.family = FAM_UP4;
+        // Columns per workgroup, as for FAM_HALO below: no choice changes a result.  The split product takes the 8-wave form that stages
+        // and splits a class window once for 256 columns (halo_bn256 = 0: the 4-wave form everywhere, A/B) where its launch still has a
+        // workgroup for every CU: one 8-wave workgroup occupies a CU, as on the halo conv (whose 32 x 32 maps at batch 8, 128 workgroups,
+        // measured -20 %).  Workgroups = N x 8 x 16 tiles of the STORED map x four classes x 256-column tiles.  fp16 storage and the
+        // backward instance stay on the 4-wave form.
+        const long long wg = (long long)d->N * (d->H / 8) * ((d->W + 15) / 16) * 4;
+        if (split && d->dtype == EOD_F32 && opt(OPT_HALO_BN256) != 0 && conv_up4_ok(d)) {
+            if (d->Cout % 256 == 0 && wg * (d->Cout / 256) >= 256) {
+                pl.bn = 256;
+            } else if (d->Cout > 256 && d->Cout % 256 == 128 && wg * ((d->Cout - 128) / 256) >= 256) {
+                pl.bn = 256;  // 384, 640, ... columns: 256 + 128
+                pl.plus128 = true;
+            }
+        }
     } else if (opt(OPT_FIRST) != 0 && conv_first_ok(d, Ho, Wo)) {  // (EOD_FIRST=0: the generic kernel, A/B)
         pl.family = FAM_FIRST;
     } else if (opt(OPT_S2_HALO) != 0 && conv_s2_halo_ok(d, Ho, Wo) && pl.splitk <= 1) {
@@ -3460,12 +3729,12 @@ extern "C" const char* eod_conv_kernel_name(const eod_conv_desc* d) {
     }
 }
 
-// output columns per workgroup of conv3x3_halo_kernel for this descriptor (32, 64, 128 or 256; 256 = the 8-wave instance, for a 256 + 128
-// conv its leading part); 0 where another family runs it
+// output columns per workgroup of conv3x3_halo_kernel or (forward) conv_up4_halo_kernel for this descriptor (32, 64, 128 or 256; 256 = the
+// 8-wave instance, for a 256 + 128 conv its leading part); 0 where another family runs it
 extern "C" int eod_conv_halo_columns(const eod_conv_desc* d) {
     if (!d) return 0;
     const ConvPlan pl = conv_plan(d);
-    return pl.family == FAM_HALO ? pl.bn : 0;
+    return pl.family == FAM_HALO || pl.family == FAM_UP4 ? pl.bn : 0;
 }
 
 static int conv_up4_bwd(const eod_conv_desc* d, void* stream) {
@@ -3642,6 +3911,17 @@ extern "C" int eod_conv2d_igemm(const eod_conv_desc* d, void* stream) {
     switch (pl.family) {
         case FAM_UP4:
             EOD_REQUIRE(conv_up4_ok(d), "conv: upsample = 3 (parity-class form of the nearest-2x conv) needs a geometry for which eod_conv_up4_ok(d) == 1");
+            if (pl.bn == 256) {  // (conv_plan: the split product only) the 8-wave form; of 256 + 128 columns the last 128 on the 4-wave one
+                if (pl.plus128) {
+                    IgemmP q = p;
+                    q.Ncols = d->Cout - 128;
+                    const int rc = launch_up4_w8(q, st);
+                    if (rc != EOD_OK) return rc;
+                    p.n_base = d->Cout - 128;
+                    return launch_up4<float, true>(p, st);
+                }
+                return launch_up4_w8(p, st);
+            }
             return f16 ? launch_up4<half_t, false>(p, st) : launch_up4<float, true>(p, st);
         case FAM_FIRST: return d->C0 == 4 ? launch_first<4>(p, st) : launch_first<8>(p, st);
         case FAM_S2_HALO: return f16 ? launch_s2<half_t, false>(p, st) : launch_s2<float, true>(p, st);

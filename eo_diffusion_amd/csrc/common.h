@@ -92,17 +92,36 @@ __device__ __forceinline__ AbScale ab_scale_of(float B, int kmin = EOD_AB_KMIN) 
     r.inv = __uint_as_float((unsigned)(4 - k + 127) << 23);
     return r;
 }
-// maximum of image n's EOD_AB table entries, wave-uniform (every lane of the wave must call); NaN entries count as +inf
-__device__ __forceinline__ float ab_wave_bound(const float* __restrict__ ab, long long n) {
-    float b = 0.0f;
-    if ((threadIdx.x & 63) < EOD_AB) {
-        b = ab[n * EOD_AB + (threadIdx.x & 63)];
-        b = (b == b) ? b : __uint_as_float(0x7f800000u);
-    }
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) b = fmaxf(b, __shfl_xor(b, o));
+// value of the lane CTRL points at inside this lane's 16-lane row, through DPP: a move on the vector ALU (hipcc folds it into the
+// consuming v_add / v_max), where __shfl_xor goes through the LDS crossbar (ds_bpermute_b32 + lgkmcnt wait).  row_ror:k = 0x120 + k
+// reads lane (l - k) mod 16 of the row.
+#define EOD_DPP_ROW_ROR(k) (0x120 + (k))
+template <int CTRL> __device__ __forceinline__ float dpp_row_f(float x) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), CTRL, 0xF, 0xF, true));
+}
+// Maximum of image n's EOD_AB table entries, wave-uniform (every lane of the wave must call); NaN entries count as +inf.  In two
+// parts, so that a kernel can have the load in flight beside its first DMA: ab_bound_issue is ONE unconditional buffer load (exact
+// num_records: lanes 32 .. 63, and every lane of a null table, read zeros and touch no memory), ab_bound_finish the reduction:
+// rotations by 8, 4, 2, 1 inside the 16-lane rows (a maximum does not depend on the order), then the two rows that hold entries.
+__device__ __forceinline__ float ab_bound_issue(const float* __restrict__ ab, long long n) {
+    const __amdgpu_buffer_rsrc_t rs =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ab ? ab + n * EOD_AB : ab), 0, ab ? EOD_AB * 4 : 0, 0x00020000);
+    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, (int)(threadIdx.x & 63) * 4, 0, 0));
+}
+__device__ __forceinline__ float ab_bound_nan(float b) { return (b == b) ? b : __uint_as_float(0x7f800000u); }  // NaN -> +inf
+__device__ __forceinline__ float ab_bound_finish(float b) {
+    b = ab_bound_nan(b);
+    b = fmaxf(b, dpp_row_f<EOD_DPP_ROW_ROR(8)>(b));
+    b = fmaxf(b, dpp_row_f<EOD_DPP_ROW_ROR(4)>(b));
+    b = fmaxf(b, dpp_row_f<EOD_DPP_ROW_ROR(2)>(b));
+    b = fmaxf(b, dpp_row_f<EOD_DPP_ROW_ROR(1)>(b));
+    // lane 0 holds row 0's maximum, lane 16 row 1's; 0 is what the lanes behind the table hold.  The result leaves through
+    // readfirstlane: a scalar, so that the scales derived from it live in scalar registers
+    const float r1 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(b), 16));
+    b = fmaxf(fmaxf(b, r1), 0.0f);
     return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(b)));
 }
+__device__ __forceinline__ float ab_wave_bound(const float* __restrict__ ab, long long n) { return ab_bound_finish(ab_bound_issue(ab, n)); }
 
 // SiLU (nn.SiLU, unet_openai.py:314,330,338): precise form for the fp32 parity mode, fast form
 // (v_exp_f32 + v_rcp_f32) for the fp16 mode where the result is rounded to 11 bits anyway.

@@ -587,34 +587,50 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmP& p, const TileGeom& 
 // (channel = 16 j + 4 (lane >> 4) + r, pixel = 16 i + (lane & 15)), i.e. a 16-byte piece of an NHWC row.  The epilogue stores straight
 // from the accumulators: no LDS transpose (2.8 us of VALU per workgroup on the transposed path, tools/debug/halo_stamps.py), no LDS at
 // all -- the operand ring is free while it runs.  Per-channel terms (bias + per-sample bias) come as 4 x TN values fetched at entry.
+// They are fetched in two parts.  edge_issue: 3 x TN UNCONDITIONAL 16-byte buffer loads, back to back, with nothing that consumes them
+// -- the kernels issue them BEHIND the DMA of their first chunk, so that one round trip covers them all (as plain loads at entry, each
+// inside its `if`, they were a chain of dependent round trips in front of the first DMA).  The three tables get descriptors with exact
+// num_records: a quad behind `ncols` (Cout is a multiple of the 16-byte chunk: a quad is inside or outside as a whole) and every quad
+// of an absent table (0 records on whatever base) read zeros and touch no memory.  edge_finish, behind the wait that drained them:
+// bias, then + per-sample bias where there is one (an absent bias is the +0 the sum started from; no addition where there was none).
 template <int TN>
-__device__ __forceinline__ void prefetch_bcol4(const IgemmP& p, int ncols, int col0, int lane, int n_first, f32x4 (&out)[TN]) {
+struct EdgeRaw {
+    f32x4 b[TN], cb[TN];
+    i32x4 we[TN];  // row exponents of the split weights for the same quads (d_j <= 100)
+    float ab, skb;  // this lane's raw entry of the activation bound table(s) (common.h)
+};
+template <int TN>
+__device__ __forceinline__ void edge_issue(const IgemmP& p, int ncols, int col0, int wrow0, int lane, int n_first, EdgeRaw<TN>& r) {
     const int lg = lane >> 4;
+    const bool hb = p.bias && p.bias_mode == 1;
+    const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.bias), 0, hb ? ncols * 4 : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(p.cbias ? p.cbias + (long long)n_first * p.cbias_stride : p.cbias), 0, p.cbias ? ncols * 4 : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rw =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<int*>(p.w_rexp ? p.w_rexp + wrow0 : p.w_rexp), 0, p.w_rexp ? ncols * 4 : 0, 0x00020000);
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
-        const int c = col0 + j * 16 + 4 * lg;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (c < ncols) {  // (Cout is a multiple of the 16-byte chunk: a quad is inside or outside as a whole)
-            if (p.bias && p.bias_mode == 1) v = *reinterpret_cast<const f32x4*>(p.bias + c);
-            if (p.cbias) v += *reinterpret_cast<const f32x4*>(p.cbias + (long long)n_first * p.cbias_stride + c);
-        }
-        out[j] = v;
+        const int v = (col0 + j * 16 + 4 * lg) * 4;
+        r.b[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rb, v, 0, 0));
+        r.cb[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rc, v, 0, 0));
+        r.we[j] = __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, v, 0, 0));
     }
 }
-
-// row exponents of the split weights for the same quads, four bytes per quad (d_j <= 100): one register per channel tile through the K loop
+// (the empty asm statements pin the arithmetic from both sides: behind the caller's s_waitcnt vmcnt(0), itself an asm -- hipcc would
+//  otherwise be free to move it, and a wait of its own, up to the loads -- and in front of the K loop: left alone, hipcc sinks the sums
+//  and the byte pack into the epilogue, their only reader, and carries the 12 raw registers per channel tile through the loop in place
+//  of the 5 finished ones: +28 registers on the 4 x 4 instances, scratch on the GroupNorm + split ones)
 template <int TN>
-__device__ __forceinline__ void prefetch_wexp4(const IgemmP& p, int ncols, int col0, int wrow0, int lane, int (&out)[TN]) {
-    const int lg = lane >> 4;
+__device__ __forceinline__ void edge_finish(const IgemmP& p, EdgeRaw<TN>& r, f32x4 (&bq)[TN], int (&we)[TN]) {
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
-        const int c = col0 + j * 16 + 4 * lg;
-        int pk = 0;
-        if (p.w_rexp && c < ncols) {
-            const i32x4 e = *reinterpret_cast<const i32x4*>(p.w_rexp + wrow0 + c);
-            pk = e[0] | (e[1] << 8) | (e[2] << 16) | (e[3] << 24);
-        }
-        out[j] = pk;
+        asm volatile("" : "+v"(r.b[j]), "+v"(r.cb[j]), "+v"(r.we[j]));
+        f32x4 v = r.b[j];
+        if (p.cbias) v += r.cb[j];
+        bq[j] = v;
+        const i32x4 e = r.we[j];
+        we[j] = e[0] | (e[1] << 8) | (e[2] << 16) | (e[3] << 24);  // four bytes per quad: one register per channel tile through the K loop
+        asm volatile("" : "+v"(bq[j]), "+v"(we[j]));
     }
 }
 
@@ -691,14 +707,20 @@ __device__ __forceinline__ void halo_epilogue_direct(const IgemmP& p, const Tile
                 sq += v * v;
             }
             if (want_stats) {
-                // per-channel sums over the wave's WM pixels: the TM pixel tiles in-lane (above), then the 16 lanes that share lg
+                // per-channel sums over the wave's WM pixels: the TM pixel tiles in-lane (above), then the 16 lanes that share lg -- one DPP
+                // row.  The butterfly's partner lane ^ k is reached by ROTATING the row by k = 8, 4, 2, 1: behind the step by 8 the sums are
+                // 8-periodic inside the row, then 4-, then 2-periodic, so lane (l - k) mod 16 holds the very value lane l ^ k does, and every
+                // lane adds the same two numbers as before (same bits), on the vector ALU, without the crossbar round trip of ds_bpermute
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-#pragma unroll
-                    for (int o = 8; o >= 1; o >>= 1) {
-                        ss[r] += __shfl_xor(ss[r], o);
-                        sq[r] += __shfl_xor(sq[r], o);
-                    }
+                    ss[r] += dpp_row_f<EOD_DPP_ROW_ROR(8)>(ss[r]);
+                    sq[r] += dpp_row_f<EOD_DPP_ROW_ROR(8)>(sq[r]);
+                    ss[r] += dpp_row_f<EOD_DPP_ROW_ROR(4)>(ss[r]);
+                    sq[r] += dpp_row_f<EOD_DPP_ROW_ROR(4)>(sq[r]);
+                    ss[r] += dpp_row_f<EOD_DPP_ROW_ROR(2)>(ss[r]);
+                    sq[r] += dpp_row_f<EOD_DPP_ROW_ROR(2)>(sq[r]);
+                    ss[r] += dpp_row_f<EOD_DPP_ROW_ROR(1)>(ss[r]);
+                    sq[r] += dpp_row_f<EOD_DPP_ROW_ROR(1)>(sq[r]);
                 }
                 if (lp == 0) {
                     float* dst = p.stats + (((long long)g.n_first * p.stats_P + slot) * p.Cout + c) * 2;
@@ -750,15 +772,12 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void igemm_kernel(const 
     if constexpr (CONV) {
         if (p.splitk > 1) pe.y = p.y + (long long)blockIdx.y * p.M * p.Cout * 4;
     }
-    // direct-epilogue instances: the per-column epilogue terms are fetched at entry (their latency passes under the first DMA round
-    // trip instead of standing between the last MFMA and the first store)
+    // direct-epilogue instances: the per-column epilogue terms are loaded behind the DMA of the first K-step (edge_issue: one round trip
+    // beside the DMA's own instead of standing between the last MFMA and the first store) and combined behind the first step's wait
     constexpr int TNQ = DIRECT ? BN / WAVES_N / 16 : 1;
     f32x4 pre_bq[TNQ];
     int pre_we[TNQ];
-    if constexpr (DIRECT) {
-        prefetch_bcol4<TNQ>(p, p.Ncols, n0 + (wave % WAVES_N) * (BN / WAVES_N), threadIdx.x & 63, g.n_first, pre_bq);
-        prefetch_wexp4<TNQ>(p, p.Ncols, n0 + (wave % WAVES_N) * (BN / WAVES_N), p.w_row0, threadIdx.x & 63, pre_we);
-    }
+    EdgeRaw<TNQ> eraw;
     // split-fp16 product: operand scales of the activation operand(s) from their bound tables (common.h).  conv: one scale per image;
     // a tile normally lies inside one image (always in patch mode) -> wave-uniform as0; a tile that straddles images (maps smaller
     // than or not a multiple of the 128-row tile) keeps a table of its images' scales in LDS: rows are scaled and un-scaled one by one.
@@ -1009,6 +1028,12 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void igemm_kernel(const 
 #pragma unroll
     for (int ps = 0; ps < STAGES - 1; ++ps)
         if (ps < KT) issue_loads(ps);
+    if constexpr (DIRECT) {
+        // (the wait is the first K-step's own, taken early: nothing younger than that step's DMA is in flight with two stages)
+        edge_issue<TNQ>(p, p.Ncols, n0 + (wave % WAVES_N) * (BN / WAVES_N), p.w_row0, threadIdx.x & 63, g.n_first, eraw);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        edge_finish<TNQ>(p, eraw, pre_bq, pre_we);
+    }
 
     for (int kt = 0; kt < KT; ++kt) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1242,32 +1267,50 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
     map_tile(p, tile_m, tile_n);
     const int n0 = p.n_base + tile_n * BN;
     const TileGeom g = make_geom<true, BM>(p, tile_m);  // patch mode: ty0, tx0, n_first
-    // epilogue operands fetched NOW (their latency passes under the prologue's DMA; older than every DMA, so the counted vmcnt waits of
-    // the loop are unaffected): per-column bias terms and the weights' scale
+    // Epilogue operands (per-column bias terms, the weights' row exponents) and the activation bound table(s).  Split instances: NOTHING
+    // is loaded here.  edge_loads() issues them all, unconditionally and back to back, in the prologue BEHIND the DMA of the first chunk
+    // and the first weight tile, and edge_ready() consumes them behind the prologue's s_waitcnt vmcnt(0): they are younger than the
+    // prologue's DMA, older than every DMA of the loop, and drained by that one wait together with the DMA -- one round trip beside the
+    // DMA's own instead of a chain of dependent ones in front of it; the counted vmcnt waits of the loop see none of them.  (Every split
+    // instance rewrites chunk 0 in place and has that wait; the fp16-storage instances fetch their terms here as before.)
     float pre_bcol[DIRECT ? 1 : TN];
     f32x4 pre_bq[DIRECT ? TN : 1];
     int pre_we[DIRECT ? TN : 1];
-    if constexpr (DIRECT) {
-        prefetch_bcol4<TN>(p, p.Ncols, n0 + wn * WN, lane, g.n_first, pre_bq);
-        prefetch_wexp4<TN>(p, p.Ncols, n0 + wn * WN, p.w_row0, lane, pre_we);
-    } else {
-        prefetch_bcol<TN, MS>(p, p.Ncols, n0 + wn * WN, lane, g.n_first, pre_bcol);
-    }
+    EdgeRaw<DIRECT ? TN : 1> eraw;
+    if constexpr (!DIRECT) prefetch_bcol<TN, MS>(p, p.Ncols, n0 + wn * WN, lane, g.n_first, pre_bcol);
     float wsc1 = 1.0f;
     if constexpr (SPLIT) wsc1 = p.w_scale[1];
     // split-fp16 product: power-of-two operand scale of this tile's image from the bound table(s) (wave-uniform, common.h); the fused
     // skip conv shares the accumulators, so the launch runs on the smaller of the two tensors' scales
     AbScale asc = {EOD_SPLIT_ASCALE, 1.0f};
     const float silu_k = p.gn_silu ? -1.44269504088896341f : 0.0f, silu_c = p.gn_silu ? 0.0f : -__builtin_inff();  // (see xf_finish)
-    if constexpr (SPLIT) {
-        if (p.a_bound) asc = ab_scale_of(ab_wave_bound(p.a_bound, g.n_first));
-        if constexpr (SKIP) {
-            if (p.skip_bound) {
-                const AbScale k = ab_scale_of(ab_wave_bound(p.skip_bound, g.n_first));
-                if (k.s < asc.s) asc = k;
-            }
+    auto edge_loads = [&]() {
+        if constexpr (DIRECT) edge_issue<TN>(p, p.Ncols, n0 + wn * WN, p.w_row0, lane, g.n_first, eraw);
+        if constexpr (SPLIT) {
+            eraw.ab = ab_bound_issue(p.a_bound, g.n_first);
+            if constexpr (SKIP) eraw.skb = ab_bound_issue(p.skip_bound, g.n_first);
         }
-    }
+    };
+    auto edge_ready = [&]() {  // (first use of the scale: chunk 0's rewrite)
+        if constexpr (DIRECT) edge_finish<TN>(p, eraw, pre_bq, pre_we);
+        if constexpr (SPLIT && SKIP) {
+            asm volatile("" : "+v"(eraw.ab), "+v"(eraw.skb));
+            if (p.a_bound && p.skip_bound) {
+                // the smaller of the two scales is the scale of the larger bound (ab_scale_of falls with the bound's exponent): one
+                // reduction over the entry-wise maximum of the two tables
+                asc = ab_scale_of(ab_bound_finish(fmaxf(ab_bound_nan(eraw.ab), ab_bound_nan(eraw.skb))));
+            } else {
+                if (p.a_bound) asc = ab_scale_of(ab_bound_finish(eraw.ab));
+                if (p.skip_bound) {
+                    const AbScale k = ab_scale_of(ab_bound_finish(eraw.skb));
+                    if (k.s < asc.s) asc = k;
+                }
+            }
+        } else if constexpr (SPLIT) {
+            asm volatile("" : "+v"(eraw.ab));
+            if (p.a_bound) asc = ab_scale_of(ab_bound_finish(eraw.ab));
+        }
+    };
 
     // ---- patch pieces of this wave: group gi = wr + RW*i, patch row = gi*8 + (lane>>3), slot = lane&7 ----
     const int srow = lane >> 3, sslot = lane & 7;
@@ -1540,7 +1583,9 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
             }
             weight_offsets(c0, bve);
             issue_weight_tile(0, c0, bve[0], sB, wm * (LBR / 2), (wm + 1) * (LBR / 2));
+            edge_loads();
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            edge_ready();
             if constexpr (GN) __builtin_amdgcn_s_barrier();  // wave 0's scale/shift table is visible
 #pragma unroll
             for (int i = 0; i < LAH; ++i)
@@ -1556,7 +1601,9 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
         issue_weights(0, c0, sB);
         if constexpr (XF) {
             // chunk 0: everything has to land before the first tap anyway; normalise / split the own pieces now
+            edge_loads();
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            edge_ready();
             if constexpr (GN) __builtin_amdgcn_s_barrier();  // wave 0's scale/shift table is visible
 #pragma unroll
             for (int i = 0; i < LAH; ++i)
@@ -1949,21 +1996,15 @@ __global__ __launch_bounds__(256, 2) void conv_up4_halo_kernel(const IgemmP p) {
     const int cls = BWD ? 0 : tile_nn / tpc, n0 = (BWD ? 0 : p.n_base) + (tile_nn - cls * tpc) * BN;  // (n_base: the last 128 of 256 + 128 columns)
     const int par_y = cls >> 1, par_x = cls & 1;        // (forward: the workgroup's class; backward: classes rotate inside the K loop)
     const TileGeom g = make_geom<true, BM>(p, tile_m);  // patch mode on the STORED map: ty0, tx0, n_first
-    float pre_bcol[DIRECT ? 1 : TN];  // epilogue operands fetched at entry (see conv3x3_halo_kernel)
+    // epilogue operands and the bound table: split instances load them in the prologue, behind chunk 0's DMA (see conv3x3_halo_kernel)
+    float pre_bcol[DIRECT ? 1 : TN];
     f32x4 pre_bq[DIRECT ? TN : 1];
     int pre_we[DIRECT ? TN : 1];
-    if constexpr (DIRECT) {
-        prefetch_bcol4<TN>(p, p.Cout, n0 + wn * WN, lane, g.n_first, pre_bq);
-        prefetch_wexp4<TN>(p, p.Cout, n0 + wn * WN, cls * p.Cout, lane, pre_we);  // (class kernels: weight row = class * Cout + column)
-    } else {
-        prefetch_bcol<TN, MS>(p, p.Cout, n0 + wn * WN, lane, g.n_first, pre_bcol);
-    }
+    EdgeRaw<DIRECT ? TN : 1> eraw;
+    if constexpr (!DIRECT) prefetch_bcol<TN, MS>(p, p.Cout, n0 + wn * WN, lane, g.n_first, pre_bcol);
     float wsc1 = 1.0f;
     if constexpr (SPLIT) wsc1 = p.w_scale[1];
     AbScale asc = {EOD_SPLIT_ASCALE, 1.0f};             // split-fp16 product: operand scale of this tile's image (see conv3x3_halo_kernel)
-    if constexpr (SPLIT) {
-        if (p.a_bound) asc = ab_scale_of(ab_wave_bound(p.a_bound, g.n_first));
-    }
 
     const int srow = lane >> 3, sslot = lane & 7;
     unsigned ppix[LAH];
@@ -2085,7 +2126,13 @@ __global__ __launch_bounds__(256, 2) void conv_up4_halo_kernel(const IgemmP p) {
             if ((wave + NW * i) < PG) issue_patch_piece(i, ch0, sA);
         issue_weights(0, ch0, sB);
         if constexpr (SPLIT) {
+            // (class kernels: weight row = class * Cout + column)
+            if constexpr (DIRECT) edge_issue<TN>(p, p.Cout, n0 + wn * WN, cls * p.Cout, lane, g.n_first, eraw);
+            eraw.ab = ab_bound_issue(p.a_bound, g.n_first);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if constexpr (DIRECT) edge_finish<TN>(p, eraw, pre_bq, pre_we);
+            asm volatile("" : "+v"(eraw.ab));
+            if (p.a_bound) asc = ab_scale_of(ab_bound_finish(eraw.ab));
 #pragma unroll
             for (int i = 0; i < LAH; ++i)
                 if ((wave + NW * i) < PG) split_piece(i, sA);
@@ -2268,13 +2315,11 @@ __global__ __launch_bounds__(512, 1) void conv_up4_halo_kernel(const IgemmP p) {
     const int cls = tile_nn / tpc, n0 = (tile_nn - cls * tpc) * BN;
     const int par_y = cls >> 1, par_x = cls & 1;
     const TileGeom g = make_geom<true, BM>(p, tile_m);  // patch mode on the STORED map: ty0, tx0, n_first
-    f32x4 pre_bq[TN];                  // epilogue operands fetched at entry (see conv3x3_halo_kernel)
+    f32x4 pre_bq[TN];                  // epilogue operands and the bound table: loaded in the prologue, behind chunk 0's DMA (see conv3x3_halo_kernel)
     int pre_we[TN];
-    prefetch_bcol4<TN>(p, p.Ncols, n0 + wn * WN, lane, g.n_first, pre_bq);
-    prefetch_wexp4<TN>(p, p.Ncols, n0 + wn * WN, cls * p.Cout, lane, pre_we);  // (class kernels: weight row = class * Cout + column)
+    EdgeRaw<TN> eraw;
     const float wsc1 = p.w_scale[1];
     AbScale asc = {EOD_SPLIT_ASCALE, 1.0f};
-    if (p.a_bound) asc = ab_scale_of(ab_wave_bound(p.a_bound, g.n_first));
 
     const int srow = lane >> 3, sslot = lane & 7;
     unsigned ppix[LAH];
@@ -2364,7 +2409,12 @@ __global__ __launch_bounds__(512, 1) void conv_up4_halo_kernel(const IgemmP p) {
         for (int i = 0; i < LAH; ++i)
             if ((i >= 3) == (wm != 0)) issue_patch_piece(i, ch0, sA);
         issue_weight_tile(0, ch0, sB, wm * (LBR / 2), (wm + 1) * (LBR / 2));
+        edge_issue<TN>(p, p.Ncols, n0 + wn * WN, cls * p.Cout, lane, g.n_first, eraw);  // (class kernels: weight row = class * Cout + column)
+        eraw.ab = ab_bound_issue(p.a_bound, g.n_first);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        edge_finish<TN>(p, eraw, pre_bq, pre_we);
+        asm volatile("" : "+v"(eraw.ab));
+        if (p.a_bound) asc = ab_scale_of(ab_bound_finish(eraw.ab));
 #pragma unroll
         for (int i = 0; i < LAH; ++i)
             if ((i >= 3) == (wm != 0)) split_piece(i, sA);
@@ -2517,21 +2567,15 @@ __global__ __launch_bounds__(256, 2) void conv_s2_halo_kernel(const IgemmP p) {
     map_tile(p, tile_m, tile_n);
     const int n0 = tile_n * BN;
     const TileGeom g = make_geom<true, BM>(p, tile_m);  // patch mode on the OUTPUT map: ty0, tx0, n_first
-    float pre_bcol[DIRECT ? 1 : TN];  // epilogue operands fetched at entry (see conv3x3_halo_kernel)
+    // epilogue operands and the bound table: the split instance loads them in the prologue, behind chunk 0's DMA (see conv3x3_halo_kernel)
+    float pre_bcol[DIRECT ? 1 : TN];
     f32x4 pre_bq[DIRECT ? TN : 1];
     int pre_we[DIRECT ? TN : 1];
-    if constexpr (DIRECT) {
-        prefetch_bcol4<TN>(p, p.Cout, n0 + wn * WN, lane, g.n_first, pre_bq);
-        prefetch_wexp4<TN>(p, p.Cout, n0 + wn * WN, 0, lane, pre_we);
-    } else {
-        prefetch_bcol<TN, MS>(p, p.Cout, n0 + wn * WN, lane, g.n_first, pre_bcol);
-    }
+    EdgeRaw<DIRECT ? TN : 1> eraw;
+    if constexpr (!DIRECT) prefetch_bcol<TN, MS>(p, p.Cout, n0 + wn * WN, lane, g.n_first, pre_bcol);
     float wsc1 = 1.0f;
     if constexpr (SPLIT) wsc1 = p.w_scale[1];
     AbScale asc = {EOD_SPLIT_ASCALE, 1.0f};  // split-fp16 product: operand scale of this tile's image (see conv3x3_halo_kernel)
-    if constexpr (SPLIT) {
-        if (p.a_bound) asc = ab_scale_of(ab_wave_bound(p.a_bound, g.n_first));
-    }
 
     // per-lane patch rows: piece i of this wave = patch rows (wave + NW i) * 8 .. + 7, lane = (row srow, 16-byte slot sslot)
     const int srow = lane >> 3, sslot = lane & 7;
@@ -2674,7 +2718,12 @@ __global__ __launch_bounds__(256, 2) void conv_s2_halo_kernel(const IgemmP p) {
         for (int i = 0; i < LAH; ++i) issue_patch_piece(i, 0, 0, sA);
         issue_weights(tap_slot(0, 0), 0, sB);
         if constexpr (SPLIT) {
+            edge_issue<TN>(p, p.Cout, n0 + wn * WN, 0, lane, g.n_first, eraw);
+            eraw.ab = ab_bound_issue(p.a_bound, g.n_first);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            edge_finish<TN>(p, eraw, pre_bq, pre_we);
+            asm volatile("" : "+v"(eraw.ab));
+            if (p.a_bound) asc = ab_scale_of(ab_bound_finish(eraw.ab));
 #pragma unroll
             for (int i = 0; i < LAH; ++i) split_piece(i, sA);
         }
@@ -3078,22 +3127,27 @@ __global__ __launch_bounds__(256, 3) void conv_first_x3_kernel(const IgemmP p) {
     const TileGeom g = make_geom<true, BM>(p, tile_m);
     f32x4 pre_bq[TN];
     int pre_we[TN];
-    prefetch_bcol4<TN>(p, p.Ncols, n0 + wn * 64, lane, g.n_first, pre_bq);
-    prefetch_wexp4<TN>(p, p.Ncols, n0 + wn * 64, 0, lane, pre_we);
+    // the bound table's entry, the epilogue operands and the patch pixel are loaded back to back (unconditional buffer loads: see
+    // edge_issue), so that one round trip covers them; the bound is the oldest and is consumed first, the epilogue operands behind the patch
+    EdgeRaw<TN> eraw;
+    eraw.ab = ab_bound_issue(p.a_bound, g.n_first);
+    edge_issue<TN>(p, p.Ncols, n0 + wn * 64, 0, lane, g.n_first, eraw);
     const float wsc1 = p.w_scale[1];
     AbScale asc = {EOD_SPLIT_ASCALE, 1.0f};
-    if (p.a_bound) asc = ab_scale_of(ab_wave_bound(p.a_bound, g.n_first));
 
     // ---- the patch: one pixel per thread, scaled and split on the way into LDS (zeros outside the image = the conv's padding) ----
+    f32x4 a = {0.f, 0.f, 0.f, 0.f}, c = {0.f, 0.f, 0.f, 0.f};
     if (tid < PR) {
         const int py = tid / PW, px = tid - py * PW;
         const int hi = g.ty0 - 1 + py, wi = g.tx0 - 1 + px;
-        f32x4 a = {0.f, 0.f, 0.f, 0.f}, c = {0.f, 0.f, 0.f, 0.f};
         if ((unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W) {
             const float* src = reinterpret_cast<const float*>(p.a0) + (((long long)g.n_first * p.H + hi) * p.W + wi) * CP;
             a = *reinterpret_cast<const f32x4*>(src);
             if constexpr (CP == 8) c = *reinterpret_cast<const f32x4*>(src + 4);
         }
+    }
+    if (p.a_bound) asc = ab_scale_of(ab_bound_finish(eraw.ab));  // (every lane of the wave: outside the patch's branch)
+    if (tid < PR) {
         int ha[2], la[2];
         split4_scaled(a, asc.s, ha, la);
         if constexpr (CP == 4) {
@@ -3108,6 +3162,7 @@ __global__ __launch_bounds__(256, 3) void conv_first_x3_kernel(const IgemmP p) {
         *reinterpret_cast<i32x4*>(sP + ZOFF + (tid - PR) * 16) = i32x4{0, 0, 0, 0};
     }
     __syncthreads();
+    edge_finish<TN>(p, eraw, pre_bq, pre_we);
 
     const int lp = lane & 15, kgl = lane >> 4;
     const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.b), 0, p.Cout * p.ldk * 4, 0x00020000);

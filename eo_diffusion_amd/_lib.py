@@ -220,6 +220,15 @@ PARAM_SYMBOLS = {
     "eod_q_sample_v": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i64, i32, vp]),
 }
 
+# every symbol include/eodiff_var.h declares (the learned-variance kernels; eodiff.h includes that header)
+VAR_SYMBOLS = {
+    "eod_ddpm_var_pred": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, i32, i64, i32, vp]),
+    "eod_ddpm_step_p0_var": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, i32, vp]),
+    "eod_hybrid_loss_workspace_size": (i64, [i32, i32, i32, i32]),
+    "eod_hybrid_loss": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, f64, f64, vp, vp,
+                              vp, vp, vp, i64, vp]),
+}
+
 _lib = None
 
 
@@ -246,7 +255,7 @@ def lib():
     import torch  # noqa: F401
     L = C.CDLL(LIB_PATH)
     abi_any = os.environ.get("EOD_ABI_ANY", "0") == "1"
-    for name, (res, args) in {**SYMBOLS, **PARAM_SYMBOLS}.items():
+    for name, (res, args) in {**SYMBOLS, **PARAM_SYMBOLS, **VAR_SYMBOLS}.items():
         if abi_any and not hasattr(L, name):  # (A/B tooling: an older build knows no entry point added since)
             continue
         fn = getattr(L, name)  # AttributeError if the .so does not export a declared symbol

@@ -18,6 +18,9 @@
 // (the bodies of the x0 / v prediction kernels at the end of the chain section)
 #define PARAM_FN __device__ __host__ __forceinline__
 #include "param_body.h"
+// (the bodies of the learned-variance prediction and step kernels after them)
+#define VAR_FN __device__ __host__ __forceinline__
+#include "var_body.h"
 
 // Caller-supplied timesteps index the schedule tables: an index outside [0, T) would read behind them (the reference's gather
 // raises there).  Such a sample is computed with index 0 and its whole output is poisoned with NaN -- loud, but memory-safe.
@@ -1228,6 +1231,59 @@ extern "C" int eod_q_sample_v(const float* x0, const float* noise, const int64_t
     EOD_REQUIRE(t && sqrt_acp && sqrt_1m_acp && v && T > 0, "q_sample_v: bad args");
     ParamArgs g = {x0, noise, (const long long*)t, sqrt_acp, sqrt_1m_acp, 0.0f, 0.0f, x_t, v, N, (long long)chw, T, PARAM_V, 0};
     return param_launch<true>("q_sample_v", g, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Learned variance: the model output is [N][2][chw], mean half and variance half, both read in place with a sample
+// stride of 2 * chw.  eod_ddpm_var_pred is eod_ddpm_pred_x0 / eod_ddpm_param_pred on the mean half, eod_ddpm_step_p0_var is
+// eod_ddpm_step_p0 with sigma = sigma_min[t] * expf(((v + 1) * 0.5) * half_gap[t]) per element.  The bodies are var_body.h (a host program
+// compiles them, too).  Streaming kernels in ddpm_p0_kernel's shape.
+// ---------------------------------------------------------------------------------------------
+template <bool STEP, bool VEC>
+__global__ void __launch_bounds__(256) var_kernel(VarArgs g) {
+    const long long first = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
+    if (STEP) var_step_thread<VEC>(g, blockIdx.y, first, stride);
+    else var_pred_thread<VEC>(g, blockIdx.y, first, stride);
+}
+
+template <bool STEP>
+static int var_launch(const char* what, const VarArgs& g, void* stream) {
+    EOD_REQUIRE(g.x && g.o && g.t && g.out && g.N > 0 && g.chw > 0 && g.T > 0, "%s: bad args", what);
+    const long long n = (long long)g.N * g.chw;
+    const float* const tensors[3] = {g.x, g.p0c, g.z};
+    const float* const tables[7] = {g.betas, g.alphas, g.acp, g.sa_tab, g.s1_tab, g.sigma_min, g.half_gap};
+    bool vec = g.chw % 4 == 0 && eod_aligned16(g.out) && eod_aligned16(g.o);
+    EOD_REQUIRE(!eod_overlap2(g.out, n, g.o, 2 * n), "%s: the output overlaps the model output", what);
+    for (const float* p : tensors) {
+        if (!p) continue;
+        EOD_REQUIRE(!eod_overlap2(g.out, n, p, n), "%s: the output overlaps an input", what);
+        vec = vec && eod_aligned16(p);
+    }
+    for (const float* p : tables) EOD_REQUIRE(!p || !eod_overlap2(g.out, n, p, g.T), "%s: the output overlaps a table", what);
+    EOD_REQUIRE(!eod_overlap2(g.out, n, reinterpret_cast<const float*>(g.t), 2LL * g.N), "%s: the output overlaps t", what);
+    const dim3 grid(blocks_for((g.chw + 3) / 4, 2048), g.N), block(256);
+    if (vec) hipLaunchKernelGGL((var_kernel<STEP, true>), grid, block, 0, (hipStream_t)stream, g);
+    else hipLaunchKernelGGL((var_kernel<STEP, false>), grid, block, 0, (hipStream_t)stream, g);
+    EOD_CHECK_LAUNCH(what);
+    return EOD_OK;
+}
+
+extern "C" int eod_ddpm_var_pred(const float* x_t, const float* o, const int64_t* t, const float* acp, const float* sqrt_acp,
+                                 const float* sqrt_1m_acp, int kind, int clip, float* p0, int N, int64_t chw, int T, void* stream) {
+    EOD_REQUIRE(kind >= PARAM_EPS && kind <= PARAM_V, "ddpm_var_pred: kind is 0 (eps), 1 (x0) or 2 (v), got %d", kind);
+    EOD_REQUIRE(kind == PARAM_EPS ? acp != nullptr : (sqrt_acp && sqrt_1m_acp), "ddpm_var_pred: bad args (a table of this kind is null)");
+    VarArgs g = {x_t, o, nullptr, nullptr, (const long long*)t, nullptr, nullptr, kind == PARAM_EPS ? acp : nullptr,
+                 kind == PARAM_EPS ? nullptr : sqrt_acp, kind == PARAM_EPS ? nullptr : sqrt_1m_acp, nullptr, nullptr, p0, N, (long long)chw, T, kind,
+                 clip};
+    return var_launch<false>("ddpm_var_pred", g, stream);
+}
+
+extern "C" int eod_ddpm_step_p0_var(const float* x_t, const float* p0, const float* o, const float* noise, const int64_t* t, const float* betas,
+                                    const float* alphas, const float* acp, const float* sigma_min, const float* half_gap, float* out, int N,
+                                    int64_t chw, int T, void* stream) {
+    EOD_REQUIRE(p0 && noise && betas && alphas && acp && sigma_min && half_gap, "ddpm_step_p0_var: bad args");
+    VarArgs g = {x_t, o, p0, noise, (const long long*)t, betas, alphas, acp, nullptr, nullptr, sigma_min, half_gap, out, N, (long long)chw, T, 0, 0};
+    return var_launch<true>("ddpm_step_p0_var", g, stream);
 }
 
 extern "C" int eod_cfg_combine(const float* e_uncond, const float* e_cond, float scale, float* out, int64_t numel, void* stream) {

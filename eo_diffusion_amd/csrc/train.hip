@@ -16,6 +16,11 @@
 // Everything here is HBM-bound elementwise / reduction work: 16-byte accesses, fixed-order sums, no atomics.
 #include "common.h"
 #include "met_sum.h"
+// (the float64 variational-bound term of eod_hybrid_loss; the header's sampling bodies are not used here)
+#define DDPM_P0_FN __device__ __host__ __forceinline__
+#define PARAM_FN __device__ __host__ __forceinline__
+#define VAR_FN __device__ __host__ __forceinline__
+#include "var_body.h"
 
 template <typename T> __device__ __forceinline__ T cvt_to(float v) { return (T)v; }
 __device__ __forceinline__ float wave_sum_t(float v) {
@@ -1247,6 +1252,201 @@ extern "C" int eod_diffusion_loss(const float* pred, const float* target, const 
     if (rc != EOD_OK) return rc;
     hipLaunchKernelGGL(dloss_final_kernel, dim3(1), dim3(64), 0, st, (const double*)sums, mask ? (const double*)S : nullptr, s_mul, mask_nstride ? 1 : 0,
                        (double)E, weight, N, loss, per_sample);
+    EOD_CHECK_LAUNCH(what);
+    return EOD_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The hybrid objective of a learned-variance model (Nichol & Dhariwal 2021): L = L_simple + lambda L_vlb in one
+// fused pass over o [N][2][E] (mean half, variance half, read in place), target, x_0, x_t [N][E].  The simple term and the mean half of the
+// gradient are dloss_kernel's statements on the mean half (its bits); the variational-bound term of an element is var_vlb_element of
+// var_body.h, float64, with the mean detached, and its gradient goes to the variance half.  Two float64 sums per workgroup (met_reduce<2>),
+// one slot pair per (sample, chunk), met_fold per sample: the discipline of met_sum.h.  grid (chunks of a sample, N): every workgroup
+// belongs to one sample, so the t = 0 / t > 0 branch is uniform within it.
+// ---------------------------------------------------------------------------------------------
+struct HybridArgs {
+    const float* o;
+    const float* target;
+    const float* x0;
+    const float* xt;
+    const long long* t;
+    const float* mask;
+    const float* weight;
+    const float* sa_tab;
+    const float* s1_tab;
+    const double* c1;
+    const double* lmin;
+    const double* gap;
+    const double* S;
+    double s_mul, lambda, h;
+    long long E, Em, mask_nstride;
+    int N, T, param_kind;
+    float delta;
+    float* grad;
+    double* part;
+};
+
+template <int KIND, bool MASK>
+__global__ void __launch_bounds__(BST_THREADS) hybrid_kernel(const HybridArgs g) {
+    __shared__ double red[2 * BST_THREADS];
+    const int t = threadIdx.x, n = blockIdx.y;
+    const long long E = g.E, e0 = (long long)blockIdx.x * BST_CHUNK + t;
+    const float* op = g.o + 2LL * n * E;
+    const float* vp = op + E;
+    const float* tp = g.target + (long long)n * E;
+    const float* x0p = g.x0 + (long long)n * E;
+    const float* xtp = g.xt + (long long)n * E;
+    const float* mp = MASK ? g.mask + (long long)n * g.mask_nstride : nullptr;
+    const long long tn_raw = g.t[n];
+    const bool bad = tn_raw < 0 || tn_raw >= (long long)g.T;
+    const long long tn = bad ? 0 : tn_raw;
+    VarLevel L;
+    L.sa = (double)g.sa_tab[tn];
+    L.s1 = (double)g.s1_tab[tn];
+    L.c1 = g.c1[tn];
+    L.lmin = g.lmin[tn];
+    L.gap = g.gap[tn];
+    L.t0 = tn == 0;
+    float pv[BST_PER], tv[BST_PER], mv[BST_PER];
+    long long r = MASK ? e0 % g.Em : 0;
+#pragma unroll
+    for (int j = 0; j < BST_PER; ++j) {
+        const long long e = e0 + BST_THREADS * j;
+        const bool in = e < E;
+        pv[j] = in ? op[e] : 0.0f;
+        tv[j] = in ? tp[e] : 0.0f;
+        mv[j] = !in ? 0.0f : (MASK ? mp[r] : 1.0f);
+        if (MASK) {
+            r += BST_THREADS;
+            if (r >= g.Em) r %= g.Em;
+        }
+    }
+    float sn = 0.0f;
+    double vn = 0.0;
+    if (g.grad) {
+        const double Sn = MASK ? g.S[g.mask_nstride ? n : 0] * g.s_mul : (double)E;
+        const double w = g.weight ? (double)g.weight[n] : 1.0;
+        sn = Sn > 0.0 ? (float)(w / ((double)g.N * Sn)) : 0.0f;
+        vn = Sn > 0.0 ? g.lambda / ((double)g.N * Sn) : 0.0;
+    }
+    const double dl = (double)g.delta;
+    double s[2] = {0.0, 0.0};
+    for (int j = 0; j < BST_PER; ++j) {
+        const long long e = e0 + BST_THREADS * j;
+        if (e >= E) break;
+        float gout = 0.0f, gv = 0.0f;
+        if (mv[j] != 0.0f) {  // (m == 0: skipped, not multiplied)
+            const double term = dloss_term<KIND>((double)pv[j] - (double)tv[j], dl);
+            s[0] += MASK ? (double)mv[j] * term : term;
+            const float slope = dloss_slope<KIND>(pv[j] - tv[j], g.delta);
+            gout = (MASK ? sn * mv[j] : sn) * slope;
+            const double p0 = var_p0_64(g.param_kind, (double)xtp[e], (double)pv[j], L.sa, L.s1);
+            double vt, dv;
+            var_vlb_element(L, (double)x0p[e], p0, (double)vp[e], g.h, vt, dv);
+            s[1] += MASK ? (double)mv[j] * vt : vt;
+            gv = (float)((MASK ? vn * (double)mv[j] : vn) * dv);
+        }
+        if (g.grad) {
+            g.grad[2LL * n * E + e] = bad ? __builtin_nanf("") : gout;
+            g.grad[(2LL * n + 1) * E + e] = bad ? __builtin_nanf("") : gv;
+        }
+    }
+    if (bad) s[0] = s[1] = __builtin_nan("");
+    const double v = met_reduce<2, -1>(red, s, t);
+    if ((t & 31) == 0 && t < 64) g.part[((long long)n * gridDim.x + blockIdx.x) * 2 + (t >> 5)] = v;
+}
+
+// simple[n] = L_n, vlb[n] = V_n, loss = (1/N) sum_n (w_n L_n + lambda V_n), the samples added in ascending order
+__global__ void hybrid_final_kernel(const double* __restrict__ sums, const double* __restrict__ S, double s_mul, int s_per_sample, double E,
+                                    const float* __restrict__ weight, double lambda, int N, float* __restrict__ loss, float* __restrict__ simple,
+                                    double* __restrict__ vlb) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double acc = 0.0;
+    for (int n = 0; n < N; ++n) {
+        const double Sn = S ? S[s_per_sample ? n : 0] * s_mul : E;
+        const double Ln = Sn > 0.0 ? sums[2 * n] / Sn : 0.0;
+        const double Vn = Sn > 0.0 ? sums[2 * n + 1] / Sn : 0.0;
+        simple[n] = (float)Ln;
+        vlb[n] = Vn;
+        const double a = (weight ? (double)weight[n] : 1.0) * Ln;
+        const double b = lambda * Vn;
+        acc += a + b;
+    }
+    loss[0] = (float)(acc / (double)N);
+}
+
+extern "C" int64_t eod_hybrid_loss_workspace_size(int N, int C, int H, int W) {
+    if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return -1;
+    const long long chunks = dloss_chunks((long long)C * H * W);
+    return (3LL * N + 2LL * N * chunks + met_fold_extra(N, chunks, 2)) * 8;
+}
+
+static inline bool hybrid_overlap(const void* a, long long abytes, const void* b, long long bbytes) {
+    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+    return a && b && pa < pb + (uintptr_t)bbytes && pb < pa + (uintptr_t)abytes;
+}
+
+extern "C" int eod_hybrid_loss(const float* o, const float* target, const float* x0, const float* x_t, const int64_t* t, const float* mask,
+                               int mask_n, int mask_c, const float* weight, const float* sqrt_acp, const float* sqrt_1m_acp, const double* c1,
+                               const double* lmin, const double* gap, int N, int C, int H, int W, int T, int param_kind, int kind, float delta,
+                               double lambda, double h, float* loss, float* simple, double* vlb, float* grad, void* ws, int64_t ws_bytes,
+                               void* stream) {
+    const char* what = "hybrid_loss";
+    EOD_REQUIRE(o && target && x0 && x_t && t && sqrt_acp && sqrt_1m_acp && c1 && lmin && gap && loss && simple && vlb && ws, "%s: bad args (a null pointer)", what);
+    EOD_REQUIRE(N > 0 && N <= 65535 && C > 0 && H > 0 && W > 0 && T > 0, "%s: bad args (a size)", what);
+    EOD_REQUIRE(kind >= 0 && kind <= 2, "%s: kind %d is none of 0 = l2, 1 = l1, 2 = huber", what, kind);
+    EOD_REQUIRE(param_kind >= 0 && param_kind <= 2, "%s: param_kind %d is none of 0 = eps, 1 = x0, 2 = v", what, param_kind);
+    EOD_REQUIRE(kind != 2 || delta > 0.0f, "%s: huber needs delta > 0, got %g", what, (double)delta);
+    EOD_REQUIRE(lambda == lambda && lambda - lambda == 0.0 && h > 0.0 && h - h == 0.0, "%s: lambda must be finite and h finite and > 0, got %g, %g", what, lambda, h);
+    EOD_REQUIRE(!mask || ((mask_n == 1 || mask_n == N) && (mask_c == 1 || mask_c == C)), "%s: the mask is [N or 1][1 or C][H][W], got [%d][%d]", what,
+                mask_n, mask_c);
+    const long long HW = (long long)H * W, E = (long long)C * HW;
+    EOD_REQUIRE(E < 0x7fffffffLL * BST_CHUNK, "%s: sample too large", what);
+    const int64_t need = eod_hybrid_loss_workspace_size(N, C, H, W);
+    EOD_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 7u) == 0 && ws_bytes >= need,
+                "%s: the workspace must be 8-byte aligned and hold eod_hybrid_loss_workspace_size = %lld bytes, got %lld", what, (long long)need,
+                (long long)ws_bytes);
+    const long long Em = mask ? (long long)mask_c * HW : 0, mask_nstride = mask && mask_n == N && N > 1 ? Em : 0;
+    {   // no output may lie on an input, a table, the workspace or another output
+        const void* const outs[4] = {loss, simple, vlb, grad};
+        const long long outb[4] = {4, 4LL * N, 8LL * N, 8LL * N * E};
+        const void* const ins[15] = {o, target, x0, x_t, t, mask, weight, sqrt_acp, sqrt_1m_acp, c1, lmin, gap, ws, nullptr, nullptr};
+        const long long inb[15] = {8LL * N * E, 4LL * N * E, 4LL * N * E, 4LL * N * E, 8LL * N, 4LL * (mask ? mask_n : 0) * Em, 4LL * N, 4LL * T, 4LL * T,
+                                   8LL * T, 8LL * T, 8LL * T, (long long)need, 0, 0};
+        for (int a = 0; a < 4; ++a) {
+            for (int b = 0; b < 13; ++b) EOD_REQUIRE(!hybrid_overlap(outs[a], outb[a], ins[b], inb[b]), "%s: an output overlaps an input, a table or the workspace", what);
+            for (int b = a + 1; b < 4; ++b) EOD_REQUIRE(!hybrid_overlap(outs[a], outb[a], outs[b], outb[b]), "%s: two outputs overlap", what);
+        }
+    }
+    hipStream_t st = (hipStream_t)stream;
+    double* S = (double*)ws;
+    double* sums = S + N;
+    double* part = sums + 2LL * N;
+    const long long chunks = dloss_chunks(E);
+    const double s_mul = mask && mask_c == 1 ? (double)C : 1.0;
+    if (mask) {
+        const int outer = mask_nstride ? N : 1;
+        const long long mchunks = dloss_chunks(Em);
+        hipLaunchKernelGGL(dloss_count_kernel, dim3((unsigned)mchunks, (unsigned)outer), dim3(BST_THREADS), 0, st, mask, Em, part);
+        EOD_CHECK_LAUNCH(what);
+        const int rc = met_fold(what, part, outer, mchunks, 1, 0, S, nullptr, nullptr, st);
+        if (rc != EOD_OK) return rc;
+    }
+    HybridArgs g = {o, target, x0, x_t, (const long long*)t, mask, weight, sqrt_acp, sqrt_1m_acp, c1, lmin, gap, (const double*)S, s_mul, lambda, h,
+                    E, Em, mask_nstride, N, T, param_kind, delta, grad, part};
+    const dim3 grid((unsigned)chunks, (unsigned)N), block(BST_THREADS);
+#define HYBRID_LAUNCH(K, M) hipLaunchKernelGGL((hybrid_kernel<K, M>), grid, block, 0, st, g)
+    if (mask) {
+        if (kind == 0) HYBRID_LAUNCH(0, true); else if (kind == 1) HYBRID_LAUNCH(1, true); else HYBRID_LAUNCH(2, true);
+    } else {
+        if (kind == 0) HYBRID_LAUNCH(0, false); else if (kind == 1) HYBRID_LAUNCH(1, false); else HYBRID_LAUNCH(2, false);
+    }
+#undef HYBRID_LAUNCH
+    EOD_CHECK_LAUNCH(what);
+    const int rc = met_fold(what, part, N, chunks, 2, 0, sums, nullptr, nullptr, st);
+    if (rc != EOD_OK) return rc;
+    hipLaunchKernelGGL(hybrid_final_kernel, dim3(1), dim3(64), 0, st, (const double*)sums, mask ? (const double*)S : nullptr, s_mul, mask_nstride ? 1 : 0,
+                       (double)E, weight, lambda, N, loss, simple, vlb);
     EOD_CHECK_LAUNCH(what);
     return EOD_OK;
 }

@@ -874,21 +874,46 @@ def ddpm_pred_x0(parameterization, x, o, t, acp, sqrt_acp, sqrt_1m_acp, clip):
     return p
 
 
-def ddpm_step(bound, k, x_t, pred, noise, t, betas, alphas, acp, clip, sqrt_acp=None, sqrt_1m_acp=None):
+def ddpm_var_pred(parameterization, x, o, t, acp, sqrt_acp, sqrt_1m_acp, clip):
+    """ddpm_pred_x0 on the mean half of a learned-variance output o [N, 2 C, ...], read in place (eod_ddpm_var_pred): the bits of
+    ddpm_pred_x0 on a dense copy of that half"""
+    kind = parameterization_kind("ddpm_var_pred", parameterization)
+    n, T, stream = x.shape[0], acp.numel(), current_stream_ptr(x.device)
+    if o.numel() != 2 * x.numel() or o.shape[0] != n:
+        raise _lib.EodError(f"ddpm_var_pred: the output of a learned-variance model has twice the state's channels, got {tuple(o.shape)} "
+                            f"for a state {tuple(x.shape)}")
+    p = torch.empty_like(x)
+    _lib.check(_lib.lib().eod_ddpm_var_pred(x.data_ptr(), o.data_ptr(), t.data_ptr(), acp.data_ptr(), _lib.ptr(sqrt_acp), _lib.ptr(sqrt_1m_acp),
+                                            kind, int(bool(clip)), p.data_ptr(), n, x.numel() // n, T, stream), "eod_ddpm_var_pred")
+    return p
+
+
+def ddpm_step(bound, k, x_t, pred, noise, t, betas, alphas, acp, clip, sqrt_acp=None, sqrt_1m_acp=None, var=None):
     """One ancestral (DDPM) update with an observation: eod_ddpm_pred_x0 -> each link's project(k, p) in order -> eod_ddpm_step_p0.
     A BoundChain of an "x0" / "v" model forms the prediction with eod_ddpm_param_pred from `pred`, the model's raw output, and the tables
     sqrt_acp / sqrt_1m_acp [T] (the model's buffers); its `links` may be empty.
     bound: a BoundObservation, BoundSpectral, BoundPsf or BoundChain (a single link is a chain of one); k: the evaluation's number in the
     walk (what `weight` sequences are indexed by; not the timestep); t int64 [N] and the schedule tables [T] on the device.  clip False:
     the same posterior form without the clamp (algebraically the reference's epsilon form, not its bits).  A chain with a threshold
-    (diffusion/threshold.py) forms its prediction without the clamp whatever `clip` says: the threshold, its link 0, replaces it."""
+    (diffusion/threshold.py) forms its prediction without the clamp whatever `clip` says: the threshold, its link 0, replaces it.
+    var: EODiffusion.variance_tables() of a learned-variance model, whose `pred` is [N, 2 C, ...] = [mean | v]: eod_ddpm_var_pred on the mean
+    half -> the links -> eod_ddpm_step_p0_var, which takes every element's standard deviation from v."""
     x, e, z = f32c(x_t), f32c(pred), f32c(noise)
     clip = clip and getattr(bound, "threshold", None) is None
     n, T, stream = x.shape[0], acp.numel(), current_stream_ptr(x.device)
-    p = ddpm_pred_x0(PARAMETERIZATIONS[getattr(bound, "kind", 0)], x, e, t, acp, sqrt_acp, sqrt_1m_acp, clip)
+    parameterization = PARAMETERIZATIONS[getattr(bound, "kind", 0)]
+    if var is None:
+        p = ddpm_pred_x0(parameterization, x, e, t, acp, sqrt_acp, sqrt_1m_acp, clip)
+    else:
+        p = ddpm_var_pred(parameterization, x, e, t, acp, sqrt_acp, sqrt_1m_acp, clip)
     for link in (bound.links if isinstance(bound, BoundChain) else (bound,)):
         p = link.project(k, p)
     out = torch.empty_like(x)
+    if var is not None:
+        _lib.check(_lib.lib().eod_ddpm_step_p0_var(x.data_ptr(), p.data_ptr(), e.data_ptr(), z.data_ptr(), t.data_ptr(), betas.data_ptr(),
+                                                   alphas.data_ptr(), acp.data_ptr(), var["sigma_min"].data_ptr(), var["half_gap"].data_ptr(),
+                                                   out.data_ptr(), n, x.numel() // n, T, stream), "eod_ddpm_step_p0_var")
+        return out
     _lib.check(_lib.lib().eod_ddpm_step_p0(x.data_ptr(), p.data_ptr(), z.data_ptr(), t.data_ptr(), betas.data_ptr(), alphas.data_ptr(),
                                            acp.data_ptr(), out.data_ptr(), n, x.numel() // n, T, stream), "eod_ddpm_step_p0")
     return out

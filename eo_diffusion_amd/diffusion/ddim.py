@@ -172,11 +172,14 @@ class DDIMSampler(object):
 
     def _eps(self, x, t, c, unconditional_guidance_scale=1.0, unconditional_conditioning=None):
         """the model output of a batch (for a scene: of a chunk of tiles), plain or with classifier-free guidance: the noise estimate, or
-        under parameterization "x0" / "v" the raw output (the guidance combine is linear, so it equals combining the noise estimates)"""
+        under parameterization "x0" / "v" the raw output (the guidance combine is linear, so it equals combining the noise estimates).
+        A learned-variance model returns [mean | v]: this sampler has no use for v and takes the mean half by one strided device copy right
+        after the UNet call, before guidance is combined; everything downstream is unchanged"""
+        mean = self.model.mean_half if getattr(self.model, "learned_variance", False) else (lambda o: o)
         if unconditional_conditioning is None or unconditional_guidance_scale == 1.0:
-            return self.model.model(x, t, cond=c)
+            return mean(self.model.model(x, t, cond=c))
         # classifier-free guidance (ddim.py:177-181): one UNet call on the doubled batch, then a fused combine
-        e_both = self.model.model(torch.cat([x] * 2), torch.cat([t] * 2), cond=torch.cat([unconditional_conditioning, c]))
+        e_both = mean(self.model.model(torch.cat([x] * 2), torch.cat([t] * 2), cond=torch.cat([unconditional_conditioning, c])))
         e_u, e_c = e_both[: x.shape[0]], e_both[x.shape[0]:]
         e_t = torch.empty_like(e_c)
         _lib.check(_lib.lib().eod_cfg_combine(e_u.data_ptr(), e_c.data_ptr(), float(unconditional_guidance_scale),

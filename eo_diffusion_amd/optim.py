@@ -1,6 +1,7 @@
 """Fused optimizer side of the training step on the HIP path (train.py:70-75,119-124): `AdamW` and
 `ExponentialMovingAverage` with the constructor signatures the reference uses, running as ONE kernel launch over flat fp32
 buffers (csrc/train.hip: eod_adamw_step, eod_ema_update) instead of torch's per-tensor loops, and `mse_loss`.
+Opt-in, for a learned-variance model: `hybrid_loss` / `HybridLoss` (L_simple + lambda L_vlb with both gradients, eod_hybrid_loss).
 Opt-in, the objective beyond plain MSE: `diffusion_loss` / `DiffusionLoss` (masked, per-sample-weighted l1 / l2 / huber with its
 gradient, eod_diffusion_loss) and `AdamW(max_grad_norm=...)` (gradient clipping to a global norm inside the guarded step).
 
@@ -138,6 +139,108 @@ class DiffusionLoss(torch.nn.Module):
 
     def forward(self, pred, target, mask=None, weight=None):
         return _DiffusionLossFn.apply(pred, target, mask, weight, self.kind, self.delta, self)
+
+
+def _finite_number(what, name, v, positive=False):
+    import math
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or (positive and not v > 0):
+        raise _lib.EodError(f"{what}: {name} must be a finite number{' > 0' if positive else ''}, got {v!r}")
+    return float(v)
+
+
+def hybrid_loss(o, target, x_0, x_t, t, diffusion, *, mask=None, weight=None, kind="l2", delta=1.0, vlb_weight=1e-3, bin_halfwidth=1.0 / 255.0,
+                want_grad=True, return_terms=False):
+    """The hybrid objective of a learned-variance model (Nichol & Dhariwal 2021) in one C call (eod_hybrid_loss):
+        loss = mean_n (weight_n * L_n + vlb_weight * V_n)
+    o [N, 2 C, H, W] = [mean | v], target, x_0, x_t [N, C, H, W] and t int64 [N]: what diffusion.forward(x_0, noise, t=t, return_target=True,
+    return_state=True) returned; diffusion: the EODiffusion (learned_variance=True), whose parameterization and variance_tables() are used.
+    L_n: diffusion_loss's per-sample term of the mean half against target (kind, delta, mask, weight: as there, bit for bit).  V_n: the
+    masked mean of the variational-bound term in bits per element, float64, with the mean detached -- the KL between the true posterior
+    and N(mu_theta, exp(lv_theta)) at t > 0, the likelihood of x_0 under that Gaussian discretised to bins of half-width bin_halfwidth at
+    t = 0 (per sample; the exact normal distribution function, not guided-diffusion's tanh approximation).  The weight applies to L_n only.
+    Returns (loss [1], dLoss/do [N, 2 C, H, W] or None); with return_terms=True also (L_n fp32 [N], V_n float64 [N])."""
+    what = "hybrid_loss"
+    if not getattr(diffusion, "learned_variance", False):
+        raise _lib.EodError(f"{what}: `diffusion` must be an EODiffusion with learned_variance=True")
+    lam, h = _finite_number(what, "vlb_weight", vlb_weight), _finite_number(what, "bin_halfwidth", bin_halfwidth, positive=True)
+    if not isinstance(o, torch.Tensor) or not isinstance(target, torch.Tensor) or o.dim() != 4 or target.dim() != 4 or \
+            tuple(o.shape) != (target.shape[0], 2 * target.shape[1]) + tuple(target.shape[2:]):
+        got = [tuple(v.shape) if isinstance(v, torch.Tensor) else type(v).__name__ for v in (o, target)]
+        raise _lib.EodError(f"{what}: o must be [N, 2 C, H, W] for a target [N, C, H, W], got {got[0]} and {got[1]}")
+    k = _loss_args(target, target, mask, weight, kind, delta)
+    for name, v in (("o", o), ("x_0", x_0), ("x_t", x_t)):
+        if not isinstance(v, torch.Tensor) or v.device != target.device or v.dtype != torch.float32:
+            raise _lib.EodError(f"{what}: `{name}` must be a float32 tensor on {target.device}")
+        if name != "o" and v.shape != target.shape:
+            raise _lib.EodError(f"{what}: `{name}` {tuple(v.shape)} does not match target {tuple(target.shape)}")
+    n, c, hh, wd = target.shape
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or tuple(t.shape) != (n,) or t.device != target.device:
+        raise _lib.EodError(f"{what}: t must be an int64 tensor [{n}] on {target.device}")
+    if c != diffusion.in_channels or diffusion.betas.device != target.device:
+        raise _lib.EodError(f"{what}: the tensors have {c} channels on {target.device}, the model {diffusion.in_channels} on {diffusion.betas.device}")
+    L = _lib.lib()
+    tb = diffusion.variance_tables()
+    od, tg, x0, xt, tt = (v.detach().contiguous() for v in (o, target, x_0, x_t, t))
+    m = None if mask is None else mask.detach().contiguous()
+    w = None if weight is None else weight.detach().contiguous()
+    loss = torch.empty((1,), dtype=torch.float32, device=od.device)
+    simple = torch.empty((n,), dtype=torch.float32, device=od.device)
+    vlb = torch.empty((n,), dtype=torch.float64, device=od.device)
+    grad = torch.empty_like(od) if want_grad else None
+    nbytes = L.eod_hybrid_loss_workspace_size(n, c, hh, wd)
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=od.device)
+    check(L.eod_hybrid_loss(ptr(od), ptr(tg), ptr(x0), ptr(xt), ptr(tt), ptr(m), 0 if m is None else m.shape[0], 0 if m is None else m.shape[1],
+                            ptr(w), ptr(diffusion.sqrt_alphas_cumprod), ptr(diffusion.sqrt_one_minus_alphas_cumprod), ptr(tb["c1"]), ptr(tb["lmin"]),
+                            ptr(tb["gap"]), n, c, hh, wd, diffusion.timesteps, _lib_param_kind(diffusion.parameterization), k, float(delta), lam, h,
+                            ptr(loss), ptr(simple), ptr(vlb), ptr(grad), ptr(ws), nbytes, current_stream_ptr(od.device)), "eod_hybrid_loss")
+    return (loss, grad, simple, vlb) if return_terms else (loss, grad)
+
+
+def _lib_param_kind(parameterization):
+    from .diffusion.consistency import parameterization_kind
+    return parameterization_kind("hybrid_loss", parameterization)
+
+
+class _HybridLossFn(torch.autograd.Function):
+    """the HIP-computed gradient of both halves kept for backward, times the incoming gradient (a loss scale included)"""
+
+    @staticmethod
+    def forward(ctx, o, target, x_0, x_t, t, mask, weight, owner):
+        loss, grad, simple, vlb = hybrid_loss(o, target, x_0, x_t, t, owner.diffusion, mask=mask, weight=weight, kind=owner.kind, delta=owner.delta,
+                                              vlb_weight=owner.vlb_weight, bin_halfwidth=owner.bin_halfwidth, want_grad=True, return_terms=True)
+        owner.per_sample, owner.per_sample_vlb = simple, vlb
+        ctx.save_for_backward(grad)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, gout):
+        grad, = ctx.saved_tensors
+        return grad * gout, None, None, None, None, None, None, None
+
+
+class HybridLoss(torch.nn.Module):
+    """hybrid_loss as a loss module, built like DiffusionLoss:
+        o, target, x_t, t = diffusion(x, noise, t=t, return_target=True, return_state=True)
+        loss = loss_fn(o, target, x, x_t, t, mask=.., weight=..); loss.backward()
+    The scalar is connected to `o` only.  `per_sample` holds the latest L_n [N], `per_sample_vlb` the latest V_n [N] (float64, bits per
+    element).  The diffusion model is referred to, not registered: it is no sub-module of the loss."""
+
+    def __init__(self, diffusion, kind="l2", delta=1.0, vlb_weight=1e-3, bin_halfwidth=1.0 / 255.0):
+        super().__init__()
+        if not getattr(diffusion, "learned_variance", False):
+            raise _lib.EodError("HybridLoss: `diffusion` must be an EODiffusion with learned_variance=True")
+        if kind not in LOSS_KINDS:
+            raise _lib.EodError(f"HybridLoss: kind must be one of {sorted(LOSS_KINDS)}, got {kind!r}")
+        if isinstance(delta, bool) or not isinstance(delta, (int, float)) or not delta > 0:
+            raise _lib.EodError(f"HybridLoss: delta must be a number > 0, got {delta!r}")
+        object.__setattr__(self, "diffusion", diffusion)
+        self.kind, self.delta = kind, float(delta)
+        self.vlb_weight = _finite_number("HybridLoss", "vlb_weight", vlb_weight)
+        self.bin_halfwidth = _finite_number("HybridLoss", "bin_halfwidth", bin_halfwidth, positive=True)
+        self.per_sample = self.per_sample_vlb = None
+
+    def forward(self, o, target, x_0, x_t, t, mask=None, weight=None):
+        return _HybridLossFn.apply(o, target, x_0, x_t, t, mask, weight, self)
 
 
 class AdamW(torch.optim.Optimizer):

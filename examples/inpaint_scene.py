@@ -20,6 +20,8 @@ checkpoint of the reference's format ({"model": state_dict}): the example shows 
 
 `--parameterization v|x0` reads the UNet's output as v or as the image instead of the noise (a checkpoint trained that way:
 examples/train_synthetic.py --parameterization); every option above stays as it is.
+`--learned-variance` reads a checkpoint whose UNet has six output channels [mean | v] (examples/train_synthetic.py --learned-variance): the
+ancestral solver takes its per-pixel standard deviation from v, DPM-Solver++ uses the mean half.
 
 `--solver dpmpp` replaces the ancestral chain (one UNet evaluation per timestep) by `DPMSolverSampler.sample_scene`: DPM-Solver++ (2M)
 over `--steps` levels of a log-SNR grid, at most `--steps` evaluations whatever `--timesteps` is.  The same tiling, mask, resampling,
@@ -91,6 +93,7 @@ def main():
                     help="dynamic thresholding of every prediction at the scene's Q-quantile (e.g. 0.995) in place of the static clamp")
     ap.add_argument("--parameterization", default="eps", choices=["eps", "x0", "v"],
                     help="what the checkpoint's UNet predicts: the noise, the image, or v (EODiffusion(parameterization=...))")
+    ap.add_argument("--learned-variance", action="store_true", help="the checkpoint's UNet returns [mean | v] (EODiffusion(learned_variance=True))")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--ckpt", default=None)
     ap.add_argument("--out", default="inpainted_scene.npy")
@@ -100,10 +103,10 @@ def main():
         ap.error("--quantiles needs --draws K with K >= 2")
     device = "cuda:0"
     torch.manual_seed(args.seed)
-    unet = UNetModel(args.image_size, in_channels=3, model_channels=64, out_channels=3, channel_mult=[1, 2, 3], attention_resolutions=[],
+    unet = UNetModel(args.image_size, in_channels=3, model_channels=64, out_channels=6 if args.learned_variance else 3, channel_mult=[1, 2, 3], attention_resolutions=[],
                      num_res_blocks=1, num_heads=1).set_precision(args.precision)
     model = EODiffusion(unet, timesteps=args.timesteps, image_size=args.image_size, in_channels=3, cond_type="sum", device=device,
-                        parameterization=args.parameterization)
+                        parameterization=args.parameterization, learned_variance=args.learned_variance)
     if args.ckpt:
         model.load_state_dict(torch.load(args.ckpt, map_location="cpu")["model"])
     else:

@@ -20,6 +20,11 @@ forward returns its own target (`model(image, noise, t=t, return_target=True)`),
 the EMA copy samples as the same kind of model (the attribute travels with the deep copy).
 
     python examples/train_synthetic.py --fused --parameterization v --weighting min_snr --gamma 5
+    python examples/train_synthetic.py --fused --learned-variance --vlb-weight 1e-3
+
+`--learned-variance` gives the UNet six output channels [mean | v] and trains it with optim.HybridLoss: the loss above on the mean half plus
+`--vlb-weight` times the variational bound, whose gradient goes to v alone; the samples at the end then take their
+per-pixel standard deviation from v.
 """
 import argparse
 import math
@@ -53,17 +58,20 @@ def main():
     ap.add_argument("--clip", type=float, default=None, help="clip the gradients to this global norm (optim.AdamW(max_grad_norm=...), needs --fused)")
     ap.add_argument("--cloud-mask", action="store_true", help="a synthetic blob mask per chip: no loss under the blob")
     ap.add_argument("--parameterization", default="eps", choices=["eps", "x0", "v"], help="what the UNet predicts (EODiffusion(parameterization=...))")
+    ap.add_argument("--learned-variance", action="store_true", help="a [mean | v] head of 6 channels trained with optim.HybridLoss")
+    ap.add_argument("--vlb-weight", type=float, default=1e-3, help="--learned-variance: the weight of the variational-bound term")
     ap.add_argument("--n-samples", type=int, default=4)
     args = ap.parse_args()
     device = "cuda:0"
-    objective = args.loss is not None or args.weighting is not None or args.cloud_mask or args.parameterization != "eps"
+    objective = args.loss is not None or args.weighting is not None or args.cloud_mask or args.parameterization != "eps" or args.learned_variance
     if args.clip is not None and not args.fused:
         ap.error("--clip runs inside eo_diffusion_amd.optim.AdamW: add --fused")
     torch.manual_seed(0)
     # train.py:50-61
-    unet = UNetModel(args.image_size, in_channels=3, model_channels=128, out_channels=3, channel_mult=[1, 2, 3, 4],
+    unet = UNetModel(args.image_size, in_channels=3, model_channels=128, out_channels=6 if args.learned_variance else 3, channel_mult=[1, 2, 3, 4],
                      attention_resolutions=[], num_res_blocks=1, num_heads=1, use_fp16=args.fp16)
-    model = EODiffusion(unet, timesteps=args.timesteps, image_size=args.image_size, in_channels=3, parameterization=args.parameterization).to(device)
+    model = EODiffusion(unet, timesteps=args.timesteps, image_size=args.image_size, in_channels=3, parameterization=args.parameterization,
+                        learned_variance=args.learned_variance).to(device)
     print(f"Diffusion with {sum(p.numel() for p in model.parameters() if p.requires_grad) / 1e6:.2f} M params")
     if args.fused:
         from eo_diffusion_amd.optim import AdamW, ExponentialMovingAverage
@@ -85,6 +93,9 @@ def main():
     if objective:
         from eo_diffusion_amd.optim import DiffusionLoss
         loss_fn = DiffusionLoss(args.loss or "l2", args.delta)
+        if args.learned_variance:
+            from eo_diffusion_amd.optim import HybridLoss
+            loss_fn = HybridLoss(model, args.loss or "l2", args.delta, vlb_weight=args.vlb_weight)
         table = model.loss_weights(args.weighting, args.gamma) if args.weighting else None
         yy, xx = torch.meshgrid(torch.arange(args.image_size, device=device), torch.arange(args.image_size, device=device), indexing="ij")
     g = torch.Generator(device=device).manual_seed(1)
@@ -100,8 +111,13 @@ def main():
                 c = torch.rand((args.batch_size, 3, 1, 1), device=device, generator=g)
                 cy, cx, rad = c[:, 0:1] * args.image_size, c[:, 1:2] * args.image_size, (0.1 + 0.1 * c[:, 2:3]) * args.image_size
                 mask = ((yy - cy) ** 2 + (xx - cx) ** 2 >= rad ** 2).float()
-            pred, target = model(image, noise, t=t, return_target=True)   # (the target of the model's parameterization: noise, image or v)
-            loss = loss_fn(pred, target, mask=mask, weight=None if table is None else table[t.to(device)])
+            weight = None if table is None else table[t.to(device)]
+            if args.learned_variance:      # ([mean | v], the target of the mean half, and the state the variational bound is taken at)
+                out, target, x_t, t_dev = model(image, noise, t=t, return_target=True, return_state=True)
+                loss = loss_fn(out, target, image, x_t, t_dev, mask=mask, weight=weight)
+            else:
+                pred, target = model(image, noise, t=t, return_target=True)   # (the target of the model's parameterization: noise, image or v)
+                loss = loss_fn(pred, target, mask=mask, weight=weight)
         else:
             pred = model(image, noise)       # train.py:116
             loss = loss_fn(pred, noise)      # :117

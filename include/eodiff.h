@@ -440,6 +440,9 @@ int eod_ddpm_step_p0(const float* x_t, const float* p0c, const float* noise, con
 /* Prediction targets other than the noise (a model output read as x0 or as v; DESIGN.md sections 8.2 and 9.16): the three entry points
  * are declared, with their operations, in eodiff_param.h, which this header includes.  They are part of this ABI revision. */
 #include "eodiff_param.h"
+/* Learned variance (a model output of 2 C channels, mean half and variance half; DESIGN.md sections 8.3 and 9.17): the entry points of the
+ * ancestral step and of the hybrid loss are declared, with their operations, in eodiff_var.h.  They only add to this ABI revision. */
+#include "eodiff_var.h"
 /* Dynamic thresholding (Saharia et al. 2022; no reference line): the data prediction is clamped to the sample's own
  * q-quantile of |p| and rescaled, where the static clamp of the entries above saturates.  p and out [B][n] fp32, s_out [B] fp32 on the
  * device; sample b is the n elements at p + b * n (64-bit indexing: B * n may exceed 2^31).  Per sample, every operation rounded once in

@@ -49,6 +49,10 @@ struct AttnBwdP {
 };
 
 constexpr int AB_ROWB = 128;  // LDS row = 64 halves (head dim padded with zeros)
+// dynamic LDS of the two backward kernels, stated once for kernel and launcher: two resident 128-row tiles and two double-buffered
+// 64-row streams; dK / dV: the streams' lse and D rows on top
+constexpr int AB_LDS_Q = (256 + 2 * 64 + 2 * 64) * AB_ROWB;
+constexpr int AB_LDS_KV = AB_LDS_Q + 2 * 2 * 64 * (int)sizeof(float);
 
 __device__ __forceinline__ int ab_swz(int row) { return (row >> 1) & 7; }
 // 16-byte chunk `c` of tile row `row`
@@ -112,6 +116,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(const AttnBwdP p) {
     char* sQ = smem + 256 * AB_ROWB;   // [2][64][128 B]
     char* sO = sQ + 2 * 64 * AB_ROWB;  // [2][64][128 B]  (dO)
     float* sL = reinterpret_cast<float*>(sO + 2 * 64 * AB_ROWB);  // [2][64] lse, then [2][64] D
+    static_assert((256 + 2 * 64 + 2 * 64) * AB_ROWB + 2 * 2 * 64 * sizeof(float) <= AB_LDS_KV, "the carve-up fits the launch's LDS");
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const float ds_over_p = exp2f(p.ds_log2 - AB_P_LOG2), ds_inv = exp2f(-p.ds_log2);  // exact powers of two
@@ -235,6 +240,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(const AttnBwdP p) {
     char* sO = smem + 128 * AB_ROWB;   // [128][128 B]  (dO)
     char* sK = smem + 256 * AB_ROWB;   // [2][64][128 B]
     char* sV = sK + 2 * 64 * AB_ROWB;  // [2][64][128 B]
+    static_assert((256 + 2 * 64 + 2 * 64) * AB_ROWB <= AB_LDS_Q, "the carve-up fits the launch's LDS");
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lr = lane & 31, lh = lane >> 5;
@@ -538,20 +544,14 @@ extern "C" int eod_attention_bwd(const void* qkv, const void* dO, const float* l
         p.ds_log2 = (float)l2;
     }
     const dim3 grid((T + 127) / 128, N * heads);
-    const size_t lds_kv = (size_t)(256 + 256) * AB_ROWB + 4 * 64 * sizeof(float);
-    const size_t lds_q = (size_t)(256 + 256) * AB_ROWB;
     hipStream_t st = (hipStream_t)stream;
     const int ds = (d + 15) / 16, dt = (d + 31) / 32;
 #define EOD_AB_LAUNCH(DS_, DT_)                                                                                                   \
     do {                                                                                                                          \
-        static bool attr = false;                                                                                                 \
-        if (!attr) {                                                                                                              \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_kv_kernel<DS_, DT_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv); \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_q_kernel<DS_, DT_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q);   \
-            attr = true;                                                                                                          \
-        }                                                                                                                         \
-        hipLaunchKernelGGL((attn_bwd_kv_kernel<DS_, DT_>), grid, dim3(256), lds_kv, st, p);                                       \
-        hipLaunchKernelGGL((attn_bwd_q_kernel<DS_, DT_>), grid, dim3(256), lds_q, st, p);                                         \
+        EOD_LDS_OPT_IN((attn_bwd_kv_kernel<DS_, DT_>), AB_LDS_KV, "attention_bwd (dK, dV)");                                         \
+        EOD_LDS_OPT_IN((attn_bwd_q_kernel<DS_, DT_>), AB_LDS_Q, "attention_bwd (dQ)");                                               \
+        hipLaunchKernelGGL((attn_bwd_kv_kernel<DS_, DT_>), grid, dim3(256), AB_LDS_KV, st, p);                                       \
+        hipLaunchKernelGGL((attn_bwd_q_kernel<DS_, DT_>), grid, dim3(256), AB_LDS_Q, st, p);                                         \
     } while (0)
     if (ds == 1) EOD_AB_LAUNCH(1, 1);
     else if (ds == 2) EOD_AB_LAUNCH(2, 1);

@@ -24,6 +24,9 @@ typedef __attribute__((address_space(3))) fp16x4w* aw_lds_h4;
 
 constexpr int AW_ROWB = 128;            // V sub-tile row = 64 halves
 constexpr int AW_VT = 32 * AW_ROWB;     // one sub-tile: 32 keys x 64 channels (fp16) = 4 KiB
+// dynamic LDS of attn_fwd_wide_kernel<T, NSL>, for kernel and launcher: per wave the V slice's 64-channel sub-tiles (hi and lo for fp32
+// storage), then the exchange buffers [2][4 waves][4 register quads][64 lanes] of 16 bytes
+template <typename T, int NSL> constexpr int AW_LDS = 4 * ((NSL + 1) / 2) * AW_VT * (sizeof(T) == 4 ? 2 : 1) + 2 * 4 * 4 * 64 * 16;
 constexpr int AW_KMIN = EOD_AB_KMIN_ATTN;
 
 __device__ __forceinline__ int aw_swz(int row) { return (row >> 1) & 7; }
@@ -90,6 +93,7 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_wide_kernel(const AttnWideP p
     char* const sVh = smem + wave * VWAVE;
     char* const sVl = sVh + NT64 * AW_VT;  // (SPLIT only)
     f32x4* const sX = reinterpret_cast<f32x4*>(smem + 4 * VWAVE);  // [2 buffers][4 waves][4 register quads][64 lanes]
+    static_assert(4 * VWAVE + 2 * 4 * 4 * 64 * sizeof(f32x4) <= AW_LDS<T, NSL>, "the carve-up fits the launch's LDS");
     const int b = blockIdx.y, n = b / p.heads, h = b - n * p.heads;
     const int q0 = blockIdx.x * 32;
     const int c0 = wave * SLW;  // this wave's first channel inside the head
@@ -311,18 +315,12 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_wide_kernel(const AttnWideP p
 }
 
 template <typename T> static int launch_wide(const AttnWideP& p, hipStream_t st) {
-    constexpr bool SPLIT = sizeof(T) == 4;
-    const int nsl = ((p.d + 3) / 4 + 31) / 32;  // 32-channel blocks per wave: the smallest slice with 4 slices >= d
+    const int nsl = ((p.d + 3) / 4 + 31) / 32;  // 32-channel blocks per wave: the smallest slice with 4 slices >= d (d <= 512: 1 .. 4)
     const dim3 grid((p.T + 31) / 32, p.N * p.heads);
-    const size_t lds = (size_t)4 * ((nsl + 1) / 2) * AW_VT * (SPLIT ? 2 : 1) + 2 * 16 * 64 * sizeof(f32x4);
 #define EOD_AW(NSL_)                                                                                                                   \
     do {                                                                                                                           \
-        static bool attr = false;                                                                                                  \
-        if (!attr) {                                                                                                               \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_wide_kernel<T, NSL_>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                      (int)lds);                                                                                   \
-            attr = true;                                                                                                           \
-        }                                                                                                                          \
+        const size_t lds = AW_LDS<T, NSL_>;                                                                                        \
+        EOD_LDS_OPT_IN((attn_fwd_wide_kernel<T, NSL_>), lds, "attention_fwd_nat (wide heads)");                                    \
         hipLaunchKernelGGL((attn_fwd_wide_kernel<T, NSL_>), grid, dim3(256), lds, st, p);                                          \
     } while (0)
     if (nsl == 1) EOD_AW(1);

@@ -26,6 +26,9 @@
 typedef __fp16 fp16x4c __attribute__((__vector_size__(4 * sizeof(__fp16))));
 
 constexpr int AX_ROWB = 128;       // LDS row = 64 halves (head dim padded with zeros)
+// dynamic LDS of attn_fwd_nat_x3_kernel<.., PS>, for kernel and launcher: buffers of four [64][128 B] tiles (K hi | K lo | V hi | V lo); the
+// pre-split form double-buffers them (64 KiB: two workgroups per CU)
+template <bool PS> constexpr int AX_LDS = (PS ? 2 : 1) * 4 * 64 * AX_ROWB;
 constexpr int AX_KMIN = EOD_AB_KMIN_ATTN;  // smallest operand scale 2^-48 (common.h)
 
 __device__ __forceinline__ int ax_swz(int row) { return (row >> 1) & 7; }
@@ -78,6 +81,7 @@ template <int DS, int DT, bool PS = false>
 __global__ __launch_bounds__(256, 2) void attn_fwd_nat_x3_kernel(const AttnX3P p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int TILE = 64 * AX_ROWB, BUF = 4 * TILE;  // one buffer = K hi | K lo | V hi | V lo tiles of [64][128 B]; PS: two buffers
+    static_assert((PS ? 2 : 1) * BUF <= AX_LDS<PS>, "the buffers fit the launch's LDS");
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lr = lane & 31, lh = lane >> 5;
@@ -335,15 +339,10 @@ int eod_attention_fwd_nat_x3(const float* qkv, float* out, float* lse, int N, in
         EOD_REQUIRE(qkv_bound && q_off % 8 == 0 && k_off % 8 == 0 && v_off % 8 == 0 && head_stride % 8 == 0 && C % 8 == 0,
                     "attention_fwd_nat (fp32, pre-split qkv): needs the table the producer scaled by, and whole 8-channel groups");
         EOD_REQUIRE((long long)T * 3 * C * 4 < 0x7fffffffLL, "attention_fwd_nat (fp32, pre-split qkv): one image of qkv exceeds the 2 GiB window");
-        const size_t lds2 = (size_t)2 * 256 * AX_ROWB;  // two buffers of four tiles (64 KiB: two workgroups per CU)
+        const size_t lds2 = AX_LDS<true>;
 #define EOD_AX_PS(DS_, DT_)                                                                                                          \
         do {                                                                                                                     \
-            static bool attr = false;                                                                                            \
-            if (!attr) {                                                                                                         \
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_nat_x3_kernel<DS_, DT_, true>),                 \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);                               \
-                attr = true;                                                                                                     \
-            }                                                                                                                    \
+            EOD_LDS_OPT_IN((attn_fwd_nat_x3_kernel<DS_, DT_, true>), lds2, "attention_fwd_nat (fp32, pre-split qkv)");           \
             hipLaunchKernelGGL((attn_fwd_nat_x3_kernel<DS_, DT_, true>), grid, dim3(256), lds2, st, p);                          \
         } while (0)
         if (ds == 1) EOD_AX_PS(1, 1);
@@ -354,7 +353,7 @@ int eod_attention_fwd_nat_x3(const float* qkv, float* out, float* lse, int N, in
         EOD_CHECK_LAUNCH("attention_fwd_nat (fp32, pre-split qkv)");
         return EOD_OK;
     }
-    const size_t lds = (size_t)256 * AX_ROWB;
+    const size_t lds = AX_LDS<false>;
     if (ds == 1) hipLaunchKernelGGL((attn_fwd_nat_x3_kernel<1, 1>), grid, dim3(256), lds, st, p);
     else if (ds == 2) hipLaunchKernelGGL((attn_fwd_nat_x3_kernel<2, 1>), grid, dim3(256), lds, st, p);
     else if (ds == 3) hipLaunchKernelGGL((attn_fwd_nat_x3_kernel<3, 2>), grid, dim3(256), lds, st, p);

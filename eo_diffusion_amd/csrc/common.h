@@ -34,6 +34,19 @@ void eod_set_error(const char* fmt, ...);
         }                                                                        \
     } while (0)
 
+// More than 64 KiB of dynamic LDS per workgroup needs hipFuncAttributeMaxDynamicSharedMemorySize set on the kernel, once per device.
+// eod_lds_opt_in (program.hip) does it once per (flag, hipGetDevice()) and reports a refusal with the kernel's name (EOD_ELAUNCH).  A
+// flag belongs to ONE kernel instance: a static of the launcher's own instantiation -- never keyed on the kernel's function type alone,
+// which instances share.  Bit d = set on device d (devices past 63: on every launch).  lds == 0 (no dynamic LDS) is a no-op.
+typedef unsigned long long EodLdsOptIn;
+int eod_lds_opt_in(const void* kern, size_t lds, EodLdsOptIn& flag, const char* what);
+#define EOD_LDS_OPT_IN(kern, lds, what)                                                               \
+    do {                                                                                              \
+        static EodLdsOptIn flag__ = 0;                                                                \
+        const int rc__ = eod_lds_opt_in(reinterpret_cast<const void*>(kern), lds, flag__, what);      \
+        if (rc__ != EOD_OK) return rc__;                                                              \
+    } while (0)
+
 static inline bool eod_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static inline int eod_esize(int dtype) { return dtype == EOD_F16 ? 2 : 4; }
 

@@ -735,26 +735,86 @@ __device__ __forceinline__ void halo_epilogue_direct(const IgemmP& p, const Tile
     }
 }
 
+// THE LAUNCH LAYER every family shares.  Each kernel has a SHAPE next to it: a constexpr struct, one type per kernel instance, that
+// states what kernel and launcher both need -- `threads`, the tiles, the LDS carve-up and its sum `lds`.  The kernel takes its
+// constants from the shape and asserts that its carve-up fits `lds`; the launcher reads `threads` and `lds` and nothing else.
+constexpr int cmax(int a, int b) { return a > b ? a : b; }
+constexpr int epilogue_slab(int nw, int wm, int wn) { return nw * wm * (wn + 4) * (int)sizeof(float); }  // igemm_epilogue: WM x (WN + 4) floats per wave
+// what the 128-pixel patch families share: NW waves of 64 x 64, two patch buffers of PH x PW rows (128 B each, DMA groups of 8
+// rows), two weight stages of BN rows, igemm_epilogue's slab
+template <int NW_, int BN_, int PH_, int PW_> struct PatchRingShape {
+    static constexpr int NW = NW_, threads = 64 * NW, WAVES_M = 2, WAVES_N = NW / 2, BM = 128, BN = BN_;
+    static constexpr int PH = PH_, PW = PW_, PR = PH * PW, PG = (PR + 7) / 8;
+    static constexpr int BKB = 128, ABUF = PG * 1024, BSTAGE = BN * BKB, WM = BM / WAVES_M, WN = BN / WAVES_N;
+    static constexpr int ring = 2 * ABUF + 2 * BSTAGE, lds = cmax(ring, epilogue_slab(NW, WM, WN));
+};
+
+// th x 16 pixel tiles of an (H x W) map: whole tile rows; the last tile column may hang over (the 8-wide maps conv_uses_halo and
+// conv_up4_ok admit run as half tiles).  Where the predicate asks for W % 16 == 0 (stride 2, first, head, up4 backward) this is W / 16.
+static inline int patch_tiles(int H, int W, int th = 8) { return (H / th) * ((W + 15) / 16); }
+// patch mode over the (H x W) map the kernel tiles: the output map, or the stored one (conv_up4_halo_kernel)
+static inline void set_patch_tiles(IgemmP& p, int th, int H, int W) {
+    p.tw_log2 = 4;
+    p.th = th;
+    p.tiles_pw = (W + 15) / 16;
+    p.tiles_pi = patch_tiles(H, W, th);
+    p.tiles_m = p.tiles_pi * p.N;
+}
+// The one launch.  The opt-in flag is keyed on Shape, which names ONE kernel instance (all conv kernels share one function type).
+template <typename Shape> static int launch_tiles(void (*kern)(const IgemmP), const IgemmP& p, int grid_y, hipStream_t st, const char* what) {
+    EOD_LDS_OPT_IN(kern, Shape::lds, what);
+    const long long nblk = (long long)p.tiles_m * p.tiles_n;
+    if (nblk <= 0 || nblk > 0x7fffffffLL) {
+        eod_set_error("%s: bad grid %lld", what, nblk);
+        return EOD_EINVAL;
+    }
+    hipLaunchKernelGGL(kern, dim3((unsigned)nblk, (unsigned)grid_y), dim3(Shape::threads), Shape::lds, st, p);
+    EOD_CHECK_LAUNCH(what);
+    return EOD_OK;
+}
+// 256 + 128 columns (384, 640, ...): all but the last 128 on the family's 8-wave 256-column form, the last 128 on its 4-wave form (n_base)
+static int launch_256_plus_128(IgemmP& p, hipStream_t st, int (*wide)(IgemmP&, hipStream_t), int (*last128)(IgemmP&, hipStream_t)) {
+    IgemmP q = p;
+    q.Ncols = p.Ncols - 128;
+    const int rc = wide(q, st);
+    if (rc != EOD_OK) return rc;
+    p.n_base = p.Ncols - 128;
+    return last128(p, st);
+}
+
+template <typename T, bool CONV, int BM, int BN, int WAVES_M, int WAVES_N, bool SPLIT = false, int MS = 32, bool DIRECT = false>
+struct IgemmShape {
+    static constexpr int NW = WAVES_M * WAVES_N, threads = 64 * NW;  // waves per workgroup (4 or 8)
+    static constexpr int BKB = 128;                                  // bytes of K per row per K-step
+    static constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N;
+    static constexpr int STAGE_A = BM * BKB, STAGE = (BM + BN) * BKB, STAGES = 2;  // ring depth (three stages measured no faster on any instance, see below)
+    static constexpr int ring = STAGES * STAGE, epi = epilogue_slab(NW, WM, WN);
+    // split conv: per-image operand scales {s, 16/s} of a tile that straddles images, at most BM + 1 images, behind ring and slab
+    static constexpr int ab_tab_off = (cmax(ring, epi) + 15) & ~15;
+    static constexpr int lds = SPLIT && CONV ? ab_tab_off + (BM + 2) * 2 * (int)sizeof(float) : cmax(ring, epi);
+};
+
 template <typename T, bool CONV, int BM, int BN, int WAVES_M, int WAVES_N, bool SPLIT = false, int MS = 32, bool DIRECT = false>
 __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void igemm_kernel(const IgemmP p) {
     static_assert(!DIRECT || (CONV && SPLIT && MS == 16 && sizeof(T) == 4 && BN >= 64), "direct epilogue: fp32-storage split conv instances");
 
     static_assert(!SPLIT || (sizeof(T) == 4 && MS == 16), "split-fp16 product: fp32 storage, 16x16x32 MFMAs");
     static_assert(MS == 32 || SPLIT || sizeof(T) == 2, "the 16x16x32 shape exists for the fp16 products only (see conv3x3_halo_kernel)");
+    using S = IgemmShape<T, CONV, BM, BN, WAVES_M, WAVES_N, SPLIT, MS, DIRECT>;
     constexpr int ES = sizeof(T);
     constexpr int EPC = 16 / ES;   // elements per 16-byte chunk
-    constexpr int BKB = 128;       // bytes of K per row per K-step
+    constexpr int BKB = S::BKB;
     constexpr int BK = BKB / ES;   // elements per K-step
-    constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N;
+    constexpr int WM = S::WM, WN = S::WN;
     constexpr int TM = WM / MS, TN = WN / MS;
-    constexpr int NW = WAVES_M * WAVES_N;                // waves per workgroup (4 or 8)
+    constexpr int NW = S::NW;
     constexpr int GA = BM / 8, GB = BN / 8;              // 8-row groups (one LDS-DMA instruction each)
     constexpr int LA = GA / NW, LB = GB / NW;            // groups per wave
     constexpr int LPW = LA + LB;                         // DMA instructions per wave per K-step
-    constexpr int STAGE_A = BM * BKB, STAGE = (BM + BN) * BKB;
-    constexpr int STAGES = 2;                            // LDS ring depth (three stages measured no faster on any instance, see below)
+    constexpr int STAGE_A = S::STAGE_A, STAGE = S::STAGE, STAGES = S::STAGES;
     constexpr int EP_LD = WN + 4;                        // fp32 epilogue row stride (floats)
     static_assert(GA % NW == 0 && GB % NW == 0, "layout");
+    static_assert(STAGES * STAGE <= S::lds && NW * WM * EP_LD * (int)sizeof(float) <= S::lds, "ring and epilogue slab fit the launch's LDS");
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -1212,8 +1272,22 @@ __device__ __forceinline__ void prefetch_bcol(const IgemmP& p, int ncols, int co
     }
 }
 
+// the kernel's shape (see the launch layer in front of igemm_kernel): pixel tile, halo patch, operand ring.  One type per kernel instance.
+template <typename T, int BN, int WAVES_M, int WAVES_N, bool UPS, bool GN, bool SPLIT = false, int MS = 32, bool SKIP = false, bool KSPLIT = false>
+struct HaloShape {
+    static constexpr int NW = WAVES_M * WAVES_N, threads = 64 * NW;  // 4 waves: 8x16 tile, 8 waves: 16x16 tile
+    static constexpr int BM = WAVES_N == 4 ? 64 * WAVES_M : 32 * NW, TH = BM / 16, TW = 16;  // (WAVES_N = 4: see the kernel)
+    static constexpr int PH = UPS ? TH / 2 + 2 : TH + 2, PW = UPS ? TW / 2 + 2 : TW + 2, PR = PH * PW;  // 180 (60) patch rows
+    static constexpr int PG = (PR + 7) / 8;                                                             // 23 (8) DMA groups of 8 rows
+    static constexpr int BKB = 128, ABUF = PG * 1024, BSTAGE = BN * BKB, BSTAGES = 2;  // (two weight stages: a K-step's stage is step & 1)
+    static constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N;
+    static constexpr int ring = 2 * ABUF + BSTAGES * BSTAGE + (GN ? 2 * 1024 : 0);  // two patch buffers, the weight stages, GN: [2][1024] scale / shift
+    static constexpr int lds = cmax(ring, epilogue_slab(NW, WM, WN));
+};
+
 template <typename T, int BN, int WAVES_M, int WAVES_N, bool UPS, bool GN, bool SPLIT = false, int MS = 32, bool SKIP = false, bool KSPLIT = false>
 __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void conv3x3_halo_kernel(const IgemmP p) {
+    using S = HaloShape<T, BN, WAVES_M, WAVES_N, UPS, GN, SPLIT, MS, SKIP, KSPLIT>;
     // KSPLIT: the K slices of a split conv (p.splitk workgroups per tile, gridDim.y) are instances of their own.  As a run-time mode of
     // every instance (round 4's first form) the chunk loop's bounds, the second epilogue of the fp16 kernels and the workspace pointer cost
     // the UNSPLIT launches 2-6 % (fp16, 128 -> 128 at 256 x 256: 0.399 -> 0.419 ms, same box) -- found by bisecting the libraries of the
@@ -1225,7 +1299,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
     constexpr bool XF = GN || SPLIT;  // the staged patch pieces are rewritten in place by the wave that DMA'd them
     // fp32-storage split instances (not the 32-column NCHW head): swapped MFMA operands + stores straight from the accumulators
     constexpr bool DIRECT = SPLIT && MS == 16 && BN >= 64;
-    constexpr int NW = WAVES_M * WAVES_N;      // 4 waves: 8x16 tile, 8 waves: 16x16 tile
+    constexpr int NW = S::NW;
     // WAVES_N = 4 (BN = 256): the 8x16 pixel tile with EIGHT waves, 2 x 4, each still 64 x 64 -- one workgroup covers the two N-tiles of a
     // 256-column conv, so the patch is fetched from HBM and normalised / split ONCE for both (one 8-wave workgroup per CU instead of two
     // 4-wave ones: the same waves per SIMD): +3.5 ... 10 % on the 256- and 512-column convs.  (The mirror image for 128-column convs -- a
@@ -1233,9 +1307,8 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
     // storage, where the weight DMA is the larger share of a K-step: -1 ... +3 %), and the
     // same 2 x 4 form of conv_up4_halo_kernel +0.4 %: neither was used; a three-stage weight ring on this instance: -2 %.  With the wave
     // roles below the 2 x 4 form of conv_up4_halo_kernel pays: DESIGN_HISTORY.md 10.23.)
-    constexpr int BM = WAVES_N == 4 ? 64 * WAVES_M : 32 * NW, TH = BM / 16, TW = 16;
-    constexpr int PH = UPS ? TH / 2 + 2 : TH + 2, PW = UPS ? TW / 2 + 2 : TW + 2, PR = PH * PW;  // 180 (60) patch rows
-    constexpr int PG = (PR + 7) / 8;                                             // 23 (8) DMA groups of 8 rows
+    constexpr int BM = S::BM, TH = S::TH, TW = S::TW;
+    constexpr int PH = S::PH, PW = S::PW, PR = S::PR, PG = S::PG;
     // ROLES (the 8-wave instance): the two waves of a SIMD are wave w and wave w + 4 of ONE workgroup; behind every barrier they ran the
     // same body, wanted the matrix pipe together and left it idle together.  The K loop's non-matrix work is therefore divided by wave
     // row: waves 4-7 issue the whole next weight tile behind the barrier, in FRONT of their MFMAs, and nothing else; waves 0-3 go
@@ -1245,11 +1318,11 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
     constexpr bool ROLES = WAVES_N == 4 && MS == 16;
     constexpr int RW = ROLES ? 4 : NW;                                           // waves that share a chunk's patch pieces / a weight tile's pieces
     constexpr int LAH = (PG + RW - 1) / RW;                                      // patch pieces per wave
-    constexpr int ES = sizeof(T), EPC = 16 / ES, BKB = 128, BK = BKB / ES;
-    constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N, TM = WM / MS, TN = WN / MS;
+    constexpr int ES = sizeof(T), EPC = 16 / ES, BKB = S::BKB, BK = BKB / ES;
+    constexpr int WM = S::WM, WN = S::WN, TM = WM / MS, TN = WN / MS;
     constexpr int GB = BN / 8, LB = GB / NW, LBR = GB / RW;                     // weight pieces per wave: skip phase / 3x3 loop
     constexpr int LBV = ROLES ? 1 : LB;                                          // per-lane offsets kept for them
-    constexpr int ABUF = PG * 1024, BSTAGE = BN * BKB, BSTAGES = 2;  // (two weight stages: a K-step's stage is step & 1)
+    constexpr int ABUF = S::ABUF, BSTAGE = S::BSTAGE, BSTAGES = S::BSTAGES;
     static_assert(GB % NW == 0 && LAH <= 6, "layout");
     static_assert(!ROLES || (XF && GB % RW == 0 && LAH % 2 == 0 && LBR % 2 == 0), "role split: in-place rewrite; the prologue halves the pieces");
 
@@ -1257,6 +1330,8 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
     char* const sA = smem;              // [2][ABUF]
     char* const sB = smem + 2 * ABUF;   // [BSTAGES][BSTAGE]
     char* const sS = sB + BSTAGES * BSTAGE;  // GN only: [2][1024] scale/shift of the 64 channels of a chunk
+    static_assert(2 * ABUF + BSTAGES * BSTAGE + (GN ? 2 * 1024 : 0) <= S::lds && (DIRECT || NW * WM * (WN + 4) * (int)sizeof(float) <= S::lds),
+                  "sA, sB, sS and igemm_epilogue's slab fit the launch's LDS");
     EOD_STAMP_AT(0);
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1968,17 +2043,21 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_N == 4 ? 1 : 2) void 
 // (H x W) output tile -- no (2H x 2W) intermediate, no 2x2 sum pool.  Weights: eod_pack_conv_weight_dgrad of the forward class-kernel
 // tensor [4*Cy][Cx][3][3] = [slot][Cx rows][4*Cy], class block `cls` at K offset cls*Cy (the flip of that packing maps the forward slots
 // {p, p+1} to {2-p, 1-p}, exactly the ones above).  p.H, p.W, p.Ho, p.Wo = stored (output) map; dY is (2H x 2W) with p.C0 channels.
+// the 4-wave kernel's shape (T names the instance: fp16 storage, or fp32 storage = the split product)
+// forward: the 9 x 17 window of the class (153 rows, 20 groups, 5 pieces per wave); backward: the whole 10 x 18 patch (180, 23, 6)
+template <typename T, bool BWD> struct Up4Shape : PatchRingShape<4, 128, BWD ? 10 : 9, BWD ? 18 : 17> {};
 template <typename T, bool SPLIT, bool BWD = false>
 __global__ __launch_bounds__(256, 2) void conv_up4_halo_kernel(const IgemmP p) {
     static_assert(!SPLIT || sizeof(T) == 4, "the split-fp16 product is a mode of fp32 storage");
     static_assert(SPLIT || sizeof(T) == 2, "fp16 storage or split fp32");
-    constexpr int NW = 4, WAVES_M = 2, WAVES_N = 2, BN = 128, BM = 128, MS = 16;
-    // forward: the 9 x 17 window of the class (153 rows, 20 groups, 5 pieces per wave); backward: the whole 10 x 18 patch (180, 23, 6)
-    constexpr int PH = BWD ? 10 : 9, PW = BWD ? 18 : 17, PR = PH * PW, PG = (PR + 7) / 8, LAH = (PG + NW - 1) / NW;
-    constexpr int ES = sizeof(T), EPC = 16 / ES, BKB = 128, BK = BKB / ES;
-    constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N, TM = WM / MS, TN = WN / MS;
+    using S = Up4Shape<T, BWD>;
+    constexpr int NW = S::NW, WAVES_M = S::WAVES_M, WAVES_N = S::WAVES_N, BN = S::BN, BM = S::BM, MS = 16;
+    constexpr int PH = S::PH, PW = S::PW, PR = S::PR, PG = S::PG, LAH = (PG + NW - 1) / NW;
+    constexpr int ES = sizeof(T), EPC = 16 / ES, BKB = S::BKB, BK = BKB / ES;
+    constexpr int WM = S::WM, WN = S::WN, TM = WM / MS, TN = WN / MS;
     constexpr int LB = (BN / 8) / NW;
-    constexpr int ABUF = PG * 1024, BSTAGE = BN * BKB;
+    constexpr int ABUF = S::ABUF, BSTAGE = S::BSTAGE;
+    static_assert(2 * ABUF + 2 * BSTAGE <= S::lds && NW * WM * (WN + 4) * (int)sizeof(float) <= S::lds, "sA, sB and the epilogue slab fit the launch's LDS");
     static_assert(LAH == (BWD ? 6 : 5), "schedule: up to three patch pieces per K-step in steps 0 and 1");
     static_assert((WAVES_M - 1) * (WM / 16) + TM + (BWD ? 1 : 0) < PH && 15 + 1 + (BWD ? 1 : 0) < PW, "the fragment reads stay inside the staged patch");
 
@@ -2246,33 +2325,14 @@ __global__ __launch_bounds__(256, 2) void conv_up4_halo_kernel(const IgemmP p) {
 }
 
 template <typename T, bool SPLIT, bool BWD = false> static int launch_up4(IgemmP& p, hipStream_t st) {
-    constexpr int BK = 128 / (int)sizeof(T);
-    const size_t ring = 2 * (size_t)((BWD ? 23 : 20) * 1024) + 2 * (size_t)128 * 128;  // patch groups: see the kernel's PG
-    const size_t epi = 4 * (size_t)64 * (64 + 4) * sizeof(float);
-    const size_t lds = ring > epi ? ring : epi;
-    auto kern = conv_up4_halo_kernel<T, SPLIT, BWD>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_done = true;
-    }
+    using S = Up4Shape<T, BWD>;
+    constexpr int BK = S::BKB / (int)sizeof(T);
     p.kc0 = (p.C0 + BK - 1) / BK;
     p.kc1 = 0;
     p.KT = p.kc0 * 4;
-    p.tiles_n = BWD ? (p.Cout + 127) / 128 : 4 * ((p.Cout - p.n_base + 127) / 128);  // forward: (class, column tile from n_base on)
-    p.tw_log2 = 4;                            // 8 x 16 tiles of the STORED map
-    p.th = 8;
-    p.tiles_pw = (p.W + 15) / 16;
-    p.tiles_pi = p.tiles_pw * (p.H / 8);
-    p.tiles_m = p.tiles_pi * p.N;
-    const long long nblk = (long long)p.tiles_m * p.tiles_n;
-    if (nblk <= 0 || nblk > 0x7fffffffLL) {
-        eod_set_error("conv_up4: bad grid %lld", nblk);
-        return EOD_EINVAL;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(256), lds, st, p);
-    EOD_CHECK_LAUNCH("conv_up4_halo");
-    return EOD_OK;
+    p.tiles_n = BWD ? (p.Cout + S::BN - 1) / S::BN : 4 * ((p.Cout - p.n_base + S::BN - 1) / S::BN);  // forward: (class, column tile from n_base on)
+    set_patch_tiles(p, 8, p.H, p.W);  // 8 x 16 tiles of the STORED map
+    return launch_tiles<S>(conv_up4_halo_kernel<T, SPLIT, BWD>, p, 1, st, "conv_up4_halo");
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2288,15 +2348,20 @@ template <typename T, bool SPLIT, bool BWD = false> static int launch_up4(IgemmP
 // are those of the 4-wave form: the same output bits and statistics, in the same (tile, class, wave row) slots.
 // (A function template of its own, overloaded on the fourth parameter: the 4-wave instances above keep their statements and code.)
 // ---------------------------------------------------------------------------------------------
+struct Up4W8Shape : PatchRingShape<8, 256, 9, 17> {
+    static constexpr int lds = ring;  // the epilogue stores from the accumulators: no slab
+};
 template <typename T, bool SPLIT, bool BWD, int WAVES_N>
 __global__ __launch_bounds__(512, 1) void conv_up4_halo_kernel(const IgemmP p) {
     static_assert(SPLIT && !BWD && sizeof(T) == 4 && WAVES_N == 4, "the 8-wave form: forward, split product of fp32 storage");
-    constexpr int NW = 8, WAVES_M = 2, RW = 4, BN = 256, BM = 128, MS = 16;
-    constexpr int PH = 9, PW = 17, PR = PH * PW, PG = (PR + 7) / 8, LAH = (PG + RW - 1) / RW;  // 153 rows, 20 groups, 5 pieces per wave of a row
-    constexpr int ES = sizeof(T), EPC = 16 / ES, BKB = 128, BK = BKB / ES;
+    using S = Up4W8Shape;
+    constexpr int NW = S::NW, WAVES_M = S::WAVES_M, RW = 4, BN = S::BN, BM = S::BM, MS = 16;
+    constexpr int PH = S::PH, PW = S::PW, PR = S::PR, PG = S::PG, LAH = (PG + RW - 1) / RW;  // 153 rows, 20 groups, 5 pieces per wave of a row
+    constexpr int ES = sizeof(T), EPC = 16 / ES, BKB = S::BKB, BK = BKB / ES;
     constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N, TM = WM / MS, TN = WN / MS;
     constexpr int LBR = (BN / 8) / RW;  // weight pieces per wave of the row that issues them (8)
-    constexpr int ABUF = PG * 1024, BSTAGE = BN * BKB;
+    constexpr int ABUF = S::ABUF, BSTAGE = S::BSTAGE;
+    static_assert(2 * ABUF + 2 * BSTAGE <= S::lds, "sA and sB fit the launch's LDS (direct epilogue: no slab)");
     constexpr bool EARLY = true;  // A rows of steps 1 .. 3 read one step early: -1.0 ... -2.5 % per layer by itself, six registers fewer (DESIGN_HISTORY.md 10.23)
     static_assert(LAH == 5 && PG == RW * LAH && LBR % 2 == 0, "schedule: 3 + 2 patch pieces, every wave holds all five; the prologue halves the weight pieces");
     static_assert((WAVES_M - 1) * (WM / 16) + TM < PH && 15 + 1 < PW, "the fragment reads stay inside the staged window");
@@ -2502,30 +2567,17 @@ __global__ __launch_bounds__(512, 1) void conv_up4_halo_kernel(const IgemmP p) {
 
 // the 8-wave form over columns [0, p.Ncols) (a multiple of 256; 256 + 128 columns: the caller sends the last 128 through launch_up4 with n_base)
 static int launch_up4_w8(IgemmP& p, hipStream_t st) {
-    const size_t lds = 2 * (size_t)(20 * 1024) + 2 * (size_t)256 * 128;
-    auto kern = conv_up4_halo_kernel<float, true, false, 4>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_done = true;
+    using S = Up4W8Shape;
+    if (p.Ncols <= 0 || p.Ncols % S::BN) {
+        eod_set_error("conv_up4_halo (8 waves): %d columns", p.Ncols);
+        return EOD_EINVAL;
     }
     p.kc0 = (p.C0 + 31) / 32;
     p.kc1 = 0;
     p.KT = p.kc0 * 4;
-    p.tiles_n = 4 * ((p.Ncols + 255) / 256);  // (class, column tile)
-    p.tw_log2 = 4;                            // 8 x 16 tiles of the STORED map
-    p.th = 8;
-    p.tiles_pw = (p.W + 15) / 16;
-    p.tiles_pi = p.tiles_pw * (p.H / 8);
-    p.tiles_m = p.tiles_pi * p.N;
-    const long long nblk = (long long)p.tiles_m * p.tiles_n;
-    if (p.Ncols <= 0 || p.Ncols % 256 || nblk <= 0 || nblk > 0x7fffffffLL) {
-        eod_set_error("conv_up4 (8 waves): bad grid %lld, %d columns", nblk, p.Ncols);
-        return EOD_EINVAL;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(512), lds, st, p);
-    EOD_CHECK_LAUNCH("conv_up4_halo (8 waves)");
-    return EOD_OK;
+    p.tiles_n = 4 * (p.Ncols / S::BN);  // (class, column tile)
+    set_patch_tiles(p, 8, p.H, p.W);    // 8 x 16 tiles of the STORED map
+    return launch_tiles<S>(conv_up4_halo_kernel<float, true, false, 4>, p, 1, st, "conv_up4_halo (8 waves)");
 }
 
 // =============================================================================================
@@ -2542,16 +2594,19 @@ static int launch_up4_w8(IgemmP& p, hipStream_t st) {
 // next pair is issued at the first step of the current one and split in place (fp32 storage) behind the MFMAs of its last step.
 // Weights: the ordinary packed [tap][Cout][Cin] tensor (eod_pack_conv_weight / _split), one 128-row stage per K-step, two stages.
 // =============================================================================================
+template <typename T> struct S2Shape : PatchRingShape<4, 128, 9, 17> {};  // (T names the instance.)  A plane's patch: 153 rows, 20 groups
 template <typename T, bool SPLIT>
 __global__ __launch_bounds__(256, 2) void conv_s2_halo_kernel(const IgemmP p) {
     static_assert(!SPLIT || sizeof(T) == 4, "the split-fp16 product is a mode of fp32 storage");
     static_assert(SPLIT || sizeof(T) == 2, "fp16 storage or split fp32");
-    constexpr int NW = 4, WAVES_M = 2, WAVES_N = 2, BN = 128, BM = 128, MS = 16;
-    constexpr int PH = 9, PW = 17, PR = PH * PW, PG = (PR + 7) / 8, LAH = (PG + NW - 1) / NW;  // 153 rows, 20 groups, 5 pieces per wave
-    constexpr int ES = sizeof(T), EPC = 16 / ES, BKB = 128, BK = BKB / ES;
-    constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N, TM = WM / MS, TN = WN / MS;
+    using S = S2Shape<T>;
+    constexpr int NW = S::NW, WAVES_M = S::WAVES_M, WAVES_N = S::WAVES_N, BN = S::BN, BM = S::BM, MS = 16;
+    constexpr int PH = S::PH, PW = S::PW, PR = S::PR, PG = S::PG, LAH = (PG + NW - 1) / NW;  // 153 rows, 20 groups, 5 pieces per wave
+    constexpr int ES = sizeof(T), EPC = 16 / ES, BKB = S::BKB, BK = BKB / ES;
+    constexpr int WM = S::WM, WN = S::WN, TM = WM / MS, TN = WN / MS;
     constexpr int LB = (BN / 8) / NW;
-    constexpr int ABUF = PG * 1024, BSTAGE = BN * BKB;
+    constexpr int ABUF = S::ABUF, BSTAGE = S::BSTAGE;
+    static_assert(2 * ABUF + 2 * BSTAGE <= S::lds && NW * WM * (WN + 4) * (int)sizeof(float) <= S::lds, "sA, sB and the epilogue slab fit the launch's LDS");
     static_assert(PG == NW * LAH && LAH * 4 <= 32, "every wave stages LAH whole pieces; 4 plane-validity bits per piece");
     static_assert(LB <= 6, "wait_vm immediates");
 
@@ -2782,34 +2837,15 @@ __global__ __launch_bounds__(256, 2) void conv_s2_halo_kernel(const IgemmP p) {
 }
 
 template <typename T, bool SPLIT> static int launch_s2(IgemmP& p, hipStream_t st) {
-    constexpr int BK = 128 / (int)sizeof(T);
-    const size_t ring = 2 * (size_t)(20 * 1024) + 2 * (size_t)128 * 128;
-    const size_t epi = 4 * (size_t)64 * (64 + 4) * sizeof(float);
-    const size_t lds = ring > epi ? ring : epi;
-    auto kern = conv_s2_halo_kernel<T, SPLIT>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_done = true;
-    }
+    using S = S2Shape<T>;
+    constexpr int BK = S::BKB / (int)sizeof(T);
     p.kc0 = (p.C0 + BK - 1) / BK;
     p.kc1 = 0;
     p.KT = p.kc0 * 9;
-    p.tiles_n = (p.Cout + 127) / 128;
-    p.tw_log2 = 4;  // 8 x 16 tiles of the OUTPUT map
-    p.th = 8;
-    p.tiles_pw = p.Wo / 16;
-    p.tiles_pi = p.tiles_pw * (p.Ho / 8);
-    p.tiles_m = p.tiles_pi * p.N;
+    p.tiles_n = (p.Cout + S::BN - 1) / S::BN;
+    set_patch_tiles(p, 8, p.Ho, p.Wo);  // 8 x 16 tiles of the OUTPUT map
     p.tiles_per_image = p.tiles_pi;  // (statistics slots: tile of the image x 2 wave rows, as the generic kernel's 128-row tiles count them)
-    const long long nblk = (long long)p.tiles_m * p.tiles_n;
-    if (nblk <= 0 || nblk > 0x7fffffffLL) {
-        eod_set_error("conv_s2_halo: bad grid %lld", nblk);
-        return EOD_EINVAL;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(256), lds, st, p);
-    EOD_CHECK_LAUNCH("conv_s2_halo");
-    return EOD_OK;
+    return launch_tiles<S>(conv_s2_halo_kernel<T, SPLIT>, p, 1, st, "conv_s2_halo");
 }
 
 // =============================================================================================
@@ -2822,15 +2858,24 @@ template <typename T, bool SPLIT> static int launch_s2(IgemmP& p, hipStream_t st
 // so a lane of the first quarter holds the <= 4 output channels of one pixel and a plane row of 16 pixels is one 64-byte store.
 // =============================================================================================
 #define HEAD_MAX_C 384  // input channels of the head (the whole scale / shift table sits in LDS)
+template <typename T> struct HeadShape {  // (T names the instance: fp16 storage, or fp32 storage = the split product)
+    static constexpr int NW = 4, threads = 64 * NW, BM = 128;
+    static constexpr int PH = 10, PW = 18, PR = PH * PW, LAH = ((PR + 7) / 8 + NW - 1) / NW, PG = LAH * NW;  // 180 rows in 24 groups of 8 (the last one
+    // is padding: every wave issues exactly LAH = 6 pieces per chunk, which keeps the counted vmcnt waits exact for the compiler too)
+    static constexpr int BKB = 128, ABUF = PG * 1024;
+    // three patch buffers, {scale, shift} of every input channel of the image, {scale, bias} of the <= 16 output channels
+    static constexpr int lds = 3 * ABUF + HEAD_MAX_C * 2 * (int)sizeof(float) + 16 * 2 * (int)sizeof(float);
+};
 template <typename T, bool SPLIT>
 __global__ __launch_bounds__(256, 2) void conv_head_kernel(const IgemmP p) {
     static_assert(SPLIT ? sizeof(T) == 4 : sizeof(T) == 2, "fp16 storage or split fp32");
-    constexpr int NW = 4, BM = 128, MS = 16;
-    constexpr int PH = 10, PW = 18, PR = PH * PW, LAH = ((PR + 7) / 8 + NW - 1) / NW, PG = LAH * NW;  // 180 rows in 24 groups of 8 (the last one
-    // is padding: every wave issues exactly LAH = 6 pieces per chunk, which keeps the counted vmcnt waits exact for the compiler too)
-    constexpr int ES = sizeof(T), EPC = 16 / ES, BKB = 128, BK = BKB / ES;
-    constexpr int ABUF = PG * 1024;
+    using S = HeadShape<T>;
+    constexpr int NW = S::NW, BM = S::BM, MS = 16;
+    constexpr int PH = S::PH, PW = S::PW, PR = S::PR, LAH = S::LAH, PG = S::PG;
+    constexpr int ES = sizeof(T), EPC = 16 / ES, BKB = S::BKB, BK = BKB / ES;
+    constexpr int ABUF = S::ABUF;
     constexpr int NSUB = SPLIT ? 1 : 2;  // 32-k MFMA sub-steps per chunk row (fp16: 64 channels)
+    static_assert(3 * ABUF + HEAD_MAX_C * 8 + 16 * 2 * (int)sizeof(float) <= S::lds, "sA, sS and sE fit the launch's LDS");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const sA = smem;              // [3][ABUF]
     char* const sS = smem + 3 * ABUF;   // [HEAD_MAX_C][2] scale / shift of every input channel of this image
@@ -3110,10 +3155,13 @@ __global__ __launch_bounds__(256, 2) void conv_head_kernel(const IgemmP p) {
 // epilogue of the halo kernel (halo_epilogue_direct: 16-byte stores from the accumulators, bias, GroupNorm partial sums in the same
 // two slots per tile).
 // =============================================================================================
+template <int CP> struct FirstShape {  // (the patch is a static array of the kernel's own: no dynamic LDS)
+    static constexpr int threads = 256, BM = 128, BN = 128, lds = 0;
+};
 template <int CP>
 __global__ __launch_bounds__(256, 3) void conv_first_x3_kernel(const IgemmP p) {
     static_assert(CP == 4 || CP == 8, "one or two 16-byte chunks of fp32 channels per pixel");
-    constexpr int BM = 128, BN = 128, TM = 4, TN = 4;
+    constexpr int BM = FirstShape<CP>::BM, BN = FirstShape<CP>::BN, TM = 4, TN = 4;
     constexpr int PW = 18, PR = 10 * PW, PB = CP * 4;        // LDS bytes per patch pixel: [CP x fp16 hi | CP x fp16 lo]
     constexpr int KG = (9 * CP + 7) / 8, STEPS = (KG + 3) / 4;  // 8-element k-groups that hold taps; MFMA steps of 4 groups
     constexpr int ZOFF = PR * PB;                            // 32 zero bytes behind the patch: what the k-groups past tap 8 read
@@ -3215,47 +3263,22 @@ __global__ __launch_bounds__(256, 3) void conv_first_x3_kernel(const IgemmP p) {
 }
 
 template <int CP> static int launch_first(IgemmP& p, hipStream_t st) {
-    p.tiles_n = (p.Ncols + 127) / 128;
-    p.tw_log2 = 4;
-    p.th = 8;
-    p.tiles_pw = p.Wo / 16;
-    p.tiles_pi = p.tiles_pw * (p.Ho / 8);
-    p.tiles_m = p.tiles_pi * p.N;
+    using S = FirstShape<CP>;
+    p.tiles_n = (p.Ncols + S::BN - 1) / S::BN;
+    set_patch_tiles(p, 8, p.Ho, p.Wo);
     p.tiles_per_image = p.tiles_pi;
-    const long long nblk = (long long)p.tiles_m * p.tiles_n;
-    if (nblk <= 0 || nblk > 0x7fffffffLL) {
-        eod_set_error("conv_first: bad grid %lld", nblk);
-        return EOD_EINVAL;
-    }
-    hipLaunchKernelGGL(conv_first_x3_kernel<CP>, dim3((unsigned)nblk), dim3(256), 0, st, p);
-    EOD_CHECK_LAUNCH("conv_first");
-    return EOD_OK;
+    return launch_tiles<S>(conv_first_x3_kernel<CP>, p, 1, st, "conv_first");
 }
 
 template <typename T, bool SPLIT> static int launch_head(IgemmP& p, hipStream_t st) {
-    constexpr int BK = 128 / (int)sizeof(T);
-    const size_t lds = 3 * (size_t)(24 * 1024) + HEAD_MAX_C * 8 + 128;
-    auto kern = conv_head_kernel<T, SPLIT>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_done = true;
-    }
+    using S = HeadShape<T>;
+    constexpr int BK = S::BKB / (int)sizeof(T);
     p.kc0 = (p.C0 + BK - 1) / BK;
     p.kc1 = 0;
     p.tiles_n = 1;
-    p.tw_log2 = 4;
-    p.th = 8;
-    p.tiles_pw = p.Wo / 16;
-    p.tiles_pi = p.tiles_pw * (p.Ho / 8);
+    set_patch_tiles(p, 8, p.Ho, p.Wo);
     p.tiles_m = p.tiles_pi / p.tpw * p.N;  // (runs of p.tpw consecutive tiles of one image per workgroup: ConvPlan.tpw)
-    if (p.tiles_m <= 0) {
-        eod_set_error("conv_head: bad grid");
-        return EOD_EINVAL;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)p.tiles_m), dim3(256), lds, st, p);
-    EOD_CHECK_LAUNCH("conv_head");
-    return EOD_OK;
+    return launch_tiles<S>(conv_head_kernel<T, SPLIT>, p, 1, st, "conv_head");
 }
 
 // split-K second pass: y[m][c] = alpha * sum_z ws[z][m][c] + bias[c] + cbias[n(m)][c] + res[m][c]   (fixed z order)
@@ -3393,22 +3416,9 @@ extern "C" int eod_get_option(const char* name) {
 
 template <typename T, bool CONV, int BM, int BN, int WAVES_M, int WAVES_N, bool SPLIT = false, int MS = 32, bool DIRECT = false>
 static int launch_cfg(IgemmP& p, int batch, hipStream_t st) {
-    constexpr int BK = 128 / (int)sizeof(T);
-    constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N, NW = WAVES_M * WAVES_N;
-    const size_t ring = 2 * (size_t)(BM + BN) * 128;  // igemm_kernel's two-stage ring
-    const size_t epi = NW * (size_t)WM * (WN + 4) * sizeof(float);
-    size_t lds = ring > epi ? ring : epi;
-    if (SPLIT && CONV) {  // per-image operand scales of a tile that straddles images: at most BM + 1 images of {s, 16/s}
-        lds = (lds + 15) & ~(size_t)15;
-        p.ab_tab_off = (int)lds;
-        lds += (BM + 2) * 2 * sizeof(float);
-    }
-    auto kern = igemm_kernel<T, CONV, BM, BN, WAVES_M, WAVES_N, SPLIT, MS, DIRECT>;
-    static bool attr_done = false;  // >64 KiB dynamic LDS needs the opt-in attribute once per kernel
-    if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_done = true;
-    }
+    using S = IgemmShape<T, CONV, BM, BN, WAVES_M, WAVES_N, SPLIT, MS, DIRECT>;
+    constexpr int BK = S::BKB / (int)sizeof(T);
+    if (SPLIT && CONV) p.ab_tab_off = S::ab_tab_off;  // (a kernel parameter: the table of a tile that straddles images)
     if (CONV) {
         p.kc0 = (p.C0 + BK - 1) / BK;
         p.kc1 = (p.C1 + BK - 1) / BK;
@@ -3419,6 +3429,7 @@ static int launch_cfg(IgemmP& p, int batch, hipStream_t st) {
     }
     p.tiles_n = (p.Ncols + BN - 1) / BN;
     p.tw_log2 = -1;
+    p.tiles_m = (int)((p.M + BM - 1) / BM);  // linear runs of BM rows, unless:
     if (CONV) {
         // patch mode: TW = min(16, Wo) if it is a power of two dividing Wo and TH = BM/TW divides Ho
         int tw = 16;
@@ -3431,20 +3442,9 @@ static int launch_cfg(IgemmP& p, int batch, hipStream_t st) {
             p.tiles_pw = p.Wd / tw;
             p.tiles_pi = p.tiles_pw * (p.Hd / p.th);
             p.tiles_m = p.tiles_pi * p.N;
-        } else {
-            p.tiles_m = (int)((p.M + BM - 1) / BM);
         }
-    } else {
-        p.tiles_m = (int)((p.M + BM - 1) / BM);
     }
-    const long long nblk = (long long)p.tiles_m * p.tiles_n;
-    if (nblk <= 0 || nblk > 0x7fffffffLL) {
-        eod_set_error("igemm: bad grid %lld", nblk);
-        return EOD_EINVAL;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk, (unsigned)batch), dim3(64 * NW), lds, st, p);
-    EOD_CHECK_LAUNCH("igemm");
-    return EOD_OK;
+    return launch_tiles<S>(igemm_kernel<T, CONV, BM, BN, WAVES_M, WAVES_N, SPLIT, MS, DIRECT>, p, batch, st, "igemm");
 }
 
 template <typename T, int BN, int WAVES_M, int WAVES_N, bool UPS, bool GN, bool SPLIT = false, int MS = 32, bool SKIP = false, bool KSPLIT = false>
@@ -3458,50 +3458,29 @@ static int launch_halo(IgemmP& p, hipStream_t st) {
             return EOD_EINVAL;
         }
     }
-    constexpr int BK = 128 / (int)sizeof(T);
-    constexpr int NW = WAVES_M * WAVES_N, BM = WAVES_N == 4 ? 64 * WAVES_M : 32 * NW, TH = BM / 16;
-    constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N;
-    constexpr int PR = UPS ? (TH / 2 + 2) * 10 : (TH + 2) * 18, PG = (PR + 7) / 8;
-    const size_t ring = 2 * (size_t)(PG * 1024) + 2 * (size_t)BN * 128 + (GN ? 2048 : 0);  // two patch buffers, two weight stages
-    const size_t epi = NW * (size_t)WM * (WN + 4) * sizeof(float);
-    const size_t lds = ring > epi ? ring : epi;
-    auto kern = conv3x3_halo_kernel<T, BN, WAVES_M, WAVES_N, UPS, GN, SPLIT, MS, SKIP, KSPLIT>;
+    using S = HaloShape<T, BN, WAVES_M, WAVES_N, UPS, GN, SPLIT, MS, SKIP, KSPLIT>;
+    constexpr int BK = S::BKB / (int)sizeof(T);
     if constexpr (SKIP) {
         p.skc0 = (p.SC0 + BK - 1) / BK;
         p.skc1 = (p.SC1 + BK - 1) / BK;
-    }
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_done = true;
     }
     p.kc0 = (p.C0 + BK - 1) / BK;
     p.kc1 = (p.C1 + BK - 1) / BK;
     p.KT = (p.kc0 + p.kc1) * 9;
     p.tiles_n = (p.Ncols - p.n_base + BN - 1) / BN;
-    p.tw_log2 = 4;  // TH x 16 pixel patches
-    p.th = TH;
-    p.tiles_pw = (p.Wo + 15) / 16;
-    p.tiles_pi = p.tiles_pw * (p.Ho / TH);
-    p.tiles_m = p.tiles_pi * p.N;
+    set_patch_tiles(p, S::TH, p.Ho, p.Wo);
     p.tiles_per_image = p.tiles_pi;  // (statistics slots: tile of the image x WAVES_M)
     p.tpw = 1;  // (read by conv_head_kernel only)
-    const long long nblk = (long long)p.tiles_m * p.tiles_n;
-    if (nblk <= 0 || nblk > 0x7fffffffLL) {
-        eod_set_error("conv_halo: bad grid %lld", nblk);
-        return EOD_EINVAL;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk, (unsigned)(p.splitk > 1 ? p.splitk : 1)), dim3(64 * NW), lds, st, p);
-    EOD_CHECK_LAUNCH("conv3x3_halo");
-    return EOD_OK;
+    return launch_tiles<S>(conv3x3_halo_kernel<T, BN, WAVES_M, WAVES_N, UPS, GN, SPLIT, MS, SKIP, KSPLIT>, p, p.splitk > 1 ? p.splitk : 1, st,
+                           "conv3x3_halo");
 }
 
-template <typename T, bool CONV> static int launch_T(IgemmP& p, int batch, hipStream_t st) {
-    constexpr int MS = sizeof(T) == 2 ? 16 : 32;  // fp16 products on v_mfma_f32_16x16x32_f16, exact fp32 on v_mfma_f32_32x32x2_f32
-    if (p.Ncols <= 32) return launch_cfg<T, CONV, 128, 32, 4, 1, false, MS>(p, batch, st);
-    if (p.Ncols <= 64) return launch_cfg<T, CONV, 128, 64, 4, 1, false, MS>(p, batch, st);
+template <typename T, bool CONV, bool SPLIT = false> static int launch_T(IgemmP& p, int batch, hipStream_t st) {
+    constexpr int MS = SPLIT || sizeof(T) == 2 ? 16 : 32;  // fp16 products on v_mfma_f32_16x16x32_f16, exact fp32 on v_mfma_f32_32x32x2_f32
+    if (p.Ncols <= 32) return launch_cfg<T, CONV, 128, 32, 4, 1, SPLIT, MS>(p, batch, st);
+    if (p.Ncols <= 64) return launch_cfg<T, CONV, 128, 64, 4, 1, SPLIT, MS>(p, batch, st);
     // (exact fp32: a 256x128 tile / 8 waves / 3-stage ring measured 0-5 % SLOWER than two co-resident 128x128 workgroups per CU)
-    return launch_cfg<T, CONV, 128, 128, 2, 2, false, MS>(p, batch, st);
+    return launch_cfg<T, CONV, 128, 128, 2, 2, SPLIT, MS>(p, batch, st);
 }
 
 // fp32 conv as the split-fp16 product on the generic kernel (1x1, stride 2, ragged maps); bn and direct come from the ConvPlan
@@ -3617,7 +3596,7 @@ static int conv_splitk(const eod_conv_desc* d, int Ho, int Wo, bool halo, bool h
         // chunks are split over gridDim.y workgroups (whole chunks: the nine taps of a chunk share its staged patch).  32 x 32 maps
         // (256 workgroups) measured SLOWER split in two: the reduce pass costs more than the second workgroup per CU gains.
         if (!halo_on || d->out_nchw_f32 || d->upsample || d->Cout <= 64 || d->Cout % 4) return 1;
-        const long long wgs = 16LL * (Ho / 8) * ((Wo + 15) / 16) * ((d->Cout + 127) / 128);
+        const long long wgs = 16LL * patch_tiles(Ho, Wo) * ((d->Cout + 127) / 128);
         const int kc = (d->C0 + bk - 1) / bk + (d->C1 + bk - 1) / bk;
         if (wgs >= 256 || kc < 4) return 1;
         int s = (int)((512 + wgs - 1) / wgs);
@@ -3674,9 +3653,9 @@ static ConvPlan conv_plan(const eod_conv_desc* d) {
 
     // GroupNorm partial sums of the output: statistics are accumulated on full 16-byte output chunks only
     if (d->out_nchw_f32 || d->Cout % (16 / eod_esize(d->dtype))) pl.stats_slots = 0;
-    else if (d->upsample == 3) pl.stats_slots = (d->H / 8) * ((d->W + 15) / 16) * 8;  // parity-class form: (8 x 16 tile of the STORED map, class, wave row)
+    else if (d->upsample == 3) pl.stats_slots = patch_tiles(d->H, d->W) * 8;  // parity-class form: (8 x 16 tile of the STORED map, class, wave row)
     else if (pl.splitk > 1) pl.stats_slots = 1;  // split-K: the reduce pass takes the sums, one slot per image
-    else if (pl.halo) pl.stats_slots = (Ho / 8) * ((Wo + 15) / 16) * 2;  // 8 x 16 pixel tiles (8-wide maps: half of each tile masked), two wave rows each
+    else if (pl.halo) pl.stats_slots = patch_tiles(Ho, Wo) * 2;  // 8 x 16 pixel tiles (8-wide maps: half of each tile masked), two wave rows each
     else if ((Ho * Wo) % 128 != 0) pl.stats_slots = 0;  // 128-row tiles must not straddle images
     else pl.stats_slots = (Ho * Wo / 128) * (d->Cout > 64 ? 2 : 4);  // (tile, wave row); conv_s2_halo_kernel / conv_first_x3_kernel count alike
 
@@ -3688,7 +3667,7 @@ static ConvPlan conv_plan(const eod_conv_desc* d) {
     pl.gn_fusable = !d->upsample && d->Cout <= max_cout && pl.halo;
     pl.skip_ok = opt(OPT_SKIP_FUSE) != 0 && conv_skip_geom_ok(d) && pl.halo;  // (EOD_SKIP_FUSE=0: the skip conv as a launch of its own, A/B)
 
-    const long long tiles_pi = (long long)(Ho / 8) * ((Wo + 15) / 16);  // 8 x 16 pixel tiles per image
+    const long long tiles_pi = patch_tiles(Ho, Wo);  // 8 x 16 pixel tiles per image
     if (d->upsample == 3) {
         pl.family = FAM_UP4;
         // Columns per workgroup, as for FAM_HALO below: no choice changes a result.  The split product takes the 8-wave form that stages
@@ -3696,7 +3675,7 @@ static ConvPlan conv_plan(const eod_conv_desc* d) {
         // workgroup for every CU: one 8-wave workgroup occupies a CU, as on the halo conv (whose 32 x 32 maps at batch 8, 128 workgroups,
         // measured -20 %).  Workgroups = N x 8 x 16 tiles of the STORED map x four classes x 256-column tiles.  fp16 storage and the
         // backward instance stay on the 4-wave form.
-        const long long wg = (long long)d->N * (d->H / 8) * ((d->W + 15) / 16) * 4;
+        const long long wg = (long long)d->N * patch_tiles(d->H, d->W) * 4;
         if (split && d->dtype == EOD_F32 && opt(OPT_HALO_BN256) != 0 && conv_up4_ok(d)) {
             if (d->Cout % 256 == 0 && wg * (d->Cout / 256) >= 256) {
                 pl.bn = 256;
@@ -3821,24 +3800,21 @@ static IgemmP splitk_partial(const IgemmP& p, const eod_conv_desc* d, const Conv
 }
 // second pass of a split-K conv: sum the gridDim.y raw fp32 partial tiles of the workspace in their fixed order, apply alpha / bias /
 // per-sample bias / residual, store y (and the next GroupNorm's partial sums: one slot per image)
-static int splitk_finish(const eod_conv_desc* d, const IgemmP& p, int splitk, hipStream_t st) {
+template <typename T> static int splitk_finish_T(const eod_conv_desc* d, const IgemmP& p, int splitk, hipStream_t st) {
     if (d->stats) {  // reduce + the next GroupNorm's partial sums (one slot per image)
         const dim3 grid((unsigned)((p.Cout + 63) / 64), (unsigned)d->N);
-        if (d->dtype == EOD_F16)
-            hipLaunchKernelGGL(splitk_reduce_stats_kernel<half_t>, grid, dim3(256), 0, st, (const float*)d->workspace, splitk, p.M, p.Cout, p.HoWo, d->alpha, d->bias, d->cbias, (long long)d->cbias_stride, (const half_t*)d->res, (half_t*)d->y, d->stats);
-        else
-            hipLaunchKernelGGL(splitk_reduce_stats_kernel<float>, grid, dim3(256), 0, st, (const float*)d->workspace, splitk, p.M, p.Cout, p.HoWo, d->alpha, d->bias, d->cbias, (long long)d->cbias_stride, (const float*)d->res, (float*)d->y, d->stats);
+        hipLaunchKernelGGL(splitk_reduce_stats_kernel<T>, grid, dim3(256), 0, st, (const float*)d->workspace, splitk, p.M, p.Cout, p.HoWo, d->alpha, d->bias, d->cbias, (long long)d->cbias_stride, (const T*)d->res, (T*)d->y, d->stats);
         EOD_CHECK_LAUNCH("splitk_reduce_stats");
         return EOD_OK;
     }
     const long long total4 = p.M * p.Cout / 4;
     const unsigned blocks = (unsigned)((total4 + 255) / 256 > 2048 ? 2048 : (total4 + 255) / 256);
-    if (d->dtype == EOD_F16)
-        hipLaunchKernelGGL(splitk_reduce_kernel<half_t>, dim3(blocks), dim3(256), 0, st, (const float*)d->workspace, splitk, p.M, p.Cout, p.HoWo, d->alpha, d->bias, d->cbias, (long long)d->cbias_stride, (const half_t*)d->res, (half_t*)d->y, (const float*)nullptr);
-    else
-        hipLaunchKernelGGL(splitk_reduce_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float*)d->workspace, splitk, p.M, p.Cout, p.HoWo, d->alpha, d->bias, d->cbias, (long long)d->cbias_stride, (const float*)d->res, (float*)d->y, (const float*)nullptr);  // (split-fp16 partial tiles arrive un-scaled)
+    hipLaunchKernelGGL(splitk_reduce_kernel<T>, dim3(blocks), dim3(256), 0, st, (const float*)d->workspace, splitk, p.M, p.Cout, p.HoWo, d->alpha, d->bias, d->cbias, (long long)d->cbias_stride, (const T*)d->res, (T*)d->y, (const float*)nullptr);  // (split-fp16 partial tiles arrive un-scaled)
     EOD_CHECK_LAUNCH("splitk_reduce");
     return EOD_OK;
+}
+static int splitk_finish(const eod_conv_desc* d, const IgemmP& p, int splitk, hipStream_t st) {
+    return d->dtype == EOD_F16 ? splitk_finish_T<half_t>(d, p, splitk, st) : splitk_finish_T<float>(d, p, splitk, st);
 }
 static int conv_require_workspace(const eod_conv_desc* d, const ConvPlan& pl) {
     EOD_REQUIRE(d->workspace && d->workspace_bytes >= pl.workspace_bytes, "conv: workspace of %lld bytes required (eod_conv_workspace_size)", (long long)pl.workspace_bytes);
@@ -3860,14 +3836,8 @@ static int launch_halo_bn(IgemmP& p, const eod_conv_desc* d, const ConvPlan& pl,
         if (pl.bn == 64) return launch_halo<T, 64, 2, 2, false, GN, SPLIT, MS, SKIP>(p, st);
     }
     if constexpr (MS == 16 && (GN || (SPLIT && SKIP))) {
-        if (pl.bn == 256 && pl.plus128) {  // 256-column tiles on the 8-wave form, the last 128 columns on the 4-wave one
-            IgemmP q = p;
-            q.Ncols = d->Cout - 128;
-            const int rc = launch_halo<T, 256, 2, 4, false, GN, SPLIT, MS, SKIP>(q, st);
-            if (rc != EOD_OK) return rc;
-            p.n_base = d->Cout - 128;
-            return launch_halo<T, 128, 2, 2, false, GN, SPLIT, MS, SKIP>(p, st);
-        }
+        if (pl.bn == 256 && pl.plus128)
+            return launch_256_plus_128(p, st, launch_halo<T, 256, 2, 4, false, GN, SPLIT, MS, SKIP>, launch_halo<T, 128, 2, 2, false, GN, SPLIT, MS, SKIP>);
         if (pl.bn == 256) return launch_halo<T, 256, 2, 4, false, GN, SPLIT, MS, SKIP>(p, st);
     }
     if (pl.bn == 128) return launch_halo<T, 128, 2, 2, false, GN, SPLIT, MS, SKIP>(p, st);
@@ -3966,17 +3936,8 @@ extern "C" int eod_conv2d_igemm(const eod_conv_desc* d, void* stream) {
     switch (pl.family) {
         case FAM_UP4:
             EOD_REQUIRE(conv_up4_ok(d), "conv: upsample = 3 (parity-class form of the nearest-2x conv) needs a geometry for which eod_conv_up4_ok(d) == 1");
-            if (pl.bn == 256) {  // (conv_plan: the split product only) the 8-wave form; of 256 + 128 columns the last 128 on the 4-wave one
-                if (pl.plus128) {
-                    IgemmP q = p;
-                    q.Ncols = d->Cout - 128;
-                    const int rc = launch_up4_w8(q, st);
-                    if (rc != EOD_OK) return rc;
-                    p.n_base = d->Cout - 128;
-                    return launch_up4<float, true>(p, st);
-                }
-                return launch_up4_w8(p, st);
-            }
+            if (pl.bn == 256)  // (conv_plan: the split product only) the 8-wave form; of 256 + 128 columns the last 128 on the 4-wave one
+                return pl.plus128 ? launch_256_plus_128(p, st, launch_up4_w8, launch_up4<float, true>) : launch_up4_w8(p, st);
             return f16 ? launch_up4<half_t, false>(p, st) : launch_up4<float, true>(p, st);
         case FAM_FIRST: return d->C0 == 4 ? launch_first<4>(p, st) : launch_first<8>(p, st);
         case FAM_S2_HALO: return f16 ? launch_s2<half_t, false>(p, st) : launch_s2<float, true>(p, st);
@@ -4088,9 +4049,7 @@ extern "C" int eod_gemm_nt(const eod_gemm_desc* d, void* stream) {
         EOD_REQUIRE(d->dtype == EOD_F32 && d->K % 8 == 0, "gemm: x3 needs fp32 operands and K %% 8 == 0");
         p.a_bound = d->a_bound;
         p.b_bound = d->b_bound;
-        if (p.Ncols <= 32) return launch_cfg<float, false, 128, 32, 4, 1, true, 16>(p, batch, st);
-        if (p.Ncols <= 64) return launch_cfg<float, false, 128, 64, 4, 1, true, 16>(p, batch, st);
-        return launch_cfg<float, false, 128, 128, 2, 2, true, 16>(p, batch, st);
+        return launch_T<float, false, true>(p, batch, st);
     }
     return d->dtype == EOD_F16 ? launch_T<half_t, false>(p, batch, st) : launch_T<float, false>(p, batch, st);
 }

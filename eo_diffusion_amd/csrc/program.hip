@@ -31,6 +31,21 @@ void eod_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
+int eod_lds_opt_in(const void* kern, size_t lds, EodLdsOptIn& flag, const char* what) {
+    if (lds == 0) return EOD_OK;
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    const unsigned long long bit = (e == hipSuccess && dev >= 0 && dev < 64) ? 1ull << dev : 0;
+    if (__atomic_load_n(&flag, __ATOMIC_RELAXED) & bit) return EOD_OK;
+    if (e == hipSuccess) e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) {
+        eod_set_error("%s: opt-in to %zu bytes of LDS failed on device %d: %s", what, lds, dev, hipGetErrorString(e));
+        return EOD_ELAUNCH;
+    }
+    __atomic_fetch_or(&flag, bit, __ATOMIC_RELAXED);
+    return EOD_OK;
+}
+
 extern "C" const char* eod_last_error(void) { return g_err; }
 extern "C" int eod_version(void) { return EOD_ABI_VERSION; }
 extern "C" int eod_struct_size(int kind) {

@@ -1636,12 +1636,19 @@ __device__ __forceinline__ int wg_swz(int row) { return ((row & 3) << 2) | ((row
 // gathered at pixel stride 2 in one of two column phases per workgroup -- odd columns 2(w0+j)-1 serve kx = 0 and kx = 2 (row offsets 0
 // and 1), even columns 2(w0+j) serve kx = 1 -- so the workgroup index enumerates (ky, phase) and the planes land in the ordinary
 // partial[split][ky*3+kx] layout (no transposed copies, no GEMM path).
+template <int WS> struct WgradShape {  // kernel and launcher, every MODE: a two-stage ring of [64 dY rows | X_ROWS X rows] x 256 B
+    static constexpr int threads = 256, RPS = 64 / WS, RPITCH = WS + 16;  // image rows per strip, staged-row pitch of an image row
+    static constexpr int A_ROWS = 64, X_ROWS = ((RPS - 1) * RPITCH + WS + 2 + 3) / 4 * 4, ROWB = 256;
+    static constexpr int A_BYTES = A_ROWS * ROWB, X_BYTES = X_ROWS * ROWB, STAGE = A_BYTES + X_BYTES, lds = 2 * STAGE;  // 16 KiB + 17 KiB
+};
 template <int WS, int MODE = 0>
 __global__ __launch_bounds__(256, 2) void conv3x3_wgrad_kernel(const WgradP p) {
+    using S = WgradShape<WS>;
     constexpr bool CLS = MODE == 1, S2 = MODE == 2;
-    constexpr int RPS = 64 / WS, RPITCH = WS + 16;                    // image rows per strip, staged-row pitch of an image row
-    constexpr int A_ROWS = 64, X_ROWS = ((RPS - 1) * RPITCH + WS + 2 + 3) / 4 * 4, ROWB = 256, XG = X_ROWS / 4;
-    constexpr int A_BYTES = A_ROWS * ROWB, X_BYTES = X_ROWS * ROWB, STAGE = A_BYTES + X_BYTES;  // 16 KiB + 17 KiB
+    constexpr int RPS = S::RPS, RPITCH = S::RPITCH;
+    constexpr int A_ROWS = S::A_ROWS, X_ROWS = S::X_ROWS, ROWB = S::ROWB, XG = X_ROWS / 4;
+    constexpr int A_BYTES = S::A_BYTES, X_BYTES = S::X_BYTES, STAGE = S::STAGE;
+    static_assert(2 * STAGE <= S::lds, "the ring fits the launch's LDS");
     extern __shared__ __attribute__((aligned(16))) char smem[];  // [2][STAGE]
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1804,6 +1811,17 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad_kernel(const WgradP p) {
     }
 }
 
+template <int WS, int MODE> static int launch_wgrad(const WgradP& p, long long grid, void* stream) {
+    using S = WgradShape<WS>;
+    EOD_LDS_OPT_IN((conv3x3_wgrad_kernel<WS, MODE>), S::lds, "conv3x3_wgrad");
+    hipLaunchKernelGGL((conv3x3_wgrad_kernel<WS, MODE>), dim3((unsigned)grid), dim3(S::threads), S::lds, (hipStream_t)stream, p);
+    EOD_CHECK_LAUNCH("conv3x3_wgrad");
+    return EOD_OK;
+}
+template <int MODE> static int launch_wgrad_ws(int ws, const WgradP& p, long long grid, void* stream) {
+    return ws == 64 ? launch_wgrad<64, MODE>(p, grid, stream) : ws == 32 ? launch_wgrad<32, MODE>(p, grid, stream) : launch_wgrad<16, MODE>(p, grid, stream);
+}
+
 extern "C" int eod_conv3x3_wgrad(const void* dy, const void* x, int dtype, int N, int H, int W, int Cx, int Ho, int Wo, int Cy, int Cout,
                                  int ups, float* partial, int ldp, int S, void* stream) {
     EOD_REQUIRE(dy && x && partial && N > 0 && H > 0 && W > 0 && Cx > 0 && Ho > 0 && Wo > 0 && Cy > 0 && Cout > 0 && S > 0 && ldp >= Cx,
@@ -1830,22 +1848,7 @@ extern "C" int eod_conv3x3_wgrad(const void* dy, const void* x, int dtype, int N
     p.strips_per = (p.strips_total + S - 1) / S;
     const long long grid = (long long)p.tiles_co * p.tiles_ci * (cls ? 8 : s2 ? 6 : 3) * S;
     EOD_REQUIRE(grid <= 0x7fffffffLL, "conv3x3_wgrad: grid too large");
-    const int rps = 64 / ws, xrows = ((rps - 1) * (ws + 16) + ws + 2 + 3) / 4 * 4;
-    const size_t lds = 2 * (size_t)(64 * 256 + xrows * 256);
-    const int mode = cls ? 1 : s2 ? 2 : 0;
-    void (*kern)(const WgradP) =
-        mode == 1 ? (ws == 64 ? conv3x3_wgrad_kernel<64, 1> : ws == 32 ? conv3x3_wgrad_kernel<32, 1> : conv3x3_wgrad_kernel<16, 1>)
-      : mode == 2 ? (ws == 64 ? conv3x3_wgrad_kernel<64, 2> : ws == 32 ? conv3x3_wgrad_kernel<32, 2> : conv3x3_wgrad_kernel<16, 2>)
-                  : (ws == 64 ? conv3x3_wgrad_kernel<64, 0> : ws == 32 ? conv3x3_wgrad_kernel<32, 0> : conv3x3_wgrad_kernel<16, 0>);
-    static bool attr_done[3][3] = {{false, false, false}, {false, false, false}, {false, false, false}};
-    const int vi = ws == 64 ? 0 : ws == 32 ? 1 : 2;
-    if (!attr_done[mode][vi]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_done[mode][vi] = true;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream, p);
-    EOD_CHECK_LAUNCH("conv3x3_wgrad");
-    return EOD_OK;
+    return cls ? launch_wgrad_ws<1>(ws, p, grid, stream) : s2 ? launch_wgrad_ws<2>(ws, p, grid, stream) : launch_wgrad_ws<0>(ws, p, grid, stream);
 }
 
 // dW[co][ci][ky][kx] (+)= sum over the classes of dW'[co][ci][(2p+q)*4 + a(p,ky)*2 + b(q,kx)]: the transpose of the tap sums that form
@@ -1947,10 +1950,15 @@ struct GemmTnP {
     float alpha;
 };
 
+struct GemmTnShape {  // what kernel and launcher both need: a two-stage ring of [A tile | B tile], 64 K rows x 256 B each
+    static constexpr int threads = 256, ROWS = 64, ROWB = 256, TILE = ROWS * ROWB, STAGE = 2 * TILE, lds = 2 * STAGE;
+};
+
 // F32OUT: fp32 C (the split-K partial tiles of the 1x1 backward-weights, eod_conv1x1_wgrad), alpha not applied
 template <bool F32OUT>
 __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const GemmTnP p) {
-    constexpr int ROWS = 64, ROWB = 256, TILE = ROWS * ROWB, STAGE = 2 * TILE;
+    constexpr int ROWS = GemmTnShape::ROWS, ROWB = GemmTnShape::ROWB, TILE = GemmTnShape::TILE, STAGE = GemmTnShape::STAGE;
+    static_assert(2 * STAGE <= GemmTnShape::lds, "the ring fits the launch's LDS");
     extern __shared__ __attribute__((aligned(16))) char smem[];  // [2][A tile | B tile]
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -2054,6 +2062,13 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const GemmTnP p) {
         }
 }
 
+template <bool F32OUT> static int launch_gemm_tn(const GemmTnP& p, long long grid, void* stream, const char* what) {
+    EOD_LDS_OPT_IN(gemm_tn_kernel<F32OUT>, GemmTnShape::lds, what);
+    hipLaunchKernelGGL(gemm_tn_kernel<F32OUT>, dim3((unsigned)grid), dim3(GemmTnShape::threads), GemmTnShape::lds, (hipStream_t)stream, p);
+    EOD_CHECK_LAUNCH(what);
+    return EOD_OK;
+}
+
 extern "C" int eod_gemm_tn(const void* a, int64_t lda, const void* b, int64_t ldb, void* c, int64_t ldc, int dtype, int M, int N, int K,
                            float alpha, int nb0, int nb1, int64_t sa0, int64_t sa1, int64_t sb0, int64_t sb1, int64_t sc0, int64_t sc1,
                            void* stream) {
@@ -2071,15 +2086,7 @@ extern "C" int eod_gemm_tn(const void* a, int64_t lda, const void* b, int64_t ld
     p.tiles_n = (N + 127) / 128;
     const long long grid = (long long)p.tiles_m * p.tiles_n * nb0 * nb1;
     EOD_REQUIRE(grid <= 0x7fffffffLL, "gemm_tn: grid too large");
-    const size_t lds = 2 * 2 * 64 * 256;
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_done = true;
-    }
-    hipLaunchKernelGGL(gemm_tn_kernel<false>, dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream, p);
-    EOD_CHECK_LAUNCH("gemm_tn");
-    return EOD_OK;
+    return launch_gemm_tn<false>(p, grid, stream, "gemm_tn");
 }
 
 // backward-weights of a 1x1 / stride-1 conv (the skip connections and the attention projections) with the same machinery:
@@ -2104,15 +2111,7 @@ extern "C" int eod_conv1x1_wgrad(const void* dy, const void* x, int dtype, int64
     p.tiles_n = (Cx + 127) / 128;
     const long long grid = (long long)p.tiles_m * p.tiles_n * S;
     EOD_REQUIRE(grid <= 0x7fffffffLL, "conv1x1_wgrad: grid too large");
-    const size_t lds = 2 * 2 * 64 * 256;
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_done = true;
-    }
-    hipLaunchKernelGGL(gemm_tn_kernel<true>, dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream, p);
-    EOD_CHECK_LAUNCH("conv1x1_wgrad");
-    return EOD_OK;
+    return launch_gemm_tn<true>(p, grid, stream, "conv1x1_wgrad");
 }
 
 // ---------------------------------------------------------------------------------------------
